@@ -17,11 +17,20 @@ nodes are independent, so the data path has no collective.
 
 Prints ONE JSON line (rank 0): value = narrowing events ("propagations", the reference's
 PROPS counter, propagate.c:77-78) per second over all ranks; `roofline` for the fixpoint
-kernel from HIP-event timing; `cpu_baseline` = the compiled reference itself
-(oracle/_ref/csolve_ref, kind "reference"; the oracle restatement, kind "port", when that
-binary is absent) replaying the same instances on one host core -- and, as `all_cores`,
-as independent processes on all of them -- which also re-checks every device result of the
-sample bit for bit.
+kernel from HIP-event timing of the same steps.  A plain run does only that: set-up, warm-up,
+the timed steps, --dump-outputs, the line.
+
+--full adds what takes runs of its own: the other entries of the C ABI on the same instances
+(`legs`), the device copy bandwidth next to the roofline, `cpu_baseline` = the compiled
+reference itself (oracle/_ref/csolve_ref, kind "reference"; the oracle restatement, kind
+"port", when that binary is absent) replaying the same instances on one host core -- and, as
+`all_cores`, as independent processes on all of them -- which also re-checks every device
+result of the sample bit for bit; the `queens128`, `sudoku25` and `end_to_end` sub-records and
+the `search` record (--no-cpu, --no-queens128, --no-sudoku25, --no-search leave them out).
+
+--dump-outputs DIR writes what the timed entry returned in its last step (a fixed seeded
+sample of the node instances, float64 .npy; see dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 Other workloads: --queens N, --sudoku N, --schedule N (propagation-only on other model
 shapes), --layout sets (the states carried as bit vectors only), --workload search (the
@@ -414,6 +423,11 @@ def search_workload(args, rank, world, local, dist):
                            slice_iterations=args.slice,
                            max_slices=args.search_slices)
     totals = r["totals"]
+    if rank == 0 and args.dump_outputs:
+        # the counters ShardedSearch.run hands its caller for the last search, in this order
+        keys = [k for k in ("solutions", "nodes", "cuts", "props", "revisions", "iterations", "best") if k in totals]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "search_totals.npy"), np.array([totals[k] for k in keys], dtype=np.float64))
     if rank == 0:
         sec = r["seconds_per_search"]
         print(json.dumps({
@@ -528,6 +542,10 @@ def main():
     ap.add_argument("--search-record-schedule", type=int, default=12, help="tasks of the MIN model of the `search` sub-record (0: none)")
     ap.add_argument("--comm", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--same-device", action="store_true", help="all ranks on cuda:0 (rehearsal on a 1-GPU box, use --comm gloo)")
+    ap.add_argument("--full", action="store_true", help="also the records that take runs of their own: the other entries "
+                    "(legs), the device copy bandwidth, the CPU baseline, queens128, sudoku25, end_to_end and search")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last "
+                    "step to DIR/*.npy (float64; a fixed seeded sample of the node instances)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 3 if args.workload == "search" else 100
@@ -575,10 +593,13 @@ def main():
         text = problems.schedule(args.schedule, 1)
         problem_name = f"schedule-{args.schedule} (examples/schedule.txt style, MIN) "
         workload_key = f"schedule-{args.schedule}"
-    legs = run_propagation_legs(args, text, args.instances, seed=12345 + rank, dist=dist, headline_only=(world > 1))
+    legs = run_propagation_legs(args, text, args.instances, seed=12345 + rank, dist=dist, headline_only=(world > 1),
+                                lean=not args.full)
     head = legs["legs"][legs["headline"]]
     model, n, B = legs["model"], legs["n"], legs["B"]
     res_h = head["results"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head)
     elapsed = torch.tensor([head["wall_s"]], dtype=torch.float64, device="cuda")
     if dist is not None:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
@@ -618,11 +639,11 @@ def main():
                    "revisions_per_node": revs_all / nodes_all},
         "roofline": roofline_record(head, workload_key, B),
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         out["roofline"]["streaming_ceiling"]["device_copy_gbps_this_run"] = device_copy_gbps()
-    if not legs["headline_only"]:
+    if args.full and not legs["headline_only"]:
         out["legs"] = {k: leg_summary(v) for k, v in legs["legs"].items()}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args, text, model, legs["states_in"], legs["nodes"], head["states_out"], res_h)
         if not (args.sudoku or args.schedule) and n_q == 64 and not args.no_queens128:
             out["queens128"] = queens128_record(args)
@@ -631,7 +652,7 @@ def main():
             e2e = end_to_end_record()
             if e2e is not None:
                 out["end_to_end"] = e2e
-    if not args.no_search and not (args.sudoku or args.schedule) and n_q == 64:
+    if args.full and not args.no_search and not (args.sudoku or args.schedule) and n_q == 64:
         # the propagation buffers are not needed any more: the search engines take their place in HBM
         legs.clear()
         del head, model
@@ -709,14 +730,15 @@ def time_steps(step, steps, warmup, use_graph, dist=None):
     return float(np.sum([a.elapsed_time(b) for a, b in ev])) / steps, t1 - t0, "launch loop"
 
 
-def run_propagation_legs(args, text, instances, seed, dist=None, headline_only=False, steps=None):
+def run_propagation_legs(args, text, instances, seed, dist=None, headline_only=False, steps=None, lean=False):
     """The batched fixpoint over one resident instance set, through the entries of the C ABI:
       state_only     csgpu_propagate_batch: interval states in, interval states out, nothing precomputed -- what
                      propagate_clauses is defined on and what the CPU baseline gets (the headline where it exists)
       resident_sets  csgpu_propagate_batch_fb: intervals + forbidden sets carried with every state (the search
                      engine's layout); the sets of the inputs are built by an untimed launch
       sets_only      csgpu_propagate_batch_sets: the states carried as bit vectors alone
-    Each leg is timed on its own with the same number of steps."""
+    Each leg is timed on its own with the same number of steps.  headline_only: state_only alone; lean: the
+    headline leg (--layout) alone."""
     model = solve_root(text)
     forced = args.kernel
     model.set_kernel(forced)
@@ -724,7 +746,17 @@ def run_propagation_legs(args, text, instances, seed, dist=None, headline_only=F
     n = model.n_vars
     steps = steps or args.steps
     want_sets = fw > 0 and forced in (0, 3, 4, 5) and not args.rebuild_sets
-    states_in, nodes, forb_in = make_instances(model, instances, seed=seed, with_sets=want_sets, restore_kernel=forced)
+    sets_legs = want_sets and not headline_only
+    headline = "state_only"
+    if args.layout == "sets" and sets_legs and model.qualifies(4) and forced in (0, 4):
+        headline = "sets_only"
+    elif args.layout == "intervals+sets" and sets_legs:
+        headline = "resident_sets"
+
+    def wanted(name):
+        return not lean or name == headline
+    states_in, nodes, forb_in = make_instances(model, instances, seed=seed, with_sets=want_sets and wanted("resident_sets"),
+                                               restore_kernel=forced)
     B = nodes.shape[0]
     legs = {}
 
@@ -745,24 +777,25 @@ def run_propagation_legs(args, text, instances, seed, dist=None, headline_only=F
     names = {1: "cs_propagate_events", 2: "cs_propagate_ne_lds", 3: "cs_propagate_ne_bitset", 4: "cs_propagate_ne_regs",
              5: "cs_propagate_ne_packed", 6: "cs_propagate_clause_rounds", 7: "cs_propagate_ne_shave"}
     # --- state only (every model) ---
-    so1 = torch.empty((B, n, 2), dtype=torch.int32, device="cuda")
-    r1 = torch.empty((B, 4), dtype=torch.int32, device="cuda")
     k1 = names[auto]
     full_lanes = n in (64, 128, 256)
-    leg("state_only", "csgpu_propagate_batch (interval states in, interval states out)", k1,
-        lambda: model.propagate(states_in, nodes, so1, r1), so1, r1, 8 * n,
-        stores_all=False, sets_precomputed=False)
-    headline = "state_only"
-    if want_sets and not headline_only:
-        so2 = torch.empty((B, n, 2), dtype=torch.int32, device="cuda")
-        r2 = torch.empty((B, 4), dtype=torch.int32, device="cuda")
-        fo2 = torch.empty((B, n, fw), dtype=torch.int64, device="cuda")
-        k2 = "cs_propagate_ne_packed" if (forced in (0, 5) and model.qualifies(5)) else \
-            ("cs_propagate_ne_regs" if (forced in (0, 4, 5) and model.qualifies(4)) else "cs_propagate_ne_bitset")
-        leg("resident_sets", "csgpu_propagate_batch_fb (intervals + forbidden sets in, the same out)", k2,
-            lambda: model.propagate_fb(states_in, nodes, forb_in=forb_in, states_out=so2, forb_out=fo2, results=r2),
-            so2, r2, 8 * n + 8 * n * fw, stores_all=(k2 == "cs_propagate_ne_regs" and full_lanes), sets_precomputed=True)
-        if model.qualifies(4) and forced in (0, 4):
+    if wanted("state_only"):
+        so1 = torch.empty((B, n, 2), dtype=torch.int32, device="cuda")
+        r1 = torch.empty((B, 4), dtype=torch.int32, device="cuda")
+        leg("state_only", "csgpu_propagate_batch (interval states in, interval states out)", k1,
+            lambda: model.propagate(states_in, nodes, so1, r1), so1, r1, 8 * n,
+            stores_all=False, sets_precomputed=False)
+    if sets_legs:
+        if wanted("resident_sets"):
+            so2 = torch.empty((B, n, 2), dtype=torch.int32, device="cuda")
+            r2 = torch.empty((B, 4), dtype=torch.int32, device="cuda")
+            fo2 = torch.empty((B, n, fw), dtype=torch.int64, device="cuda")
+            k2 = "cs_propagate_ne_packed" if (forced in (0, 5) and model.qualifies(5)) else \
+                ("cs_propagate_ne_regs" if (forced in (0, 4, 5) and model.qualifies(4)) else "cs_propagate_ne_bitset")
+            leg("resident_sets", "csgpu_propagate_batch_fb (intervals + forbidden sets in, the same out)", k2,
+                lambda: model.propagate_fb(states_in, nodes, forb_in=forb_in, states_out=so2, forb_out=fo2, results=r2),
+                so2, r2, 8 * n + 8 * n * fw, stores_all=(k2 == "cs_propagate_ne_regs" and full_lanes), sets_precomputed=True)
+        if model.qualifies(4) and forced in (0, 4) and wanted("sets_only"):
             sets_in = model.pack_sets(states_in)
             torch.cuda.synchronize()
             fo3 = torch.empty((B, n, fw), dtype=torch.int64, device="cuda")
@@ -771,12 +804,30 @@ def run_propagation_legs(args, text, instances, seed, dist=None, headline_only=F
                 "cs_propagate_ne_regs",
                 lambda: model.propagate_sets(sets_in, nodes, sets_out=fo3, results=r3), None, r3, 8 * n * fw,
                 stores_all=full_lanes, sets_precomputed=True, finish=lambda: model.unpack_sets(fo3))
-    if args.layout == "sets" and "sets_only" in legs:
-        headline = "sets_only"
-    elif args.layout == "intervals+sets" and "resident_sets" in legs:
-        headline = "resident_sets"
     return {"legs": legs, "headline": headline, "model": model, "n": n, "B": B, "states_in": states_in, "nodes": nodes,
             "headline_only": headline_only}
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: the files of one run stay below this
+
+
+def dump_outputs(path, leg, seed=20260101):
+    """--dump-outputs: what the caller of the leg's entry received from its last timed step, as float64 .npy (exact for
+    every int32) on a fixed seeded sample of the node instances, as many as fit in DUMP_BYTES:
+      rows.npy        [S]        the sampled instance indices, ascending
+      results.npy     [S, 4]     csgpu_result: status, props, revisions, rounds
+      states_out.npy  [S, n, 2]  the fixpoint (lo, hi per variable); 0 where the node is inconsistent (status -1), whose
+                                 rows the C ABI leaves unspecified"""
+    B, n = leg["B"], leg["n"]
+    count = min(B, DUMP_BYTES // (8 * (1 + 4 + 2 * n)))
+    rows = np.arange(B) if count == B else np.sort(np.random.default_rng(seed).choice(B, count, replace=False))
+    res = leg["results"][rows]
+    so = leg["states_out"][torch.from_numpy(rows).to(leg["states_out"].device)].cpu().numpy().astype(np.float64)
+    so[res[:, 0] < 0] = 0
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "results.npy"), res.astype(np.float64))
+    np.save(os.path.join(path, "states_out.npy"), so)
 
 
 def device_copy_gbps(bytes_each=1 << 30, reps=5):

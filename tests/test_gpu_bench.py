@@ -22,7 +22,8 @@ def _bench(args, timeout=300):
 
 
 def test_bench_line_has_the_contracted_fields():
-    r = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--instances", "16384", "--cpu-seconds", "1", "--no-queens128", "--no-search"])
+    r = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--instances", "16384", "--cpu-seconds", "1", "--no-queens128", "--no-search",
+                "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in r, k
@@ -36,6 +37,31 @@ def test_bench_line_has_the_contracted_fields():
     cpu = r["cpu_baseline"]
     assert cpu["kind"] == "reference" and cpu["cores"] == 1 and cpu["value"] > 0 and "bit for bit" in cpu["sample"]
     assert r["value"] > 1000 * cpu["value"]
+
+
+def test_a_plain_line_is_the_headline_alone_and_its_outputs_are_dumped_alike(tmp_path):
+    """without --full: the headline and its roofline, nothing that takes runs of its own; --dump-outputs: float64 results
+    and fixpoints of the last timed step on a seeded sample of the instances (65,536 queens-64 instances are more than
+    fit), the same in a second run"""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "4", "--warmup", "1", "--instances", "65536"]
+    r = _bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert r["steps"] == 4 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0 and r["dtype"] == "int32"
+    for k in ("legs", "cpu_baseline", "queens128", "sudoku25", "end_to_end", "search"):
+        assert k not in r, k
+    assert r["roofline"]["kernel_ms"] > 0 and "device_copy_gbps_this_run" not in r["roofline"]["streaming_ceiling"]
+    names = ("rows.npy", "results.npy", "states_out.npy")
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    rows, res, so = (np.load(tmp_path / "a" / f) for f in names)
+    assert rows.dtype == res.dtype == so.dtype == np.float64
+    assert 0 < len(rows) < 65536 and res.shape == (len(rows), 4) and so.shape == (len(rows), 64, 2)
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < 65536
+    ok = res[:, 0] >= 0
+    assert 0 < ok.sum() < len(rows) and (so[~ok] == 0).all()
+    assert ((so[ok, :, 0] != so[ok, :, 1]).sum(1) == res[ok, 0]).all() and (so[ok, :, 0] <= so[ok, :, 1]).all()
+    _bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
 
 
 SMALL_SEARCH = ["--search-queens", "11", "--search-steps", "1", "--search-time-limit", "0.5", "--search-record-schedule", "6"]
@@ -58,7 +84,7 @@ def _check_search_record(rec, ranks):
 
 
 def test_the_default_line_carries_the_search_record_at_one_gpu():
-    r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--instances", "8192", "--no-cpu"] + SMALL_SEARCH)
+    r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--instances", "8192", "--no-cpu", "--full"] + SMALL_SEARCH)
     assert r["n_gpus"] == 1 and r["scaling"] == "weak" and "roofline" in r
     rec = r["search"]
     assert rec["process_group"] is None and rec["launched_by"].startswith("a single process")
@@ -71,7 +97,7 @@ def test_bench_starts_its_own_ranks():
     The sharded search of the two ranks walks the one-rank tree."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--instances", "8192",
-           "--comm", "gloo", "--same-device"] + SMALL_SEARCH
+           "--comm", "gloo", "--same-device", "--full"] + SMALL_SEARCH
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=420, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -81,7 +107,7 @@ def test_bench_starts_its_own_ranks():
     rec = r["search"]
     assert rec["process_group"] == "gloo" and rec["launched_by"].startswith("bench.py itself") and rec["same_device"] is True
     two = _check_search_record(rec, 2)
-    one = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--instances", "8192", "--no-cpu"] + SMALL_SEARCH)["search"]["queens11_all"]
+    one = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--instances", "8192", "--no-cpu", "--full"] + SMALL_SEARCH)["search"]["queens11_all"]
     assert (two["nodes"], two["cuts"], two["solutions"]) == (one["nodes"], one["cuts"], one["solutions"])
 
 
