@@ -43,6 +43,34 @@ extern "C" int csgpu_internal_set_error(int code, const char *msg) { return set_
 #define CS_TICKET_STREAMS 64
 #define CS_TICKET_SLOT_WORDS (CS_SHAVE_SHARDS * CS_SHAVE_TICKET_STRIDE)
 
+#define CS_CU_LDS (160u * 1024u) /* LDS of one CU */
+
+/* one kernel a model may launch, resolved by csgpu_model_finalize (fn == NULL: the model does not qualify) */
+struct cs_planned {
+  const void *fn; /* the instantiation; its LDS attribute was set for `lds` */
+  size_t lds;     /* dynamic LDS bytes per workgroup */
+  int waves;      /* waves per workgroup */
+  int per_cu;     /* resident workgroups per CU */
+};
+
+/* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
+struct cs_kernel_plan {
+  cs_planned events, traced;       /* kernel 1; its tracing variant (one node) */
+  cs_planned rounds;               /* kernel 6 */
+  int rounds_cpl;                  /* its clauses per lane (1, 2, 4, 8) */
+  cs_planned lds;                  /* kernel 2 */
+  cs_planned bitset;               /* kernel 3 */
+  cs_planned regs[4];              /* kernel 4: [fast | sets_only << 1] */
+  cs_planned packed;               /* kernel 5 */
+  int packed_nodes;                /* its nodes per wave */
+  cs_planned shave, shave_trace;   /* kernel 7 (the instantiation whose FULL matches the model); its tracing variant */
+  cs_planned server;               /* the resident single-node server */
+  cs_planned step_shave, step_packed, step_import;
+  int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
+  int step_kind;                   /* csgpu_internal_step_kind */
+  int max_width;                   /* widest root interval, at least 2 */
+};
+
 struct csgpu_model {
   cs_model *host;
   int from_dump;     /* clause lists came with the file: keep them */
@@ -58,16 +86,15 @@ struct csgpu_model {
   int packed_nw;     /* kernel 5: set words per variable it works on (1: all root domains within 32 values) */
   int kernel_choice; /* 0 auto, 1 general, 2 LDS-resident, 3 forbidden sets, 4 forbidden sets in registers, 5 = 4 with
                         several nodes per wave */
+  cs_kernel_plan plan;
   void *d_adj_packed;
-  int lds_waves;     /* waves per workgroup of the LDS-resident kernel, 0 = not eligible */
-  size_t lds_bytes;  /* its dynamic LDS size */
   int lds_adj_global; /* kernel 2 reads its adjacency through L2 (the lists would leave LDS for fewer than 16 waves) */
+  int k2_csz;         /* kernel 2's nodes per chunk when CSGPU_K2_CSZ sets them (0: by the batch) */
+  int shave_static;   /* CSGPU_SHAVE_STATIC: kernel 7 without tickets */
+  int step_chunk_max; /* cs_step_packed: most parents per ticket */
   size_t k1_tab_bytes; /* general kernel: adj_off + adj + lit copied into LDS by every workgroup (0: read through L2) */
   int fb_words;      /* forbidden-set words per variable (0 = not eligible) */
-  int fb_waves;
-  size_t fb_bytes;
-  int dense_waves;    /* register-resident forbidden-set kernel: waves per workgroup, 0 = not eligible */
-  size_t dense_bytes; /* its LDS table */
+  size_t dense_bytes; /* the dense pair table of kernels 4, 5 and 7 */
   void *d_dense_tab;
   void *d_packed_tab; /* kernel 5: 16-bit table relative to the pushing variable */
   int *d_root_lo;
@@ -274,10 +301,9 @@ static void free_device(csgpu_model *m) {
   m->d_sym_off = NULL;
   m->d_sym_packed = NULL;
   m->d_dense_tab = NULL;
-  m->dense_waves = 0;
   m->d_adj_packed = NULL;
   m->d_root_lo = NULL;
-  m->lds_waves = 0;
+  memset(&m->plan, 0, sizeof m->plan);
   m->fb_words = 0;
   (void)hipHostFree(m->h_one);
   m->h_one = NULL;
@@ -415,7 +441,7 @@ static void free_tables(dev_tables_owner *o) {
 }
 
 static int lds_limit(size_t bytes, const void *func) {
-  if (bytes > 160u * 1024u) return set_err(CSGPU_E_LIMIT, "%zu bytes of LDS per workgroup exceed the 160 KiB of a CU", bytes);
+  if (bytes > CS_CU_LDS) return set_err(CSGPU_E_LIMIT, "%zu bytes of LDS per workgroup exceed the 160 KiB of a CU", bytes);
   if (bytes > 48u * 1024u)
     HIP_TRY(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return CSGPU_OK;
@@ -717,30 +743,93 @@ static int packed_nodes_per_wave(int fw, int n_vars, int dense_width) {
   return fw == 1 && dense_width == 1 && n_vars <= 32 ? (n_vars <= 16 ? 4 : 2) : 0;
 }
 
-static const void *ne_packed_kernel(int n_vars, int nw, int s3) {
-#define CS_PICK_S(G, NW)                                                                           \
-  return s3 ? (const void *)cs_propagate_ne_packed<G, NW, true> : (const void *)cs_propagate_ne_packed<G, NW, false>;
-#define CS_PICK_NW(G)                                                                              \
-  if (nw == 1) { CS_PICK_S(G, 1) }                                                                 \
-  CS_PICK_S(G, 2)
-  if (n_vars <= 16) { CS_PICK_NW(4) }
-  CS_PICK_NW(2)
-#undef CS_PICK_NW
+/* kernel 5 and the step kernels built on it: 64 / n_vars nodes per wave (4 or 2), set words per variable, three slots */
+#define CS_PACKED_PICKER(NAME, KERNEL)                                                                 \
+  static const void *NAME(int n_vars, int nw, int s3) {                                                \
+    if (n_vars <= 16) {                                                                                \
+      if (nw == 1) return s3 ? (const void *)KERNEL<4, 1, true> : (const void *)KERNEL<4, 1, false>;    \
+      return s3 ? (const void *)KERNEL<4, 2, true> : (const void *)KERNEL<4, 2, false>;                 \
+    }                                                                                                  \
+    if (nw == 1) return s3 ? (const void *)KERNEL<2, 1, true> : (const void *)KERNEL<2, 1, false>;      \
+    return s3 ? (const void *)KERNEL<2, 2, true> : (const void *)KERNEL<2, 2, false>;                   \
+  }
+CS_PACKED_PICKER(ne_packed_kernel, cs_propagate_ne_packed)
+CS_PACKED_PICKER(step_packed_kernel, cs_step_packed)
+CS_PACKED_PICKER(step_import_kernel, cs_step_import)
+#undef CS_PACKED_PICKER
+
+/* ---- cs_step.hip.h: one level of the search tree per launch ---- */
+static const void *step_shave_kernel(int width, int n_vars, int slots, int full) {
+  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
+#define CS_PICK_S(E, R)                                                                                   \
+  if (slots == 1) return full ? (const void *)cs_step_shave<E, R, 1, true> : (const void *)cs_step_shave<E, R, 1, false>; \
+  if (slots == 3) return full ? (const void *)cs_step_shave<E, R, 3, true> : (const void *)cs_step_shave<E, R, 3, false>; \
+  return full ? (const void *)cs_step_shave<E, R, 0, true> : (const void *)cs_step_shave<E, R, 0, false>;
+#define CS_PICK(E)                                                                                 \
+  switch (chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4)) {                                               \
+  case 1: CS_PICK_S(E, 1)                                                                          \
+  case 2: CS_PICK_S(E, 2)                                                                          \
+  default: CS_PICK_S(E, 4)                                                                         \
+  }
+  if (width == 1) { CS_PICK(unsigned char) }
+  CS_PICK(unsigned short)
+#undef CS_PICK
 #undef CS_PICK_S
 }
 
-static const void *step_packed_kernel(int n_vars, int nw, int s3); /* below, with the step launcher */
-static const void *step_import_kernel(int n_vars, int nw, int s3);
-static const void *step_shave_kernel(int width, int n_vars, int slots, int full);
+/* ---- the resident single-node server (cs_shave.hip.h) ---- */
+static const void *shave_server_kernel(int width, int n_vars, int slots) {
+  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
+  const int r = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4);
+  const int sl = slots == 1 ? 1 : (slots == 3 ? 3 : 0);
+#define CS_PICK_S(E, RR)                                                                           \
+  switch (sl) {                                                                                    \
+  case 1: return (const void *)cs_shave_server<E, RR, 1>;                                           \
+  case 3: return (const void *)cs_shave_server<E, RR, 3>;                                           \
+  default: return (const void *)cs_shave_server<E, RR, 0>;                                          \
+  }
+#define CS_PICK(E)                                                                                 \
+  switch (r) {                                                                                     \
+  case 1: CS_PICK_S(E, 1)                                                                          \
+  case 2: CS_PICK_S(E, 2)                                                                          \
+  default: CS_PICK_S(E, 4)                                                                         \
+  }
+  if (width == 1) { CS_PICK(unsigned char) }
+  CS_PICK(unsigned short)
+#undef CS_PICK
+#undef CS_PICK_S
+}
 
-/* kernel 6: clauses per lane (1, 2, 4, 8) if the model has at most 512 clauses, else 0 */
-static int clause_rounds_cpl(const csgpu_model *m) {
-  if (m->img == NULL || m->img->n_clauses <= 0 || m->img->n_clauses > 8 * CS_WAVE) return 0;
-  const int per = (m->img->n_clauses + CS_WAVE - 1) / CS_WAVE;
-  return per <= 1 ? 1 : (per <= 2 ? 2 : (per <= 4 ? 4 : 8));
+/* LDS of a step workgroup of `waves` waves: the 16-bit table, then per wave the parent slots and the child queue */
+static size_t step_packed_lds(const csgpu_model *m, int waves) {
+  return ((2 * m->dense_bytes + 15) & ~(size_t)15) + (size_t)waves * ((1 + m->packed_nw) * 256 + CS_STEP_QN) * sizeof(unsigned);
 }
 
 /* ---- finalize ---------------------------------------------------------------------- */
+
+/* resident workgroups per CU of `lds` bytes and `waves` waves each: LDS- and wave-slot-limited (32 waves per CU) */
+static int resident_per_cu(size_t lds, int waves) {
+  size_t wgs = lds > 0 ? CS_CU_LDS / lds : (size_t)32;
+  if (wgs > (size_t)(32 / waves)) wgs = (size_t)(32 / waves);
+  return (int)wgs;
+}
+
+/* nodes per chunk: `csz` halved while the batch would make fewer than `min_chunks` chunks */
+static int shrink_chunk(int csz, int64_t batch, int64_t min_chunks) {
+  while (csz > 1 && (batch + csz - 1) / csz < min_chunks) csz >>= 1;
+  return csz;
+}
+
+/* plan `fn` with `lds` bytes and `waves` waves per workgroup, and set its LDS attribute */
+static int plan_kernel(cs_planned *p, const void *fn, size_t lds, int waves) {
+  const int rc = lds_limit(lds, fn);
+  if (rc != CSGPU_OK) return rc;
+  p->fn = fn;
+  p->lds = lds;
+  p->waves = waves;
+  p->per_cu = resident_per_cu(lds, waves);
+  return CSGPU_OK;
+}
 
 extern "C" int csgpu_model_build_tables(csgpu_model *m) {
   if (m == NULL) return set_err(CSGPU_E_ARG, "null argument");
@@ -759,18 +848,13 @@ extern "C" int csgpu_model_build_tables(csgpu_model *m) {
   return CSGPU_OK;
 }
 
-extern "C" int csgpu_model_finalize(csgpu_model *m) {
-  if (m == NULL) return set_err(CSGPU_E_ARG, "null argument");
+/* Upload the tables.  Clauses that already evaluate to true in the root state are entailed for the whole search:
+ * evaluate every clause once on the device and drop those from the tables. */
+static int drop_entailed_clauses(csgpu_model *m) {
   cs_model *h = m->host;
-  free_device(m);
-  int rc0 = csgpu_model_build_tables(m);
-  if (rc0 != CSGPU_OK) return rc0;
-
   dev_tables_owner own;
   int rc = upload_image(m->img, &own, &m->tab);
   if (rc == CSGPU_OK && h->n_clauses > 0 && !m->not_root) {
-    /* Clauses that already evaluate to true in the root state are entailed for the whole
-     * search: evaluate every clause once on the device and drop those from the tables. */
     cs_val *d_state = NULL, *d_vals = NULL;
     const size_t lds0 = (size_t)h->n_vars * sizeof(cs_val) + 16;
     cs_val *vals = (cs_val *)malloc((size_t)h->n_clauses * sizeof(cs_val));
@@ -810,218 +894,287 @@ extern "C" int csgpu_model_finalize(csgpu_model *m) {
   m->d_adj_off = own.adj_off; m->d_adj = own.adj; m->d_clause = own.clause; m->d_clause_by_kind = own.clause_by_kind;
   m->d_tree_off = own.tree_off; m->d_tnode = own.tnode; m->d_tkid = own.tkid; m->d_tree_want = own.tree_want;
   m->d_lit = own.lit;
-  if (rc != CSGPU_OK) return rc;
+  return rc;
+}
 
+/* kernels every model runs: the general kernel (1) and its tracing variant, the clause-resident kernel (6), the
+ * clause evaluation */
+static int plan_general(csgpu_model *m) {
+  const cs_model *h = m->host;
   const size_t slice = (size_t)h->n_vars * sizeof(cs_val) + 2 * (size_t)m->tab.n_words * sizeof(unsigned);
   m->slice = (slice + 15) & ~(size_t)15;
   m->has_tree_adj = 0;
   for (int32_t i = 0; i < m->img->n_adj; i++)
     if (m->img->adj[2 * i] < 0 && m->img->adj[2 * i + 1] == 0) { m->has_tree_adj = 1; break; }
   /* small tables travel into LDS with every workgroup of the general kernel */
-  {
-    const size_t tb = ((((size_t)h->n_vars + 1) * 4 + 15) & ~(size_t)15) + (((size_t)m->img->n_adj * 8 + 15) & ~(size_t)15) +
-                      (((size_t)m->img->n_lits * 16 + 15) & ~(size_t)15);
-    m->k1_tab_bytes = (tb <= 32u * 1024u && m->img->n_adj > 0) ? tb : 0;
-  }
-  const size_t lds = m->slice * CS_WAVES_PER_BLOCK + m->k1_tab_bytes;
-  if ((rc = lds_limit(lds, (const void *)cs_propagate_events<false, false>))) return rc;
-  if ((rc = lds_limit(lds, (const void *)cs_propagate_events<true, false>))) return rc;
-  if ((rc = lds_limit(lds, (const void *)cs_propagate_events<false, true>))) return rc;
-  if ((rc = lds_limit(lds, (const void *)cs_propagate_events<true, true>))) return rc;
+  const size_t tb = ((((size_t)h->n_vars + 1) * 4 + 15) & ~(size_t)15) + (((size_t)m->img->n_adj * 8 + 15) & ~(size_t)15) +
+                    (((size_t)m->img->n_lits * 16 + 15) & ~(size_t)15);
+  m->k1_tab_bytes = (tb <= 32u * 1024u && m->img->n_adj > 0) ? tb : 0;
+  const void *k1 = m->has_tree_adj ? (m->k1_tab_bytes ? (const void *)cs_propagate_events<true, true>
+                                                      : (const void *)cs_propagate_events<true, false>)
+                                   : (m->k1_tab_bytes ? (const void *)cs_propagate_events<false, true>
+                                                      : (const void *)cs_propagate_events<false, false>);
+  int rc;
+  if ((rc = plan_kernel(&m->plan.events, k1, m->slice * CS_WAVES_PER_BLOCK + m->k1_tab_bytes, CS_WAVES_PER_BLOCK)))
+    return rc;
+  if (m->plan.events.per_cu < 1) m->plan.events.per_cu = 1;
   if ((rc = lds_limit((size_t)h->n_vars * sizeof(cs_val) + 16, (const void *)cs_eval_root))) return rc;
   if ((rc = lds_limit((size_t)h->n_vars * sizeof(cs_val) + 16, (const void *)cs_eval_clauses))) return rc;
+  if ((rc = plan_kernel(&m->plan.traced, (const void *)cs_propagate_events<true, false, true>, m->slice * CS_WAVES_PER_BLOCK,
+                        CS_WAVES_PER_BLOCK)))
+    return rc;
+  /* kernel 6: launched without an LDS attribute; its grid is eight workgroups per CU, four times over */
+  const int per = (m->img->n_clauses + CS_WAVE - 1) / CS_WAVE; /* clauses per lane: 1, 2, 4, 8 for at most 512 clauses */
+  m->plan.rounds_cpl = m->img->n_clauses <= 0 || per > 8 ? 0 : (per <= 1 ? 1 : (per <= 2 ? 2 : (per <= 4 ? 4 : 8)));
+  if (m->plan.rounds_cpl) {
+#define CS_PICK6(CPL)                                                                              \
+  m->plan.rounds.fn = m->has_tree_adj ? (const void *)cs_propagate_clause_rounds<CPL, true>         \
+                                      : (const void *)cs_propagate_clause_rounds<CPL, false>
+    switch (m->plan.rounds_cpl) {
+    case 1: CS_PICK6(1); break;
+    case 2: CS_PICK6(2); break;
+    case 4: CS_PICK6(4); break;
+    default: CS_PICK6(8); break;
+    }
+#undef CS_PICK6
+    m->plan.rounds.lds = ((((size_t)h->n_vars * sizeof(cs_val) + 16 + 15) & ~(size_t)15)) * CS_WAVES_PER_BLOCK;
+    m->plan.rounds.waves = CS_WAVES_PER_BLOCK;
+    m->plan.rounds.per_cu = 8;
+  }
+  m->plan.max_width = 2;
+  for (int32_t v = 0; v < h->n_vars; v++) {
+    const int64_t w = (int64_t)h->dom[v].hi - (int64_t)h->dom[v].lo + 1;
+    if (w > m->plan.max_width) m->plan.max_width = w > 0x7fffffff ? 0x7fffffff : (int)w;
+  }
+  return CSGPU_OK;
+}
 
-  /* LDS-resident kernel: adj_off + packed adjacency + one slice per wave must fit in a CU's LDS */
-  m->lds_waves = 0;
-  if (m->img->packed_width != 0) {
-    const size_t off_bytes = (((size_t)h->n_vars * 2 * sizeof(int)) + 15) & ~(size_t)15;
-    const size_t adj_bytes = (((size_t)m->img->n_adj * (size_t)m->img->packed_width) + 15) & ~(size_t)15;
-    const size_t lds_slice = ((size_t)h->n_vars * sizeof(cs_val) + (2 * (size_t)m->tab.n_words + 1) * sizeof(unsigned) + 15) & ~(size_t)15;
-    m->lds_adj_global = 0;
-    /* as many waves as fit next to the lists (not only 16, 8 or 4: the 25x25 sudoku's lists leave room for fifteen
-     * slices, and with eight its nodes' chains of dependent steps had two waves per SIMD to hide behind) */
-    int waves_max = 16;
-    { const char *e = getenv("CSGPU_K2_WAVES"); if (e != NULL && atoi(e) >= 4 && atoi(e) <= 16) waves_max = atoi(e); } /* measurement override */
-    for (int waves = waves_max; waves >= 4; waves--) {
-      const size_t need = off_bytes + adj_bytes + (size_t)waves * lds_slice;
-      if (need <= 160u * 1024u) {
-        m->lds_waves = waves;
-        m->lds_bytes = need;
-        break;
-      }
-    }
-    const char *force = getenv("CSGPU_K2_ADJ"); /* "global": measurement override */
-    const int want_global = force != NULL && force[0] == 'g';
-    if (want_global && 8 * lds_slice <= 160u * 1024u) {
-      /* the lists in device memory (L2-resident) and LDS for the node slices only: 24 waves per CU instead of 16 on
-       * the 25x25 sudoku network -- and 1.23 ms instead of 0.75 ms for 2^18 nodes: the two-byte gathers through L2
-       * cost more than the extra waves hide.  Kept for measurements; never chosen automatically. */
-      m->lds_adj_global = 1;
-      m->lds_waves = 8;
-      m->lds_bytes = 8 * lds_slice;
-    }
-    if (m->lds_waves) {
-      if ((rc = upload(m->img->adj_packed, (size_t)m->img->n_adj * (size_t)m->img->packed_width,
-                       (int **)&m->d_adj_packed)))
-        return rc;
-      if ((rc = lds_limit(m->lds_bytes, ne_lds_kernel(m->img->packed_width, h->n_vars, m->lds_adj_global)))) return rc;
+/* LDS-resident kernel (2): adj_off + packed adjacency + one slice per wave must fit in a CU's LDS */
+static int plan_lds_resident(csgpu_model *m) {
+  const cs_model *h = m->host;
+  if (m->img->packed_width == 0) return CSGPU_OK;
+  const size_t off_bytes = (((size_t)h->n_vars * 2 * sizeof(int)) + 15) & ~(size_t)15;
+  const size_t adj_bytes = (((size_t)m->img->n_adj * (size_t)m->img->packed_width) + 15) & ~(size_t)15;
+  const size_t lds_slice = ((size_t)h->n_vars * sizeof(cs_val) + (2 * (size_t)m->tab.n_words + 1) * sizeof(unsigned) + 15) & ~(size_t)15;
+  m->lds_adj_global = 0;
+  /* as many waves as fit next to the lists (not only 16, 8 or 4: the 25x25 sudoku's lists leave room for fifteen
+   * slices, and with eight its nodes' chains of dependent steps had two waves per SIMD to hide behind) */
+  int waves_max = 16, waves = 0;
+  size_t bytes = 0;
+  { const char *e = getenv("CSGPU_K2_WAVES"); if (e != NULL && atoi(e) >= 4 && atoi(e) <= 16) waves_max = atoi(e); } /* measurement override */
+  for (int w = waves_max; w >= 4; w--) {
+    const size_t need = off_bytes + adj_bytes + (size_t)w * lds_slice;
+    if (need <= CS_CU_LDS) {
+      waves = w;
+      bytes = need;
+      break;
     }
   }
-
-  /* forbidden-set kernel: additionally root intervals of at most 256 values, and only when the
-   * host domains really are the root state (the bit windows are anchored at the root bounds) */
-  m->fb_words = 0;
-  if (m->img->sym_width != 0 && !m->not_root) {
-    int64_t width = 1;
-    for (int32_t v = 0; v < h->n_vars; v++) {
-      const int64_t w = (int64_t)h->dom[v].hi - (int64_t)h->dom[v].lo + 1;
-      if (w > width) width = w;
-    }
-    const int fw = width <= 64 ? 1 : (width <= 128 ? 2 : (width <= 256 ? 4 : 0));
-    if (fw) {
-      const size_t off_bytes = (((size_t)h->n_vars * 2 * sizeof(int)) + 15) & ~(size_t)15;
-      const size_t base_bytes = (((size_t)h->n_vars * sizeof(int)) + 15) & ~(size_t)15;
-      const size_t adj_bytes = (((size_t)m->img->sym_n_adj * (size_t)m->img->sym_width) + 15) & ~(size_t)15;
-      const size_t sl = ((size_t)h->n_vars * sizeof(cs_val) + (size_t)h->n_vars * fw * 8 +
-                         (2 * (size_t)m->tab.n_words + 2) * sizeof(unsigned) + 15) & ~(size_t)15;
-      for (int waves = 16; waves >= 1; waves--) { /* as many waves as fit next to the tables */
-        const size_t need = off_bytes + base_bytes + adj_bytes + (size_t)waves * sl;
-        if (need <= 160u * 1024u) {
-          m->fb_words = fw;
-          m->fb_waves = waves;
-          m->fb_bytes = need;
-          break;
-        }
-      }
-    }
-    if (m->fb_words) {
-      int *lo = (int *)malloc((size_t)(h->n_vars ? h->n_vars : 1) * sizeof(int));
-      for (int32_t v = 0; v < h->n_vars; v++) lo[v] = h->dom[v].lo;
-      rc = upload(lo, (size_t)h->n_vars * sizeof(int), &m->d_root_lo);
-      free(lo);
-      if (rc) return rc;
-      if ((rc = upload(m->img->sym_off, ((size_t)h->n_vars + 1) * sizeof(int), &m->d_sym_off))) return rc;
-      if ((rc = upload(m->img->sym_packed, (size_t)m->img->sym_n_adj * (size_t)m->img->sym_width,
-                       (int **)&m->d_sym_packed)))
-        return rc;
-      if ((rc = lds_limit(m->fb_bytes, ne_bitset_kernel(m->img->sym_width, m->fb_words, m->host->n_vars)))) return rc;
-      /* the register-resident variant: the dense table must fit a CU's LDS; the workgroup size that keeps
-       * the most waves resident (32 per CU at most), smaller workgroups on ties */
-      if (m->img->dense_width != 0) {
-        const size_t bytes = (size_t)h->n_vars * m->img->dense_slots * m->img->dense_cols * m->img->dense_width;
-        int best = 0, best_waves = 0;
-        for (int waves = 4; waves <= 16; waves <<= 1) {
-          size_t wgs = (160u * 1024u) / bytes;
-          if (wgs > (size_t)(32 / waves)) wgs = (size_t)(32 / waves);
-          if ((int)wgs * waves > best) { best = (int)wgs * waves; best_waves = waves; }
-        }
-        if (best_waves) {
-          m->dense_waves = best_waves;
-          m->dense_bytes = bytes;
-          if ((rc = upload(m->img->dense_tab, bytes, (int **)&m->d_dense_tab))) return rc;
-          for (int variant = 0; variant < 4; variant++)
-            if ((rc = lds_limit(bytes, ne_regs_kernel(m->img->dense_width, m->fb_words, h->n_vars, variant & 1, variant >> 1))))
-              return rc;
-          for (int full = 0; full < 2; full++)
-            if ((rc = lds_limit(bytes, ne_shave_kernel(m->img->dense_width, h->n_vars, m->img->dense_slots, full)))) return rc;
-          if (((bytes + 15) & ~(size_t)15) + (size_t)best_waves * 32 <= 160u * 1024u)
-            for (int full = 0; full < 2; full++)
-              if ((rc = lds_limit(((bytes + 15) & ~(size_t)15) + (size_t)best_waves * 32,
-                                  step_shave_kernel(m->img->dense_width, h->n_vars, m->img->dense_slots, full))))
-                return rc;
-          if (((bytes + 15) & ~(size_t)15) + CS_SHAVE_TRACE_LDS * 16 <= 160u * 1024u &&
-              (rc = lds_limit(((bytes + 15) & ~(size_t)15) + CS_SHAVE_TRACE_LDS * 16,
-                              ne_shave_trace_kernel(m->img->dense_width, h->n_vars, m->img->dense_slots))))
-            return rc;
-          HIP_TRY(hipMalloc((void **)&m->d_tickets, (size_t)CS_TICKET_SLOTS * CS_TICKET_SLOT_WORDS * sizeof(unsigned)));
-          HIP_TRY(hipMemset(m->d_tickets, 0, (size_t)CS_TICKET_SLOTS * CS_TICKET_SLOT_WORDS * sizeof(unsigned)));
-          m->ticket_slots = CS_TICKET_SLOTS;
-          m->packed_nw = 1; /* one set word per variable when every root domain has at most 32 values */
-          for (int32_t v = 0; v < h->n_vars; v++)
-            if ((int64_t)h->dom[v].hi - (int64_t)h->dom[v].lo + 1 > 32) m->packed_nw = 2;
-          m->packed_bias = 0;
-          for (int32_t v = 0; v < h->n_vars; v++)
-            if (h->dom[v].lo - m->img->dense_dmin > m->packed_bias) m->packed_bias = h->dom[v].lo - m->img->dense_dmin;
-          if (packed_nodes_per_wave(m->fb_words, h->n_vars, m->img->dense_width)) {
-            if ((rc = lds_limit(2 * bytes, ne_packed_kernel(h->n_vars, m->packed_nw, m->img->dense_slots == 3)))) return rc;
-            /* entry e of row u becomes e - (root_lo[u] - dmin) + bias (cs_kernels.hip.h, kernel 5) */
-            const size_t per_row = (size_t)m->img->dense_slots * m->img->dense_cols, total = (size_t)h->n_vars * per_row;
-            uint16_t *rel = (uint16_t *)malloc(total * sizeof(uint16_t));
-            const uint8_t *src = (const uint8_t *)m->img->dense_tab;
-            for (size_t i = 0; i < total; i++) {
-              const int32_t u = (int32_t)(i / per_row);
-              rel[i] = src[i] == 0xffu ? (uint16_t)0xffffu
-                                       : (uint16_t)((int)src[i] - (h->dom[u].lo - m->img->dense_dmin) + m->packed_bias);
-            }
-            rc = upload(rel, total * sizeof(uint16_t), (int **)&m->d_packed_tab);
-            free(rel);
-            if (rc) return rc;
-            {
-              const size_t step_lds = ((2 * bytes + 15) & ~(size_t)15) + (size_t)16 * ((1 + m->packed_nw) * 256 + CS_STEP_QN) * sizeof(unsigned);
-              if (step_lds <= 80u * 1024u &&
-                  ((rc = lds_limit(step_lds, step_packed_kernel(h->n_vars, m->packed_nw, m->img->dense_slots == 3))) ||
-                   (rc = lds_limit((2 * bytes + 15) & ~(size_t)15, step_import_kernel(h->n_vars, m->packed_nw, m->img->dense_slots == 3)))))
-                return rc;
-            }
-          }
-        }
-      }
-    }
+  const char *force = getenv("CSGPU_K2_ADJ"); /* "global": measurement override */
+  const int want_global = force != NULL && force[0] == 'g';
+  if (want_global && 8 * lds_slice <= CS_CU_LDS) {
+    /* the lists in device memory (L2-resident) and LDS for the node slices only: 24 waves per CU instead of 16 on
+     * the 25x25 sudoku network -- and 1.23 ms instead of 0.75 ms for 2^18 nodes: the two-byte gathers through L2
+     * cost more than the extra waves hide.  Kept for measurements; never chosen automatically. */
+    m->lds_adj_global = 1;
+    waves = 8;
+    bytes = 8 * lds_slice;
   }
+  { const char *e = getenv("CSGPU_K2_CSZ"); m->k2_csz = e != NULL && atoi(e) >= 1 && atoi(e) <= CS_CHUNK ? atoi(e) : 0; } /* measurement override */
+  if (!waves) return CSGPU_OK;
+  int rc;
+  if ((rc = upload(m->img->adj_packed, (size_t)m->img->n_adj * (size_t)m->img->packed_width, (int **)&m->d_adj_packed)))
+    return rc;
+  if ((rc = plan_kernel(&m->plan.lds, ne_lds_kernel(m->img->packed_width, h->n_vars, m->lds_adj_global), bytes, waves)))
+    return rc;
+  if (m->plan.lds.per_cu < 1) m->plan.lds.per_cu = 1;
+  return CSGPU_OK;
+}
 
+/* forbidden-set kernel (3): additionally root intervals of at most 256 values, and only when the
+ * host domains really are the root state (the bit windows are anchored at the root bounds) */
+static int plan_forbidden_sets(csgpu_model *m) {
+  const cs_model *h = m->host;
+  if (m->img->sym_width == 0 || m->not_root) return CSGPU_OK;
+  int64_t width = 1;
+  for (int32_t v = 0; v < h->n_vars; v++) {
+    const int64_t w = (int64_t)h->dom[v].hi - (int64_t)h->dom[v].lo + 1;
+    if (w > width) width = w;
+  }
+  const int fw = width <= 64 ? 1 : (width <= 128 ? 2 : (width <= 256 ? 4 : 0));
+  if (!fw) return CSGPU_OK;
+  const size_t off_bytes = (((size_t)h->n_vars * 2 * sizeof(int)) + 15) & ~(size_t)15;
+  const size_t base_bytes = (((size_t)h->n_vars * sizeof(int)) + 15) & ~(size_t)15;
+  const size_t adj_bytes = (((size_t)m->img->sym_n_adj * (size_t)m->img->sym_width) + 15) & ~(size_t)15;
+  const size_t sl = ((size_t)h->n_vars * sizeof(cs_val) + (size_t)h->n_vars * fw * 8 +
+                     (2 * (size_t)m->tab.n_words + 2) * sizeof(unsigned) + 15) & ~(size_t)15;
+  int waves = 16;
+  for (; waves >= 1; waves--) /* as many waves as fit next to the tables */
+    if (off_bytes + base_bytes + adj_bytes + (size_t)waves * sl <= CS_CU_LDS) break;
+  if (waves < 1) return CSGPU_OK;
+  m->fb_words = fw;
+  int *lo = (int *)malloc((size_t)(h->n_vars ? h->n_vars : 1) * sizeof(int));
+  for (int32_t v = 0; v < h->n_vars; v++) lo[v] = h->dom[v].lo;
+  int rc = upload(lo, (size_t)h->n_vars * sizeof(int), &m->d_root_lo);
+  free(lo);
+  if (rc) return rc;
+  if ((rc = upload(m->img->sym_off, ((size_t)h->n_vars + 1) * sizeof(int), &m->d_sym_off))) return rc;
+  if ((rc = upload(m->img->sym_packed, (size_t)m->img->sym_n_adj * (size_t)m->img->sym_width, (int **)&m->d_sym_packed)))
+    return rc;
+  if ((rc = plan_kernel(&m->plan.bitset, ne_bitset_kernel(m->img->sym_width, fw, h->n_vars),
+                        off_bytes + base_bytes + adj_bytes + (size_t)waves * sl, waves)))
+    return rc;
+  if (m->plan.bitset.per_cu < 1) m->plan.bitset.per_cu = 1;
+  return CSGPU_OK;
+}
+
+/* the dense pair table in LDS: the register-resident forbidden-set kernel (4), the interval-only kernel (7) with its
+ * tracing variant, the server and cs_step_shave; kernel 7's ticket counters */
+static int plan_dense_table(csgpu_model *m) {
+  const cs_model *h = m->host;
+  if (!m->fb_words || m->img->dense_width == 0) return CSGPU_OK;
+  const int n = h->n_vars, width = m->img->dense_width, slots = m->img->dense_slots;
+  /* the dense table must fit a CU's LDS; the workgroup size that keeps the most waves resident (32 per CU at most),
+   * smaller workgroups on ties */
+  const size_t bytes = (size_t)n * slots * m->img->dense_cols * width;
+  int best = 0, waves = 0;
+  for (int w = 4; w <= 16; w <<= 1)
+    if (resident_per_cu(bytes, w) * w > best) { best = resident_per_cu(bytes, w) * w; waves = w; }
+  if (!waves) return CSGPU_OK;
+  m->dense_bytes = bytes;
+  int rc;
+  if ((rc = upload(m->img->dense_tab, bytes, (int **)&m->d_dense_tab))) return rc;
+  for (int variant = 0; variant < 4; variant++)
+    if ((rc = plan_kernel(&m->plan.regs[variant], ne_regs_kernel(width, m->fb_words, n, variant & 1, variant >> 1), bytes, waves)))
+      return rc;
+  const int chunks = (n + CS_WAVE - 1) / CS_WAVE;
+  m->plan.full = n == (chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4)) * CS_WAVE;
+  if ((rc = plan_kernel(&m->plan.shave, ne_shave_kernel(width, n, slots, m->plan.full), bytes, waves))) return rc;
+  const size_t table = (bytes + 15) & ~(size_t)15;
+  /* cs_step_shave: the table, then eight mask words per wave */
+  if (table + (size_t)waves * 32 <= CS_CU_LDS &&
+      (rc = plan_kernel(&m->plan.step_shave, step_shave_kernel(width, n, slots, m->plan.full), table + (size_t)waves * 32, waves)))
+    return rc;
+  /* the single-node kernels keep the trail in LDS after the table; the server sets its attribute when it first starts */
+  if (table + CS_SHAVE_TRACE_LDS * 16 <= CS_CU_LDS) {
+    if ((rc = plan_kernel(&m->plan.shave_trace, ne_shave_trace_kernel(width, n, slots), table + CS_SHAVE_TRACE_LDS * 16, waves)))
+      return rc;
+    m->plan.server = m->plan.shave_trace;
+    m->plan.server.fn = shave_server_kernel(width, n, slots);
+  }
+  HIP_TRY(hipMalloc((void **)&m->d_tickets, (size_t)CS_TICKET_SLOTS * CS_TICKET_SLOT_WORDS * sizeof(unsigned)));
+  HIP_TRY(hipMemset(m->d_tickets, 0, (size_t)CS_TICKET_SLOTS * CS_TICKET_SLOT_WORDS * sizeof(unsigned)));
+  m->ticket_slots = CS_TICKET_SLOTS;
+  m->shave_static = getenv("CSGPU_SHAVE_STATIC") != NULL; /* measurement switch: static shares instead of tickets */
+  return CSGPU_OK;
+}
+
+/* several nodes per wave: kernel 5 and its 16-bit table relative to the pushing variable, cs_step_packed and
+ * cs_step_import */
+static int plan_packed(csgpu_model *m) {
+  const cs_model *h = m->host;
+  if (m->plan.shave.fn == NULL) return CSGPU_OK;
+  const int n = h->n_vars, s3 = m->img->dense_slots == 3;
+  m->packed_nw = 1; /* one set word per variable when every root domain has at most 32 values */
+  for (int32_t v = 0; v < n; v++)
+    if ((int64_t)h->dom[v].hi - (int64_t)h->dom[v].lo + 1 > 32) m->packed_nw = 2;
+  m->packed_bias = 0;
+  for (int32_t v = 0; v < n; v++)
+    if (h->dom[v].lo - m->img->dense_dmin > m->packed_bias) m->packed_bias = h->dom[v].lo - m->img->dense_dmin;
+  m->plan.packed_nodes = packed_nodes_per_wave(m->fb_words, n, m->img->dense_width);
+  if (!m->plan.packed_nodes) return CSGPU_OK;
+  const size_t bytes = m->dense_bytes;
+  int rc;
+  if ((rc = plan_kernel(&m->plan.packed, ne_packed_kernel(n, m->packed_nw, s3), 2 * bytes, m->plan.regs[0].waves))) return rc;
+  m->plan.packed.per_cu = m->plan.regs[0].per_cu; /* its grid is kernel 4's */
+  /* entry e of row u becomes e - (root_lo[u] - dmin) + bias (cs_kernels.hip.h, kernel 5) */
+  const size_t per_row = (size_t)m->img->dense_slots * m->img->dense_cols, total = (size_t)n * per_row;
+  uint16_t *rel = (uint16_t *)malloc(total * sizeof(uint16_t));
+  const uint8_t *src = (const uint8_t *)m->img->dense_tab;
+  for (size_t i = 0; i < total; i++) {
+    const int32_t u = (int32_t)(i / per_row);
+    rel[i] = src[i] == 0xffu ? (uint16_t)0xffffu : (uint16_t)((int)src[i] - (h->dom[u].lo - m->img->dense_dmin) + m->packed_bias);
+  }
+  rc = upload(rel, total * sizeof(uint16_t), (int **)&m->d_packed_tab);
+  free(rel);
+  if (rc) return rc;
+  /* the step kernels: two workgroups of sixteen waves per CU */
+  if (step_packed_lds(m, 16) <= 80u * 1024u &&
+      ((rc = plan_kernel(&m->plan.step_packed, step_packed_kernel(n, m->packed_nw, s3), step_packed_lds(m, 16), 16)) ||
+       (rc = plan_kernel(&m->plan.step_import, step_import_kernel(n, m->packed_nw, s3), (2 * bytes + 15) & ~(size_t)15, 4))))
+    return rc;
+  /* one word takes about 88 atomics per microsecond (MI355X_MICROARCH.md): with 32 parents per ticket a queens-16 frontier
+   * of three million parents drew 78 tickets per microsecond and the whole launch waited for them (61 ms per search; 51 ms
+   * with 64 and with 128 per ticket, 181 ms with 8) */
+  m->step_chunk_max = 128;
+  { const char *e = getenv("CSGPU_STEP_CHUNK_MAX"); if (e != NULL && atoi(e) > 0) m->step_chunk_max = atoi(e); } /* tuning */
+  return CSGPU_OK;
+}
+
+/* the device and the mapped staging area of the single-node calls */
+static int stage_single_node(csgpu_model *m) {
   int dev = 0;
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipGetDeviceProperties(&prop, dev));
   m->n_cus = prop.multiProcessorCount;
+  const size_t nbytes = (size_t)(m->host->n_vars ? m->host->n_vars : 1) * sizeof(cs_val);
+  const size_t part = (nbytes + 63) & ~(size_t)63;
+  unsigned char *d = NULL;
+  HIP_TRY(hipHostMalloc((void **)&m->h_one, 2 * part + 128, hipHostMallocMapped));
+  HIP_TRY(hipHostGetDevicePointer((void **)&d, m->h_one, 0));
+  m->d_one_in = (cs_val *)d;
+  m->d_one_node = (cs_node_in *)(d + part);
+  m->d_one_res = (cs_node_out *)(d + part + 64);
+  m->d_one_out = (cs_val *)(d + part + 128);
+  return CSGPU_OK;
+}
 
-  const size_t nbytes = (size_t)(h->n_vars ? h->n_vars : 1) * sizeof(cs_val);
-  {
-    const size_t part = (nbytes + 63) & ~(size_t)63;
-    unsigned char *dev = NULL;
-    HIP_TRY(hipHostMalloc((void **)&m->h_one, 2 * part + 128, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void **)&dev, m->h_one, 0));
-    m->d_one_in = (cs_val *)dev;
-    m->d_one_node = (cs_node_in *)(dev + part);
-    m->d_one_res = (cs_node_out *)(dev + part + 64);
-    m->d_one_out = (cs_val *)(dev + part + 128);
-  }
+extern "C" int csgpu_model_finalize(csgpu_model *m) {
+  if (m == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  free_device(m);
+  int rc;
+  if ((rc = csgpu_model_build_tables(m)) || (rc = drop_entailed_clauses(m)) || (rc = plan_general(m)) ||
+      (rc = plan_lds_resident(m)) || (rc = plan_forbidden_sets(m)) || (rc = plan_dense_table(m)) || (rc = plan_packed(m)) ||
+      (rc = stage_single_node(m)))
+    return rc;
+  /* the search engine's step kernel: several nodes per wave, else cs_step_shave for intervals of at most 256 values */
+  m->plan.step_kind = m->plan.step_packed.fn != NULL ? 1
+                      : (m->plan.step_shave.fn != NULL && m->host->n_vars <= 256 && m->plan.max_width <= 256 ? 2 : 0);
   m->finalized = 1;
   return CSGPU_OK;
 }
 
+/* may the finalized model run kernel `which` (1-7)?  The one statement of the rules: what finalize planned */
+static int kernel_qualifies(const csgpu_model *m, int which) {
+  if (!m->finalized) return 0;
+  switch (which) {
+  case 1: return 1;
+  case 2: return m->plan.lds.fn != NULL;
+  case 3: return m->plan.bitset.fn != NULL;
+  case 4: return m->plan.regs[0].fn != NULL;
+  case 5: return m->plan.packed.fn != NULL;
+  case 6: return m->plan.rounds.fn != NULL;
+  case 7: return m->plan.shave.fn != NULL;
+  default: return 0;
+  }
+}
+
 extern "C" int csgpu_model_set_kernel(csgpu_model *m, int which) {
+  static const char *const kernel_name[8] = {
+    NULL, NULL, "the LDS-resident kernel", "the forbidden-set kernel", "the register-resident forbidden-set kernel",
+    "the several-nodes-per-wave kernel (at most 32 variables, 64 values)", "the clause-resident kernel (at most 512 clauses)",
+    "the interval-only shaving kernel (dense pair table in LDS)" };
   if (m == NULL || which < 0 || which > 7) return set_err(CSGPU_E_ARG, "bad argument");
   if (which >= 2) {
     if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-    if (which == 2 && !m->lds_waves) return set_err(CSGPU_E_LIMIT, "model does not qualify for the LDS-resident kernel");
-    if (which == 3 && !m->fb_words) return set_err(CSGPU_E_LIMIT, "model does not qualify for the forbidden-set kernel");
-    if (which == 4 && !m->dense_waves)
-      return set_err(CSGPU_E_LIMIT, "model does not qualify for the register-resident forbidden-set kernel");
-    if (which == 7 && !m->dense_waves)
-      return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (dense pair table in LDS)");
-    if (which == 6 && !clause_rounds_cpl(m))
-      return set_err(CSGPU_E_LIMIT, "model does not qualify for the clause-resident kernel (at most 512 clauses)");
-    if (which == 5 && !(m->dense_waves && packed_nodes_per_wave(m->fb_words, m->host->n_vars, m->img->dense_width)))
-      return set_err(CSGPU_E_LIMIT, "model does not qualify for the several-nodes-per-wave kernel (at most 32 variables, 64 values)");
+    if (!kernel_qualifies(m, which)) return set_err(CSGPU_E_LIMIT, "model does not qualify for %s", kernel_name[which]);
   }
   m->kernel_choice = which;
   return CSGPU_OK;
 }
 
-extern "C" int csgpu_model_qualifies(const csgpu_model *m, int which) {
-  if (m == NULL || !m->finalized) return 0;
-  switch (which) {
-  case 1: return 1;
-  case 2: return m->lds_waves != 0;
-  case 3: return m->fb_words != 0;
-  case 4: return m->dense_waves != 0;
-  case 7: return m->dense_waves != 0;
-  case 6: return clause_rounds_cpl(m) != 0;
-  case 5: return m->dense_waves != 0 && packed_nodes_per_wave(m->fb_words, m->host->n_vars, m->img->dense_width) != 0;
-  default: return 0;
-  }
-}
+extern "C" int csgpu_model_qualifies(const csgpu_model *m, int which) { return m != NULL && kernel_qualifies(m, which); }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
   if (m != NULL) const_cast<csgpu_model *>(m)->engines += delta;
@@ -1033,85 +1186,15 @@ extern "C" const int32_t *csgpu_internal_root_lo(const csgpu_model *m) {
 
 extern "C" int csgpu_model_forbidden_words(const csgpu_model *m) { return m && m->finalized ? m->fb_words : 0; }
 
-/* ---- cs_step.hip.h: one level of the search tree per launch ---- */
-static const void *step_packed_kernel(int n_vars, int nw, int s3) {
-#define CS_PICK_S(G, NW)                                                                           \
-  return s3 ? (const void *)cs_step_packed<G, NW, true> : (const void *)cs_step_packed<G, NW, false>;
-#define CS_PICK_NW(G)                                                                              \
-  if (nw == 1) { CS_PICK_S(G, 1) }                                                                 \
-  CS_PICK_S(G, 2)
-  if (n_vars <= 16) { CS_PICK_NW(4) }
-  CS_PICK_NW(2)
-#undef CS_PICK_NW
-#undef CS_PICK_S
-}
-
-static const void *step_import_kernel(int n_vars, int nw, int s3) {
-#define CS_PICK_S(G, NW)                                                                           \
-  return s3 ? (const void *)cs_step_import<G, NW, true> : (const void *)cs_step_import<G, NW, false>;
-#define CS_PICK_NW(G)                                                                              \
-  if (nw == 1) { CS_PICK_S(G, 1) }                                                                 \
-  CS_PICK_S(G, 2)
-  if (n_vars <= 16) { CS_PICK_NW(4) }
-  CS_PICK_NW(2)
-#undef CS_PICK_NW
-#undef CS_PICK_S
-}
-
-/* LDS of a step workgroup of `waves` waves: the 16-bit table, then per wave the parent slots and the child queue */
-static size_t step_packed_lds(const csgpu_model *m, int waves) {
-  return ((2 * m->dense_bytes + 15) & ~(size_t)15) + (size_t)waves * ((1 + m->packed_nw) * 256 + CS_STEP_QN) * sizeof(unsigned);
-}
-
-static const void *step_shave_kernel(int width, int n_vars, int slots, int full) {
-  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
-#define CS_PICK_S(E, R)                                                                                   \
-  if (slots == 1) return full ? (const void *)cs_step_shave<E, R, 1, true> : (const void *)cs_step_shave<E, R, 1, false>; \
-  if (slots == 3) return full ? (const void *)cs_step_shave<E, R, 3, true> : (const void *)cs_step_shave<E, R, 3, false>; \
-  return full ? (const void *)cs_step_shave<E, R, 0, true> : (const void *)cs_step_shave<E, R, 0, false>;
-#define CS_PICK(E)                                                                                 \
-  switch (chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4)) {                                               \
-  case 1: CS_PICK_S(E, 1)                                                                          \
-  case 2: CS_PICK_S(E, 2)                                                                          \
-  default: CS_PICK_S(E, 4)                                                                         \
-  }
-  if (width == 1) { CS_PICK(unsigned char) }
-  CS_PICK(unsigned short)
-#undef CS_PICK
-#undef CS_PICK_S
-}
-
-static int model_max_width(const csgpu_model *m) {
-  int maxw = 2;
-  for (int32_t v = 0; v < m->host->n_vars; v++) {
-    const int64_t w = (int64_t)m->host->dom[v].hi - (int64_t)m->host->dom[v].lo + 1;
-    if (w > maxw) maxw = w > 0x7fffffff ? 0x7fffffff : (int)w;
-  }
-  return maxw;
-}
-
-/* LDS of a cs_step_shave workgroup: the dense table, then eight mask words per wave */
-static size_t step_shave_lds(const csgpu_model *m) {
-  return ((m->dense_bytes + 15) & ~(size_t)15) + (size_t)m->dense_waves * 8 * sizeof(unsigned);
-}
-
-extern "C" int csgpu_internal_step_kind(const csgpu_model *m) {
-  if (m == NULL || !m->finalized || m->img == NULL || !m->dense_waves) return 0;
-  if (m->d_packed_tab != NULL && packed_nodes_per_wave(m->fb_words, m->host->n_vars, m->img->dense_width) &&
-      step_packed_lds(m, 16) <= 80u * 1024u) /* two workgroups of sixteen waves per CU */
-    return 1;
-  if (m->host->n_vars <= 256 && model_max_width(m) <= 256 && step_shave_lds(m) <= 160u * 1024u) return 2;
-  return 0;
-}
+extern "C" int csgpu_internal_step_kind(const csgpu_model *m) { return m == NULL || !m->finalized ? 0 : m->plan.step_kind; }
 
 /* waves of a cs_step_shave launch with `stage_rows` staging rows: the resident grid, fewer when a wave's region would
  * not hold the children of four parents */
 static int64_t step_shave_waves(const csgpu_model *m, int64_t stage_rows) {
-  size_t wgs = (160u * 1024u) / step_shave_lds(m);
-  if (wgs > (size_t)(32 / m->dense_waves)) wgs = (size_t)(32 / m->dense_waves);
-  int64_t waves = (int64_t)m->n_cus * (int64_t)wgs * m->dense_waves;
-  const int64_t by_stage = stage_rows / (4 * (int64_t)model_max_width(m));
-  if (waves > by_stage) waves = by_stage / m->dense_waves * m->dense_waves;
+  const cs_planned *k = &m->plan.step_shave;
+  int64_t waves = (int64_t)m->n_cus * (int64_t)k->per_cu * k->waves;
+  const int64_t by_stage = stage_rows / (4 * (int64_t)m->plan.max_width);
+  if (waves > by_stage) waves = by_stage / k->waves * k->waves;
   return waves;
 }
 
@@ -1119,7 +1202,7 @@ extern "C" int64_t csgpu_internal_step_parents_limit(const csgpu_model *m, int64
   const int kind = csgpu_internal_step_kind(m);
   if (kind == 1) return 0x3fffffff;
   if (kind != 2) return 0;
-  const int maxw = model_max_width(m);
+  const int maxw = m->plan.max_width;
   const int64_t waves = step_shave_waves(m, stage_rows);
   if (waves < 1) return 0;
   return (stage_rows - waves * 2 * maxw) / maxw; /* every child of every parent may survive, and a wave stops two parents short of its region's end */
@@ -1127,19 +1210,20 @@ extern "C" int64_t csgpu_internal_step_parents_limit(const csgpu_model *m, int64
 
 extern "C" int64_t csgpu_internal_step_stage_rows(const csgpu_model *m) {
   if (csgpu_internal_step_kind(m) != 2) return 0;
-  return (int64_t)m->n_cus * 32 * 4 * model_max_width(m);
+  return (int64_t)m->n_cus * 32 * 4 * m->plan.max_width;
 }
 
 extern "C" int64_t csgpu_internal_step_waves(const csgpu_model *m) { return m == NULL ? 0 : (int64_t)m->n_cus * 32; }
 
 static int launch_step_shave(const csgpu_model *m, const csgpu_step_launch *L, void *stream) {
-  const int n = m->host->n_vars, maxw = model_max_width(m);
+  const cs_planned *k = &m->plan.step_shave;
+  const int n = m->host->n_vars, maxw = m->plan.max_width;
   int64_t waves = step_shave_waves(m, L->stage_rows);
-  if (waves < m->dense_waves || (int64_t)L->parents > csgpu_internal_step_parents_limit(m, L->stage_rows))
+  if (waves < k->waves || (int64_t)L->parents > csgpu_internal_step_parents_limit(m, L->stage_rows))
     return set_err(CSGPU_E_LIMIT, "step kernel: staging buffer too small for the frontier");
-  const int64_t by_parents = ((int64_t)L->parents + m->dense_waves - 1) / m->dense_waves * m->dense_waves;
+  const int64_t by_parents = ((int64_t)L->parents + k->waves - 1) / k->waves * k->waves;
   if (waves > by_parents) waves = by_parents;
-  const int64_t grid = waves / m->dense_waves;
+  const int64_t grid = waves / k->waves;
   const int64_t K = L->stage_rows / waves;
   cs_step_io io;
   io.pool = (const uint2 *)L->pool;
@@ -1161,10 +1245,7 @@ static int launch_step_shave(const csgpu_model *m, const csgpu_step_launch *L, v
   const int *root_lo_d = m->d_root_lo, *sym_off = m->d_sym_off;
   size_t tab_bytes = m->dense_bytes;
   void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &sym_off, &tab_bytes, &io };
-  const int chunks_v = (n + CS_WAVE - 1) / CS_WAVE;
-  const int lanes = (chunks_v <= 1 ? 1 : (chunks_v <= 2 ? 2 : 4)) * CS_WAVE;
-  HIP_TRY(hipLaunchKernel(step_shave_kernel(m->img->dense_width, n, slots, n == lanes), dim3((unsigned)grid),
-                          dim3((unsigned)(m->dense_waves * CS_WAVE)), args, step_shave_lds(m), (hipStream_t)stream));
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)grid), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   hipLaunchKernelGGL(cs_collect, dim3((unsigned)waves), dim3(256), 0, (hipStream_t)stream, (const unsigned *)L->fill, (int)waves,
                      (const uint2 *)L->stage, io.K, n, (uint2 *)L->pool, (long long)L->first_row, (int)L->parents,
                      0 /* every parent is drawn */, (const unsigned *)L->ticket, (const unsigned long long *)L->wstat,
@@ -1178,12 +1259,7 @@ extern "C" int csgpu_internal_step(const csgpu_model *m, const csgpu_step_launch
   if (kind == 0 || L == NULL || L->parents < 1) return set_err(CSGPU_E_ARG, "bad argument");
   if (kind == 2) return launch_step_shave(m, L, stream);
   const int n = m->host->n_vars;
-  const int G = n <= 16 ? 4 : 2;
-  int maxw = 2;
-  for (int32_t v = 0; v < n; v++) {
-    const int64_t w = (int64_t)m->host->dom[v].hi - (int64_t)m->host->dom[v].lo + 1;
-    if (w > maxw) maxw = (int)w;
-  }
+  const int G = m->plan.packed_nodes, maxw = m->plan.max_width;
   if (G * maxw > CS_STEP_QN) return set_err(CSGPU_E_LIMIT, "step kernel: interval too wide for the child queue");
   /* waves: the machine's, fewer when the staging buffer would leave a wave less than two rounds of worst-case children;
    * and no more than the parents need */
@@ -1198,17 +1274,9 @@ extern "C" int csgpu_internal_step(const csgpu_model *m, const csgpu_step_launch
   const int64_t grid = waves / wg_waves;
   waves = grid * wg_waves;
   const int64_t K = L->stage_rows / waves;
-  /* parents per ticket: about eight tickets per wave, at most 32 parents, and a chunk's worst case fits half a region */
+  /* parents per ticket: about eight tickets per wave, at most step_chunk_max, and a chunk's worst case fits half a region */
   int64_t chunk = (int64_t)L->parents / (waves * 8);
-  /* one word takes about 88 atomics per microsecond (MI355X_MICROARCH.md): with 32 parents per ticket a queens-16 frontier
-   * of three million parents drew 78 tickets per microsecond and the whole launch waited for them (61 ms per search; 51 ms
-   * with 64 and with 128 per ticket, 181 ms with 8) */
-  int64_t chunk_max = 128;
-  {
-    const char *e = getenv("CSGPU_STEP_CHUNK_MAX"); /* tuning */
-    if (e != NULL && atoi(e) > 0) chunk_max = atoi(e);
-  }
-  if (chunk > chunk_max) chunk = chunk_max;
+  if (chunk > m->step_chunk_max) chunk = m->step_chunk_max;
   if (chunk * maxw > K / 2) chunk = K / (2 * maxw);
   chunk = chunk / G * G;
   if (chunk < G) chunk = G;
@@ -1232,8 +1300,8 @@ extern "C" int csgpu_internal_step(const csgpu_model *m, const csgpu_step_launch
   const int *root_lo_d = m->d_root_lo, *sym_off = m->d_sym_off;
   size_t tab_bytes = 2 * m->dense_bytes;
   void *args[] = { &nn, &tab_d, &slots, &root_lo_d, &sym_off, &bias, &tab_bytes, &io };
-  HIP_TRY(hipLaunchKernel(step_packed_kernel(n, m->packed_nw, slots == 3), dim3((unsigned)grid),
-                          dim3((unsigned)(wg_waves * CS_WAVE)), args, step_packed_lds(m, wg_waves), (hipStream_t)stream));
+  HIP_TRY(hipLaunchKernel(m->plan.step_packed.fn, dim3((unsigned)grid), dim3((unsigned)(wg_waves * CS_WAVE)), args,
+                          step_packed_lds(m, wg_waves), (hipStream_t)stream));
   hipLaunchKernelGGL(cs_collect, dim3((unsigned)waves), dim3(256), 0, (hipStream_t)stream, (const unsigned *)L->fill, (int)waves,
                      (const uint2 *)L->stage, io.K, n, (uint2 *)L->pool, (long long)L->first_row, (int)L->parents,
                      (int)chunk, (const unsigned *)L->ticket, (const unsigned long long *)L->wstat,
@@ -1244,27 +1312,29 @@ extern "C" int csgpu_internal_step(const csgpu_model *m, const csgpu_step_launch
 
 extern "C" int csgpu_internal_step_import(const csgpu_model *m, csgpu_val *d_rows, int64_t first_row, int64_t count,
                                           void *stream) {
-  if (csgpu_internal_step_kind(m) == 2) return CSGPU_OK; /* that path's pool holds interval rows */
-  if (csgpu_internal_step_kind(m) != 1 || d_rows == NULL || count < 0) return set_err(CSGPU_E_ARG, "bad argument");
+  const int kind = csgpu_internal_step_kind(m);
+  if (kind == 2) return CSGPU_OK; /* that path's pool holds interval rows */
+  if (kind != 1 || d_rows == NULL || count < 0) return set_err(CSGPU_E_ARG, "bad argument");
   if (count == 0) return CSGPU_OK;
-  const int n = m->host->n_vars, G = n <= 16 ? 4 : 2;
+  const cs_planned *k = &m->plan.step_import;
+  const int n = m->host->n_vars, G = m->plan.packed_nodes;
   int nn = n, slots = m->img->dense_slots, bias = m->packed_bias;
   const void *tab_d = m->d_packed_tab;
   const int *root_lo_d = m->d_root_lo;
   size_t tab_bytes = 2 * m->dense_bytes;
   long long fr = first_row, cnt = count;
-  int64_t grid = (count + (int64_t)G * 4 - 1) / ((int64_t)G * 4); /* four waves per workgroup, G rows per wave and step */
+  int64_t grid = (count + (int64_t)G * k->waves - 1) / ((int64_t)G * k->waves); /* G rows per wave and step */
   if (grid > (int64_t)m->n_cus * 8) grid = (int64_t)m->n_cus * 8;
   void *args[] = { &nn, &tab_d, &slots, &root_lo_d, &bias, &tab_bytes, &d_rows, &fr, &cnt };
-  HIP_TRY(hipLaunchKernel(step_import_kernel(n, m->packed_nw, slots == 3), dim3((unsigned)grid), dim3(256), args,
-                          (tab_bytes + 15) & ~(size_t)15, (hipStream_t)stream));
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)grid), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
 
 extern "C" int csgpu_internal_step_export(const csgpu_model *m, csgpu_val *d_rows, int64_t first_row, int64_t count,
                                           void *stream) {
-  if (csgpu_internal_step_kind(m) == 2) return CSGPU_OK;
-  if (csgpu_internal_step_kind(m) != 1 || d_rows == NULL || count < 0) return set_err(CSGPU_E_ARG, "bad argument");
+  const int kind = csgpu_internal_step_kind(m);
+  if (kind == 2) return CSGPU_OK;
+  if (kind != 1 || d_rows == NULL || count < 0) return set_err(CSGPU_E_ARG, "bad argument");
   if (count == 0) return CSGPU_OK;
   const int n = m->host->n_vars;
   const long long elements = (long long)count * n;
@@ -1282,41 +1352,32 @@ extern "C" int csgpu_internal_step_export(const csgpu_model *m, csgpu_val *d_row
 static int launch_regs(const csgpu_model *m, const csgpu_val *d_states_in, const uint64_t *d_forb_in,
                        const csgpu_node *d_nodes, csgpu_val *d_states_out, uint64_t *d_forb_out, csgpu_result *d_results,
                        int64_t batch, const uint64_t *d_batch, int sets_only, int flags, void *stream) {
-  int csz = CS_CHUNK;
-  {
-    const int64_t machine_waves = (int64_t)m->n_cus * 32;
-    while (csz > 1 && (batch + csz - 1) / csz < machine_waves) csz >>= 1;
-  }
-  const int64_t chunks = (batch + csz - 1) / csz;
-  size_t wgs = (160u * 1024u) / m->dense_bytes;
-  if (wgs > (size_t)(32 / m->dense_waves)) wgs = (size_t)(32 / m->dense_waves);
-  int64_t g = (int64_t)m->n_cus * (int64_t)wgs;
-  const int64_t need_wg = (chunks + m->dense_waves - 1) / m->dense_waves;
-  g *= 2; /* twice the resident grid: the dispatcher backfills CUs whose waves finish early (measured +1.5 %) */
-  if (g > need_wg) g = need_wg;
+  int csz = shrink_chunk(CS_CHUNK, batch, (int64_t)m->n_cus * 32);
   int n = m->host->n_vars, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
   const void *tab_d = m->d_dense_tab;
   const int *root_lo_d = m->d_root_lo, *sym_off = m->d_sym_off;
   long long nb_d = (long long)batch;
   void *args_d[] = { &n, &tab_d, &slots, &dmin_d, &root_lo_d, &sym_off, &d_states_in, &d_forb_in, &d_nodes,
                      &d_states_out, &d_forb_out, &d_results, &nb_d, &d_batch, &csz, &flags };
-  const int per_wave = sets_only || m->kernel_choice == 4 ? 0 : packed_nodes_per_wave(m->fb_words, n, m->img->dense_width);
-  if (per_wave) { /* kernel 5: one wave per group of nodes, grid-stride */
-    const int64_t groups = (batch + per_wave - 1) / per_wave;
-    int64_t gp = (int64_t)m->n_cus * (int64_t)wgs * 2;
-    const int64_t need_gp = (groups + m->dense_waves - 1) / m->dense_waves;
+  if (!sets_only && m->kernel_choice != 4 && kernel_qualifies(m, 5)) { /* kernel 5: one wave per group of nodes, grid-stride */
+    const cs_planned *k = &m->plan.packed;
+    const int64_t groups = (batch + m->plan.packed_nodes - 1) / m->plan.packed_nodes;
+    int64_t gp = (int64_t)m->n_cus * (int64_t)k->per_cu * 2;
+    const int64_t need_gp = (groups + k->waves - 1) / k->waves;
     if (gp > need_gp) gp = need_gp;
     csz = m->packed_bias; /* this kernel's arguments in those positions */
     tab_d = m->d_packed_tab;
-    HIP_TRY(hipLaunchKernel(ne_packed_kernel(n, m->packed_nw, slots == 3), dim3((unsigned)gp),
-                            dim3((unsigned)(m->dense_waves * CS_WAVE)), args_d, 2 * m->dense_bytes, (hipStream_t)stream));
+    HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)gp), dim3((unsigned)(k->waves * CS_WAVE)), args_d, k->lds, (hipStream_t)stream));
     return CSGPU_OK;
   }
-  const int chunks_v = (n + CS_WAVE - 1) / CS_WAVE;
-  const int lanes = (chunks_v <= 1 ? 1 : (chunks_v <= 2 ? 2 : 4)) * CS_WAVE;
-  const int fast = n == lanes && d_forb_in != NULL && d_forb_out != NULL && flags == 0;
-  HIP_TRY(hipLaunchKernel(ne_regs_kernel(m->img->dense_width, m->fb_words, n, fast, sets_only), dim3((unsigned)g),
-                          dim3((unsigned)(m->dense_waves * CS_WAVE)), args_d, m->dense_bytes, (hipStream_t)stream));
+  const int fast = m->plan.full && d_forb_in != NULL && d_forb_out != NULL && flags == 0;
+  const cs_planned *k = &m->plan.regs[fast | sets_only << 1];
+  const int64_t chunks = (batch + csz - 1) / csz;
+  int64_t g = (int64_t)m->n_cus * (int64_t)k->per_cu;
+  const int64_t need_wg = (chunks + k->waves - 1) / k->waves;
+  g *= 2; /* twice the resident grid: the dispatcher backfills CUs whose waves finish early (measured +1.5 %) */
+  if (g > need_wg) g = need_wg;
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)g), dim3((unsigned)(k->waves * CS_WAVE)), args_d, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
 
@@ -1347,30 +1408,25 @@ static unsigned *ticket_slot(csgpu_model *m, void *stream) {
 static int launch_shave(const csgpu_model *m, const csgpu_val *d_states_in, const csgpu_node *d_nodes,
                         csgpu_val *d_states_out, csgpu_result *d_results, int64_t batch, const uint64_t *d_batch,
                         void *stream) {
-  /* four or two nodes per chunk; fewer while that would leave a wave with less than four chunks */
-  int csz = m->host->n_vars <= CS_WAVE ? 2 * CS_SHAVE_CHUNK : CS_SHAVE_CHUNK; /* four per ticket when a node is one register per lane */
-  const int64_t machine_waves = (int64_t)m->n_cus * 32;
-  while (csz > 1 && (batch + csz - 1) / csz < 4 * machine_waves) csz >>= 1; /* every wave gets several chunks */
+  const cs_planned *k = &m->plan.shave;
+  /* four or two nodes per chunk (four per ticket when a node is one register per lane); fewer while that would leave a
+   * wave with less than four chunks */
+  int csz = shrink_chunk(m->host->n_vars <= CS_WAVE ? 2 * CS_SHAVE_CHUNK : CS_SHAVE_CHUNK, batch, 4 * (int64_t)m->n_cus * 32);
   const int64_t chunks = (batch + csz - 1) / csz;
-  size_t wgs = (160u * 1024u) / m->dense_bytes;
-  if (wgs > (size_t)(32 / m->dense_waves)) wgs = (size_t)(32 / m->dense_waves);
-  int64_t g = (int64_t)m->n_cus * (int64_t)wgs; /* the resident grid: persistent waves, work drawn by ticket */
-  const int64_t need_wg = (chunks + m->dense_waves - 1) / m->dense_waves;
+  int64_t g = (int64_t)m->n_cus * (int64_t)k->per_cu; /* the resident grid: persistent waves, work drawn by ticket */
+  const int64_t need_wg = (chunks + k->waves - 1) / k->waves;
   if (g > need_wg) g = need_wg;
   int n = m->host->n_vars, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
   const void *tab_d = m->d_dense_tab;
   const int *root_lo_d = m->d_root_lo, *sym_off = m->d_sym_off;
   long long nb_d = (long long)batch;
-  unsigned *tickets = getenv("CSGPU_SHAVE_STATIC") != NULL ? NULL : ticket_slot((csgpu_model *)m, stream);
+  unsigned *tickets = m->shave_static ? NULL : ticket_slot((csgpu_model *)m, stream);
   int4 *no_trace = NULL;
   unsigned *no_trace_n = NULL;
   unsigned no_trace_cap = 0u;
   void *args[] = { &n, &tab_d, &slots, &dmin_d, &root_lo_d, &sym_off, &d_states_in, &d_nodes, &d_states_out, &d_results,
                    &nb_d, &d_batch, &csz, &tickets, &no_trace, &no_trace_n, &no_trace_cap };
-  const int chunks_v = (n + CS_WAVE - 1) / CS_WAVE;
-  const int lanes = (chunks_v <= 1 ? 1 : (chunks_v <= 2 ? 2 : 4)) * CS_WAVE;
-  HIP_TRY(hipLaunchKernel(ne_shave_kernel(m->img->dense_width, n, slots, n == lanes), dim3((unsigned)g),
-                          dim3((unsigned)(m->dense_waves * CS_WAVE)), args, m->dense_bytes, (hipStream_t)stream));
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)g), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
 
@@ -1396,25 +1452,19 @@ extern "C" int csgpu_internal_propagate_fb(const csgpu_model *m, const csgpu_val
                                            void *stream) {
   if (m == NULL || batch < 0) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (!m->fb_words) return set_err(CSGPU_E_LIMIT, "model does not qualify for the forbidden-set kernel");
+  if (!kernel_qualifies(m, 3)) return set_err(CSGPU_E_LIMIT, "model does not qualify for the forbidden-set kernel");
   if (batch == 0) return CSGPU_OK;
   if (d_states_in == NULL || d_nodes == NULL || d_states_out == NULL || d_results == NULL)
     return set_err(CSGPU_E_ARG, "null argument");
+  if (kernel_qualifies(m, 4) && m->kernel_choice != 3)
+    return launch_regs(m, d_states_in, d_forb_in, d_nodes, d_states_out, d_forb_out, d_results, batch, d_batch, 0, 0, stream);
+  const cs_planned *k = &m->plan.bitset;
   /* nodes per wave at a time: CS_CHUNK for large batches (one coalesced record load per 16 nodes); a batch
    * smaller than the machine is spread thinner so that it does not run 16 nodes deep on a few waves */
-  int csz = CS_CHUNK;
-  {
-    const int64_t machine_waves = (int64_t)m->n_cus * 32;
-    while (csz > 1 && (batch + csz - 1) / csz < machine_waves) csz >>= 1;
-  }
+  int csz = shrink_chunk(CS_CHUNK, batch, (int64_t)m->n_cus * 32);
   const int64_t chunks = (batch + csz - 1) / csz;
-  if (m->dense_waves && m->kernel_choice != 3)
-    return launch_regs(m, d_states_in, d_forb_in, d_nodes, d_states_out, d_forb_out, d_results, batch, d_batch, 0, 0, stream);
-  size_t wg_per_cu = (160u * 1024u) / m->fb_bytes;
-  if (wg_per_cu > (size_t)(32 / m->fb_waves)) wg_per_cu = (size_t)(32 / m->fb_waves);
-  if (wg_per_cu < 1) wg_per_cu = 1;
-  int64_t grid = (int64_t)m->n_cus * (int64_t)wg_per_cu;
-  const int64_t need = (chunks + m->fb_waves - 1) / m->fb_waves;
+  int64_t grid = (int64_t)m->n_cus * (int64_t)k->per_cu;
+  const int64_t need = (chunks + k->waves - 1) / k->waves;
   if (grid > need) grid = need;
   cs_tables tab = m->tab;
   tab.adj_off = m->d_sym_off; /* the symmetric lists */
@@ -1424,8 +1474,7 @@ extern "C" int csgpu_internal_propagate_fb(const csgpu_model *m, const csgpu_val
   long long nb = (long long)batch;
   void *args[] = { &tab, &packed, &n_adj, &obits, &dmin, &root_lo, &d_states_in, &d_forb_in, &d_nodes,
                    &d_states_out, &d_forb_out, &d_results, &nb, &d_batch, &csz };
-  HIP_TRY(hipLaunchKernel(ne_bitset_kernel(m->img->sym_width, m->fb_words, m->host->n_vars), dim3((unsigned)grid),
-                          dim3((unsigned)(m->fb_waves * CS_WAVE)), args, m->fb_bytes, (hipStream_t)stream));
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)grid), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
 
@@ -1443,7 +1492,7 @@ __global__ void cs_fill_identity_nodes(cs_node_in *nodes, long long count) {
 static int sets_ready(const csgpu_model *m) {
   if (m == NULL) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (!m->dense_waves) return set_err(CSGPU_E_LIMIT, "model does not qualify for the register-resident forbidden-set kernel");
+  if (!kernel_qualifies(m, 4)) return set_err(CSGPU_E_LIMIT, "model does not qualify for the register-resident forbidden-set kernel");
   return CSGPU_OK;
 }
 
@@ -1509,19 +1558,19 @@ extern "C" int csgpu_model_get_kernel(const csgpu_model *m) {
   if (m->kernel_choice) return m->kernel_choice;
   /* pure != networks: the forbidden-set kernels, the sets rebuilt from the incoming state when the caller
    * carries none (queens-64, 2^18 nodes: 0.14 ms against 0.51 ms of kernel 2; queens-16: 0.06 against 0.51) */
-  if (m->fb_words) {
+  if (kernel_qualifies(m, 3)) {
     /* no sets passed: small models several nodes per wave with the sets rebuilt (5), otherwise the
      * interval-only shaving kernel (7), which needs no sets at all */
-    if (m->dense_waves) return packed_nodes_per_wave(m->fb_words, m->host->n_vars, m->img->dense_width) ? 5 : 7;
+    if (kernel_qualifies(m, 4)) return kernel_qualifies(m, 5) ? 5 : 7;
     /* more than 256 variables and no sets to inherit: rebuilding them costs one list scan per VALUED variable of
      * the incoming state (sudoku-25, 2^18 nodes: 6.2 ms), the event-driven kernels scan one list per narrowing
      * (kernel 2: 1.16 ms, kernel 1: 1.18 ms).  Callers that carry the sets use csgpu_propagate_batch_fb (kernel 3:
      * 0.91 ms on that batch). */
-    return m->lds_waves ? 2 : 1;
+    return kernel_qualifies(m, 2) ? 2 : 1;
   }
-  if (m->lds_waves) return 2;
-  const int cpl = clause_rounds_cpl(m);
-  return cpl >= 1 && cpl <= 4 ? 6 : 1; /* 8 clauses per lane: kernel 6 for small batches only, see below */
+  if (kernel_qualifies(m, 2)) return 2;
+  /* 8 clauses per lane: kernel 6 for small batches only, see csgpu_internal_propagate_objdev */
+  return kernel_qualifies(m, 6) && m->plan.rounds_cpl <= 4 ? 6 : 1;
 }
 
 /* ---- batched propagation ----------------------------------------------------------- */
@@ -1556,15 +1605,6 @@ extern "C" int csgpu_internal_propagate_objdev(const csgpu_model *m, const csgpu
   if (batch == 0) return CSGPU_OK; /* an empty batch needs no buffers */
   if (d_states_in == NULL || d_nodes == NULL || d_states_out == NULL || d_results == NULL)
     return set_err(CSGPU_E_ARG, "null argument");
-  const size_t lds = m->slice * CS_WAVES_PER_BLOCK + m->k1_tab_bytes;
-  /* resident workgroups per CU: LDS- and wave-slot-limited (32 waves per CU) */
-  size_t per_cu = (160u * 1024u) / lds;
-  if (per_cu > 32 / CS_WAVES_PER_BLOCK) per_cu = 32 / CS_WAVES_PER_BLOCK;
-  if (per_cu < 1) per_cu = 1;
-  int64_t blocks = (batch + CS_WAVES_PER_BLOCK - 1) / CS_WAVES_PER_BLOCK;
-  const int64_t resident = (int64_t)m->n_cus * (int64_t)per_cu;
-  /* enough workgroups to fill the chip several times over, the rest by grid stride */
-  if (blocks > resident * 4) blocks = resident * 4;
   hipStream_t s = (hipStream_t)stream;
   const cs_val *in = (const cs_val *)d_states_in;
   const cs_node_in *nodes = (const cs_node_in *)d_nodes;
@@ -1580,72 +1620,43 @@ extern "C" int csgpu_internal_propagate_objdev(const csgpu_model *m, const csgpu
       tab.obj_sense = sense;
     }
   }
-  const int auto_kernel = csgpu_model_get_kernel(m);
-  if (auto_kernel == 7 && tab.obj_var < 0)
+  const int kernel = csgpu_model_get_kernel(m);
+  if (kernel == 7 && tab.obj_var < 0)
     return launch_shave(m, d_states_in, d_nodes, d_states_out, d_results, batch, d_batch, stream);
-  if (auto_kernel >= 3 && auto_kernel <= 5 && tab.obj_var < 0)
+  if (kernel >= 3 && kernel <= 5 && tab.obj_var < 0)
     return csgpu_internal_propagate_fb(m, d_states_in, NULL, d_nodes, d_states_out, NULL, d_results, batch, d_batch, stream);
   const unsigned long long *bdev = (const unsigned long long *)d_batch;
-  if (csgpu_model_get_kernel(m) == 2 && tab.obj_var < 0 && d_batch == NULL) {
-    /* persistent workgroups: as many as stay resident (LDS- and wave-slot-limited) */
-    size_t wg_per_cu = (160u * 1024u) / m->lds_bytes;
-    if (wg_per_cu > (size_t)(32 / m->lds_waves)) wg_per_cu = (size_t)(32 / m->lds_waves);
-    if (wg_per_cu < 1) wg_per_cu = 1;
-    int64_t grid = (int64_t)m->n_cus * (int64_t)wg_per_cu;
+  long long nb = (long long)batch;
+  if (kernel == 2 && tab.obj_var < 0 && d_batch == NULL) {
+    const cs_planned *k = &m->plan.lds;
+    /* persistent workgroups: as many as stay resident */
+    int64_t grid = (int64_t)m->n_cus * (int64_t)k->per_cu;
     /* nodes a wave takes at a time: 16 when every wave gets several such chunks, fewer for smaller batches (a wave
      * with two chunks next to one with one is a launch twice as long as it needs to be) */
-    int csz = (int)(batch / (grid * m->lds_waves * 4));
+    int csz = (int)(batch / (grid * k->waves * 4));
     csz = csz < 1 ? 1 : (csz > CS_CHUNK ? CS_CHUNK : csz);
-    { const char *e = getenv("CSGPU_K2_CSZ"); if (e != NULL && atoi(e) >= 1 && atoi(e) <= CS_CHUNK) csz = atoi(e); } /* measurement override */
+    if (m->k2_csz) csz = m->k2_csz;
     const int64_t chunks = (batch + csz - 1) / csz;
-    const int64_t need = (chunks + m->lds_waves - 1) / m->lds_waves;
+    const int64_t need = (chunks + k->waves - 1) / k->waves;
     if (grid > need) grid = need;
-    const dim3 blk((unsigned)(m->lds_waves * CS_WAVE));
     int n_adj = m->img->n_adj, obits = m->img->packed_obits, dmin = m->img->packed_dmin;
-    long long nb = (long long)batch;
     const void *packed = m->d_adj_packed;
     void *args[] = { &tab, &packed, &n_adj, &obits, &dmin, &in, &nodes, &out, &res, &nb, &csz };
-    HIP_TRY(hipLaunchKernel(ne_lds_kernel(m->img->packed_width, m->host->n_vars, m->lds_adj_global), dim3((unsigned)grid),
-                            blk, args, m->lds_bytes, s));
+    HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)grid), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, s));
     return CSGPU_OK;
   }
   /* kernel 6 when asked for; automatically for models of at most 256 clauses (faster at every batch size
    * measured), and with 257-512 clauses for small batches only (lower latency, 14 us against 21 us per launch
    * on schedule-20, but less throughput: 215 us against 122 us for 65,536 nodes) -- the search engine's
    * device-counted batches are small by construction */
-  const int cpl6 = clause_rounds_cpl(m);
-  const int use6 = m->kernel_choice == 6 ||
-                   (m->kernel_choice == 0 && !m->lds_waves && !m->fb_words && cpl6 != 0 && (cpl6 <= 4 || d_batch != NULL || batch <= 8192));
-  if (use6) {
-    const size_t lds6 = ((((size_t)m->host->n_vars * sizeof(cs_val) + 16 + 15) & ~(size_t)15)) * CS_WAVES_PER_BLOCK;
-    int64_t blocks6 = (batch + CS_WAVES_PER_BLOCK - 1) / CS_WAVES_PER_BLOCK;
-    if (blocks6 > (int64_t)m->n_cus * 8 * 4) blocks6 = (int64_t)m->n_cus * 8 * 4;
-#define CS_LAUNCH6(CPL, TREE)                                                                       \
-  hipLaunchKernelGGL((cs_propagate_clause_rounds<CPL, TREE>), dim3((unsigned)blocks6), dim3(CS_BLOCK), lds6, s, tab, in, \
-                     nodes, out, res, (long long)batch, bdev)
-    switch (clause_rounds_cpl(m)) {
-    case 1: if (m->has_tree_adj) CS_LAUNCH6(1, true); else CS_LAUNCH6(1, false); break;
-    case 2: if (m->has_tree_adj) CS_LAUNCH6(2, true); else CS_LAUNCH6(2, false); break;
-    case 4: if (m->has_tree_adj) CS_LAUNCH6(4, true); else CS_LAUNCH6(4, false); break;
-    default: if (m->has_tree_adj) CS_LAUNCH6(8, true); else CS_LAUNCH6(8, false); break;
-    }
-#undef CS_LAUNCH6
-    HIP_TRY(hipGetLastError());
-    return CSGPU_OK;
-  }
-  if (m->has_tree_adj && m->k1_tab_bytes)
-    hipLaunchKernelGGL((cs_propagate_events<true, true>), dim3((unsigned)blocks), dim3(CS_BLOCK), lds, s, tab, in, nodes,
-                       out, res, (long long)batch, bdev);
-  else if (m->has_tree_adj)
-    hipLaunchKernelGGL((cs_propagate_events<true, false>), dim3((unsigned)blocks), dim3(CS_BLOCK), lds, s, tab, in, nodes,
-                       out, res, (long long)batch, bdev);
-  else if (m->k1_tab_bytes)
-    hipLaunchKernelGGL((cs_propagate_events<false, true>), dim3((unsigned)blocks), dim3(CS_BLOCK), lds, s, tab, in, nodes,
-                       out, res, (long long)batch, bdev);
-  else
-    hipLaunchKernelGGL((cs_propagate_events<false, false>), dim3((unsigned)blocks), dim3(CS_BLOCK), lds, s, tab, in, nodes,
-                       out, res, (long long)batch, bdev);
-  HIP_TRY(hipGetLastError());
+  const int use6 = kernel == 6 || (m->kernel_choice == 0 && kernel == 1 && !kernel_qualifies(m, 3) && kernel_qualifies(m, 6) &&
+                                   (d_batch != NULL || batch <= 8192));
+  const cs_planned *k = use6 ? &m->plan.rounds : &m->plan.events;
+  /* enough workgroups to fill the chip several times over, the rest by grid stride */
+  int64_t blocks = (batch + CS_WAVES_PER_BLOCK - 1) / CS_WAVES_PER_BLOCK;
+  if (blocks > (int64_t)m->n_cus * k->per_cu * 4) blocks = (int64_t)m->n_cus * k->per_cu * 4;
+  void *args[] = { &tab, &in, &nodes, &out, &res, &nb, &bdev };
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)blocks), dim3(CS_BLOCK), args, k->lds, s));
   return CSGPU_OK;
 }
 
@@ -1789,13 +1800,14 @@ extern "C" int csgpu_propagate_one_traced(const csgpu_model *cm, const csgpu_val
   tab.trace_log = (int4 *)dev;
   tab.trace_n = (unsigned *)((int32_t *)dev + (size_t)m->trace_cap * 4); /* where h_trace_n points */
   tab.trace_cap = (unsigned)cap;
-  const size_t lds = m->slice * CS_WAVES_PER_BLOCK;
-  int rc = lds_limit(lds, (const void *)cs_propagate_events<true, false, true>);
-  if (rc != CSGPU_OK) return rc;
-  hipLaunchKernelGGL((cs_propagate_events<true, false, true>), dim3(1), dim3(CS_BLOCK), lds, 0, tab,
-                     (const cs_val *)m->d_one_in, (const cs_node_in *)m->d_one_node, (cs_val *)m->d_one_out,
-                     (cs_node_out *)m->d_one_res, 1ll, (const unsigned long long *)NULL);
-  HIP_TRY(hipGetLastError());
+  const cs_val *in = m->d_one_in;
+  const cs_node_in *nd = m->d_one_node;
+  cs_val *out = m->d_one_out;
+  cs_node_out *res = m->d_one_res;
+  long long one = 1;
+  const unsigned long long *no_count = NULL;
+  void *args[] = { &tab, &in, &nd, &out, &res, &one, &no_count };
+  HIP_TRY(hipLaunchKernel(m->plan.traced.fn, dim3(1), dim3(CS_BLOCK), args, m->plan.traced.lds, (hipStream_t)NULL));
   { const int rcw = wait_null_stream(); if (rcw != CSGPU_OK) return rcw; }
   memcpy(result, m->h_one + part + 64, sizeof *result);
   if (result->status >= 0) memcpy(state_out, m->h_one + part + 128, nbytes);
@@ -1806,29 +1818,6 @@ extern "C" int csgpu_propagate_one_traced(const csgpu_model *cm, const csgpu_val
 }
 
 /* One node of a pure != network with its trail as causes: kernel 7's tracing variant, one wave. */
-/* ---- the resident single-node server (cs_shave.hip.h) ---- */
-static const void *shave_server_kernel(int width, int n_vars, int slots) {
-  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
-  const int r = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4);
-  const int sl = slots == 1 ? 1 : (slots == 3 ? 3 : 0);
-#define CS_PICK_S(E, RR)                                                                           \
-  switch (sl) {                                                                                    \
-  case 1: return (const void *)cs_shave_server<E, RR, 1>;                                           \
-  case 3: return (const void *)cs_shave_server<E, RR, 3>;                                           \
-  default: return (const void *)cs_shave_server<E, RR, 0>;                                          \
-  }
-#define CS_PICK(E)                                                                                 \
-  switch (r) {                                                                                     \
-  case 1: CS_PICK_S(E, 1)                                                                          \
-  case 2: CS_PICK_S(E, 2)                                                                          \
-  default: CS_PICK_S(E, 4)                                                                         \
-  }
-  if (width == 1) { CS_PICK(unsigned char) }
-  CS_PICK(unsigned short)
-#undef CS_PICK
-#undef CS_PICK_S
-}
-
 static double srv_now(void) {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -1840,8 +1829,7 @@ static int server_usable(csgpu_model *m) {
   if (m->srv_off) return 0;
   if (m->h_box != NULL) return 1;
   const char *e = getenv("CSGPU_SERVER");
-  const size_t lds = ((m->dense_bytes + 15) & ~(size_t)15) + CS_SHAVE_TRACE_LDS * 16;
-  if ((e != NULL && e[0] == '0') || !m->dense_waves || lds > 160u * 1024u) { m->srv_off = 1; return 0; }
+  if ((e != NULL && e[0] == '0') || m->plan.server.fn == NULL) { m->srv_off = 1; return 0; }
   const size_t nbytes = ((size_t)m->host->n_vars * sizeof(cs_val) + 63) & ~(size_t)63;
   m->box_state_off = (sizeof(cs_mailbox_head) + 63) & ~(size_t)63;
   m->box_out_off = m->box_state_off + nbytes;
@@ -1849,8 +1837,7 @@ static int server_usable(csgpu_model *m) {
   const size_t total = m->box_trace_off + (size_t)CS_SHAVE_TRACE_LDS * 16;
   if (hipHostMalloc((void **)&m->h_box, total, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipStreamCreateWithFlags(&m->srv_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipFuncSetAttribute(shave_server_kernel(m->img->dense_width, m->host->n_vars, m->img->dense_slots),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      hipFuncSetAttribute(m->plan.server.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->plan.server.lds) != hipSuccess) {
     (void)hipGetLastError();
     if (m->h_box != NULL) (void)hipHostFree(m->h_box);
     m->h_box = NULL;
@@ -1881,9 +1868,8 @@ static int server_start(csgpu_model *m) {
   unsigned long long idle = 200000ull; /* 2 ms of the 100 MHz clock: a search calls every few microseconds */
   { const char *e = getenv("CSGPU_SERVER_IDLE_US"); if (e != NULL && atoll(e) > 0) idle = (unsigned long long)atoll(e) * 100ull; }
   void *args[] = { &n, &tab_d, &slots, &dmin_d, &root_lo_d, &sym_off, &d_box, &d_in, &d_out, &d_trace, &cap, &idle };
-  const size_t lds = ((m->dense_bytes + 15) & ~(size_t)15) + CS_SHAVE_TRACE_LDS * 16;
-  HIP_TRY(hipLaunchKernel(shave_server_kernel(m->img->dense_width, n, slots), dim3(1), dim3((unsigned)(m->dense_waves * CS_WAVE)),
-                          args, lds, m->srv_stream));
+  const cs_planned *k = &m->plan.server;
+  HIP_TRY(hipLaunchKernel(k->fn, dim3(1), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, m->srv_stream));
   m->srv_launched = 1;
   m->srv_starts++;
   const double t0 = srv_now();
@@ -1990,7 +1976,7 @@ extern "C" int csgpu_propagate_one_causes(const csgpu_model *cm, const csgpu_val
   if (m == NULL || state == NULL || state_out == NULL || result == NULL || trace == NULL || cap < 1 || count == NULL)
     return set_err(CSGPU_E_ARG, "bad argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (!m->dense_waves) return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel");
+  if (!kernel_qualifies(m, 7)) return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel");
   if (server_usable(m)) return server_call(m, state, node, state_out, result, trace, cap, count);
   if (m->trace_cap < cap) {
     if (m->h_trace != NULL) (void)hipHostFree(m->h_trace);
@@ -2023,11 +2009,10 @@ extern "C" int csgpu_propagate_one_causes(const csgpu_model *cm, const csgpu_val
   csgpu_result *d_res = (csgpu_result *)m->d_one_res;
   void *args[] = { &n, &tab_d, &slots, &dmin_d, &root_lo_d, &sym_off, &d_in, &d_node, &d_out, &d_res,
                    &nb_d, &d_batch, &csz, &tickets, &d_trace, &d_trace_n, &ucap };
-  const size_t lds_trace = ((m->dense_bytes + 15) & ~(size_t)15) + CS_SHAVE_TRACE_LDS * 16;
-  if (lds_trace > 160u * 1024u) return set_err(CSGPU_E_LIMIT, "no room in LDS for the trail next to the pair table");
+  const cs_planned *k = &m->plan.shave_trace;
+  if (k->fn == NULL) return set_err(CSGPU_E_LIMIT, "no room in LDS for the trail next to the pair table");
   const double tl1 = srv_now();
-  HIP_TRY(hipLaunchKernel(ne_shave_trace_kernel(m->img->dense_width, n, slots), dim3(1), dim3((unsigned)(m->dense_waves * CS_WAVE)),
-                          args, lds_trace, (hipStream_t)NULL));
+  HIP_TRY(hipLaunchKernel(k->fn, dim3(1), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)NULL));
   const double tl2 = srv_now();
   { const int rcw = wait_null_stream(); if (rcw != CSGPU_OK) return rcw; }
   const double tl3 = srv_now();
@@ -2063,7 +2048,7 @@ static int chain_build(csgpu_model *m) {
   const cs_model *h = m->host;
   m->chain_state = -1;
   if (!m->finalized || h->n_clauses < 1 || h->n_clauses > 60000 || h->n_vars < 1 || h->list_off == NULL) return -1;
-  if ((size_t)h->n_vars * sizeof(cs_val) + (size_t)h->n_clauses * 2 + 64 > 160u * 1024u) return -1;
+  if ((size_t)h->n_vars * sizeof(cs_val) + (size_t)h->n_clauses * 2 + 64 > CS_CU_LDS) return -1;
   cs_chain_clause *cl = (cs_chain_clause *)malloc((size_t)h->n_clauses * sizeof *cl);
   if (cl == NULL) return -1;
   for (int32_t c = 0; c < h->n_clauses; c++) {
@@ -2086,7 +2071,7 @@ static int chain_build(csgpu_model *m) {
   if (rc != CSGPU_OK) return -1;
   if (hipMalloc((void **)&m->d_chain_frames, (size_t)CS_CHAIN_FRAMES * sizeof(cs_chain_frame)) != hipSuccess ||
       hipHostMalloc((void **)&m->h_chain_out, (4 + CS_CHAIN_BUMPS) * sizeof(int), hipHostMallocMapped) != hipSuccess ||
-      hipFuncSetAttribute((const void *)cs_ne_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+      hipFuncSetAttribute((const void *)cs_ne_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_CU_LDS) != hipSuccess) {
     (void)hipGetLastError();
     return -1;
   }
@@ -2129,7 +2114,7 @@ extern "C" int csgpu_propagate_one(const csgpu_model *m, const csgpu_val *state,
                                    csgpu_result *result) {
   if (m == NULL || state == NULL || state_out == NULL || result == NULL) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if ((m->kernel_choice == 0 || m->kernel_choice == 7) && m->dense_waves && server_usable(const_cast<csgpu_model *>(m)))
+  if ((m->kernel_choice == 0 || m->kernel_choice == 7) && kernel_qualifies(m, 7) && server_usable(const_cast<csgpu_model *>(m)))
     return server_call(const_cast<csgpu_model *>(m), state, node, state_out, result, NULL, 0, NULL);
   const size_t nbytes = (size_t)m->host->n_vars * sizeof(cs_val);
   const size_t part = (nbytes + 63) & ~(size_t)63;
