@@ -40,7 +40,43 @@ def declared_symbols(header: str = HEADER_PATH):
     return sorted(set(re.findall(r"\b(csgpu_\w+)\s*\(", text)))
 
 
+# kernel families of a model's plan, in the order of csgpu_internal_plan_symbol (cs_internal.h)
+PLAN_FAMILIES = ("events", "traced", "rounds", "lds", "bitset", "regs0", "regs1", "regs2", "regs3", "packed",
+                 "shave", "shave_trace", "server", "step_shave", "step_packed", "step_import")
+
 _lib = None
+_demangler = None
+
+
+def demangle(symbol: str) -> str:
+    """The template-id of a mangled kernel symbol, e.g. `cs_propagate_ne_lds<unsigned short, 4, 1, true>`: the
+    C++ runtime's demangler, return type and parameter list dropped."""
+    global _demangler
+    if _demangler is None:
+        cxx = C.CDLL("libstdc++.so.6")
+        cxx.__cxa_demangle.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        cxx.__cxa_demangle.restype = C.c_void_p
+        libc = C.CDLL(None)
+        libc.free.argtypes = [C.c_void_p]
+        _demangler = (cxx.__cxa_demangle, libc.free)
+    fn, free = _demangler
+    status = C.c_int()
+    p = fn(symbol.encode(), None, None, C.byref(status))
+    if status.value != 0 or not p:
+        raise ValueError(f"cannot demangle {symbol!r}")
+    try:
+        text = C.string_at(p).decode()
+    finally:
+        free(p)
+    if text.startswith("void "):
+        text = text[5:]
+    depth = 0
+    for i, ch in enumerate(text):  # cut at the parameter list: the first '(' outside the template arguments
+        depth += ch == "<"
+        depth -= ch == ">"
+        if ch == "(" and depth == 0:
+            return text[:i]
+    return text
 
 
 def load_library():
@@ -131,6 +167,8 @@ def load_library():
     L.csgpu_propagate_one_chain.argtypes = [vp, vp, Node, C.POINTER(i32), C.POINTER(i32), vp, i32, C.POINTER(i32)]
     L.csgpu_search_set_strategy.argtypes = [vp, C.c_int, C.c_int]
     L.csgpu_search_set_restart_on_improvement.argtypes = [vp, C.c_int]
+    L.csgpu_internal_plan_symbol.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
+    L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 
+#include <dlfcn.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -658,8 +659,7 @@ static const void *ne_bitset_kernel(int width, int fw, int n_vars) {
 /* register-resident forbidden-set kernel: entry width, set words, variables per lane; the FAST
  * instantiation (n_vars a multiple of 64 that fills the lanes, both set buffers) keeps D nodes in flight */
 static const void *ne_regs_kernel(int width, int fw, int n_vars, int fast, int sets_only) {
-  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
-  const int r = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4);
+  const int r = cs_dense_strides(n_vars);
 #define CS_PICK_D(E, F, RR)                                                                        \
   if (sets_only)                                                                                   \
     return fast ? (const void *)cs_propagate_ne_regs<E, F, RR, 2, true, true>                       \
@@ -688,8 +688,7 @@ static const void *ne_regs_kernel(int width, int fw, int n_vars, int fast, int s
 /* kernel 7 (cs_shave.hip.h): interval states only; entry width, variables per lane, slots per pair known at
  * compile time when 1 or 3, FULL when the variables fill the lanes */
 static const void *ne_shave_kernel(int width, int n_vars, int slots, int full) {
-  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
-  const int r = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4);
+  const int r = cs_dense_strides(n_vars);
   const int sl = slots == 1 ? 1 : (slots == 3 ? 3 : 0);
 #define CS_PICK_F(E, RR, SS)                                                                       \
   return full ? (const void *)cs_propagate_ne_shave<E, RR, SS, true>                                \
@@ -716,8 +715,7 @@ static const void *ne_shave_kernel(int width, int n_vars, int slots, int full) {
 /* its tracing variant for single nodes (guarded lanes; the slot count a constant when 1 or 3: with the run-time loop
  * the six LDS reads of a row operation are waited for one by one, which is the latency of a single wavefront) */
 static const void *ne_shave_trace_kernel(int width, int n_vars, int slots) {
-  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
-  const int r = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4);
+  const int r = cs_dense_strides(n_vars);
   const int sl = slots == 1 ? 1 : (slots == 3 ? 3 : 0);
 #define CS_PICK_S(E, RR)                                                                           \
   switch (sl) {                                                                                    \
@@ -760,13 +758,12 @@ CS_PACKED_PICKER(step_import_kernel, cs_step_import)
 
 /* ---- cs_step.hip.h: one level of the search tree per launch ---- */
 static const void *step_shave_kernel(int width, int n_vars, int slots, int full) {
-  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
 #define CS_PICK_S(E, R)                                                                                   \
   if (slots == 1) return full ? (const void *)cs_step_shave<E, R, 1, true> : (const void *)cs_step_shave<E, R, 1, false>; \
   if (slots == 3) return full ? (const void *)cs_step_shave<E, R, 3, true> : (const void *)cs_step_shave<E, R, 3, false>; \
   return full ? (const void *)cs_step_shave<E, R, 0, true> : (const void *)cs_step_shave<E, R, 0, false>;
 #define CS_PICK(E)                                                                                 \
-  switch (chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4)) {                                               \
+  switch (cs_dense_strides(n_vars)) {                                                              \
   case 1: CS_PICK_S(E, 1)                                                                          \
   case 2: CS_PICK_S(E, 2)                                                                          \
   default: CS_PICK_S(E, 4)                                                                         \
@@ -779,8 +776,7 @@ static const void *step_shave_kernel(int width, int n_vars, int slots, int full)
 
 /* ---- the resident single-node server (cs_shave.hip.h) ---- */
 static const void *shave_server_kernel(int width, int n_vars, int slots) {
-  const int chunks = (n_vars + CS_WAVE - 1) / CS_WAVE;
-  const int r = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4);
+  const int r = cs_dense_strides(n_vars);
   const int sl = slots == 1 ? 1 : (slots == 3 ? 3 : 0);
 #define CS_PICK_S(E, RR)                                                                           \
   switch (sl) {                                                                                    \
@@ -1047,8 +1043,7 @@ static int plan_dense_table(csgpu_model *m) {
   for (int variant = 0; variant < 4; variant++)
     if ((rc = plan_kernel(&m->plan.regs[variant], ne_regs_kernel(width, m->fb_words, n, variant & 1, variant >> 1), bytes, waves)))
       return rc;
-  const int chunks = (n + CS_WAVE - 1) / CS_WAVE;
-  m->plan.full = n == (chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4)) * CS_WAVE;
+  m->plan.full = n == cs_dense_strides(n) * CS_WAVE;
   if ((rc = plan_kernel(&m->plan.shave, ne_shave_kernel(width, n, slots, m->plan.full), bytes, waves))) return rc;
   const size_t table = (bytes + 15) & ~(size_t)15;
   /* cs_step_shave: the table, then eight mask words per wave */
@@ -1175,6 +1170,27 @@ extern "C" int csgpu_model_set_kernel(csgpu_model *m, int which) {
 }
 
 extern "C" int csgpu_model_qualifies(const csgpu_model *m, int which) { return m != NULL && kernel_qualifies(m, which); }
+
+/* the planned instantiation of `family` (the order of cs_internal.h) by its dynamic symbol: the mangled name of the
+ * very pointer the launchers use, "" when the family is not planned for this model */
+extern "C" int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char *buf, size_t len) {
+  if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  const cs_kernel_plan *p = &m->plan;
+  const cs_planned *fam[] = { &p->events, &p->traced, &p->rounds, &p->lds, &p->bitset, &p->regs[0], &p->regs[1],
+                              &p->regs[2], &p->regs[3], &p->packed, &p->shave, &p->shave_trace, &p->server,
+                              &p->step_shave, &p->step_packed, &p->step_import };
+  if (family < 0 || family >= (int)(sizeof fam / sizeof fam[0])) return set_err(CSGPU_E_ARG, "no plan family %d", family);
+  buf[0] = '\0';
+  const void *fn = fam[family]->fn;
+  if (fn == NULL) return CSGPU_OK;
+  Dl_info info;
+  if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
+    return set_err(CSGPU_E_STATE, "plan family %d: the kernel handle has no dynamic symbol", family);
+  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "plan family %d: symbol longer than the buffer", family);
+  strcpy(buf, info.dli_sname);
+  return CSGPU_OK;
+}
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
   if (m != NULL) const_cast<csgpu_model *>(m)->engines += delta;

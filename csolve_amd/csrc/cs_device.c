@@ -378,7 +378,8 @@ cs_dev_image *cs_dev_image_build(const cs_model *m, int with_lists, const unsign
     free(cnt);
     /* dense [u][slot][w] table of the same relation (register-resident kernel) */
     if (width != 0 && n <= 256) {
-      const int32_t cols = ((n + 63) / 64) * 64;
+      /* one column per lane of the kernels' register strides (129 to 192 variables take four of them) */
+      const int32_t cols = cs_dense_strides(n) * 64;
       uint8_t *mult = (uint8_t *)calloc((size_t)n * (size_t)n, 1);
       int slots = 0, ok = 1;
       for (int32_t c = 0; c < g->n_clauses && ok; c++) {

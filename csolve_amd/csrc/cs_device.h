@@ -58,6 +58,10 @@ enum { CS_CL_SKIP = 0, CS_CL_NE = 1, CS_CL_TREE = 2, CS_CL_EQ = 3, CS_CL_LT = 4,
 enum { CS_REL_NE = 0, CS_REL_EQ = 1, CS_REL_LT = 2, CS_REL_GT = 3 };
 #define CS_ADJ_VAR_MASK 0x0fffffff
 
+/* register strides of 64 variables per lane of the dense-table kernels (4, 7, their tracing variant, the server, the
+ * step kernel): 1, 2 or 4 for up to 64, 128, 256 variables.  Their table rows hold 64 of them columns. */
+static inline int cs_dense_strides(int32_t n_vars) { return n_vars <= 64 ? 1 : (n_vars <= 128 ? 2 : 4); }
+
 /* largest tree a device lane can revise (per-lane value scratch), and the deepest
  * pending-push stack it keeps */
 #define CS_MAX_TREE_NODES 256
@@ -93,7 +97,8 @@ typedef struct cs_dev_image {
   void *sym_packed;     /* [sym_n_adj] */
   /* the same symmetric relation as a dense table for models of at most 256 variables (register-resident
    * kernel): dense_tab[(u * dense_slots + k) * dense_cols + w] = (d + root_lo[w]) - dense_dmin of the k-th
-   * clause between u and w, or the all-ones sentinel; dense_cols = n_vars rounded up to 64.
+   * clause between u and w, or the all-ones sentinel; dense_cols = 64 R for the kernels' R = 1, 2, 4
+   * register strides of 64 variables (n_vars up to 64, 128, 256).
    * dense_width = bytes per entry (1 or 2), 0 = not available. */
   int32_t dense_width, dense_slots, dense_cols, dense_dmin;
   void *dense_tab;

@@ -44,6 +44,11 @@ int csgpu_internal_eval_list(const csgpu_model *m, const csgpu_val *d_states, co
  * is part of the set-up and not of the driver's first propagate_clauses.  No-op for models without a server. */
 int csgpu_internal_server_warm(csgpu_model *m);
 
+/* the instantiation finalize planned for one kernel family, as the mangled name of its kernel handle ("" when the
+ * family is not planned).  Families in this order (csolve_amd/_lib.py PLAN_FAMILIES): events, traced, rounds, lds,
+ * bitset, regs[0..3], packed, shave, shave_trace, server, step_shave, step_packed, step_import */
+int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char *buf, size_t len);
+
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */
 typedef struct csgpu_step_launch {
   const csgpu_val *pool;  /* parents (engine rows): rows first_row .. first_row + parents - 1, drawn from the top down */

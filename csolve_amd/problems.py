@@ -167,3 +167,39 @@ def linear(n: int = 12, seed: int = 1, objective: str = "ANY") -> str:
         lo = rng.below(7) - 3
         lines.append(f"{lo} <= {v[i]}; {v[i]} <= {lo + 20 + rng.below(20)};")
     return "\n".join(lines) + "\n"
+
+
+def sparse_ne(n: int, degree: int = 3, width: int = 16, seed: int = 1, per_pair: int = 1, offset_spread: int = 4,
+              lo_spread: int = 0, pinned: int = 0, objective: str = "ANY") -> str:
+    """A seeded sparse binary != network: n variables of `width` values each, variable i's lower bound drawn from
+    [0, lo_spread], about `degree` neighbours per variable and `per_pair` constraints `Vi != Vj + d` per related
+    pair.  Every d lies within `offset_spread` of lo_i - lo_j, so no constraint is entailed by the root domains
+    (|d - (lo_i - lo_j)| < width); the spreads set the table entry widths of the kernels (offsets and lower bounds
+    far apart need wide entries).  `pinned` variables get a seeded one-value domain and no constraint (a constraint on
+    a fixed variable would be folded into a unary clause, which takes the network off the != kernels); the n - pinned
+    free ones are spread evenly over the index range, the last variable among them, so that they reach every register
+    stride.  Pinning keeps exhaustive searches small at large n while the kernels still see all n variables."""
+    assert n >= 1 and width >= 1 and per_pair >= 1 and 0 <= pinned < n
+    assert per_pair <= 2 * min(offset_spread, width - 1) + 1, "not enough distinct offsets for per_pair"
+    rng = LCG(seed * 1000003 + n * 8191 + width * 131 + per_pair)
+    lo = [rng.below(lo_spread + 1) for _ in range(n)]
+    free = sorted({n - 1 - j * n // (n - pinned) for j in range(n - pinned)})
+    value = {v: lo[v] + rng.below(width) for v in sorted(set(range(n)) - set(free))}
+    lines = [f"# sparse != network, {n} variables x {width} values, degree {degree}, {per_pair} per pair, seed {seed}",
+             f"{objective};"]
+    pairs = set()
+    for k, i in enumerate(free):
+        for _ in range(degree if len(free) > 1 else 0):
+            j = free[(k + 1 + rng.below(len(free) - 1)) % len(free)]
+            pairs.add((min(i, j), max(i, j)))
+    reach = min(offset_spread, width - 1)
+    for i, j in sorted(pairs):
+        ds = set()
+        while len(ds) < per_pair:
+            ds.add(lo[i] - lo[j] + rng.below(2 * reach + 1) - reach)
+        for d in sorted(ds):
+            lines.append(f"V{i + 1} != V{j + 1} {'+' if d >= 0 else '-'} {abs(d)};")
+    for v in range(n):
+        a, b = (value[v], value[v]) if v in value else (lo[v], lo[v] + width - 1)
+        lines.append(f"{a} <= V{v + 1}; V{v + 1} <= {b};")
+    return "\n".join(lines) + "\n"

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Node, Result, SearchStats, Val, check, load_library
+from ._lib import PLAN_FAMILIES, Node, Result, SearchStats, Val, check, demangle, load_library
 
 STATUS_FAIL = -1
 
@@ -162,6 +162,16 @@ class Model:
 
     def qualifies(self, which: int) -> bool:
         return bool(load_library().csgpu_model_qualifies(self._h, which))
+
+    def plan(self) -> dict:
+        """The instantiation finalize planned for every kernel family (_lib.PLAN_FAMILIES): its template-id, read
+        back from the launched kernel handle's dynamic symbol, or None where the family is not planned."""
+        buf = C.create_string_buffer(1024)
+        out = {}
+        for i, fam in enumerate(PLAN_FAMILIES):
+            check(load_library().csgpu_internal_plan_symbol(self._h, i, buf, len(buf)))
+            out[fam] = demangle(buf.value.decode()) if buf.value else None
+        return out
 
     def kernel(self) -> int:
         return check(load_library().csgpu_model_get_kernel(self._h))
@@ -328,6 +338,13 @@ class Model:
         check(load_library().csgpu_propagate_values(self._h, state.ctypes.data, var, values.ctypes.data, len(values),
                                                     outs.ctypes.data, res.ctypes.data))
         return res, outs
+
+    def server_stats(self):
+        """-> (calls, starts): single-node calls answered by the resident server or kernel 7's tracing launch, and the
+        server's (re)starts, for this model (csgpu_debug_one_timing)"""
+        seconds, calls, starts = (C.c_double * 4)(), C.c_uint64(), C.c_uint64()
+        check(load_library().csgpu_debug_one_timing(self._h, seconds, C.byref(calls), C.byref(starts)))
+        return calls.value, starts.value
 
     def root_propagate_limit(self, limit: int):
         """propagate(root, limit): at most limit + 1 sweeps.  -> (status, rounds)"""

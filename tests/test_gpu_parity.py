@@ -375,7 +375,10 @@ def test_full_batches_against_the_compiled_reference(kind, size, count):
     from csolve_amd import problems
     from csolve_amd.solver import solve_root
     if not os.path.exists(bench.REF_BIN):
-        pytest.skip("oracle/_ref/csolve_ref not built (needs the reference tree)")
+        # a missing reference binary is a failure, not a silent pass; CSOLVE_ALLOW_NO_REF=1 where it cannot be built
+        if os.environ.get("CSOLVE_ALLOW_NO_REF") == "1":
+            pytest.skip("oracle/_ref/csolve_ref not built (needs the reference tree; CSOLVE_ALLOW_NO_REF=1)")
+        pytest.fail("oracle/_ref/csolve_ref is missing: build() makes it where the reference tree exists")
     text = _text(kind, size)
     model = solve_root(text)
     n, fw = model.n_vars, model.forbidden_words()

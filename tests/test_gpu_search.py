@@ -110,7 +110,6 @@ def test_search_counters_match_oracle_tree_on_all(which):
     plain CPU walk of the same tree that uses the oracle for every child (the engine counts the children
     that a parent's own forbidden set rules out without launching them; the walk propagates every one)."""
     from csolve_amd import problems
-    from oracle.cs_oracle import Model as OModel, Oracle
     # the last four take cs_step_shave (one wave per parent: 40 and 64 variables in one register per lane, 81 in two,
     # 256 in four); the first three cs_step_packed
     text = {"queens7": lambda: problems.queens(7, "ALL"), "offsets6x5": lambda: problems.offsets(6, 5, 2, "ALL"),
@@ -118,12 +117,22 @@ def test_search_counters_match_oracle_tree_on_all(which):
             "offsets64x8": lambda: problems.offsets(64, 8, 1, "ALL"), "sudoku9": lambda: problems.sudoku(3, 0.35, 1, "ALL"),
             "sudoku16": lambda: problems.sudoku(4, 0.6, 3, "ALL")}[which]()
     model, s, st = _solve(text)
+    calls, cuts, sols, props = oracle_all_tree(text, model.domains())
+    assert (st["nodes"], st["cuts"], st["solutions"]) == (calls, cuts, sols)
+    # the engine's propagations are those of the consistent children: on a != network the reference's PROPS
+    assert st["props"] == props
+
+
+def oracle_all_tree(text, root, max_calls=None):
+    """The ALL tree below the root domains `root`, walked on the host with the oracle for every child and the
+    engine's branching rule -> (nodes, cuts, solutions, props).  max_calls: give up (AssertionError) beyond it."""
+    from oracle.cs_oracle import Model as OModel, Oracle
     om = OModel.parse(text)
-    om.set_domains(model.domains())
+    om.set_domains(root)
     om.index()
     orc = Oracle(om)
     calls = cuts = sols = props = 0
-    stack = [model.domains()]
+    stack = [root]
     while stack:
         state = stack.pop()
         width = (state[:, 1] - state[:, 0]).astype(np.int64)
@@ -140,9 +149,8 @@ def test_search_counters_match_oracle_tree_on_all(which):
                 sols += 1
             else:
                 stack.append(out)
-    assert (st["nodes"], st["cuts"], st["solutions"]) == (calls, cuts, sols)
-    # the engine's propagations are those of the consistent children: on a != network the reference's PROPS
-    assert st["props"] == props
+        assert max_calls is None or calls <= max_calls, f"ALL tree beyond {max_calls} nodes"
+    return calls, cuts, sols, props
 
 
 @pytest.mark.parametrize("which", ["queens11", "offsets40x8", "sudoku9", "sudoku9_30"])

@@ -388,3 +388,35 @@ def test_a_specialised_model_drops_what_its_prefix_decides():
     bad[starts[0], 1] += 1
     with pytest.raises(CsolveError):
         m.specialize(bad, build_only=True)
+
+
+FIXPOINT_FAMILIES = ("cs_propagate_events", "cs_propagate_clause_rounds", "cs_propagate_ne_lds", "cs_propagate_ne_bitset",
+                     "cs_propagate_ne_regs", "cs_propagate_ne_packed", "cs_propagate_ne_shave", "cs_shave_server",
+                     "cs_step_shave", "cs_step_packed", "cs_step_import")
+
+
+def test_every_fixpoint_instantiation_is_catalogued_or_excluded():
+    """The fixpoint-family kernels the library ships (their host handles are dynamic symbols) are exactly the
+    instantiations the GPU tests launch for the shape catalogue's entries, plus the explicit exclusions; a picker or
+    launcher change that strands an instantiation, or a catalogue entry naming a kernel the library lacks, fails here"""
+    import subprocess
+    import kernel_catalogue as cat
+    from csolve_amd import _lib
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    shipped = set()
+    for line in out.splitlines():
+        parts = line.split()
+        if len(parts) == 3 and parts[2].startswith("_Z"):
+            name = _lib.demangle(parts[2])
+            if name.split("<")[0] in FIXPOINT_FAMILIES and "<" in name:
+                shipped.add(name)
+    assert set(cat.PLANS) == set(cat.BY_ID), "every catalogue entry has its plan"
+    planned = {name for plan in cat.PLANS.values() for name in plan.values()}
+    launched = set().union(*(cat.launched(i) for i in cat.BY_ID))
+    assert not planned & set(cat.EXCLUDED), sorted(planned & set(cat.EXCLUDED))
+    assert all(reason.strip() for reason in cat.EXCLUDED.values())
+    assert sorted(planned - shipped) == [], "catalogued plans name kernels the library does not ship"
+    assert sorted(set(cat.EXCLUDED) - shipped) == [], "exclusions name kernels the library does not ship"
+    assert sorted(planned - launched) == [], "planned by some entry but launched by no test"
+    assert sorted(shipped - launched - set(cat.EXCLUDED)) == [], "shipped kernels neither launched nor excluded"
+    print(f"fixpoint-family kernels: {len(launched)} launched + {len(cat.EXCLUDED)} excluded = {len(shipped)}")
