@@ -159,6 +159,10 @@ def load_library():
     L.csgpu_search_solutions.argtypes = [vp, vp, i64]
     L.csgpu_search_best_solution.argtypes = [vp, vp]
     L.csgpu_search_solutions.restype = i64
+    L.csgpu_search_set_solution_stream.argtypes = [vp, i64]
+    L.csgpu_search_drain_solutions.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.csgpu_search_drain_solutions_device.argtypes = [vp, vp, i64, C.POINTER(i64), vp]
+    L.csgpu_search_pending_solutions.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.csgpu_propagate_one.argtypes = [vp, vp, Node, vp, C.POINTER(Result)]
     L.csgpu_propagate_one_traced.argtypes = [vp, vp, Node, vp, C.POINTER(Result), vp, i32, C.POINTER(i32)]
     L.csgpu_propagate_one_causes.argtypes = [vp, vp, Node, vp, C.POINTER(Result), vp, i32, C.POINTER(i32)]

@@ -1256,6 +1256,7 @@ static int launch_step_shave(const csgpu_model *m, const csgpu_step_launch *L, v
   io.stored = (unsigned long long *)L->stored;
   io.max_solutions = (long long)L->max_solutions;
   io.store_open = L->store_open;
+  io.stream_on = L->stream != NULL;
   int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
   const void *tab_d = m->d_dense_tab;
   const int *root_lo_d = m->d_root_lo, *sym_off = m->d_sym_off;
@@ -1265,7 +1266,9 @@ static int launch_step_shave(const csgpu_model *m, const csgpu_step_launch *L, v
   hipLaunchKernelGGL(cs_collect, dim3((unsigned)waves), dim3(256), 0, (hipStream_t)stream, (const unsigned *)L->fill, (int)waves,
                      (const uint2 *)L->stage, io.K, n, (uint2 *)L->pool, (long long)L->first_row, (int)L->parents,
                      0 /* every parent is drawn */, (const unsigned *)L->ticket, (const unsigned long long *)L->wstat,
-                     (unsigned long long *)L->out, (const unsigned long long *)L->stored);
+                     (unsigned long long *)L->out, (const unsigned long long *)L->stored,
+                     L->stream, (long long)L->stream_base, (long long)L->stream_limit, (long long)L->stream_cap,
+                     (unsigned long long *)L->stream_err);
   HIP_TRY(hipGetLastError());
   return CSGPU_OK;
 }
@@ -1311,6 +1314,7 @@ extern "C" int csgpu_internal_step(const csgpu_model *m, const csgpu_step_launch
   io.stored = (unsigned long long *)L->stored;
   io.max_solutions = (long long)L->max_solutions;
   io.store_open = L->store_open;
+  io.stream_on = L->stream != NULL;
   int nn = n, slots = m->img->dense_slots, bias = m->packed_bias;
   const void *tab_d = m->d_packed_tab;
   const int *root_lo_d = m->d_root_lo, *sym_off = m->d_sym_off;
@@ -1321,7 +1325,9 @@ extern "C" int csgpu_internal_step(const csgpu_model *m, const csgpu_step_launch
   hipLaunchKernelGGL(cs_collect, dim3((unsigned)waves), dim3(256), 0, (hipStream_t)stream, (const unsigned *)L->fill, (int)waves,
                      (const uint2 *)L->stage, io.K, n, (uint2 *)L->pool, (long long)L->first_row, (int)L->parents,
                      (int)chunk, (const unsigned *)L->ticket, (const unsigned long long *)L->wstat,
-                     (unsigned long long *)L->out, (const unsigned long long *)L->stored);
+                     (unsigned long long *)L->out, (const unsigned long long *)L->stored,
+                     L->stream, (long long)L->stream_base, (long long)L->stream_limit, (long long)L->stream_cap,
+                     (unsigned long long *)L->stream_err);
   HIP_TRY(hipGetLastError());
   return CSGPU_OK;
 }

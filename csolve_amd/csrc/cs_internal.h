@@ -64,6 +64,11 @@ typedef struct csgpu_step_launch {
   uint64_t *stored;
   int64_t max_solutions;
   int32_t store_open;
+  int32_t *stream;        /* NULL, or the solution stream, a ring of stream_cap rows: every solution of the launch */
+  int64_t stream_base;    /* goes to positions stream_base, stream_base + 1, ... (row = position mod stream_cap), all */
+  int64_t stream_limit;   /* below stream_limit (the caller's frontier is sized for it), else nothing is written */
+  int64_t stream_cap;     /* and *stream_err = 1 */
+  uint64_t *stream_err;
 } csgpu_step_launch;
 /* 0: the model has no step kernel; 1: cs_step_packed (pure != network of at most 32 variables, engine rows in the pool);
  * 2: cs_step_shave (33 to 256 variables, plain interval rows) */

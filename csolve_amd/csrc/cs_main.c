@@ -15,6 +15,8 @@
  * the reference's host structures and are accepted and ignored.
  * The search order differs from the reference's (batched expansion), so CALLS/CUTS and WHICH
  * solution an ANY run prints are engine-specific; the set of solutions and the optimum are not.
+ * ALL prints every solution (csolve.c:222-244): the engine's solution stream is drained and printed after every
+ * csgpu_search_run call, so the SOLUTION lines are as many as the final SOLUTIONS count, in the engine's order.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,6 +31,14 @@ static void die(const char *msg) {
   fprintf(stderr, "%s: error: %s\n", prog, msg);
   exit(EXIT_FAILURE);
 }
+
+static void print_solution(const csgpu_model *m, int n, const int32_t *vals, int32_t best) {
+  printf("#1: SOLUTION: ");
+  for (int v = 0; v < n; v++) printf("%s = %d, ", csgpu_model_var_name(m, v), vals[v]);
+  printf("BEST: %d\n", best);
+}
+
+#define STREAM_BYTES (16 << 20) /* ALL: the solution stream (and the host buffer it is drained into), drained after every run call */
 
 static char *read_all(FILE *f) {
   size_t cap = 1 << 16, n = 0;
@@ -99,31 +109,43 @@ int main(int argc, char **argv) {
     if (csgpu_search_set_restart(s, restart_freq) != CSGPU_OK) die(csgpu_last_error());
     if (csgpu_search_set_restart_on_improvement(s, restart_freq > 0) != CSGPU_OK) die(csgpu_last_error());
   }
+  const int obj = csgpu_model_objective(m), ov = csgpu_model_objective_var(m);
+  const int all = obj == 1;
+  int32_t *drained = NULL;
+  /* rows of the stream: 16 MiB of them, and at least one parent's children (the engine refuses fewer) */
+  int64_t stream_rows = (int64_t)STREAM_BYTES / ((int64_t)n * (int64_t)sizeof(int32_t));
+  if (stream_rows < 1024) stream_rows = 1024;
+  if (all) {
+    if (csgpu_search_set_solution_stream(s, stream_rows) != CSGPU_OK) die(csgpu_last_error());
+    drained = (int32_t *)malloc((size_t)stream_rows * (size_t)n * sizeof(int32_t));
+    if (drained == NULL) die("out of memory");
+  }
   if (csgpu_search_put_host(s, root, 1) != CSGPU_OK) die(csgpu_last_error());
   csgpu_search_stats stats;
-  if (time_max <= 0) {
-    if (csgpu_search_run(s, (int64_t)1 << 60, &stats) != CSGPU_OK) die(csgpu_last_error());
-  } else {
-    /* -t: the clock is looked at between slices of 64 iterations (the reference's SIGALRM sets a flag its loop tests) */
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (;;) {
-      if (csgpu_search_run(s, 64, &stats) != CSGPU_OK) die(csgpu_last_error());
+  /* -t: the clock is looked at between slices of 64 iterations (the reference's SIGALRM sets a flag its loop tests).
+   * ALL: a run call also returns when the stream is full; what it holds is printed before the next one. */
+  struct timespec t0, t1;
+  clock_gettime(CLOCK_MONOTONIC, &t0);
+  for (;;) {
+    if (csgpu_search_run(s, time_max > 0 ? 64 : (int64_t)1 << 60, &stats) != CSGPU_OK) die(csgpu_last_error());
+    if (all) {
+      int64_t got = 0;
+      if (csgpu_search_drain_solutions(s, drained, stream_rows, &got) != CSGPU_OK) die(csgpu_last_error());
+      for (int64_t i = 0; i < got; i++) print_solution(m, n, drained + i * n, 0);
+    }
+    if (stats.done) break;
+    if (time_max > 0) {
       clock_gettime(CLOCK_MONOTONIC, &t1);
-      if (stats.done || (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec) >= (double)time_max) break;
+      if ((double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec) >= (double)time_max) break;
     }
   }
 
-  const int64_t shown = (int64_t)(stats.solutions < 1024 ? stats.solutions : 1024);
-  int32_t *vals = (int32_t *)malloc((size_t)(shown ? shown : 1) * (size_t)n * sizeof(int32_t));
-  int64_t k = csgpu_search_solutions(s, vals, shown);
-  const int obj = csgpu_model_objective(m), ov = csgpu_model_objective_var(m);
-  if (obj >= 2) /* MIN/MAX: the solution that attains the optimum (the reference's last line) */
-    k = csgpu_search_best_solution(s, vals) == 1 ? 1 : 0;
-  for (int64_t i = 0; i < k; i++) {
-    printf("#1: SOLUTION: ");
-    for (int v = 0; v < n; v++) printf("%s = %d, ", csgpu_model_var_name(m, v), vals[i * n + v]);
-    printf("BEST: %d\n", (obj >= 2 && ov >= 0) ? vals[i * n + ov] : 0);
+  int32_t *vals = (int32_t *)malloc((size_t)n * sizeof(int32_t));
+  if (!all) {
+    int64_t k = csgpu_search_solutions(s, vals, 1);
+    if (obj >= 2) /* MIN/MAX: the solution that attains the optimum (the reference's last line) */
+      k = csgpu_search_best_solution(s, vals) == 1 ? 1 : 0;
+    if (k == 1) print_solution(m, n, vals, (obj >= 2 && ov >= 0) ? vals[ov] : 0);
   }
   printf("#1: CALLS: %lu, CUTS: %lu, PROPS: %lu, CONFL: 0, RESTARTS: %lu, LEVEL: 0/%d, AVG LEVEL: 0.000000, MEM: 0, CMEM: 0, SOLUTIONS: %lu\n",
          (unsigned long)stats.nodes, (unsigned long)stats.cuts, (unsigned long)stats.props,
@@ -131,6 +153,6 @@ int main(int argc, char **argv) {
   if (stats.solutions == 0) printf("NO SOLUTION FOUND\n");
   csgpu_search_free(s);
   csgpu_model_free(m);
-  free(root); free(vals);
+  free(root); free(vals); free(drained);
   return EXIT_SUCCESS;
 }

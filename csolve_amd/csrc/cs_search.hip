@@ -21,9 +21,13 @@
 
 /* device counters.  [C_SURVIVORS, C_PER_ITERATION) are zeroed at the start of every iteration (C_SKIPPED: children
  * cut without a launch, see cs_holes); C_SOLUTIONS and C_STORED run over the whole search; C_BEST holds the
- * incumbent (an int in the low half) */
+ * incumbent (an int in the low half).  The solution stream is a ring of stream_cap rows; positions count the rows
+ * appended since it was last emptied, position p lives at row p mod stream_cap: C_STREAM = the next free position (the
+ * accept kernels take theirs there; the fused levels are given theirs by the host), C_STREAM_HEAD = the oldest
+ * position not drained (a position below C_STREAM_HEAD + stream_cap is free to write), C_STREAM_ERR != 0: a kernel
+ * found no room */
 enum { C_SURVIVORS = 0, C_COMPLETE, C_CUTS, C_PROPS, C_REVS, C_TOTAL_CHILDREN, C_SKIPPED, C_PER_ITERATION,
-       C_SOLUTIONS = C_PER_ITERATION, C_STORED, C_BEST, C_COUNT };
+       C_SOLUTIONS = C_PER_ITERATION, C_STORED, C_BEST, C_STREAM, C_STREAM_HEAD, C_STREAM_ERR, C_COUNT };
 
 /* Values that the parent's own forbidden set already rules out (models whose states carry one set word per
  * variable): the child "variable = such a value" violates a != clause with a valued neighbour, so its fixpoint
@@ -134,6 +138,13 @@ struct csgpu_search {
   int burst_no_eval;   /* device-driven iterations launch no root evaluation: see enqueue_burst */
   int burst_split;     /* MIN / MAX: expansion and classification of a device-driven iteration by several workgroups
                         * (CSGPU_SEARCH_BURST_SPLIT=0: by one, as ANY) */
+  /* the solution stream (csgpu_search_set_solution_stream): a ring of [stream_cap][n] int32 rows.  stream_head = the
+   * position of the oldest waiting row (= counters[C_STREAM_HEAD]), stream_rows = the host's count of waiting rows,
+   * exact whenever no accept is pending (the device's next position is counters[C_STREAM]).  stream_failed: a kernel
+   * found no room (CSGPU_E_LIMIT); the stream serves nothing more until csgpu_search_reset */
+  int32_t *d_stream;
+  int64_t stream_cap, stream_rows, stream_head;
+  int stream_failed;
 };
 
 extern "C" int csgpu_internal_set_error(int code, const char *msg); /* cs_capi.hip */
@@ -681,6 +692,17 @@ __global__ __launch_bounds__(1024) void cs_classify_small(const csgpu_result *__
   }
 }
 
+/* the next free position of the solution stream for `rows` rows, and ring row of position `at`: -1 and the error flag
+ * when they would overwrite rows not yet drained (the host sizes the iterations so that this never happens) */
+__device__ __forceinline__ long long cs_stream_take(unsigned long long *__restrict__ counters, unsigned long long at,
+                                                    unsigned rows, long long stream_cap) {
+  if (at + rows > counters[C_STREAM_HEAD] + (unsigned long long)stream_cap) {
+    counters[C_STREAM_ERR] = 1ull;
+    return -1;
+  }
+  return (long long)(at % (unsigned long long)stream_cap);
+}
+
 /* cs_accept + cs_pick_best for the complete children of a small iteration, by one workgroup, nothing read by the
  * host: counts the solutions, moves the incumbent, keeps a state that attains it (and, ANY: the first one).
  * Called by every thread of a workgroup of at least 256 threads (the first 256 work; uniform control flow). */
@@ -689,10 +711,13 @@ __device__ __forceinline__ void cs_accept_block(const cs_val *__restrict__ child
                                                 unsigned long long *__restrict__ counters,
                                                 unsigned long long *__restrict__ burst, int32_t *__restrict__ solutions,
                                                 long long max_solutions, int32_t *__restrict__ best_solution,
-                                                int *__restrict__ best /* the incumbent: may be shared between engines */) {
+                                                int *__restrict__ best /* the incumbent: may be shared between engines */,
+                                                int32_t *__restrict__ stream /* nullable: the picked row is appended */,
+                                                long long stream_cap) {
   __shared__ long long s_key[256];
   __shared__ int s_cnt[256];
   __shared__ int s_pick;
+  __shared__ long long s_slot;
   const int count = (int)counters[C_COMPLETE];
   if (count == 0) return; /* uniform */
   const int t = (int)threadIdx.x;
@@ -732,6 +757,7 @@ __device__ __forceinline__ void cs_accept_block(const cs_val *__restrict__ child
   }
   if (t == 0) {
     s_pick = -1;
+    s_slot = -1;
     const int accepted = s_cnt[0];
     if (accepted > 0) {
       const long long best_key = s_key[0];
@@ -757,12 +783,24 @@ __device__ __forceinline__ void cs_accept_block(const cs_val *__restrict__ child
         }
       }
     }
+    /* the stream takes the picked row too (ANY: the one solution; MIN / MAX: the one that improved the incumbent);
+     * one workgroup, one row: the slot is this thread's to take */
+    if (stream != nullptr && s_pick >= 0) {
+      const unsigned long long at = counters[C_STREAM];
+      s_slot = cs_stream_take(counters, at, 1u, stream_cap);
+      if (s_slot >= 0) counters[C_STREAM] = at + 1ull;
+    }
   }
   __syncthreads();
   const int pick = s_pick;
   if (pick >= 0 && t < 256) {
     int32_t *out = objective == CS_OBJ_ANY ? solutions : best_solution;
-    for (int v = t; v < n; v += 256) out[v] = child_states[(size_t)list[pick] * n + v].lo;
+    const long long slot = s_slot;
+    for (int v = t; v < n; v += 256) {
+      const int32_t x = child_states[(size_t)list[pick] * n + v].lo;
+      out[v] = x;
+      if (slot >= 0) stream[(size_t)slot * n + v] = x;
+    }
   }
   __syncthreads();
 }
@@ -773,9 +811,10 @@ __global__ __launch_bounds__(256) void cs_accept_burst(const cs_val *__restrict_
                                                        unsigned long long *__restrict__ counters,
                                                        unsigned long long *__restrict__ burst,
                                                        int32_t *__restrict__ solutions, long long max_solutions,
-                                                       int32_t *__restrict__ best_solution, int *__restrict__ best) {
+                                                       int32_t *__restrict__ best_solution, int *__restrict__ best,
+                                                       int32_t *__restrict__ stream, long long stream_cap) {
   cs_accept_block(child_states, list, truth, n, objective, obj_var, counters, burst, solutions, max_solutions, best_solution,
-                  best);
+                  best, stream, stream_cap);
   if (threadIdx.x == 0) counters[C_COMPLETE] = 0ull; /* accepted: the next burst's first expansion must not do it again */
 }
 
@@ -824,7 +863,8 @@ __global__ __launch_bounds__(1024) void cs_expand_burst(const cs_val *__restrict
                                                         const int *__restrict__ complete_list,
                                                         const int *__restrict__ truth, int obj_var,
                                                         int32_t *__restrict__ solutions, long long max_solutions,
-                                                        int32_t *__restrict__ best_solution, int *__restrict__ best) {
+                                                        int32_t *__restrict__ best_solution, int *__restrict__ best,
+                                                        int32_t *__restrict__ stream, long long stream_cap) {
   __shared__ cs_choice s_choice[SMALL_PARENTS];
   __shared__ int s_off[SMALL_PARENTS];
   __shared__ long long s_part[16];
@@ -833,7 +873,7 @@ __global__ __launch_bounds__(1024) void cs_expand_burst(const cs_val *__restrict
   /* first the accept of the previous iteration's complete children (their root evaluation has run): it decides
    * whether ANY is done and moves the incumbent this iteration's fixpoints will see */
   cs_accept_block(child_states, complete_list, truth, n, objective, obj_var, counters, burst, solutions, max_solutions,
-                  best_solution, best);
+                  best_solution, best, stream, stream_cap);
   if (threadIdx.x == 0) {
     const cs_burst_head h = cs_burst_decide(burst, objective == CS_OBJ_ANY && counters[C_STORED] != 0ull, max_width, cap, room_limit);
     if (h.error) burst[B_ERROR] = 1ull;
@@ -902,14 +942,15 @@ __global__ __launch_bounds__(1024) void cs_burst_branch(const cs_val *__restrict
                                                         const int *__restrict__ complete_list,
                                                         const int *__restrict__ truth, int obj_var,
                                                         int32_t *__restrict__ solutions, long long max_solutions,
-                                                        int32_t *__restrict__ best_solution, int *__restrict__ best) {
+                                                        int32_t *__restrict__ best_solution, int *__restrict__ best,
+                                                        int32_t *__restrict__ stream, long long stream_cap) {
   __shared__ int s_cnt[BURST_PPW], s_skip[BURST_PPW];
   __shared__ long long s_first;
   __shared__ int s_parents;
   const int g = (int)blockIdx.x;
   if (g == 0) /* uniform within the workgroup */
     cs_accept_block(child_states, complete_list, truth, n, objective, obj_var, counters, burst, solutions, max_solutions,
-                    best_solution, best);
+                    best_solution, best, stream, stream_cap);
   if (threadIdx.x == 0) {
     const cs_burst_head h = cs_burst_decide(burst, false, max_width, cap, room_limit);
     s_parents = h.parents;
@@ -1181,12 +1222,15 @@ __global__ __launch_bounds__(SB) void cs_gather_complete(const cs_val *__restric
 }
 
 /* accept the complete children whose root evaluated to true: count, incumbent, store some.
- * One thread per complete child; one atomic per wave for the count and the incumbent. */
+ * One thread per complete child; one atomic per wave for the count and the incumbent.
+ * stream != nullptr (ALL, ANY): every accepted child is also appended to the solution stream -- slots reserved once per
+ * workgroup, at counters[C_STREAM], like the count. */
 __global__ __launch_bounds__(SB) void cs_accept(const cs_val *__restrict__ complete, const int *__restrict__ truth,
                                                 int count, int n, int objective, int obj_var,
                                                 unsigned long long *__restrict__ counters,
                                                 int32_t *__restrict__ solutions, long long max_solutions,
-                                                const int *__restrict__ list /* nullable: child i is row list[i] */) {
+                                                const int *__restrict__ list /* nullable: child i is row list[i] */,
+                                                int32_t *__restrict__ stream, long long stream_cap) {
   const int lane = threadIdx.x & 63;
   int i = blockIdx.x * SB + threadIdx.x;
   if (objective == CS_OBJ_ANY) {
@@ -1199,21 +1243,45 @@ __global__ __launch_bounds__(SB) void cs_accept(const cs_val *__restrict__ compl
     if (first < 0 || counters[C_STORED] != 0ull) return;
     counters[C_SOLUTIONS] += 1ull;
     counters[C_STORED] = 1ull;
-    for (int v = 0; v < n; v++) solutions[v] = complete[(size_t)(list != nullptr ? list[first] : first) * n + v].lo;
+    long long slot = -1;
+    if (stream != nullptr) {
+      const unsigned long long at = counters[C_STREAM];
+      slot = cs_stream_take(counters, at, 1u, stream_cap);
+      if (slot >= 0) counters[C_STREAM] = at + 1ull;
+    }
+    for (int v = 0; v < n; v++) {
+      const int32_t x = complete[(size_t)(list != nullptr ? list[first] : first) * n + v].lo;
+      solutions[v] = x;
+      if (slot >= 0) stream[(size_t)slot * n + v] = x;
+    }
     return;
   }
   /* the count goes through LDS: one device atomic per workgroup (a word takes about 88 atomics per microsecond, and an
    * ALL iteration of queens-16 accepts 80,000 children: one atomic per wave was 14 of the kernel's 17 us) */
   __shared__ unsigned s_accepted;
+  __shared__ unsigned long long s_stream0;
   if (threadIdx.x == 0) s_accepted = 0u;
   __syncthreads();
   const bool ok = i < count && (truth == nullptr || truth[i] == 1); /* truth == NULL: every complete child is a solution */
   const size_t row = ok ? (size_t)(list != nullptr ? list[i] : i) * n : 0;
   const unsigned long long mask = __ballot(ok);
   const int accepted = __popcll(mask), leader = mask != 0ull ? __builtin_ctzll(mask) : 0;
-  if (mask != 0ull && lane == leader) atomicAdd(&s_accepted, (unsigned)accepted);
+  unsigned wave_off = 0u; /* the wave's first row among the workgroup's accepted children */
+  if (mask != 0ull && lane == leader) wave_off = atomicAdd(&s_accepted, (unsigned)accepted);
   __syncthreads();
   if (threadIdx.x == 0 && s_accepted != 0u) atomicAdd(&counters[C_SOLUTIONS], (unsigned long long)s_accepted);
+  if (stream != nullptr) { /* uniform: the workgroup's stream rows, one device atomic */
+    if (threadIdx.x == 0) s_stream0 = s_accepted != 0u ? atomicAdd(&counters[C_STREAM], (unsigned long long)s_accepted) : 0ull;
+    __syncthreads();
+    wave_off = (unsigned)__shfl((int)wave_off, leader);
+    if (ok) {
+      const unsigned long long at =
+          s_stream0 + wave_off + (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+      const long long r = cs_stream_take(counters, at, 1u, stream_cap);
+      if (r >= 0)
+        for (int v = 0; v < n; v++) stream[(size_t)r * n + v] = complete[row + v].lo;
+    }
+  }
   if (mask == 0ull) return;
   if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX) {
     int val = objective == CS_OBJ_MIN ? 0x7fffffff : (int)0x80000000;
@@ -1242,9 +1310,11 @@ __global__ __launch_bounds__(SB) void cs_accept(const cs_val *__restrict__ compl
   }
 }
 
-/* one wave: the first accepted complete child whose objective value equals the incumbent */
+/* one wave: the first accepted complete child whose objective value equals the incumbent (stream != nullptr: appended
+ * to the solution stream as well) */
 __global__ void cs_pick_best(const cs_val *__restrict__ complete, const int *__restrict__ truth, int count, int n,
-                             int objective, int obj_var, int best, int32_t *__restrict__ out) {
+                             int objective, int obj_var, int best, int32_t *__restrict__ out,
+                             int32_t *__restrict__ stream, long long stream_cap, unsigned long long *__restrict__ counters) {
   const int lane = threadIdx.x;
   int pick = -1;
   for (int k = 0; k < count && pick < 0; k++) {
@@ -1252,7 +1322,21 @@ __global__ void cs_pick_best(const cs_val *__restrict__ complete, const int *__r
     if (truth[k] == 1 && (objective == CS_OBJ_MIN ? o.lo : o.hi) == best) pick = k;
   }
   if (pick < 0) return;
-  for (int v = lane; v < n; v += 64) out[v] = complete[(size_t)pick * n + v].lo;
+  long long slot = -1;
+  if (stream != nullptr) {
+    const unsigned long long at = counters[C_STREAM]; /* every lane reads before lane 0 writes: one wave */
+    slot = at + 1ull > counters[C_STREAM_HEAD] + (unsigned long long)stream_cap ? -1ll
+                                                                               : (long long)(at % (unsigned long long)stream_cap);
+    if (lane == 0) {
+      if (slot >= 0) counters[C_STREAM] = at + 1ull;
+      else counters[C_STREAM_ERR] = 1ull;
+    }
+  }
+  for (int v = lane; v < n; v += 64) {
+    const int32_t x = complete[(size_t)pick * n + v].lo;
+    out[v] = x;
+    if (slot >= 0) stream[(size_t)slot * n + v] = x;
+  }
 }
 
 /* move the newest `count` rows into the hole left by taking the oldest ones */
@@ -1290,6 +1374,7 @@ extern "C" void csgpu_search_free(csgpu_search *s) {
   (void)hipFree(s->d_best_solution);
   (void)hipFree(s->d_burst);
   (void)hipFree(s->d_prio);
+  (void)hipFree(s->d_stream);
   (void)hipFree(s->d_fill); (void)hipFree(s->d_ticket); (void)hipFree(s->d_wstat); (void)hipFree(s->d_step_out);
   if (s->h_step_out) (void)hipHostFree(s->h_step_out);
   if (s->h_burst) (void)hipHostFree(s->h_burst);
@@ -1554,6 +1639,9 @@ extern "C" int csgpu_search_reset(csgpu_search *s) {
   s->pending_complete = 0;
   s->surv_per_parent = (double)s->max_width;
   s->stored_seen = 0;
+  s->stream_rows = 0; /* the counters below hold the device's positions: the stream is empty and stays on */
+  s->stream_head = 0;
+  s->stream_failed = 0;
   if (s->d_prio != NULL) HIP_OK(hipMemset(s->d_prio, 0, sizeof(int) * (size_t)s->n));
   HIP_OK(hipMemset(s->d_counters, 0, sizeof(unsigned long long) * C_COUNT));
   HIP_OK(hipMemcpy(s->d_best, &s->st.best, sizeof(int), hipMemcpyHostToDevice));
@@ -1666,10 +1754,44 @@ extern "C" int csgpu_search_set_best(csgpu_search *s, int32_t best) {
   return CSGPU_OK;
 }
 
+extern "C" int csgpu_search_set_solution_stream(csgpu_search *s, int64_t rows) {
+  if (s == NULL) return fail(CSGPU_E_ARG, "bad argument");
+  if (hipSetDevice(s->device) != hipSuccess) return fail(CSGPU_E_HIP, "hipSetDevice");
+  if (s->top != 0 || s->st.iterations != 0) return fail(CSGPU_E_STATE, "the solution stream is set before the first state is put");
+  if (s->lender != NULL || s->borrowers > 0)
+    return fail(CSGPU_E_STATE, "an engine that shares its incumbent has no solution stream");
+  /* one parent's children at most per row of room: the rule by which an iteration is sized (stream_room) */
+  if (rows < s->max_width || rows > 0x7fffffff) return fail(CSGPU_E_ARG, "solution stream rows out of range");
+  if (s->d_stream != NULL && s->stream_cap != rows) {
+    (void)hipFree(s->d_stream);
+    s->d_stream = NULL;
+  }
+  if (s->d_stream == NULL) HIP_OK(hipMalloc((void **)&s->d_stream, (size_t)rows * s->n * sizeof(int32_t)));
+  s->stream_cap = rows;
+  s->stream_rows = 0;
+  s->stream_head = 0;
+  s->stream_failed = 0;
+  HIP_OK(hipMemset(s->d_counters + C_STREAM, 0, sizeof(unsigned long long) * 3)); /* C_STREAM, C_STREAM_HEAD, C_STREAM_ERR */
+  if (s->burst_exec != NULL) { /* the graph holds the old arguments */
+    (void)hipGraphExecDestroy(s->burst_exec);
+    s->burst_exec = NULL;
+  }
+  return CSGPU_OK;
+}
+
+/* rows of the stream that are free for what the coming iterations append: the accept that is still unread counts with
+ * what it may add (ALL: every complete child of its iteration; otherwise one row) */
+static int64_t stream_room(const csgpu_search *s) {
+  const int64_t pending = s->objective == CS_OBJ_ALL ? s->pending_complete : (s->pending_complete > 0 ? 1 : 0);
+  return s->stream_cap - s->stream_rows - pending;
+}
+
 extern "C" int csgpu_search_share_incumbent(csgpu_search *s, csgpu_search *with) {
   if (s == NULL || with == NULL || s->objective != with->objective || s->obj_var != with->obj_var)
     return fail(CSGPU_E_ARG, "bad argument");
   if (hipSetDevice(s->device) != hipSuccess) return fail(CSGPU_E_HIP, "hipSetDevice");
+  if (s->d_stream != NULL || with->d_stream != NULL)
+    return fail(CSGPU_E_STATE, "an engine with a solution stream does not share its incumbent");
   if (s->objective != CS_OBJ_MIN && s->objective != CS_OBJ_MAX) return CSGPU_OK; /* nothing to share */
   if (!burst_applicable(s) || !burst_applicable(with))
     return fail(CSGPU_E_STATE, "a shared incumbent needs the device-driven iterations");
@@ -1701,11 +1823,16 @@ static int apply_accept_results(csgpu_search *s, unsigned long long solutions_to
   if (s->pending_complete == 0) return CSGPU_OK;
   const int improved = (s->objective == CS_OBJ_MIN || s->objective == CS_OBJ_MAX) && solutions_total > s->st.solutions &&
                        best != s->st.best;
+  /* ALL / ANY: every accepted solution went to the stream; MIN / MAX: the pick below goes there */
+  if (s->d_stream != NULL && (s->objective == CS_OBJ_ALL || s->objective == CS_OBJ_ANY))
+    s->stream_rows += (int64_t)(solutions_total - s->st.solutions);
   s->st.solutions = solutions_total;
   if (improved) {
     /* the complete children and their truth values of that iteration are still in place */
     hipLaunchKernelGGL(cs_pick_best, dim3(1), dim3(64), 0, 0, s->d_complete_states, s->d_truth, (int)s->pending_complete,
-                       s->n, s->objective, s->obj_var, best, s->d_best_solution);
+                       s->n, s->objective, s->obj_var, best, s->d_best_solution, s->d_stream, (long long)s->stream_cap,
+                       s->d_counters);
+    if (s->d_stream != NULL) s->stream_rows++;
     s->have_best_solution = 1;
     s->best_solution_value = best;
   }
@@ -1740,6 +1867,9 @@ static int one_iteration_fused(csgpu_search *s) {
   if (parents > by_pool) parents = by_pool;
   if (parents > 0x3fffffff) parents = 0x3fffffff;
   if (parents < 1) parents = 1;
+  /* the solution stream: a parent has at most max_width children, so room / max_width parents cannot overflow it
+   * (csgpu_search_run has seen to room >= max_width) */
+  if (s->d_stream != NULL && parents > stream_room(s) / s->max_width) parents = stream_room(s) / s->max_width;
   /* (no worst-case test "every child of every parent survives": the staging rows handed to the launch below are
    * capped by what the pool has room for, and a wave whose region could overflow stops drawing parents) */
   if (s->top - 1 + s->max_width > s->cap) return fail(CSGPU_E_LIMIT, "state pool is full");
@@ -1769,6 +1899,11 @@ static int one_iteration_fused(csgpu_search *s) {
   L.stored = (uint64_t *)(s->d_counters + C_STORED);
   L.max_solutions = s->max_solutions;
   L.store_open = s->stored_seen < (uint64_t)s->max_solutions;
+  L.stream = s->d_stream;
+  L.stream_base = s->stream_head + s->stream_rows;
+  L.stream_limit = s->stream_head + s->stream_cap;
+  L.stream_cap = s->stream_cap;
+  L.stream_err = (uint64_t *)(s->d_counters + C_STREAM_ERR);
   HIP_OK(hipMemsetAsync(s->d_ticket, 0, 1024, 0));
   const int rc = csgpu_internal_step(s->m, &L, NULL);
   if (rc != CSGPU_OK) return rc;
@@ -1785,6 +1920,7 @@ static int one_iteration_fused(csgpu_search *s) {
   s->st.props += h[4];
   s->st.revisions += h[5];
   s->st.solutions += h[6];
+  if (s->d_stream != NULL) s->stream_rows += (int64_t)h[6];
   s->stored_seen = h[7];
   s->surv_per_parent = 0.5 * s->surv_per_parent + 0.5 * ((double)survivors / (double)consumed);
   if (getenv("CSGPU_SEARCH_TRACE") != NULL)
@@ -1823,6 +1959,9 @@ static int one_iteration(csgpu_search *s) {
       if (s->top - parents + parents * s->max_width > s->cap) return fail(CSGPU_E_LIMIT, "state pool is full");
     }
   }
+  /* the solution stream (ALL): room / max_width parents cannot overflow it (csgpu_search_run has seen to room >= max_width) */
+  if (s->d_stream != NULL && s->objective == CS_OBJ_ALL && parents > stream_room(s) / s->max_width)
+    parents = stream_room(s) / s->max_width;
   long long first_row = s->top - parents;
   if (parents == 0) return CSGPU_OK;
   const int small = parents <= SMALL_PARENTS && parents <= s->max_parents;
@@ -1966,7 +2105,7 @@ static int one_iteration(csgpu_search *s) {
       }
       hipLaunchKernelGGL(cs_accept, dim3((unsigned)((complete + SB - 1) / SB)), dim3(SB), 0, 0, s->d_child_states,
                          truth, (int)complete, n, s->objective, s->obj_var, s->d_counters, s->d_solutions,
-                         (long long)s->max_solutions, (const int *)s->d_complete_list);
+                         (long long)s->max_solutions, (const int *)s->d_complete_list, s->d_stream, (long long)s->stream_cap);
     } else {
       /* MIN / MAX keep the complete children of the iteration together: cs_pick_best looks at them one host
        * round trip later */
@@ -1975,9 +2114,11 @@ static int one_iteration(csgpu_search *s) {
                          (int)complete, n, s->d_complete_states);
       rc = csgpu_eval_batch(s->m, (const csgpu_val *)s->d_complete_states, s->d_truth, complete, NULL);
       if (rc != CSGPU_OK) return rc;
+      /* ANY: its one solution goes to the stream here; MIN / MAX: the improving row, by cs_pick_best */
       hipLaunchKernelGGL(cs_accept, dim3((unsigned)((complete + SB - 1) / SB)), dim3(SB), 0, 0, s->d_complete_states,
                          s->d_truth, (int)complete, n, s->objective, s->obj_var, s->d_counters, s->d_solutions,
-                         (long long)s->max_solutions, (const int *)NULL);
+                         (long long)s->max_solutions, (const int *)NULL,
+                         s->objective == CS_OBJ_ANY ? s->d_stream : (int32_t *)NULL, (long long)s->stream_cap);
     }
     /* what accept found is read together with the next iteration's child count (or at the end of the
      * run); ANY stops on the first solution, so it looks at once */
@@ -2028,7 +2169,7 @@ static int enqueue_burst(csgpu_search *s, hipStream_t st) {
                          s->objective, (long long)s->max_width, (long long)s->cap, room_limit, s->holes, s->d_choice,
                          s->d_block_sum, s->d_block_skip, (const cs_val *)s->d_child_states,
                          (const int *)s->d_complete_list, truth, s->obj_var, s->d_solutions,
-                         (long long)s->max_solutions, s->d_best_solution, s->d_best);
+                         (long long)s->max_solutions, s->d_best_solution, s->d_best, s->d_stream, (long long)s->stream_cap);
       hipLaunchKernelGGL(cs_burst_emit, dim3(burst_wgs), dim3(1024), 0, st, s->d_nodes, s->d_counters, s->d_burst,
                          s->objective, (const cs_choice *)s->d_choice, (const int *)s->d_block_sum,
                          (const int *)s->d_block_skip);
@@ -2036,7 +2177,8 @@ static int enqueue_burst(csgpu_search *s, hipStream_t st) {
       hipLaunchKernelGGL(cs_expand_burst, dim3(1), dim3(1024), 0, st, s->pool, n, s->d_nodes, s->d_counters, s->d_burst,
                          s->objective, (long long)s->max_width, (long long)s->cap, room_limit, s->holes,
                          (const cs_val *)s->d_child_states, (const int *)s->d_complete_list, truth,
-                         s->obj_var, s->d_solutions, (long long)s->max_solutions, s->d_best_solution, s->d_best);
+                         s->obj_var, s->d_solutions, (long long)s->max_solutions, s->d_best_solution, s->d_best,
+                         s->d_stream, (long long)s->stream_cap);
     int rc;
     if (s->fw > 0)
       rc = csgpu_internal_propagate_fb(s->m, (const csgpu_val *)s->pool, (const uint64_t *)s->pool_forb, s->d_nodes,
@@ -2076,7 +2218,7 @@ static int enqueue_burst(csgpu_search *s, hipStream_t st) {
   /* the last iteration's accept (the others ran at the head of the following expansion) */
   hipLaunchKernelGGL(cs_accept_burst, dim3(1), dim3(256), 0, st, s->d_child_states, s->d_complete_list, truth, n,
                      s->objective, s->obj_var, s->d_counters, s->d_burst, s->d_solutions, (long long)s->max_solutions,
-                     s->d_best_solution, s->d_best);
+                     s->d_best_solution, s->d_best, s->d_stream, (long long)s->stream_cap);
   HIP_OK(hipGetLastError());
   return CSGPU_OK;
 }
@@ -2141,6 +2283,7 @@ static int run_burst(csgpu_search *s, int64_t budget, int64_t *done) {
   s->st.props += h[B_PROPS];
   s->st.revisions += h[B_REVS];
   s->st.solutions = h[B_COUNT + C_SOLUTIONS];
+  if (s->d_stream != NULL) s->stream_rows = (int64_t)h[B_COUNT + C_STREAM] - s->stream_head;
   if (s->objective == CS_OBJ_MIN || s->objective == CS_OBJ_MAX) s->st.best = *(const int *)(h + B_COUNT + C_COUNT);
   if (h[B_IMPROVED] != 0ull) {
     s->have_best_solution = 1;
@@ -2152,15 +2295,21 @@ static int run_burst(csgpu_search *s, int64_t budget, int64_t *done) {
 extern "C" int csgpu_search_run(csgpu_search *s, int64_t max_iterations, csgpu_search_stats *stats) {
   if (s == NULL || stats == NULL) return fail(CSGPU_E_ARG, "bad argument");
   if (hipSetDevice(s->device) != hipSuccess) return fail(CSGPU_E_HIP, "hipSetDevice");
+  if (s->stream_failed) return fail(CSGPU_E_STATE, "the solution stream overflowed: reset the engine");
   for (int64_t it = 0; it < max_iterations; it++) {
     if (s->top == 0) break;
     if (s->objective == CS_OBJ_ANY && s->st.solutions > 0) break;
+    /* the solution stream: stop (not done) while it cannot take the worst case of the next iteration -- ALL: every
+     * child of one parent; otherwise one row per iteration, so a burst takes at most as many iterations as there are
+     * free rows.  The caller drains and runs on. */
+    if (s->d_stream != NULL && stream_room(s) < (s->objective == CS_OBJ_ALL ? s->max_width : 1)) break;
     int rc;
     int64_t steps = 1; /* iterations this pass of the loop made */
     const int32_t best_before = s->st.best;
     const int restarts_on = s->restart_base > 0 && s->seed_count > 0 && s->st.solutions == 0;
     if (burst_applicable(s)) {
       int64_t budget = max_iterations - it;
+      if (s->d_stream != NULL && budget > stream_room(s)) budget = stream_room(s);
       if (restarts_on) { /* stop where check_restart would fire */
         const int64_t until = (int64_t)s->luby_threshold * s->restart_base + 1 - s->since_restart;
         if (until < budget) budget = until < 1 ? 1 : until;
@@ -2209,6 +2358,14 @@ extern "C" int csgpu_search_run(csgpu_search *s, int64_t max_iterations, csgpu_s
     const int rcf = flush_accept_results(s);
     if (rcf != CSGPU_OK) return rcf;
   }
+  if (s->d_stream != NULL) { /* the kernels' own test: a row that found no room is never dropped silently */
+    unsigned long long err = 0ull;
+    HIP_OK(hipMemcpy(&err, s->d_counters + C_STREAM_ERR, sizeof err, hipMemcpyDeviceToHost));
+    if (err != 0ull) {
+      s->stream_failed = 1; /* the host's count of rows may include rows that were not written */
+      return fail(CSGPU_E_LIMIT, "solution stream overflow");
+    }
+  }
   s->st.pool = s->top;
   s->st.pool_peak = s->peak;
   s->st.done = s->top == 0 || (s->objective == CS_OBJ_ANY && s->st.solutions > 0);
@@ -2237,4 +2394,48 @@ extern "C" int csgpu_search_best_solution(const csgpu_search *s, int32_t *values
   if (hipMemcpy(values, s->d_best_solution, (size_t)s->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
     return CSGPU_E_HIP;
   return 1;
+}
+
+/* ---- the solution stream: rows move out oldest first, from the ring's head; nothing else moves ---- */
+static int stream_drain(csgpu_search *s, int32_t *values, int64_t max, int64_t *count, hipMemcpyKind kind, hipStream_t st) {
+  if (s == NULL || values == NULL || count == NULL || max < 0) return fail(CSGPU_E_ARG, "bad argument");
+  if (hipSetDevice(s->device) != hipSuccess) return fail(CSGPU_E_HIP, "hipSetDevice");
+  if (s->d_stream == NULL) return fail(CSGPU_E_STATE, "no solution stream");
+  if (s->stream_failed) return fail(CSGPU_E_STATE, "the solution stream overflowed: reset the engine");
+  const int rc = flush_accept_results(s); /* the last iteration's accept: its rows (MIN / MAX: its pick) */
+  if (rc != CSGPU_OK) return rc;
+  *count = 0;
+  const int64_t k = max < s->stream_rows ? max : s->stream_rows;
+  if (k == 0) return CSGPU_OK;
+  HIP_OK(hipDeviceSynchronize()); /* the engine's kernels run on the null stream and its burst stream */
+  const size_t row = (size_t)s->n * sizeof(int32_t);
+  /* at most two pieces: from the head to the ring's end, then from row 0 */
+  const int64_t first = s->stream_head % s->stream_cap, part = k < s->stream_cap - first ? k : s->stream_cap - first;
+  HIP_OK(hipMemcpyAsync(values, s->d_stream + (size_t)first * s->n, (size_t)part * row, kind, st));
+  if (k > part) HIP_OK(hipMemcpyAsync(values + (size_t)part * s->n, s->d_stream, (size_t)(k - part) * row, kind, st));
+  HIP_OK(hipStreamSynchronize(st));
+  s->stream_head += k;
+  s->stream_rows -= k;
+  const unsigned long long head = (unsigned long long)s->stream_head; /* the freed rows may be written again */
+  HIP_OK(hipMemcpy(s->d_counters + C_STREAM_HEAD, &head, sizeof head, hipMemcpyHostToDevice));
+  *count = k;
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_search_drain_solutions(csgpu_search *s, int32_t *values, int64_t max, int64_t *count) {
+  return stream_drain(s, values, max, count, hipMemcpyDeviceToHost, (hipStream_t)0);
+}
+
+extern "C" int csgpu_search_drain_solutions_device(csgpu_search *s, int32_t *d_values, int64_t max, int64_t *count,
+                                                   void *stream) {
+  return stream_drain(s, d_values, max, count, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+extern "C" int csgpu_search_pending_solutions(const csgpu_search *s, int64_t *rows, int64_t *room) {
+  if (s == NULL || rows == NULL || room == NULL) return fail(CSGPU_E_ARG, "bad argument");
+  if (s->d_stream == NULL) return fail(CSGPU_E_STATE, "no solution stream");
+  if (s->stream_failed) return fail(CSGPU_E_STATE, "the solution stream overflowed: reset the engine");
+  *rows = s->stream_rows;
+  *room = s->stream_cap - s->stream_rows;
+  return CSGPU_OK;
 }

@@ -21,6 +21,14 @@
  *             the counters up.
  * A wave stops drawing parents when its region could overflow; the parents nobody drew stay in the pool.
  *
+ * SOLUTION STREAM (io.stream_on, csgpu_search_set_solution_stream).  Every complete child is also written, as a row
+ * whose element v holds variable v's value in its first word, to the BACK of the wave's own region: solution j of
+ * the wave at row K - 1 - j, survivors still at rows 0, 1, ... from the front.  A child is one or the other, so the
+ * room test that guards the survivors (rows written + children queued + the worst case of the parents drawn <= K)
+ * guards both with `fill` read as survivors + solutions.  No slot is asked of anyone: the wave's count is in its
+ * wstat[4] already, and cs_collect appends the regions' solutions behind the stream's rows in wave order.  With the
+ * stream off the extra count stays zero and nothing else changes.
+ *
  * cs_step_packed<G, NW, S3>: models of at most 32 variables (G = 4 segments of 16 lanes, or 2 of 32), the forbidden-set
  * fixpoint of kernel 5 (cs_kernels.hip.h).  A parent's bounds and sets go into a slot of LDS when it is loaded; its
  * children (descriptors {slot, variable, value} in a queue of the wave's own in LDS) start from there.  Branching works
@@ -63,6 +71,7 @@ struct cs_step_io {
   unsigned long long *stored;
   long long max_solutions;
   int store_open;            /* 0: the store is full, nobody asks for a slot */
+  int stream_on;             /* complete children also go to the back of the wave's region (see above) */
 };
 
 /* segment-wide broadcast of lane `src` (segment-relative) through the LDS crossbar */
@@ -173,6 +182,7 @@ __global__ __launch_bounds__(1024, 8) void cs_step_packed(int n, const unsigned 
   int qhead = 0, qlen = 0;    /* the child queue */
   int grp_tail = 0;           /* next group of parent slots to fill (0 .. 3) */
   int fill = 0;               /* rows written to the wave's region */
+  int sfill = 0;              /* solutions written to the back of it (stream on) */
   int store_open = io.store_open;
   int acc_fail = 0, acc_sol = 0, acc_parents = 0;
   int acc_nodes = 0, acc_skip = 0, acc_props = 0, acc_revs = 0; /* per lane, summed at the end */
@@ -190,7 +200,7 @@ __global__ __launch_bounds__(1024, 8) void cs_step_packed(int n, const unsigned 
 #define CS_STEP_ASK_TICKET()                                                                                        \
   do {                                                                                                              \
     if (!exhausted && !tk_pending) {                                                                                \
-      if (fill + qlen + (c_end - c_cur + io.chunk) * io.maxw <= io.K) {                                             \
+      if (fill + sfill + qlen + (c_end - c_cur + io.chunk) * io.maxw <= io.K) {                                     \
         tk_v = 0u;                                                                                                  \
         if (lane == 0) tk_v = __hip_atomic_fetch_add(io.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    \
         tk_pending = 1;                                                                                             \
@@ -212,6 +222,7 @@ __global__ __launch_bounds__(1024, 8) void cs_step_packed(int n, const unsigned 
     qlen = __builtin_amdgcn_readfirstlane(qlen);
     grp_tail = __builtin_amdgcn_readfirstlane(grp_tail);
     fill = __builtin_amdgcn_readfirstlane(fill);
+    sfill = __builtin_amdgcn_readfirstlane(sfill);
     store_open = __builtin_amdgcn_readfirstlane(store_open);
     acc_fail = __builtin_amdgcn_readfirstlane(acc_fail);
     acc_sol = __builtin_amdgcn_readfirstlane(acc_sol);
@@ -369,6 +380,12 @@ __global__ __launch_bounds__(1024, 8) void cs_step_packed(int n, const unsigned 
     if (complm != 0ull) {
       const int ns = __popcll(complm) >> LOG_S;
       acc_sol += ns;
+      if (io.stream_on) { /* solution j of the wave at row K - 1 - j of its region: no atomic */
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(complm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)complm, 0u)) >> LOG_S;
+        if (__builtin_amdgcn_inverse_ballot_w64(complm) && live)
+          io.stage[(region + (size_t)(io.K - 1 - (sfill + rank))) * n + v] = make_uint2((unsigned)(b0 + rl), 0u);
+        sfill += ns;
+      }
       if (store_open) { /* which solutions are kept may vary from run to run; their count does not */
         unsigned long long s0 = 0ull;
         if (lane == 0) s0 = atomicAdd(io.stored, (unsigned long long)ns);
@@ -523,7 +540,7 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_step_shave(int n, c
   }
   constexpr int W = CS_WAVE * R;
 
-  int fill = 0, store_open = io.store_open;
+  int fill = 0, sfill = 0 /* solutions at the back of the region (stream on) */, store_open = io.store_open;
   int acc_nodes = 0, acc_cuts = 0, acc_sol = 0, acc_parents = 0, acc_revs = 0; /* scalars */
   int acc_props = 0;                                                           /* per lane */
   const size_t region = (size_t)wave_global * (size_t)io.K;
@@ -559,6 +576,7 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_step_shave(int n, c
   while (p_cur >= 0) {
     p_cur = __builtin_amdgcn_readfirstlane(p_cur);
     fill = __builtin_amdgcn_readfirstlane(fill);
+    sfill = __builtin_amdgcn_readfirstlane(sfill);
     shard = __builtin_amdgcn_readfirstlane(shard);
     tried = __builtin_amdgcn_readfirstlane(tried);
     store_open = __builtin_amdgcn_readfirstlane(store_open);
@@ -572,7 +590,7 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_step_shave(int n, c
     acc_parents++;
     /* room for one more parent's children behind this one's (worst case both)? */
     int p_next = -1;
-    if (fill + 2 * io.maxw <= io.K) CS_STEP_DRAW(p_next);
+    if (fill + sfill + 2 * io.maxw <= io.K) CS_STEP_DRAW(p_next);
     if (p_next >= 0) load_parent(p_next, pd);
     u64 pval[R];
     unsigned key = 0xffffffffu;
@@ -653,6 +671,13 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_step_shave(int n, c
             fill++;
           } else {
             acc_sol++;
+            if (io.stream_on) {
+              const size_t orow = (region + (size_t)(io.K - 1 - sfill)) * n;
+#pragma unroll
+              for (int r = 0; r < R; r++)
+                if (live[r]) stage[orow + lane + r * CS_WAVE] = cs_value(rlo[r] + b0[r]);
+              sfill++;
+            }
             if (store_open) {
               unsigned long long s0 = 0ull;
               if (lane == 0) s0 = atomicAdd(io.stored, 1ull);
@@ -688,13 +713,20 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_step_shave(int n, c
 /* Appends the waves' regions to the pool (after the parents nobody drew) and adds the waves' counters up.
  * Workgroup w: rows before region w's = sum of fill[0 .. w), then a flat copy of its fill[w] * n elements.
  * out[0] = parents consumed, out[1] = survivors, out[2 ..] = nodes, cuts, props, revisions, solutions, out[7] = rows in
- * the solution store (workgroup 0). */
+ * the solution store (workgroup 0).
+ * Solution stream (stream != nullptr, a ring of stream_cap rows): workgroup w also moves its wave's solutions
+ * (wstat[w][4] rows at the back of region w) to stream positions stream_base + (solutions of the waves before w) ...,
+ * position p at row p mod stream_cap: the stream stays dense, in wave order.  Positions count every row appended since
+ * the stream was emptied; those below stream_limit - stream_cap have been drained.  The host sized the frontier so
+ * that the rows fit below stream_limit; if they would not, nothing is written and *stream_err is set. */
 __global__ __launch_bounds__(256) void cs_collect(const unsigned *__restrict__ fill, int waves, const uint2 *__restrict__ stage,
                                                   int K, int n, uint2 *__restrict__ pool, long long first_row, int parents,
                                                   int chunk, const unsigned *__restrict__ ticket,
                                                   const unsigned long long *__restrict__ wstat,
                                                   unsigned long long *__restrict__ out,
-                                                  const unsigned long long *__restrict__ stored) {
+                                                  const unsigned long long *__restrict__ stored,
+                                                  int32_t *__restrict__ stream, long long stream_base, long long stream_limit,
+                                                  long long stream_cap, unsigned long long *__restrict__ stream_err) {
   __shared__ unsigned long long s_red[256];
   const int w = blockIdx.x, t = threadIdx.x;
   /* chunk == 0: the launch drew every parent (cs_step_shave, sized for the worst case) */
@@ -719,6 +751,36 @@ __global__ __launch_bounds__(256) void cs_collect(const unsigned *__restrict__ f
     dst[e] = a; dst[e + 256] = b; dst[e + 512] = c; dst[e + 768] = d;
   }
   for (; e < count; e += 256) dst[e] = src[e];
+  if (stream != nullptr) { /* uniform */
+    unsigned long long sb = 0ull;
+    for (int i = t; i < w; i += 256) sb += wstat[(size_t)i * CS_STEP_STATS + 4];
+    __syncthreads(); /* s_red's last reader above is done */
+    s_red[t] = sb;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+      if (t < d) s_red[t] += s_red[t + d];
+      __syncthreads();
+    }
+    const long long sbefore = (long long)s_red[0];
+    __syncthreads();
+    const int rows = (int)wstat[(size_t)w * CS_STEP_STATS + 4];
+    const long long at = stream_base + sbefore;
+    if (rows > 0 && at + rows > stream_limit) {
+      if (t == 0) *stream_err = 1ull;
+    } else {
+      /* solution j of the wave lies at row K - 1 - j of its region; the stream rows are written flat, coalesced (rows
+       * <= stream_cap: one wrap at most) */
+      const uint2 *rsrc = stage + (size_t)w * K * n;
+      const long long r0 = at % stream_cap;
+      const int total = rows * n;
+      for (int f = t; f < total; f += 256) {
+        const int j = f / n, v = f - j * n;
+        long long r = r0 + j;
+        r = r >= stream_cap ? r - stream_cap : r;
+        stream[(size_t)r * n + v] = (int32_t)rsrc[(size_t)(K - 1 - j) * n + v].x;
+      }
+    }
+  }
   if (w == 0) {
     for (int k = 0; k < 6; k++) {
       unsigned long long x = 0ull;

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import PLAN_FAMILIES, Node, Result, SearchStats, Val, check, demangle, load_library
+from ._lib import PLAN_FAMILIES, CsolveError, Node, Result, SearchStats, Val, check, demangle, load_library
 
 STATUS_FAIL = -1
 
@@ -367,6 +367,8 @@ class Search:
         self.model = model
         self._h = C.c_void_p()
         check(load_library().csgpu_search_create(model._h, pool_capacity, max_children, C.byref(self._h)))
+        self.device = torch.device("cuda", torch.cuda.current_device())  # the engine's (csgpu_search_create's)
+        self.stats = None  # iter_solutions: the statistics of the finished run
 
     def close(self):
         if self._h:
@@ -447,6 +449,61 @@ class Search:
         k = load_library().csgpu_search_solutions(self._h, out.ctypes.data, max_solutions)
         check(k)
         return out[:k]
+
+    # ---- the solution stream (csgpu_search_set_solution_stream) ----------------------------------------------------
+    DEFAULT_STREAM_ROWS = 1 << 18
+
+    def stream_solutions(self, rows: int | None = None):
+        """turn the solution stream on with room for `rows` rows (before the first put): ALL streams every solution,
+        ANY its one, MIN / MAX each improving one.  run() then returns early (done 0) when the stream is too full for
+        its next iteration; drain and run on."""
+        check(load_library().csgpu_search_set_solution_stream(self._h, int(rows or self.DEFAULT_STREAM_ROWS)))
+
+    def pending_solutions(self):
+        """-> (rows waiting, rows of room)"""
+        rows, room = C.c_int64(), C.c_int64()
+        check(load_library().csgpu_search_pending_solutions(self._h, C.byref(rows), C.byref(room)))
+        return rows.value, room.value
+
+    def drain_solutions(self, max_rows: int | None = None) -> np.ndarray:
+        """every waiting row (at most max_rows), oldest first: [k, n_vars] int32 (host)"""
+        rows, _ = self.pending_solutions()
+        rows = rows if max_rows is None else min(rows, int(max_rows))
+        out = np.empty((max(1, rows), self.model.n_vars), dtype=np.int32)
+        cnt = C.c_int64()
+        check(load_library().csgpu_search_drain_solutions(self._h, out.ctypes.data, rows, C.byref(cnt)))
+        return out[: cnt.value]
+
+    def drain_solutions_device(self, max_rows: int | None = None) -> torch.Tensor:
+        """every waiting row (at most max_rows), oldest first: [k, n_vars] int32 on the engine's device (no host copy of
+        the rows)"""
+        rows, _ = self.pending_solutions()
+        rows = rows if max_rows is None else min(rows, int(max_rows))
+        out = torch.empty((max(1, rows), self.model.n_vars), dtype=torch.int32, device=self.device)
+        cnt = C.c_int64()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+        check(load_library().csgpu_search_drain_solutions_device(self._h, out.data_ptr(), rows, C.byref(cnt),
+                                                                 int(stream.cuda_stream)))
+        return out[: cnt.value]
+
+    def iter_solutions(self, slice_iterations: int = 64, device: bool = False):
+        """run the search to its end in slices of `slice_iterations`, yielding every drained batch of rows (numpy, or
+        torch on the engine's device); the final statistics are left in self.stats.  Turns the stream on with its
+        default size if it is off."""
+        try:
+            self.pending_solutions()
+        except CsolveError:
+            self.stream_solutions()
+        drain = self.drain_solutions_device if device else self.drain_solutions
+        while True:
+            st = self.run(slice_iterations)
+            batch = drain()
+            if len(batch):
+                yield batch
+            if st["done"]:
+                break
+        self.stats = st
 
 
 def solve_root(text: str, weights_on: bool = True) -> Model:

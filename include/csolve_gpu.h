@@ -342,6 +342,35 @@ int csgpu_search_run(csgpu_search *s, int64_t max_iterations, csgpu_search_stats
 /* copy up to `max` stored solutions ([k][n_vars] values, host memory); returns k */
 int64_t csgpu_search_solutions(const csgpu_search *s, int32_t *values, int64_t max);
 
+/* ---- the solution stream: every solution to the caller, not only the first 1,024 of the store above ----
+ * Off by default; nothing changes while it is off.  csgpu_search_set_solution_stream turns it on with room for `rows`
+ * rows of n_vars int32 values in device memory; set before the first state is put (CSGPU_E_STATE otherwise, and on
+ * an engine that shares an incumbent in either direction -- csgpu_search_share_incumbent then refuses too);
+ * rows < the widest root interval (the children of one parent at most) is CSGPU_E_ARG.
+ * What the kernels append, per objective:
+ *   ALL       every accepted solution, once: over a whole search the rows drained = stats.solutions;
+ *   ANY       the one accepted solution (the row csgpu_search_solutions gives);
+ *   MIN / MAX per iteration, the accepted solution that improved the incumbent, if one did (what the reference prints,
+ *             update_solution, csolve.c:222-244): objective values strictly improving, the last row attains
+ *             stats.best and equals csgpu_search_best_solution's.
+ * With the stream on, csgpu_search_run returns early (CSGPU_OK, done == 0) when the stream cannot take the worst case
+ * of the next iteration (ALL: room for every child of every parent it expands -- the iteration is sized so) or burst
+ * (one row per iteration); a row is never dropped nor written twice, and a kernel that still finds no room makes the
+ * call return CSGPU_E_LIMIT.  After that error the engine must be reset: until then csgpu_search_run, the drains and
+ * csgpu_search_pending_solutions answer CSGPU_E_STATE (what the kernels had appended is not trusted).
+ * The caller's loop: while (!st.done) { csgpu_search_run(s, N, &st); drain(...); }.
+ * The stream is a ring: a drain copies the rows it returns and moves nothing else, so draining in small batches costs
+ * what the batches hold.  csgpu_search_reset empties the stream and keeps it on. */
+int csgpu_search_set_solution_stream(csgpu_search *s, int64_t rows);
+/* move up to `max` waiting rows, oldest first, into `values` ([k][n_vars], host memory); *count = k (max = 0: none,
+ * the stream is left as it is).  Rows left over stay for the next call.  What the engine still holds back (the accept
+ * of its last iteration) is flushed first. */
+int csgpu_search_drain_solutions(csgpu_search *s, int32_t *values, int64_t max, int64_t *count);
+/* the same into device memory, ordered on `stream` (a hipStream_t, NULL = the null stream); returns when it is done */
+int csgpu_search_drain_solutions_device(csgpu_search *s, int32_t *d_values, int64_t max, int64_t *count, void *stream);
+/* rows waiting in the stream and rows it has room for (after csgpu_search_run or a drain: exact) */
+int csgpu_search_pending_solutions(const csgpu_search *s, int64_t *rows, int64_t *room);
+
 /* MIN/MAX: the values ([n_vars], host memory) of a solution that attains the incumbent
  * (csgpu_search_stats.best); returns 1 if there is one, 0 if no solution was found yet */
 int csgpu_search_best_solution(const csgpu_search *s, int32_t *values);
