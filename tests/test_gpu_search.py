@@ -678,3 +678,18 @@ def test_a_model_specialised_for_a_subtree_gives_the_subtrees_results(which, ste
         assert (a["nodes"], a["cuts"]) == (b["nodes"], b["cuts"])
     print(which, steps, "adjacency", info["adjacency_entries"], "->", info_s["adjacency_entries"],
           "clauses", model.n_clauses, "->", special.n_clauses, "nodes", a["nodes"], b["nodes"])
+
+
+def test_a_refused_engine_leaves_its_model_open_to_conflicts():
+    """csgpu_search_create checks max_children and pool_capacity before it counts the engine on its model: after two
+    refused engines the model still takes a learnt conflict clause (csgpu_model_add_conflict refuses one while an
+    engine holds the model's device tables)."""
+    from csolve_amd import problems
+    from csolve_amd._lib import CsolveError
+    from csolve_amd.solver import Search, solve_root
+    model = solve_root(problems.queens(8))
+    with pytest.raises(CsolveError):
+        Search(model, 1 << 20, 1 << 30)  # max_children too large
+    with pytest.raises(CsolveError):
+        Search(model, 1 << 31, 1 << 16)  # pool_capacity too large
+    model.add_conflict([(0, 1), (1, 3)])  # raised CsolveError while the refused engines were still counted
