@@ -30,6 +30,16 @@ class SearchStats(C.Structure):
                 ("best", C.c_int32), ("done", C.c_int32)]
 
 
+# csgpu_shard_solution_fn: (user, rank, rows, count, best)
+SHARD_SOLUTION_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.c_int32)
+
+
+class ShardOptions(C.Structure):
+    _fields_ = [("slice_iterations", C.c_int64), ("poll_iterations", C.c_int64), ("seed_states_per_rank", C.c_int64),
+                ("low_water", C.c_int64), ("time_limit", C.c_double), ("on_solution", SHARD_SOLUTION_FN),
+                ("user", C.c_void_p)]
+
+
 class Result(C.Structure):
     _fields_ = [("status", C.c_int32), ("props", C.c_int32), ("revisions", C.c_int32), ("rounds", C.c_int32)]
 
@@ -139,6 +149,16 @@ def load_library():
     L.csgpu_search_put.argtypes = [vp, vp, i64]
     L.csgpu_search_put_host.argtypes = [vp, vp, i64]
     L.csgpu_search_take.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.csgpu_search_take_host.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.csgpu_plan_transfers.argtypes = [vp, C.c_int, i64, i64, vp, C.POINTER(C.c_int)]
+    L.csgpu_shard_region_size.argtypes = [C.c_int, C.c_int, i64, C.POINTER(C.c_size_t)]
+    L.csgpu_shard_region_init.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, i64]
+    L.csgpu_shard_barrier.argtypes = [vp]
+    L.csgpu_text_num_vars.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    L.csgpu_shard_default_options.argtypes = [C.POINTER(ShardOptions)]
+    L.csgpu_shard_default_options.restype = None
+    L.csgpu_shard_run.argtypes = [vp, vp, C.c_int, vp, C.POINTER(ShardOptions), C.POINTER(SearchStats),
+                                  C.POINTER(SearchStats)]
     L.csgpu_search_set_best.argtypes = [vp, i32]
     L.csgpu_model_add_conflict.argtypes = [vp, i32, vp, vp]
     L.csgpu_search_put_cost.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]

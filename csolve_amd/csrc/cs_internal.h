@@ -39,6 +39,15 @@ void csgpu_internal_engine_ref(const csgpu_model *m, int delta);
 int csgpu_internal_eval_list(const csgpu_model *m, const csgpu_val *d_states, const int32_t *d_list,
                              const uint64_t *d_count, int64_t bound, int32_t *d_truth, void *stream);
 
+/* set the message csgpu_last_error() gives; returns `code` (cs_capi.hip) */
+int csgpu_internal_set_error(int code, const char *msg);
+/* what the sharded coordinator (cs_shard.c) needs to know of an engine: its objective (0 ANY 1 ALL 2 MIN 3 MAX), the
+ * objective variable (-1: none), n_vars, whether Luby restarts or restart-on-improvement are on (restarts re-put
+ * only the states put before the first iteration, so on a rank they would drop the subtrees it was given), and the
+ * rows of its solution stream (0: off).  Sets no error. */
+int csgpu_internal_search_info(const csgpu_search *s, int *objective, int *obj_var, int *n_vars, int *restarts,
+                               int64_t *stream_rows);
+
 /* start the resident single-node server of this model now (csolve_gpu.h, csgpu_debug_one_timing) instead of with the
  * first single-node call: the drop-in does it when it attaches, so that the start (stream, mailbox, code load, launch)
  * is part of the set-up and not of the driver's first propagate_clauses.  No-op for models without a server. */

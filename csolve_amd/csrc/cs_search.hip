@@ -553,6 +553,37 @@ extern "C" int csgpu_search_take(csgpu_search *s, csgpu_val *d_states, int64_t m
   return CSGPU_OK;
 }
 
+extern "C" int csgpu_search_take_host(csgpu_search *s, csgpu_val *states, int64_t max, int64_t *count) {
+  if (s == NULL || states == NULL || count == NULL || max < 0) return fail(CSGPU_E_ARG, "bad argument");
+  if (hipSetDevice(s->device) != hipSuccess) return fail(CSGPU_E_HIP, "hipSetDevice");
+  const int64_t k = max < s->top ? max : s->top;
+  *count = 0;
+  if (k == 0) return CSGPU_OK;
+  cs_val *tmp = NULL;
+  const size_t bytes = (size_t)k * s->n * sizeof(cs_val);
+  HIP_OK(hipMalloc((void **)&tmp, bytes));
+  int64_t got = 0;
+  int rc = csgpu_search_take(s, (csgpu_val *)tmp, k, &got);
+  if (rc == CSGPU_OK) {
+    const hipError_t e = hipMemcpy(states, tmp, (size_t)got * s->n * sizeof(cs_val), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) *count = got;
+    else rc = fail(CSGPU_E_HIP, hipGetErrorString(e));
+  }
+  (void)hipFree(tmp);
+  return rc;
+}
+
+extern "C" int csgpu_internal_search_info(const csgpu_search *s, int *objective, int *obj_var, int *n_vars,
+                                          int *restarts, int64_t *stream_rows) {
+  if (s == NULL) return CSGPU_E_ARG;
+  if (objective != NULL) *objective = s->objective;
+  if (obj_var != NULL) *obj_var = s->obj_var;
+  if (n_vars != NULL) *n_vars = s->n;
+  if (restarts != NULL) *restarts = s->restart_base > 0 || s->restart_on_improvement;
+  if (stream_rows != NULL) *stream_rows = s->d_stream != NULL ? s->stream_cap : 0;
+  return CSGPU_OK;
+}
+
 extern "C" int csgpu_search_set_parents(csgpu_search *s, int64_t parents_per_iteration) {
   if (s == NULL || parents_per_iteration < 1) return fail(CSGPU_E_ARG, "bad argument");
   const int64_t limit = parents_per_iteration < s->max_parents ? parents_per_iteration : s->max_parents;

@@ -272,6 +272,8 @@ int csgpu_search_put(csgpu_search *s, const csgpu_val *d_states, int64_t count);
 int csgpu_search_put_host(csgpu_search *s, const csgpu_val *states, int64_t count);
 /* remove up to `max` of the OLDEST states (the largest subtrees) into d_states; *count = how many */
 int csgpu_search_take(csgpu_search *s, csgpu_val *d_states, int64_t max, int64_t *count);
+/* the same into host memory (states: [max][n_vars]), the twin of csgpu_search_put_host */
+int csgpu_search_take_host(csgpu_search *s, csgpu_val *states, int64_t max, int64_t *count);
 /* cap on the open states expanded per iteration (default: as many as max_children allows for
  * ALL; 64 for ANY/MIN/MAX, which makes the walk depth-first enough to reach a first solution or a
  * good incumbent early with a small pool; MIN/MAX go up to 256 while the pool holds a backlog of
@@ -374,6 +376,66 @@ int csgpu_search_pending_solutions(const csgpu_search *s, int64_t *rows, int64_t
 /* MIN/MAX: the values ([n_vars], host memory) of a solution that attains the incumbent
  * (csgpu_search_stats.best); returns 1 if there is one, 0 if no solution was found yet */
 int csgpu_search_best_solution(const csgpu_search *s, int32_t *values);
+
+/* ---- the sharded search of one node: one engine per rank (process), coordinated in host C (cs_shard.c) ----
+ * The reference forks a worker that takes half of the branching interval whenever a slot is free, and its workers
+ * share one page: the incumbent, the solutions found, the timeout flag (csolve.c:86-152, 190-244).  Here the ranks
+ * exist up front, rank 0 expands the root and deals its frontier out, and the ranks exchange open states (the OLDEST of
+ * a pool: whole subtrees), the incumbent and their status through a REGION of shared memory that every rank of the
+ * node maps.  The protocol is that of ShardedSearch (csolve_amd/parallel.py); INTEGRATION.md describes it.
+ *
+ * csgpu_plan_transfers: the rebalancing plan from the ranks' pool sizes, the same on every rank (parallel.py
+ * plan_transfers): pair the richest rank with the poorest while the poorest holds fewer than `low_water` states and
+ * give half the difference, at most `max_give` (>= 1).  plan: room for world / 2 rows of {src, dst, count};
+ * *count = rows.  1 <= world <= 1024. */
+int csgpu_plan_transfers(const int64_t *pools, int world, int64_t low_water, int64_t max_give, int64_t *plan,
+                         int *count);
+/* The region: a process-shared lock and barrier (waits sleep), per rank the status words (waiting at exchange,
+ * incumbent, found, pool, timed out), the exchange table and final counters, and an inbox of `inbox_rows` states
+ * ([inbox_rows][n_vars] csgpu_val); the solutions reported on the node.  Host-only, no device: the launcher sizes it,
+ * places it in memory every rank maps (MAP_SHARED), and initialises it once before any rank starts.  One region serves
+ * one search.  1 <= world <= 8 (one rank per GPU of a node), n_vars >= 1, inbox_rows >= 1; CSGPU_E_ARG otherwise, and
+ * when `bytes` is short of the size. */
+#define CSGPU_SHARD_MAX_WORLD 8
+int csgpu_shard_region_size(int world, int n_vars, int64_t inbox_rows, size_t *bytes);
+int csgpu_shard_region_init(void *region, size_t bytes, int world, int n_vars, int64_t inbox_rows);
+/* every rank of the region waits here until all have arrived */
+int csgpu_shard_barrier(void *region);
+/* the number of variables of a problem text, for a launcher sizing the region: the host front end alone (no device, no
+ * HIP call; csgpu_model_free is a device call).  CSGPU_E_PARSE with the front end's message. */
+int csgpu_text_num_vars(const char *text, int weights_on, int *n_vars);
+
+/* rows: [count][n_vars] values; best: the objective value of the row (MIN / MAX), 0 for ANY / ALL.  Called with the
+ * region's lock held, so what one rank writes never interleaves with another's output. */
+typedef void (*csgpu_shard_solution_fn)(void *user, int rank, const int32_t *rows, int64_t count, int32_t best);
+
+typedef struct csgpu_shard_options {
+  int64_t slice_iterations;     /* iterations between exchanges (64) */
+  int64_t poll_iterations;      /* a slice runs in bursts of this many; the region is looked at between them (4) */
+  int64_t seed_states_per_rank; /* rank 0 expands the root until its pool holds this many x world (64) */
+  int64_t low_water;            /* a rank with fewer open states is given some at an exchange (64) */
+  double time_limit;            /* seconds, 0 = none: every rank stops at the same exchange (-t) */
+  csgpu_shard_solution_fn on_solution; /* nullable */
+  void *user;
+} csgpu_shard_options;
+void csgpu_shard_default_options(csgpu_shard_options *options);
+
+/* One rank's whole search on engine `s` (fresh: nothing put, nothing run; a solution stream, if on, is drained here).
+ * Every rank of the region calls it with its own engine of the same model and the same options; rank 0 passes the
+ * root state ([n_vars], host memory), the others NULL.  Solutions go to options->on_solution as they are found:
+ *   ALL       every row, as the engine's solution stream gives it (the stream must be on when there is a callback);
+ *   ANY       the node's first row only;
+ *   MIN / MAX one row at the end: the row attaining the node's optimum, of the lowest rank that holds one.
+ * local: this rank's engine statistics (rank 0's include expanding the root).  totals: the counters summed over the
+ * ranks, best = min / max over them, pool = what was left open (non-zero after a time limit), done = nothing left
+ * open or ANY solved; solutions = ALL: the rows (the sum over ranks), ANY: 1 if one was found, MIN / MAX: the sum of
+ * the ranks' accepted solutions.  With world > 1, an engine whose restarts are on (csgpu_search_set_restart > 0 for
+ * ANY, which is the default, or csgpu_search_set_restart_on_improvement) is refused with CSGPU_E_STATE before the
+ * rank touches the region: a restart re-puts the states put before the first iteration and would drop what the rank
+ * was given later.  world == 1 runs the same search as csgpu_search_run to completion.  A rank whose call fails
+ * leaves the others waiting at the next barrier: the launcher ends them (the command line's -j does). */
+int csgpu_shard_run(csgpu_search *s, void *region, int rank, const csgpu_val *root, const csgpu_shard_options *options,
+                    csgpu_search_stats *local, csgpu_search_stats *totals);
 
 /* `count` values of variable `var` on ONE parent state, host buffers: node i assigns values[i].  results and
  * states_out ([count][n_vars]; rows of inconsistent nodes unspecified) are host memory.  What the reference
