@@ -44,6 +44,19 @@ class Result(C.Structure):
     _fields_ = [("status", C.c_int32), ("props", C.c_int32), ("revisions", C.c_int32), ("rounds", C.c_int32)]
 
 
+# csgpu_solve_many: status of an instance
+MANY_DONE, MANY_LIMIT, MANY_BAD_ROOT = 0, 1, 2
+
+
+class ManyResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("root_props", C.c_int32), ("nodes", C.c_int64), ("cuts", C.c_int64),
+                ("props", C.c_int64), ("solutions", C.c_int64)]
+
+
+class ManyOptions(C.Structure):
+    _fields_ = [("objective", C.c_int32), ("reserved", C.c_int32), ("max_nodes", C.c_int64)]
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Names of every function declared in include/csolve_gpu.h."""
     text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
@@ -192,6 +205,10 @@ def load_library():
     L.csgpu_search_set_strategy.argtypes = [vp, C.c_int, C.c_int]
     L.csgpu_search_set_restart_on_improvement.argtypes = [vp, C.c_int]
     L.csgpu_internal_plan_symbol.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp]
+    L.csgpu_internal_many_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_internal_many_waves.argtypes = [vp, i64]
+    L.csgpu_internal_many_waves.restype = i64
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L

@@ -17,6 +17,7 @@
 #include "cs_kernels.hip.h"
 #include "cs_shave.hip.h"
 #include "cs_step.hip.h"
+#include "cs_dive.hip.h"
 #include "cs_chain.hip.h"
 #include "cs_internal.h"
 
@@ -67,6 +68,7 @@ struct cs_kernel_plan {
   cs_planned shave, shave_trace;   /* kernel 7 (the instantiation whose FULL matches the model); its tracing variant */
   cs_planned server;               /* the resident single-node server */
   cs_planned step_shave, step_packed, step_import;
+  cs_planned dive;                 /* cs_dive_shave (csgpu_solve_many): not one of csgpu_internal_plan_symbol's families */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -99,6 +101,12 @@ struct csgpu_model {
   void *d_dense_tab;
   void *d_packed_tab; /* kernel 5: 16-bit table relative to the pushing variable */
   int *d_root_lo;
+  int *d_root_hi;    /* csgpu_solve_many: a root row must lie inside the root domains */
+  /* csgpu_solve_many: the waves' stacks (sized at the first call, grown when a later call launches more waves) and the
+   * ticket counters of cs_dive_shave, which the kernel leaves at zero */
+  void *d_many_stack;
+  int64_t many_stack_waves;
+  unsigned *d_many_tickets;
   int *d_sym_off;
   void *d_sym_packed;
   int n_cus;
@@ -291,6 +299,13 @@ static void free_device(csgpu_model *m) {
   m->d_lit = NULL;
   (void)hipFree(m->d_adj_packed);
   (void)hipFree(m->d_root_lo);
+  (void)hipFree(m->d_root_hi);
+  (void)hipFree(m->d_many_stack);
+  (void)hipFree(m->d_many_tickets);
+  m->d_root_hi = NULL;
+  m->d_many_stack = NULL;
+  m->d_many_tickets = NULL;
+  m->many_stack_waves = 0;
   (void)hipFree(m->d_sym_off);
   (void)hipFree(m->d_sym_packed);
   (void)hipFree(m->d_dense_tab);
@@ -774,6 +789,19 @@ static const void *step_shave_kernel(int width, int n_vars, int slots, int full)
 #undef CS_PICK_S
 }
 
+/* ---- cs_dive.hip.h: a depth-first search per wave (csgpu_solve_many); the slot count is always a run-time value ---- */
+static const void *dive_kernel(int width, int n_vars) {
+#define CS_PICK(E)                                                                                 \
+  switch (cs_dense_strides(n_vars)) {                                                              \
+  case 1: return (const void *)cs_dive_shave<E, 1>;                                                 \
+  case 2: return (const void *)cs_dive_shave<E, 2>;                                                 \
+  default: return (const void *)cs_dive_shave<E, 4>;                                                \
+  }
+  if (width == 1) { CS_PICK(unsigned char) }
+  CS_PICK(unsigned short)
+#undef CS_PICK
+}
+
 /* ---- the resident single-node server (cs_shave.hip.h) ---- */
 static const void *shave_server_kernel(int width, int n_vars, int slots) {
   const int r = cs_dense_strides(n_vars);
@@ -1057,6 +1085,16 @@ static int plan_dense_table(csgpu_model *m) {
     m->plan.server = m->plan.shave_trace;
     m->plan.server.fn = shave_server_kernel(width, n, slots);
   }
+  /* cs_dive_shave: the table alone; the upper bounds of the root domains for its check of the root rows */
+  if ((rc = plan_kernel(&m->plan.dive, dive_kernel(width, n), table, waves))) return rc;
+  {
+    int *hi = (int *)malloc((size_t)n * sizeof(int));
+    if (hi == NULL) return set_err(CSGPU_E_ARG, "out of memory");
+    for (int32_t v = 0; v < n; v++) hi[v] = h->dom[v].hi;
+    rc = upload(hi, (size_t)n * sizeof(int), &m->d_root_hi);
+    free(hi);
+    if (rc) return rc;
+  }
   HIP_TRY(hipMalloc((void **)&m->d_tickets, (size_t)CS_TICKET_SLOTS * CS_TICKET_SLOT_WORDS * sizeof(unsigned)));
   HIP_TRY(hipMemset(m->d_tickets, 0, (size_t)CS_TICKET_SLOTS * CS_TICKET_SLOT_WORDS * sizeof(unsigned)));
   m->ticket_slots = CS_TICKET_SLOTS;
@@ -1188,6 +1226,21 @@ extern "C" int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char
   if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
     return set_err(CSGPU_E_STATE, "plan family %d: the kernel handle has no dynamic symbol", family);
   if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "plan family %d: symbol longer than the buffer", family);
+  strcpy(buf, info.dli_sname);
+  return CSGPU_OK;
+}
+
+/* the same for cs_dive_shave, which is no family of the list above (the plan dictionary stays what it was) */
+extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len) {
+  if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  buf[0] = '\0';
+  const void *fn = m->plan.dive.fn;
+  if (fn == NULL) return CSGPU_OK;
+  Dl_info info;
+  if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
+    return set_err(CSGPU_E_STATE, "cs_dive_shave: the kernel handle has no dynamic symbol");
+  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "cs_dive_shave: symbol longer than the buffer");
   strcpy(buf, info.dli_sname);
   return CSGPU_OK;
 }
@@ -1449,6 +1502,70 @@ static int launch_shave(const csgpu_model *m, const csgpu_val *d_states_in, cons
   void *args[] = { &n, &tab_d, &slots, &dmin_d, &root_lo_d, &sym_off, &d_states_in, &d_nodes, &d_states_out, &d_results,
                    &nb_d, &d_batch, &csz, &tickets, &no_trace, &no_trace_n, &no_trace_cap };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)g), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
+  return CSGPU_OK;
+}
+
+/* ---- csgpu_solve_many: a depth-first search per wavefront (cs_dive.hip.h) ---- */
+
+static_assert(sizeof(csgpu_many_result) == sizeof(cs_dive_result) && sizeof(csgpu_many_result) == 40, "csgpu_many_result layout");
+
+extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count) {
+  if (m == NULL || !m->finalized || m->plan.dive.fn == NULL || count < 1) return 0;
+  const cs_planned *k = &m->plan.dive;
+  int64_t grid = (int64_t)m->n_cus * k->per_cu;
+  const int64_t by_count = (count + k->waves - 1) / k->waves;
+  if (grid > by_count) grid = by_count;
+  return grid * k->waves;
+}
+
+extern "C" int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                                csgpu_many_result *d_results, int32_t *d_solutions, void *stream) {
+  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every instance has a budget");
+  if (options->objective == CS_OBJ_MIN || options->objective == CS_OBJ_MAX)
+    return set_err(CSGPU_E_LIMIT, "csgpu_solve_many searches with ANY or ALL: MIN / MAX are not supported");
+  if (options->objective != CS_OBJ_ANY && options->objective != CS_OBJ_ALL) return set_err(CSGPU_E_ARG, "no objective %d", options->objective);
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (m->plan.dive.fn == NULL)
+    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
+                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
+  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  if (count == 0) return CSGPU_OK;
+  csgpu_model *mm = const_cast<csgpu_model *>(m);
+  const cs_planned *k = &m->plan.dive;
+  const int n = m->host->n_vars;
+  const int64_t waves = csgpu_internal_many_waves(m, count);
+  const int frames = n; /* open levels + 1: at most n - 1 frames are ever in use (cs_dive.hip.h) */
+  if (mm->d_many_tickets == NULL) {
+    quiesce_servers();
+    HIP_TRY(hipMalloc((void **)&mm->d_many_tickets, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
+    HIP_TRY(hipMemset(mm->d_many_tickets, 0, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
+  }
+  if (mm->many_stack_waves < waves) { /* one call in flight per model: nothing reads the old workspace */
+    quiesce_servers();
+    if (mm->d_many_stack != NULL) (void)hipFree(mm->d_many_stack);
+    mm->d_many_stack = NULL;
+    mm->many_stack_waves = 0;
+    HIP_TRY(hipMalloc(&mm->d_many_stack, (size_t)waves * (size_t)frames * ((size_t)n + 1) * sizeof(cs_val)));
+    mm->many_stack_waves = waves;
+  }
+  cs_dive_io io;
+  io.roots = (const cs_val *)d_roots;
+  io.count = (int)count;
+  io.all = options->objective == CS_OBJ_ALL;
+  io.max_nodes = (long long)options->max_nodes;
+  io.results = (cs_dive_result *)d_results;
+  io.solutions = d_solutions;
+  io.stack = (cs_val *)mm->d_many_stack;
+  io.frames = frames;
+  io.tickets = mm->d_many_tickets;
+  int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
+  const void *tab_d = m->d_dense_tab;
+  const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
+  size_t tab_bytes = m->dense_bytes;
+  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io };
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
 

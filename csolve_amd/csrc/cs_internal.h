@@ -57,6 +57,10 @@ int csgpu_internal_server_warm(csgpu_model *m);
  * family is not planned).  Families in this order (csolve_amd/_lib.py PLAN_FAMILIES): events, traced, rounds, lds,
  * bitset, regs[0..3], packed, shave, shave_trace, server, step_shave, step_packed, step_import */
 int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char *buf, size_t len);
+/* the same for cs_dive_shave (csgpu_solve_many), which is not one of those families; and the waves a call with `count`
+ * instances launches (0: the model does not qualify) */
+int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len);
+int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count);
 
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */
 typedef struct csgpu_step_launch {

@@ -108,6 +108,29 @@ def sudoku(box: int = 3, revealed: float = 0.4, seed: int = 1, objective: str = 
     return "\n".join(lines) + "\n"
 
 
+def sudoku_roots(box: int, revealed: float, seeds, objective: str = "ANY"):
+    """Many sudokus as instances of ONE model (Model.solve_many): -> (text of the EMPTY box^2 x box^2 model -- the
+    all_different and bound lines of sudoku(), no givens --, int32 array [len(seeds), n_cells, 2] of root rows).  Row k
+    holds the givens sudoku(box, revealed, seeds[k]) writes as single values and 1 .. box^2 elsewhere; cells are
+    numbered row by row, which is the order the empty model declares them in."""
+    import numpy as np
+    n = box * box
+    text = "\n".join(line for line in sudoku(box, 0.0, 0).split("\n") if not line.startswith("#"))
+    text = text.replace("ANY;", f"{objective};", 1)
+    text = f"# sudoku {n}x{n}, no givens: the model of sudoku_roots\n" + text
+    roots = np.empty((len(seeds), n * n, 2), dtype=np.int32)
+    roots[:, :, 0] = 1
+    roots[:, :, 1] = n
+    for k, seed in enumerate(seeds):
+        grid = sudoku_solution(box, seed)
+        rng = LCG(seed ^ 0x9E3779B97F4A7C15)
+        cells = [(r, c) for r in range(n) for c in range(n)]
+        rng.shuffle(cells)
+        for r, c in cells[: int(round(revealed * n * n))]:
+            roots[k, r * n + c] = grid[r][c]
+    return text, roots
+
+
 def schedule(tasks: int = 16, seed: int = 1, horizon_slack: int = 3) -> str:
     """Single-machine scheduling after examples/schedule.txt: per task release, WCET and
     deadline, pairwise non-overlap disjunctions, MIN end."""

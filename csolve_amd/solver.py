@@ -10,7 +10,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import PLAN_FAMILIES, CsolveError, Node, Result, SearchStats, Val, check, demangle, load_library
+from ._lib import (PLAN_FAMILIES, CsolveError, ManyOptions, ManyResult, Node, Result, SearchStats, Val, check, demangle,
+                   load_library)
 
 STATUS_FAIL = -1
 
@@ -204,6 +205,55 @@ class Model:
                                                    states_out.data_ptr(), results.data_ptr(), B,
                                                    _stream_ptr(stream)))
         return states_out, results
+
+    # ---- many instances of this model in one call (csgpu_solve_many) -------------------------------
+    MANY_OBJECTIVES = {"ANY": 0, "ALL": 1, "MIN": 2, "MAX": 3}
+
+    def solve_many(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None) -> dict:
+        """K instances of this model, a depth-first search per wavefront (csgpu_solve_many; the model must qualify for
+        kernel 7).  roots: int32 [K, n_vars, 2] root rows inside the model's root domains, a torch tensor on the device
+        (a numpy array is uploaded).  max_nodes: the budget per instance (children tried); there is no "unlimited".
+        -> dict of device tensors [K]: status (0 done, 1 stopped at max_nodes, 2 bad root row), root_props, nodes, cuts,
+        props, solutions, and with solutions=True `first` [K, n_vars] int32: the first solution of every instance that
+        has one (zeros elsewhere).  Asynchronous on the stream; one call in flight per model."""
+        L = load_library()
+        n = self.n_vars
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        opt = ManyOptions(obj, 0, int(max_nodes))
+        if not torch.is_tensor(roots):
+            roots = np.ascontiguousarray(roots, dtype=np.int32)
+            assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
+            if not self.qualifies(7):
+                # not finalized, or not a model of kernel 7: the library says which, before any device call (it
+                # touches neither buffer), and nothing is uploaded for it
+                check(L.csgpu_solve_many(self._h, roots.ctypes.data, roots.shape[0], C.byref(opt), roots.ctypes.data,
+                                         None, None))
+            roots = torch.from_numpy(roots).cuda()
+        assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
+        assert roots.dim() == 3 and tuple(roots.shape[1:]) == (n, 2), "roots is [K, n_vars, 2]"
+        K = roots.shape[0]
+        buf = torch.zeros((max(K, 1), 5), dtype=torch.int64, device=roots.device)  # csgpu_many_result: 40 bytes
+        res = buf[:K]
+        first = torch.zeros((K, n), dtype=torch.int32, device=roots.device) if solutions else None
+        # (an empty batch still goes through the library's checks: any non-null pointer stands for its rows)
+        check(L.csgpu_solve_many(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                                 first.data_ptr() if solutions and K else None, _stream_ptr(stream)))
+        head = res.view(torch.int32)  # [K, 10]: the two 32-bit fields lead the record
+        out = {"status": head[:, 0], "root_props": head[:, 1], "nodes": res[:, 1], "cuts": res[:, 2], "props": res[:, 3],
+               "solutions": res[:, 4]}
+        if solutions:
+            out["first"] = first
+        return out
+
+    def many_kernel(self):
+        """the cs_dive_shave instantiation solve_many launches for this model (template-id), None if it does not qualify"""
+        buf = C.create_string_buffer(1024)
+        check(load_library().csgpu_internal_many_symbol(self._h, buf, len(buf)))
+        return demangle(buf.value.decode()) if buf.value else None
+
+    def many_waves(self, count: int) -> int:
+        """waves a solve_many of `count` instances launches"""
+        return int(load_library().csgpu_internal_many_waves(self._h, int(count)))
 
     def forbidden_words(self) -> int:
         """64-bit words of forbidden-set per variable (0: the model does not qualify)"""

@@ -219,6 +219,50 @@ int csgpu_propagate_batch_fb(const csgpu_model *m, const csgpu_val *d_states_in,
                              const csgpu_node *d_nodes, csgpu_val *d_states_out, uint64_t *d_forb_out,
                              csgpu_result *d_results, int64_t batch, void *stream);
 
+/* ---- many instances of one model in one call: a depth-first search per wavefront ----
+ * For models that qualify for kernel 7 (csgpu_model_qualifies(m, 7): a pure != network of at most 256 variables whose
+ * dense pair table fits LDS).  An instance is a row of root domains d_roots[i][n_vars] INSIDE the model's own root
+ * domains (same clauses, other givens -- e.g. the empty sudoku model and one row of givens per puzzle).  One wavefront
+ * takes an instance from its root row to its answer: the root node (every valued variable pushes), then depth-first
+ * with the engine's default rule (the open variable with the smallest interval, ties to the lowest index; values in
+ * ascending order; a child is the assignment followed by the fixpoint).  Instances are drawn by ticket; the launch
+ * keeps no more than the resident waves of the device busy, whatever `count` is.
+ *   options->objective  0 ANY: stop at an instance's first solution; 1 ALL: walk its whole tree and count
+ *   options->max_nodes  budget per instance (children tried), > 0: there is no "unlimited".  An instance that would
+ *                       need one more node stops with status CSGPU_MANY_LIMIT, nodes == max_nodes and the counters
+ *                       of what it did; the caller re-runs such an instance through a csgpu_search
+ *   d_results[i]        status; nodes = children tried (a value that a valued neighbour forbids is a node and a cut),
+ *                       cuts = inconsistent children, props = narrowings of the consistent children (the reference's
+ *                       PROPS on such networks), solutions; root_props = narrowings of the root node (0 when the root
+ *                       is inconsistent).  An inconsistent root is no error: CSGPU_MANY_DONE, 0 nodes, 0 solutions.
+ *                       A row outside the model's root domains, or with lo > hi, is CSGPU_MANY_BAD_ROOT and is not
+ *                       searched (the device tables are relative to the root domains, and finalize has dropped the
+ *                       clauses that are true on all of them)
+ *   d_solutions         NULL, or [count][n_vars] int32: row i receives the FIRST solution of instance i (ANY and ALL);
+ *                       rows of instances without a solution are left untouched
+ * Device pointers; asynchronous on `stream`, no host synchronisation inside once the model's workspace exists.  That
+ * workspace (the waves' stacks: waves x n_vars frames x (n_vars + 1) x 8 bytes with min(count, resident waves) waves,
+ * and the ticket counters, which the kernel leaves at zero) belongs to the model: it is allocated by the first call,
+ * grown by a call that launches more waves, and freed with the model.  Hence ONE call in flight per model: a second
+ * call may be queued behind the first on the same stream, never on another stream or from another thread.
+ * Errors before any HIP call: null model / roots / results / options, count < 0, max_nodes <= 0 -> CSGPU_E_ARG;
+ * objective MIN / MAX -> CSGPU_E_LIMIT; model not finalized -> CSGPU_E_STATE; model does not qualify for kernel 7 ->
+ * CSGPU_E_LIMIT.  count == 0 -> CSGPU_OK, nothing is launched. */
+#define CSGPU_MANY_DONE 0     /* ANY: solved, or proven to have no solution; ALL: whole tree walked */
+#define CSGPU_MANY_LIMIT 1    /* stopped at max_nodes; the counters hold what was done */
+#define CSGPU_MANY_BAD_ROOT 2 /* row outside the model's root domains, or lo > hi: not searched */
+typedef struct csgpu_many_result {
+  int32_t status, root_props;
+  int64_t nodes, cuts, props, solutions;
+} csgpu_many_result;
+typedef struct csgpu_many_options {
+  int32_t objective; /* 0 ANY, 1 ALL */
+  int32_t reserved;  /* 0 */
+  int64_t max_nodes;
+} csgpu_many_options;
+int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                     csgpu_many_result *d_results, int32_t *d_solutions, void *stream);
+
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */
 int csgpu_eval_batch(const csgpu_model *m, const csgpu_val *d_states, int32_t *d_truth, int64_t batch,

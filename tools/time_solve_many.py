@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""K instances of one model through Model.solve_many, and the SAME instances through the per-instance loop that was the
+only route before it: one Search, reset and seeded per instance (the instance's root fixpoint by kernel 7, put, run),
+one after the other -- on a sample of the instances when all K would take minutes (the output says how many).
+
+Prints one JSON line: instances/s and nodes/s of both routes, their ratio, the spread over the repetitions, the launch
+time as a function of max_nodes (bulk against tail), and a seeded sample of the device's answers re-checked against the
+oracle walk (tests/many_walk.py).
+
+  python tools/time_solve_many.py --set sudoku9 [--count 65536] [--reps 5] [--loop-sample 256] [--check 32]
+  sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY)
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from csolve_amd import problems  # noqa: E402
+from csolve_amd.solver import Search, solve_root  # noqa: E402
+
+
+def instances(which, count):
+    if which == "sudoku9":
+        parts, per = [], -(-count // 11)
+        for i in range(11):  # revealed 0.35, 0.36, ... 0.45
+            text, rows = problems.sudoku_roots(3, 0.35 + 0.01 * i, list(range(1 + i * per, 1 + (i + 1) * per)))
+            parts.append(rows)
+        return text, np.concatenate(parts)[:count], "ANY", 1 << 16
+    if which == "sudoku16":
+        text, rows = problems.sudoku_roots(4, 0.6, list(range(1, count + 1)))
+        return text, rows, "ANY", 1 << 16
+    if which == "queens12":
+        import many_sets
+        return problems.queens(12, "ALL"), many_sets.queens_two(12, count, 7), "ALL", 1 << 20
+    raise SystemExit(f"no set {which}")
+
+
+def commit():
+    try:
+        return open(os.path.join(ROOT, "csolve_amd", "csrc", "build", "COMMIT")).read().strip()
+    except OSError:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--set", default="sudoku9")
+    ap.add_argument("--count", type=int, default=None)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--loop-sample", type=int, default=256)
+    ap.add_argument("--check", type=int, default=32)
+    ap.add_argument("--seed", type=int, default=1)
+    args = ap.parse_args()
+    count = args.count or {"sudoku9": 65536, "queens12": 16384, "sudoku16": 4096}[args.set]
+    text, roots, objective, budget = instances(args.set, count)
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+
+    def many(max_nodes, rows=dev):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = model.solve_many(rows, objective, max_nodes=max_nodes)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    many(budget)  # warm-up: code load, workspace
+    many(budget)
+    times = []
+    for _ in range(args.reps):
+        dt, out = many(budget)
+        times.append(dt)
+    nodes = int(out["nodes"].sum())
+    status = torch.bincount(out["status"].long(), minlength=3).tolist()
+    t_many = statistics.median(times)
+    # bulk against tail: the launch time under smaller budgets (instances beyond a budget stop there)
+    per_budget = {}
+    largest = int(out["nodes"].max())
+    for b in sorted({16, 64, 256, 1024, 4096, max(1, largest)}):
+        if b <= budget:
+            per_budget[b] = round(statistics.median(many(b)[0] for _ in range(3)) * 1e3, 3)
+
+    # the per-instance loop: one Search, reset and seeded per instance
+    rng = np.random.default_rng(args.seed)
+    sample = np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
+    search = Search(model, 1 << 18, 1 << 14)
+    node = torch.tensor([[-1, 0, 0, 0]], dtype=torch.int32, device="cuda")
+
+    def loop():
+        total = 0
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for i in sample:
+            state, res = model.propagate(dev[i:i + 1], node)
+            st = int(res[0, 0])
+            if st <= 0:  # inconsistent, or solved by the root node
+                continue
+            search.reset()
+            search.put(state)
+            total += search.run()["nodes"]
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, total
+
+    loop()  # warm-up
+    loop_times = []
+    for _ in range(max(2, args.reps // 2)):
+        dt, loop_nodes = loop()
+        loop_times.append(dt)
+    t_loop = statistics.median(loop_times)
+
+    # a seeded sample of the answers against the oracle walk
+    import many_walk
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    want = many_walk.dive_many(text, roots[picks], objective, budget)
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    checked_ok = all((host[f][picks] == want[f]).all() for f in ("status", "root_props", "nodes", "cuts", "props", "solutions"))
+    has = want["solutions"] > 0
+    checked_ok = bool(checked_ok and (host["first"][picks][has] == want["first"][has]).all())
+
+    many_rate, loop_rate = count / t_many, len(sample) / t_loop
+    print(json.dumps({
+        "tool": "time_solve_many", "commit": commit(), "command": " ".join(sys.argv), "set": args.set, "objective": objective,
+        "instances": count, "max_nodes": budget, "status_counts": status, "nodes": nodes, "largest_tree": largest,
+        "waves": model.many_waves(count), "kernel": model.many_kernel(),
+        "solve_many_ms": {"median": round(t_many * 1e3, 3), "min": round(min(times) * 1e3, 3), "max": round(max(times) * 1e3, 3),
+                          "reps": args.reps},
+        "solve_many_instances_per_s": round(many_rate), "solve_many_nodes_per_s": round(nodes / t_many),
+        "launch_ms_by_max_nodes": per_budget,
+        "loop_instances": len(sample), "loop_nodes": loop_nodes,
+        "loop_s": {"median": round(t_loop, 4), "min": round(min(loop_times), 4), "max": round(max(loop_times), 4),
+                   "reps": len(loop_times)},
+        "loop_instances_per_s": round(loop_rate), "loop_nodes_per_s": round(loop_nodes / t_loop),
+        "ratio_instances_per_s": round(many_rate / loop_rate, 1),
+        "oracle_checked": len(picks), "oracle_ok": checked_ok,
+    }))
+    return 0 if checked_ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
