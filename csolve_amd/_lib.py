@@ -46,6 +46,7 @@ class Result(C.Structure):
 
 # csgpu_solve_many: status of an instance
 MANY_DONE, MANY_LIMIT, MANY_BAD_ROOT = 0, 1, 2
+MANY_BAD_SLOT = 3  # csgpu_solve_many_resume: the slot number names no checkpoint
 
 
 class ManyResult(C.Structure):
@@ -209,6 +210,16 @@ def load_library():
     L.csgpu_internal_many_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_internal_many_waves.argtypes = [vp, i64]
     L.csgpu_internal_many_waves.restype = i64
+    L.csgpu_internal_many_resume_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_many_checkpoint_bytes.argtypes = [vp]
+    L.csgpu_many_checkpoint_bytes.restype = C.c_size_t
+    L.csgpu_many_checkpoints_create.argtypes = [vp, i64, C.POINTER(vp)]
+    L.csgpu_many_checkpoints_reset.argtypes = [vp, vp]
+    L.csgpu_many_checkpoints_free.argtypes = [vp]
+    L.csgpu_many_checkpoints_free.restype = None
+    L.csgpu_solve_many_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_resume.argtypes = [vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
+    L.csgpu_many_checkpoint_states.argtypes = [vp, C.c_int32, vp, i64, C.POINTER(i64), vp]
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L

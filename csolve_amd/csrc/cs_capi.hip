@@ -69,6 +69,7 @@ struct cs_kernel_plan {
   cs_planned server;               /* the resident single-node server */
   cs_planned step_shave, step_packed, step_import;
   cs_planned dive;                 /* cs_dive_shave (csgpu_solve_many): not one of csgpu_internal_plan_symbol's families */
+  cs_planned dive_ck;              /* cs_dive_resume (csgpu_solve_many_checkpointed / _resume): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -802,6 +803,19 @@ static const void *dive_kernel(int width, int n_vars) {
 #undef CS_PICK
 }
 
+/* the same loop with checkpoints (csgpu_solve_many_checkpointed / _resume) */
+static const void *dive_resume_kernel(int width, int n_vars) {
+#define CS_PICK(E)                                                                                 \
+  switch (cs_dense_strides(n_vars)) {                                                              \
+  case 1: return (const void *)cs_dive_resume<E, 1>;                                                \
+  case 2: return (const void *)cs_dive_resume<E, 2>;                                                \
+  default: return (const void *)cs_dive_resume<E, 4>;                                               \
+  }
+  if (width == 1) { CS_PICK(unsigned char) }
+  CS_PICK(unsigned short)
+#undef CS_PICK
+}
+
 /* ---- the resident single-node server (cs_shave.hip.h) ---- */
 static const void *shave_server_kernel(int width, int n_vars, int slots) {
   const int r = cs_dense_strides(n_vars);
@@ -1017,25 +1031,39 @@ static int plan_lds_resident(csgpu_model *m) {
 
 /* forbidden-set kernel (3): additionally root intervals of at most 256 values, and only when the
  * host domains really are the root state (the bit windows are anchored at the root bounds) */
-static int plan_forbidden_sets(csgpu_model *m) {
+/* its shape from the host image alone: waves per workgroup (0: the model does not qualify), set words per variable and
+ * LDS bytes per workgroup */
+static int forbidden_sets_shape(const csgpu_model *m, int *fw_out, size_t *lds_out) {
   const cs_model *h = m->host;
-  if (m->img->sym_width == 0 || m->not_root) return CSGPU_OK;
+  if (m->img->sym_width == 0 || m->not_root) return 0;
   int64_t width = 1;
   for (int32_t v = 0; v < h->n_vars; v++) {
     const int64_t w = (int64_t)h->dom[v].hi - (int64_t)h->dom[v].lo + 1;
     if (w > width) width = w;
   }
   const int fw = width <= 64 ? 1 : (width <= 128 ? 2 : (width <= 256 ? 4 : 0));
-  if (!fw) return CSGPU_OK;
+  if (!fw) return 0;
+  const size_t n_words = ((size_t)h->n_vars + 31) / 32; /* cs_tables.n_words */
   const size_t off_bytes = (((size_t)h->n_vars * 2 * sizeof(int)) + 15) & ~(size_t)15;
   const size_t base_bytes = (((size_t)h->n_vars * sizeof(int)) + 15) & ~(size_t)15;
   const size_t adj_bytes = (((size_t)m->img->sym_n_adj * (size_t)m->img->sym_width) + 15) & ~(size_t)15;
-  const size_t sl = ((size_t)h->n_vars * sizeof(cs_val) + (size_t)h->n_vars * fw * 8 +
-                     (2 * (size_t)m->tab.n_words + 2) * sizeof(unsigned) + 15) & ~(size_t)15;
+  const size_t sl = ((size_t)h->n_vars * sizeof(cs_val) + (size_t)h->n_vars * fw * 8 + (2 * n_words + 2) * sizeof(unsigned) + 15) &
+                    ~(size_t)15;
   int waves = 16;
   for (; waves >= 1; waves--) /* as many waves as fit next to the tables */
     if (off_bytes + base_bytes + adj_bytes + (size_t)waves * sl <= CS_CU_LDS) break;
-  if (waves < 1) return CSGPU_OK;
+  if (waves < 1) return 0;
+  *fw_out = fw;
+  *lds_out = off_bytes + base_bytes + adj_bytes + (size_t)waves * sl;
+  return waves;
+}
+
+static int plan_forbidden_sets(csgpu_model *m) {
+  const cs_model *h = m->host;
+  int fw = 0;
+  size_t lds = 0;
+  const int waves = forbidden_sets_shape(m, &fw, &lds);
+  if (!waves) return CSGPU_OK;
   m->fb_words = fw;
   int *lo = (int *)malloc((size_t)(h->n_vars ? h->n_vars : 1) * sizeof(int));
   for (int32_t v = 0; v < h->n_vars; v++) lo[v] = h->dom[v].lo;
@@ -1045,25 +1073,33 @@ static int plan_forbidden_sets(csgpu_model *m) {
   if ((rc = upload(m->img->sym_off, ((size_t)h->n_vars + 1) * sizeof(int), &m->d_sym_off))) return rc;
   if ((rc = upload(m->img->sym_packed, (size_t)m->img->sym_n_adj * (size_t)m->img->sym_width, (int **)&m->d_sym_packed)))
     return rc;
-  if ((rc = plan_kernel(&m->plan.bitset, ne_bitset_kernel(m->img->sym_width, fw, h->n_vars),
-                        off_bytes + base_bytes + adj_bytes + (size_t)waves * sl, waves)))
-    return rc;
+  if ((rc = plan_kernel(&m->plan.bitset, ne_bitset_kernel(m->img->sym_width, fw, h->n_vars), lds, waves))) return rc;
   if (m->plan.bitset.per_cu < 1) m->plan.bitset.per_cu = 1;
   return CSGPU_OK;
 }
 
 /* the dense pair table in LDS: the register-resident forbidden-set kernel (4), the interval-only kernel (7) with its
  * tracing variant, the server and cs_step_shave; kernel 7's ticket counters */
-static int plan_dense_table(csgpu_model *m) {
-  const cs_model *h = m->host;
-  if (!m->fb_words || m->img->dense_width == 0) return CSGPU_OK;
-  const int n = h->n_vars, width = m->img->dense_width, slots = m->img->dense_slots;
+/* waves per workgroup of the kernels with the dense table in LDS, from the host image alone (0: the model has no such
+ * table, or it does not fit) */
+static int dense_table_waves(const csgpu_model *m, size_t *bytes_out) {
+  if (m->img->dense_width == 0) return 0;
   /* the dense table must fit a CU's LDS; the workgroup size that keeps the most waves resident (32 per CU at most),
    * smaller workgroups on ties */
-  const size_t bytes = (size_t)n * slots * m->img->dense_cols * width;
+  const size_t bytes = (size_t)m->host->n_vars * m->img->dense_slots * m->img->dense_cols * m->img->dense_width;
   int best = 0, waves = 0;
   for (int w = 4; w <= 16; w <<= 1)
     if (resident_per_cu(bytes, w) * w > best) { best = resident_per_cu(bytes, w) * w; waves = w; }
+  *bytes_out = bytes;
+  return waves;
+}
+
+static int plan_dense_table(csgpu_model *m) {
+  const cs_model *h = m->host;
+  if (!m->fb_words) return CSGPU_OK;
+  const int n = h->n_vars, width = m->img->dense_width, slots = m->img->dense_slots;
+  size_t bytes = 0;
+  const int waves = dense_table_waves(m, &bytes);
   if (!waves) return CSGPU_OK;
   m->dense_bytes = bytes;
   int rc;
@@ -1087,6 +1123,7 @@ static int plan_dense_table(csgpu_model *m) {
   }
   /* cs_dive_shave: the table alone; the upper bounds of the root domains for its check of the root rows */
   if ((rc = plan_kernel(&m->plan.dive, dive_kernel(width, n), table, waves))) return rc;
+  if ((rc = plan_kernel(&m->plan.dive_ck, dive_resume_kernel(width, n), table, waves))) return rc;
   {
     int *hi = (int *)malloc((size_t)n * sizeof(int));
     if (hi == NULL) return set_err(CSGPU_E_ARG, "out of memory");
@@ -1231,18 +1268,26 @@ extern "C" int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char
 }
 
 /* the same for cs_dive_shave, which is no family of the list above (the plan dictionary stays what it was) */
-extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len) {
+static int many_symbol(const csgpu_model *m, int checkpointed, char *buf, size_t len) {
   if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
   buf[0] = '\0';
-  const void *fn = m->plan.dive.fn;
+  const void *fn = checkpointed ? m->plan.dive_ck.fn : m->plan.dive.fn;
+  const char *name = checkpointed ? "cs_dive_resume" : "cs_dive_shave";
   if (fn == NULL) return CSGPU_OK;
   Dl_info info;
   if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
-    return set_err(CSGPU_E_STATE, "cs_dive_shave: the kernel handle has no dynamic symbol");
-  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "cs_dive_shave: symbol longer than the buffer");
+    return set_err(CSGPU_E_STATE, "%s: the kernel handle has no dynamic symbol", name);
+  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "%s: symbol longer than the buffer", name);
   strcpy(buf, info.dli_sname);
   return CSGPU_OK;
+}
+
+extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, 0, buf, len); }
+
+/* and for cs_dive_resume, the kernel of csgpu_solve_many_checkpointed and csgpu_solve_many_resume */
+extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_symbol(m, 1, buf, len);
 }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
@@ -1518,6 +1563,25 @@ extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count
   return grid * k->waves;
 }
 
+/* the model's ticket counters and, for `waves` > 0, stacks for that many waves */
+static int many_workspace(csgpu_model *mm, int64_t waves, int frames) {
+  const int n = mm->host->n_vars;
+  if (mm->d_many_tickets == NULL) {
+    quiesce_servers();
+    HIP_TRY(hipMalloc((void **)&mm->d_many_tickets, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
+    HIP_TRY(hipMemset(mm->d_many_tickets, 0, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
+  }
+  if (mm->many_stack_waves < waves) { /* one call in flight per model: nothing reads the old workspace */
+    quiesce_servers();
+    if (mm->d_many_stack != NULL) (void)hipFree(mm->d_many_stack);
+    mm->d_many_stack = NULL;
+    mm->many_stack_waves = 0;
+    HIP_TRY(hipMalloc(&mm->d_many_stack, (size_t)waves * (size_t)frames * ((size_t)n + 1) * sizeof(cs_val)));
+    mm->many_stack_waves = waves;
+  }
+  return CSGPU_OK;
+}
+
 extern "C" int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
                                 csgpu_many_result *d_results, int32_t *d_solutions, void *stream) {
   if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL) return set_err(CSGPU_E_ARG, "null argument");
@@ -1537,19 +1601,8 @@ extern "C" int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, 
   const int n = m->host->n_vars;
   const int64_t waves = csgpu_internal_many_waves(m, count);
   const int frames = n; /* open levels + 1: at most n - 1 frames are ever in use (cs_dive.hip.h) */
-  if (mm->d_many_tickets == NULL) {
-    quiesce_servers();
-    HIP_TRY(hipMalloc((void **)&mm->d_many_tickets, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
-    HIP_TRY(hipMemset(mm->d_many_tickets, 0, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
-  }
-  if (mm->many_stack_waves < waves) { /* one call in flight per model: nothing reads the old workspace */
-    quiesce_servers();
-    if (mm->d_many_stack != NULL) (void)hipFree(mm->d_many_stack);
-    mm->d_many_stack = NULL;
-    mm->many_stack_waves = 0;
-    HIP_TRY(hipMalloc(&mm->d_many_stack, (size_t)waves * (size_t)frames * ((size_t)n + 1) * sizeof(cs_val)));
-    mm->many_stack_waves = waves;
-  }
+  int rc;
+  if ((rc = many_workspace(mm, waves, frames))) return rc;
   cs_dive_io io;
   io.roots = (const cs_val *)d_roots;
   io.count = (int)count;
@@ -1566,6 +1619,162 @@ extern "C" int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, 
   size_t tab_bytes = m->dense_bytes;
   void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
+  return CSGPU_OK;
+}
+
+/* ---- checkpoints: csgpu_solve_many in slices (cs_dive_resume) ---- */
+
+struct csgpu_many_checkpoints {
+  const csgpu_model *m;
+  int64_t capacity;
+  size_t slot_bytes;
+  cs_val *d_pool;
+  unsigned long long *d_next; /* slots handed out since the last reset */
+  int counted;                /* the model counts this pool among the objects that hold its device tables */
+};
+
+/* does the model run cs_dive_shave?  What finalize planned; before finalize, the same rules on the host tables
+ * (csgpu_model_build_tables), which is all they depend on */
+static int many_qualifies(const csgpu_model *m) {
+  if (m->finalized) return m->plan.dive.fn != NULL;
+  if (m->img == NULL) return 0;
+  int fw = 0;
+  size_t bytes = 0;
+  return forbidden_sets_shape(m, &fw, &bytes) > 0 && dense_table_waves(m, &bytes) > 0 && ((bytes + 15) & ~(size_t)15) <= CS_CU_LDS;
+}
+
+extern "C" size_t csgpu_many_checkpoint_bytes(const csgpu_model *m) {
+  if (m == NULL || !many_qualifies(m)) return 0;
+  const size_t n = (size_t)m->host->n_vars;
+  return (n + 1) * (n + 1) * sizeof(cs_val); /* the header frame, n - 1 stack frames at most, the current node */
+}
+
+extern "C" int csgpu_many_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out) {
+  if (m == NULL || out == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (capacity < 1) return set_err(CSGPU_E_ARG, "a checkpoint pool has at least one slot");
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (m->plan.dive_ck.fn == NULL)
+    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel, which csgpu_solve_many is built on");
+  if (capacity > 0x7fffffff) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 1 slots");
+  csgpu_many_checkpoints *ck = (csgpu_many_checkpoints *)calloc(1, sizeof *ck);
+  if (ck == NULL) return set_err(CSGPU_E_LIMIT, "out of memory");
+  ck->m = m;
+  ck->capacity = capacity;
+  ck->slot_bytes = csgpu_many_checkpoint_bytes(m);
+  hipError_t e;
+  if ((e = hipMalloc((void **)&ck->d_pool, (size_t)capacity * ck->slot_bytes)) != hipSuccess ||
+      (e = hipMalloc((void **)&ck->d_next, sizeof *ck->d_next)) != hipSuccess ||
+      (e = hipMemset(ck->d_pool, 0, (size_t)capacity * ck->slot_bytes)) != hipSuccess || /* no slot holds a checkpoint */
+      (e = hipMemset(ck->d_next, 0, sizeof *ck->d_next)) != hipSuccess) {
+    csgpu_many_checkpoints_free(ck);
+    return set_err(CSGPU_E_HIP, "checkpoint pool of %lld slots: %s", (long long)capacity, hipGetErrorString(e));
+  }
+  csgpu_internal_engine_ref(m, 1); /* the pool reads the model's device tables: no clause is added under it */
+  ck->counted = 1;
+  *out = ck;
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_checkpoints_reset(csgpu_many_checkpoints *ck, void *stream) {
+  if (ck == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  HIP_TRY(hipMemsetAsync(ck->d_next, 0, sizeof *ck->d_next, (hipStream_t)stream));
+  return CSGPU_OK;
+}
+
+extern "C" void csgpu_many_checkpoints_free(csgpu_many_checkpoints *ck) {
+  if (ck == NULL) return;
+  if (ck->counted) csgpu_internal_engine_ref(ck->m, -1);
+  (void)hipFree(ck->d_pool);
+  (void)hipFree(ck->d_next);
+  free(ck);
+}
+
+/* the checks both calls share, in csgpu_solve_many's order; nothing here touches the device */
+static int many_ck_args(const csgpu_model *m, const void *d_roots, int64_t count, const csgpu_many_options *options,
+                        const void *d_results, const csgpu_many_checkpoints *ck, const int32_t *d_slots) {
+  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL || ck == NULL || d_slots == NULL)
+    return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every slice has a budget");
+  if (options->objective == CS_OBJ_MIN || options->objective == CS_OBJ_MAX)
+    return set_err(CSGPU_E_LIMIT, "csgpu_solve_many searches with ANY or ALL: MIN / MAX are not supported");
+  if (options->objective != CS_OBJ_ANY && options->objective != CS_OBJ_ALL) return set_err(CSGPU_E_ARG, "no objective %d", options->objective);
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (m->plan.dive_ck.fn == NULL)
+    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
+                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
+  if (ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
+  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  return CSGPU_OK;
+}
+
+static int many_ck_launch(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                          csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                          int resume, void *stream) {
+  if (count == 0) return CSGPU_OK;
+  csgpu_model *mm = const_cast<csgpu_model *>(m);
+  const cs_planned *k = &m->plan.dive_ck;
+  const int n = m->host->n_vars;
+  const int64_t waves = csgpu_internal_many_waves(m, count);
+  const int frames = n; /* as csgpu_solve_many; a resumed instance walks on the n frames of its slot */
+  int rc;
+  if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
+  cs_dive_io io;
+  io.roots = (const cs_val *)d_roots;
+  io.count = (int)count;
+  io.all = options->objective == CS_OBJ_ALL;
+  io.max_nodes = (long long)options->max_nodes;
+  io.results = (cs_dive_result *)d_results;
+  io.solutions = d_solutions;
+  io.stack = resume ? NULL : (cs_val *)mm->d_many_stack;
+  io.frames = frames;
+  io.tickets = mm->d_many_tickets;
+  cs_dive_ck dk;
+  dk.pool = ck->d_pool;
+  dk.next = ck->d_next;
+  dk.capacity = (int)ck->capacity;
+  dk.resume = resume;
+  dk.slots = d_slots;
+  int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
+  const void *tab_d = m->d_dense_tab;
+  const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
+  size_t tab_bytes = m->dense_bytes;
+  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io, &dk };
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_solve_many_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                             const csgpu_many_options *options, csgpu_many_result *d_results,
+                                             int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
+  const int rc = many_ck_args(m, d_roots, count, options, d_results, ck, d_slots);
+  return rc != CSGPU_OK ? rc : many_ck_launch(m, d_roots, count, options, d_results, d_solutions, ck, d_slots, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                       csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                       int32_t *d_slots, void *stream) {
+  const int rc = many_ck_args(m, d_results /* no roots: any non-null pointer */, count, options, d_results, ck, d_slots);
+  return rc != CSGPU_OK ? rc : many_ck_launch(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
+}
+
+extern "C" int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
+                                            int64_t *count, void *stream) {
+  if (ck == NULL || d_states == NULL || count == NULL || cap < 0) return set_err(CSGPU_E_ARG, "null argument");
+  if (slot < 0 || slot >= ck->capacity) return set_err(CSGPU_E_ARG, "no slot %d in a pool of %lld", slot, (long long)ck->capacity);
+  const int n = ck->m->host->n_vars;
+  const cs_val *base = ck->d_pool + (size_t)slot * ((size_t)n + 1) * ((size_t)n + 1);
+  cs_val head;
+  HIP_TRY(hipMemcpyAsync(&head, base, sizeof head, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (head.hi != CS_DIVE_CK_MAGIC || head.lo < 0 || head.lo >= n) return set_err(CSGPU_E_STATE, "slot %d holds no checkpoint", slot);
+  *count = (int64_t)head.lo + 1;
+  if (cap < *count)
+    return set_err(CSGPU_E_LIMIT, "the checkpoint has %lld open subtrees, the buffer holds %lld", (long long)*count, (long long)cap);
+  const int *root_lo_d = ck->m->d_root_lo;
+  hipLaunchKernelGGL(cs_dive_export, dim3((unsigned)*count), dim3(CS_WAVE), 0, (hipStream_t)stream, n, root_lo_d, base,
+                     (cs_val *)d_states);
+  HIP_TRY(hipGetLastError());
   return CSGPU_OK;
 }
 

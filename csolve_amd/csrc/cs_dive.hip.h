@@ -30,7 +30,25 @@
  * CS_DIVE_SHARDS) counters, each on its own 64-byte line), workgroup b draws from shard b mod S, and every wave stops
  * at its first ticket past the end.  A launch therefore draws exactly (instances of the shard + waves of the shard)
  * tickets per counter, and the wave that draws the last of them writes the counter back to zero: nothing is cleared
- * between launches, back-to-back launches on one stream need no host in between. */
+ * between launches, back-to-back launches on one stream need no host in between.
+ *
+ * Checkpoints (cs_dive_resume, csgpu_solve_many_checkpointed / _resume): the same loop -- both kernels include
+ * cs_dive_body.hip.h, with CS_DIVE_CK 0 and 1.  An instance that stops at max_nodes with work left draws a slot of a
+ * pool (one relaxed atomic add by lane 0) and leaves there what the loop needs to go on at "try value nv of variable bv
+ * on the node plo / phi":
+ *
+ *   slot = n + 1 frames of n + 1 entries (8 bytes each)
+ *   frame 0       the header: entry 0 = {depth, CS_DIVE_CK_MAGIC}, written and read by lane 0
+ *   frame 1 + d   stack frame d (d < depth), exactly as in the workspace
+ *   frame 1 + depth   the current node: its row and {bv, nv}
+ *
+ * The counters (props reduced over the wave) go to the instance's result record as always and are read back from
+ * there; xlo / bhi are those of variable bv in the current node's row and are read from it again.  A resumed instance
+ * uses the frames of its slot AS its stack: the slot stays with the instance until the pool is reset, so a slice after
+ * the first copies nothing in and, when it stops again, writes only the current node; it needs no workspace at all.  A
+ * fresh instance walks in the wave's workspace slice and copies its depth frames out when it stops (every lane copies
+ * the entries it wrote itself).  The budget of a resumed instance counts the nodes of this launch; everything else
+ * accumulates, so a walk in slices gives, counter for counter, the walk with the summed budget. */
 #ifndef CS_DIVE_HIP_H
 #define CS_DIVE_HIP_H
 
@@ -46,6 +64,13 @@ struct cs_dive_result {
   long long nodes, cuts, props, solutions;
 };
 
+/* a value every lane loaded from the same address, as the scalar it is */
+static __device__ __forceinline__ long long cs_dive_uniform(long long x) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)x);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)x >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
 struct cs_dive_io {
   const cs_val *roots;     /* [count][n] */
   int count;
@@ -58,243 +83,52 @@ struct cs_dive_io {
   unsigned *tickets;       /* CS_DIVE_SHARDS counters, zero between launches */
 };
 
+#define CS_DIVE_CK_MAGIC 0x636b7074 /* header entry 0 .hi of a slot that holds a checkpoint */
+
+/* the checkpoint pool and the slot numbers of a call (cs_dive_resume) */
+struct cs_dive_ck {
+  cs_val *pool;              /* [capacity][n + 1][n + 1] */
+  unsigned long long *next;  /* slots handed out since the last reset (it counts on past capacity) */
+  int capacity;
+  int resume;                /* 0: fresh instances from io.roots; 1: instance i goes on from slot slots[i] */
+  int *slots;                /* [count]: the slot of an instance stopped with a checkpoint, else -1 */
+};
+
 template <typename E, int R>
 __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_shave(int n, const E *__restrict__ tab_g, int slots, int dmin,
                                                                         const int *__restrict__ root_lo,
                                                                         const int *__restrict__ root_hi,
                                                                         const int *__restrict__ sym_off, size_t tab_bytes,
                                                                         cs_dive_io io) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
-  typedef unsigned long long u64;
-  const int lane = threadIdx.x & (CS_WAVE - 1);
-  const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int waves_per_block = blockDim.x >> 6;
-  const int wave_global = (int)blockIdx.x * waves_per_block + wave_in_block;
-  {
-    const int vecs = (int)(tab_bytes / 16);
-    const uint4 *src = (const uint4 *)tab_g;
-    uint4 *dst = (uint4 *)cs_lds;
-    for (int i = threadIdx.x; i < vecs; i += blockDim.x) dst[i] = src[i];
-  }
-  __syncthreads();
+#define CS_DIVE_CK 0
+#include "cs_dive_body.hip.h"
+#undef CS_DIVE_CK
+}
 
-  cs_shave_core<E, R, 0, false> C;
-  C.s_tab = (const E *)cs_lds; C.slots = slots; C.lane = lane; C.s_trace = nullptr; C.tcount = 0u;
-  int b0[R], h0[R];
-  bool live[R];
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int v = lane + r * CS_WAVE;
-    live[r] = v < n;
-    const int vc = live[r] ? v : n - 1;
-    b0[r] = live[r] ? root_lo[vc] : 0;
-    h0[r] = live[r] ? root_hi[vc] : 0;
-    C.b0[r] = b0[r];
-    C.kb[r] = b0[r] - dmin;
-    C.deg[r] = live[r] ? sym_off[vc + 1] - sym_off[vc] : 0;
-    C.livemask[r] = __ballot(live[r]);
-  }
+/* the same with checkpoints: fresh instances (ck.resume == 0) or the instances of ck.slots going on */
+template <typename E, int R>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_resume(int n, const E *__restrict__ tab_g, int slots, int dmin,
+                                                                         const int *__restrict__ root_lo,
+                                                                         const int *__restrict__ root_hi,
+                                                                         const int *__restrict__ sym_off, size_t tab_bytes,
+                                                                         cs_dive_io io, cs_dive_ck ck) {
+#define CS_DIVE_CK 1
+#include "cs_dive_body.hip.h"
+#undef CS_DIVE_CK
+}
 
-  const int nsh = (int)gridDim.x < CS_DIVE_SHARDS ? (int)gridDim.x : CS_DIVE_SHARDS;
-  const int shard = (int)(blockIdx.x % nsh);
-  const unsigned count_x = io.count > shard ? (unsigned)((io.count - 1 - shard) / nsh + 1) : 0u; /* instances of this shard */
-  const unsigned waves_x = (unsigned)((((int)gridDim.x - 1 - shard) / nsh + 1) * waves_per_block);
-  unsigned *my_ticket = io.tickets + (size_t)shard * CS_DIVE_TICKET_STRIDE;
+/* csgpu_many_checkpoint_states: frame d of slot `slot` (d <= depth, the oldest first) as a state in absolute bounds, its
+ * branching variable narrowed to the values not tried yet, [next, hi].  One workgroup per frame. */
+__global__ void cs_dive_export(int n, const int *__restrict__ root_lo, const cs_val *__restrict__ slot_base,
+                               cs_val *__restrict__ states) {
   const size_t fstride = (size_t)n + 1;
-  cs_val *stack = io.stack + (size_t)wave_global * (size_t)io.frames * fstride;
-
-  /* the branching variable of the node in plo / phi (an open variable exists) and the valued variables of the node (a
-   * macro: a lambda that changes captured scalars leaves them in scratch memory) */
-#define CS_DIVE_SELECT()                                                                                             \
-  do {                                                                                                               \
-    unsigned key_ = 0xffffffffu;                                                                                     \
-    _Pragma("unroll") for (int r = R - 1; r >= 0; r--) {                                                             \
-      const bool open_ = live[r] && plo[r] != phi[r];                                                                \
-      const unsigned k_ = ((unsigned)(phi[r] - plo[r]) << 8) | (unsigned)(lane + r * CS_WAVE);                       \
-      key_ = open_ && k_ < key_ ? k_ : key_;                                                                         \
-    }                                                                                                                \
-    bv = (int)(cs_wave_min_u32(key_) & 0xffu);                                                                       \
-  } while (0)
-  /* register, lane and bounds of variable bv in the current node; the node's valued variables */
-#define CS_DIVE_ENTER()                                                                                              \
-  do {                                                                                                               \
-    br = bv >> 6;                                                                                                    \
-    bl = bv & 63;                                                                                                    \
-    _Pragma("unroll") for (int r = 0; r < R; r++) {                                                                  \
-      pval[r] = __ballot(plo[r] == phi[r]) & C.livemask[r];                                                          \
-      if (r == br) {                                                                                                 \
-        xlo = __builtin_amdgcn_readlane(plo[r], bl);                                                                 \
-        bhi = __builtin_amdgcn_readlane(phi[r], bl);                                                                 \
-      }                                                                                                              \
-    }                                                                                                                \
-  } while (0)
-
-  for (;;) {
-    /* The wave meets here before lane 0 draws.  Without this convergent no-op the compiler joins the `lane == 0` of
-     * the result store at the end of the body with the `lane == 0` of the draw, gives the loop a second back edge for
-     * the other 63 lanes and lets them go round alone with ticket 0: the launch never ends (seen in the ISA). */
-    __builtin_amdgcn_wave_barrier();
-    unsigned t = 0u;
-    if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-    if (t == count_x + waves_x - 1u && lane == 0) __hip_atomic_store(my_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t >= count_x) break;
-    const int inst = (int)t * nsh + shard;
-    const size_t rrow = (size_t)inst * (size_t)n;
-
-    int plo[R], phi[R]; /* the current node, relative to the root lower bounds; a lane without a variable is the value 0 */
-    bool bad_l = false;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      plo[r] = 0; phi[r] = 0;
-      if (live[r]) {
-        const cs_val d = io.roots[rrow + lane + r * CS_WAVE];
-        bad_l = bad_l || d.lo > d.hi || d.lo < b0[r] || d.hi > h0[r];
-        plo[r] = d.lo - b0[r];
-        phi[r] = d.hi - b0[r];
-      }
-    }
-    int status = 0 /* CSGPU_MANY_DONE */, root_props = 0;
-    long long nodes = 0, cuts = 0, sols = 0, props = 0; /* scalars */
-    int acc_props = 0;                                  /* per lane, added to props every 64 nodes */
-
-    if (__ballot(bad_l) != 0ull) {
-      status = 2; /* CSGPU_MANY_BAD_ROOT */
-    } else {
-      int fail_var;
-      { /* the root node: nothing is taken for granted, every valued variable pushes */
-        u64 pushed[R], push[R], dl[R], dh[R], val[R];
-        int shaved = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-          pushed[r] = ~C.livemask[r];
-          dl[r] = 0ull; dh[r] = 0ull;
-          val[r] = __ballot(plo[r] == phi[r]) & C.livemask[r];
-          push[r] = val[r];
-          shaved -= phi[r] - plo[r];
-        }
-        int rounds = 0, revisions = 0;
-        fail_var = C.fixpoint(plo, phi, pushed, push, dl, dh, val, rounds, revisions);
-        if (rounds != 0) __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-        for (int r = 0; r < R; r++) shaved += phi[r] - plo[r];
-        if (fail_var < 0) root_props = -cs_wave_sum(shaved);
-      }
-      int open_vars = 0;
-#pragma unroll
-      for (int r = 0; r < R; r++) open_vars += __popcll(__ballot(plo[r] != phi[r]));
-      if (fail_var >= 0) {
-        /* an inconsistent root: DONE, no node, no solution */
-      } else if (open_vars == 0) {
-        sols = 1;
-        if (io.solutions != nullptr) {
-#pragma unroll
-          for (int r = 0; r < R; r++)
-            if (live[r]) io.solutions[rrow + lane + r * CS_WAVE] = plo[r] + b0[r];
-        }
-      } else {
-        int depth = 0, bv, br, bl, xlo = 0, bhi = 0, nv;
-        u64 pval[R];
-        CS_DIVE_SELECT();
-        CS_DIVE_ENTER();
-        nv = xlo;
-        for (;;) {
-          depth = __builtin_amdgcn_readfirstlane(depth);
-          nv = __builtin_amdgcn_readfirstlane(nv);
-          bv = __builtin_amdgcn_readfirstlane(bv);
-          if (nodes >= io.max_nodes) { status = 1; /* CSGPU_MANY_LIMIT */ break; }
-          const int value = nv;
-          const bool last = value == bhi;
-          int rlo[R], rhi[R];
-          u64 pushed[R], push[R], dl[R], dh[R], val[R];
-#pragma unroll
-          for (int r = 0; r < R; r++) {
-            rlo[r] = plo[r]; rhi[r] = phi[r];
-            pushed[r] = pval[r] | ~C.livemask[r]; /* lanes without a variable look like values: they never push */
-            push[r] = 0ull; dl[r] = 0ull; dh[r] = 0ull;
-            val[r] = pval[r];
-            if (r == br) {
-              if (lane == bl) { rlo[r] = value; rhi[r] = value; }
-              push[r] = 1ull << bl; /* a scalar shift */
-              val[r] |= push[r];
-            }
-          }
-          int rounds = 0, revisions = 0;
-          const int fail_var = C.fixpoint(rlo, rhi, pushed, push, dl, dh, val, rounds, revisions);
-          if (rounds != 0) __builtin_amdgcn_s_setprio(0);
-          nodes++;
-          bool descend = false;
-          if (fail_var >= 0) {
-            cuts++;
-          } else {
-            int open_c = 0;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-              open_c += __popcll(__ballot(rlo[r] != rhi[r]));
-              acc_props += (rlo[r] - plo[r]) + (phi[r] - rhi[r]); /* consistent children only: the reference's PROPS */
-            }
-            props -= bhi - xlo; /* the assignment itself is no narrowing */
-            if (open_c == 0) {
-              sols++;
-              if (sols == 1 && io.solutions != nullptr) {
-#pragma unroll
-                for (int r = 0; r < R; r++)
-                  if (live[r]) io.solutions[rrow + lane + r * CS_WAVE] = rlo[r] + b0[r];
-              }
-              if (!io.all) break;
-            } else {
-              descend = true;
-            }
-          }
-          if ((nodes & 63) == 0) { props += cs_wave_sum(acc_props); acc_props = 0; }
-          if (descend) {
-            if (!last) { /* the node comes back for its next value */
-              if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames >= n - 1): never write past the slice */
-              cs_val *f = stack + (size_t)depth * fstride;
-#pragma unroll
-              for (int r = 0; r < R; r++)
-                if (live[r]) f[lane + r * CS_WAVE] = cs_interval(plo[r], phi[r]);
-              if (lane == 0) f[n] = cs_interval(bv, value + 1);
-              depth++;
-            }
-#pragma unroll
-            for (int r = 0; r < R; r++) { plo[r] = rlo[r]; phi[r] = rhi[r]; }
-            CS_DIVE_SELECT();
-            CS_DIVE_ENTER();
-            nv = xlo;
-          } else if (last) { /* the node's values are used up */
-            if (depth == 0) break;
-            depth--;
-            const cs_val *f = stack + (size_t)depth * fstride;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-              plo[r] = 0; phi[r] = 0;
-              if (live[r]) {
-                const cs_val d = f[lane + r * CS_WAVE];
-                plo[r] = d.lo; phi[r] = d.hi;
-              }
-            }
-            cs_val meta = cs_interval(0, 0);
-            if (lane == 0) meta = f[n];
-            bv = __builtin_amdgcn_readfirstlane(meta.lo);
-            nv = __builtin_amdgcn_readfirstlane(meta.hi);
-            CS_DIVE_ENTER();
-          } else {
-            nv = value + 1;
-          }
-        }
-      }
-    }
-    props += cs_wave_sum(acc_props);
-    if (lane == 0) {
-      cs_dive_result res;
-      res.status = status; res.root_props = root_props;
-      res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
-      io.results[inst] = res;
-    }
+  const cs_val *f = slot_base + fstride * (1 + (size_t)blockIdx.x);
+  const cs_val meta = f[n];
+  for (int v = threadIdx.x; v < n; v += blockDim.x) {
+    cs_val d = f[v];
+    if (v == meta.lo) d.lo = meta.hi;
+    states[(size_t)blockIdx.x * n + v] = cs_interval(d.lo + root_lo[v], d.hi + root_lo[v]);
   }
-#undef CS_DIVE_SELECT
-#undef CS_DIVE_ENTER
 }
 
 #endif

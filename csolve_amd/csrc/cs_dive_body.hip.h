@@ -1,0 +1,343 @@
+/* cs_dive_body.hip.h -- the body of cs_dive_shave (CS_DIVE_CK 0) and of cs_dive_resume (CS_DIVE_CK 1), included by
+ * cs_dive.hip.h inside either kernel.  Text, not a __device__ function: inlined from a function, the loop of
+ * cs_dive_shave<E, 2> takes 42 vector registers instead of 39.  With CS_DIVE_CK 0 the text is the kernel as it was before
+ * there were checkpoints, and compiles to the same instructions. */
+  extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
+  typedef unsigned long long u64;
+  const int lane = threadIdx.x & (CS_WAVE - 1);
+  const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int waves_per_block = blockDim.x >> 6;
+  const int wave_global = (int)blockIdx.x * waves_per_block + wave_in_block;
+  {
+    const int vecs = (int)(tab_bytes / 16);
+    const uint4 *src = (const uint4 *)tab_g;
+    uint4 *dst = (uint4 *)cs_lds;
+    for (int i = threadIdx.x; i < vecs; i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+
+  cs_shave_core<E, R, 0, false> C;
+  C.s_tab = (const E *)cs_lds; C.slots = slots; C.lane = lane; C.s_trace = nullptr; C.tcount = 0u;
+  int b0[R], h0[R];
+  bool live[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int v = lane + r * CS_WAVE;
+    live[r] = v < n;
+    const int vc = live[r] ? v : n - 1;
+    b0[r] = live[r] ? root_lo[vc] : 0;
+    h0[r] = live[r] ? root_hi[vc] : 0;
+    C.b0[r] = b0[r];
+    C.kb[r] = b0[r] - dmin;
+    C.deg[r] = live[r] ? sym_off[vc + 1] - sym_off[vc] : 0;
+    C.livemask[r] = __ballot(live[r]);
+  }
+
+  const int nsh = (int)gridDim.x < CS_DIVE_SHARDS ? (int)gridDim.x : CS_DIVE_SHARDS;
+  const int shard = (int)(blockIdx.x % nsh);
+  const unsigned count_x = io.count > shard ? (unsigned)((io.count - 1 - shard) / nsh + 1) : 0u; /* instances of this shard */
+  const unsigned waves_x = (unsigned)((((int)gridDim.x - 1 - shard) / nsh + 1) * waves_per_block);
+  unsigned *my_ticket = io.tickets + (size_t)shard * CS_DIVE_TICKET_STRIDE;
+  const size_t fstride = (size_t)n + 1;
+  cs_val *const wave_stack = io.stack + (size_t)wave_global * (size_t)io.frames * fstride;
+
+  /* the branching variable of the node in plo / phi (an open variable exists) and the valued variables of the node (a
+   * macro: a lambda that changes captured scalars leaves them in scratch memory) */
+#define CS_DIVE_SELECT()                                                                                             \
+  do {                                                                                                               \
+    unsigned key_ = 0xffffffffu;                                                                                     \
+    _Pragma("unroll") for (int r = R - 1; r >= 0; r--) {                                                             \
+      const bool open_ = live[r] && plo[r] != phi[r];                                                                \
+      const unsigned k_ = ((unsigned)(phi[r] - plo[r]) << 8) | (unsigned)(lane + r * CS_WAVE);                       \
+      key_ = open_ && k_ < key_ ? k_ : key_;                                                                         \
+    }                                                                                                                \
+    bv = (int)(cs_wave_min_u32(key_) & 0xffu);                                                                       \
+  } while (0)
+  /* register, lane and bounds of variable bv in the current node; the node's valued variables */
+#define CS_DIVE_ENTER()                                                                                              \
+  do {                                                                                                               \
+    br = bv >> 6;                                                                                                    \
+    bl = bv & 63;                                                                                                    \
+    _Pragma("unroll") for (int r = 0; r < R; r++) {                                                                  \
+      pval[r] = __ballot(plo[r] == phi[r]) & C.livemask[r];                                                          \
+      if (r == br) {                                                                                                 \
+        xlo = __builtin_amdgcn_readlane(plo[r], bl);                                                                 \
+        bhi = __builtin_amdgcn_readlane(phi[r], bl);                                                                 \
+      }                                                                                                              \
+    }                                                                                                                \
+  } while (0)
+
+  for (;;) {
+    /* The wave meets here before lane 0 draws.  Without this convergent no-op the compiler joins the `lane == 0` of
+     * the result store at the end of the body with the `lane == 0` of the draw, gives the loop a second back edge for
+     * the other 63 lanes and lets them go round alone with ticket 0: the launch never ends (seen in the ISA). */
+    __builtin_amdgcn_wave_barrier();
+    unsigned t = 0u;
+    if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+    if (t == count_x + waves_x - 1u && lane == 0) __hip_atomic_store(my_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t >= count_x) break;
+    const int inst = (int)t * nsh + shard;
+    const size_t rrow = (size_t)inst * (size_t)n;
+
+    int plo[R], phi[R]; /* the current node, relative to the root lower bounds; a lane without a variable is the value 0 */
+    bool bad_l = false;
+#if CS_DIVE_CK
+    /* the instance's slot (-1: none yet), the slot a checkpoint was written to in this launch, the stack the instance
+     * walks on and, resuming, the checkpoint's depth */
+    int slot = -1, kept = -1, depth0 = 0;
+    cs_val *stack = wave_stack;
+    bool resumed = false;
+    {
+      if (ck.resume) {
+        slot = __builtin_amdgcn_readfirstlane(ck.slots[inst]);
+        if (slot < 0) continue; /* not stopped, or stopped without a checkpoint: nothing of it is written */
+        cs_val head = cs_interval(-1, 0);
+        if (slot < ck.capacity) head = ck.pool[(size_t)slot * (fstride * fstride)]; /* compared before it is read */
+        depth0 = __builtin_amdgcn_readfirstlane(head.lo);
+        if (depth0 < 0 || depth0 >= n || __builtin_amdgcn_readfirstlane(head.hi) != CS_DIVE_CK_MAGIC) {
+          if (lane == 0) io.results[inst].status = 3; /* CSGPU_MANY_BAD_SLOT */
+          continue;
+        }
+        resumed = true;
+        stack = ck.pool + (size_t)slot * (fstride * fstride) + fstride;
+        const cs_val *f = stack + (size_t)depth0 * fstride; /* the current node */
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          plo[r] = 0; phi[r] = 0;
+          if (live[r]) {
+            const cs_val d = f[lane + r * CS_WAVE];
+            plo[r] = d.lo; phi[r] = d.hi;
+          }
+        }
+      }
+    }
+#else
+    cs_val *const stack = wave_stack;
+    const bool resumed = false;
+    const int depth0 = 0;
+#endif
+    if (!resumed) {
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        plo[r] = 0; phi[r] = 0;
+        if (live[r]) {
+          const cs_val d = io.roots[rrow + lane + r * CS_WAVE];
+          bad_l = bad_l || d.lo > d.hi || d.lo < b0[r] || d.hi > h0[r];
+          plo[r] = d.lo - b0[r];
+          phi[r] = d.hi - b0[r];
+        }
+      }
+    }
+    int status = 0 /* CSGPU_MANY_DONE */, root_props = 0;
+    long long nodes = 0, cuts = 0, sols = 0, props = 0; /* scalars */
+    int acc_props = 0;                                  /* per lane, added to props every 64 nodes */
+#if CS_DIVE_CK
+    long long nodes0 = 0; /* the nodes of earlier launches: the budget counts those of this one */
+    {
+      if (resumed) { /* the counters go on from the instance's record */
+        const cs_dive_result *was = io.results + inst;
+        root_props = __builtin_amdgcn_readfirstlane(was->root_props);
+        nodes0 = cs_dive_uniform(was->nodes);
+        cuts = cs_dive_uniform(was->cuts);
+        props = cs_dive_uniform(was->props);
+        sols = cs_dive_uniform(was->solutions);
+        nodes = nodes0;
+      }
+    }
+#else
+    const long long nodes0 = 0;
+#endif
+
+    if (__ballot(bad_l) != 0ull) {
+      status = 2; /* CSGPU_MANY_BAD_ROOT */
+    } else {
+#if CS_DIVE_CK
+      int fail_var = -1;
+      if (!resumed)
+#else
+      int fail_var; /* (left without a value as it always was: with one, cs_dive_shave's scalar registers are allotted anew) */
+#endif
+      { /* the root node: nothing is taken for granted, every valued variable pushes */
+        u64 pushed[R], push[R], dl[R], dh[R], val[R];
+        int shaved = 0;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          pushed[r] = ~C.livemask[r];
+          dl[r] = 0ull; dh[r] = 0ull;
+          val[r] = __ballot(plo[r] == phi[r]) & C.livemask[r];
+          push[r] = val[r];
+          shaved -= phi[r] - plo[r];
+        }
+        int rounds = 0, revisions = 0;
+        fail_var = C.fixpoint(plo, phi, pushed, push, dl, dh, val, rounds, revisions);
+        if (rounds != 0) __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+        for (int r = 0; r < R; r++) shaved += phi[r] - plo[r];
+        if (fail_var < 0) root_props = -cs_wave_sum(shaved);
+      }
+      int open_vars = 0; /* (a checkpoint's current node has one: the variable it branches on) */
+#pragma unroll
+      for (int r = 0; r < R; r++) open_vars += __popcll(__ballot(plo[r] != phi[r]));
+      if (fail_var >= 0) {
+        /* an inconsistent root: DONE, no node, no solution */
+      } else if (open_vars == 0) {
+        sols = 1;
+        if (io.solutions != nullptr) {
+#pragma unroll
+          for (int r = 0; r < R; r++)
+            if (live[r]) io.solutions[rrow + lane + r * CS_WAVE] = plo[r] + b0[r];
+        }
+      } else {
+        int depth = 0, bv, br, bl, xlo = 0, bhi = 0, nv;
+        u64 pval[R];
+        if (resumed) { /* "try value nv of variable bv on the node plo / phi" */
+          depth = depth0;
+          cs_val meta = cs_interval(0, 0);
+          if (lane == 0) meta = stack[(size_t)depth0 * fstride + n];
+          bv = __builtin_amdgcn_readfirstlane(meta.lo);
+          nv = __builtin_amdgcn_readfirstlane(meta.hi);
+          CS_DIVE_ENTER();
+        } else {
+          CS_DIVE_SELECT();
+          CS_DIVE_ENTER();
+          nv = xlo;
+        }
+        for (;;) {
+          depth = __builtin_amdgcn_readfirstlane(depth);
+          nv = __builtin_amdgcn_readfirstlane(nv);
+          bv = __builtin_amdgcn_readfirstlane(bv);
+          if (nodes - nodes0 >= io.max_nodes) {
+            status = 1; /* CSGPU_MANY_LIMIT */
+#if CS_DIVE_CK
+            { /* leave a checkpoint, if the pool has a slot */
+              if (!resumed) {
+                unsigned long long drawn = 0ull;
+                if (lane == 0) drawn = __hip_atomic_fetch_add(ck.next, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned dlo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)drawn);
+                const unsigned dhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(drawn >> 32));
+                slot = dhi == 0u && dlo < (unsigned)ck.capacity ? (int)dlo : -1;
+              }
+              if (depth >= n) slot = -1; /* cannot happen (at most n - 1 frames in use): never write past the slot */
+              if (slot >= 0) {
+                cs_val *base = ck.pool + (size_t)slot * (fstride * fstride);
+                cs_val *frames = base + fstride;
+                if (!resumed) { /* the frames in use, every lane the entries it wrote */
+                  for (int d = 0; d < depth; d++) {
+                    const cs_val *src = stack + (size_t)d * fstride;
+                    cs_val *dst = frames + (size_t)d * fstride;
+#pragma unroll
+                    for (int r = 0; r < R; r++)
+                      if (live[r]) dst[lane + r * CS_WAVE] = src[lane + r * CS_WAVE];
+                    if (lane == 0) dst[n] = src[n];
+                  }
+                }
+                cs_val *f = frames + (size_t)depth * fstride;
+#pragma unroll
+                for (int r = 0; r < R; r++)
+                  if (live[r]) f[lane + r * CS_WAVE] = cs_interval(plo[r], phi[r]);
+                if (lane == 0) {
+                  f[n] = cs_interval(bv, nv);
+                  base[0] = cs_interval(depth, CS_DIVE_CK_MAGIC);
+                }
+              }
+              kept = slot;
+            }
+#endif
+            break;
+          }
+          const int value = nv;
+          const bool last = value == bhi;
+          int rlo[R], rhi[R];
+          u64 pushed[R], push[R], dl[R], dh[R], val[R];
+#pragma unroll
+          for (int r = 0; r < R; r++) {
+            rlo[r] = plo[r]; rhi[r] = phi[r];
+            pushed[r] = pval[r] | ~C.livemask[r]; /* lanes without a variable look like values: they never push */
+            push[r] = 0ull; dl[r] = 0ull; dh[r] = 0ull;
+            val[r] = pval[r];
+            if (r == br) {
+              if (lane == bl) { rlo[r] = value; rhi[r] = value; }
+              push[r] = 1ull << bl; /* a scalar shift */
+              val[r] |= push[r];
+            }
+          }
+          int rounds = 0, revisions = 0;
+          const int fail_var = C.fixpoint(rlo, rhi, pushed, push, dl, dh, val, rounds, revisions);
+          if (rounds != 0) __builtin_amdgcn_s_setprio(0);
+          nodes++;
+          bool descend = false;
+          if (fail_var >= 0) {
+            cuts++;
+          } else {
+            int open_c = 0;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+              open_c += __popcll(__ballot(rlo[r] != rhi[r]));
+              acc_props += (rlo[r] - plo[r]) + (phi[r] - rhi[r]); /* consistent children only: the reference's PROPS */
+            }
+            props -= bhi - xlo; /* the assignment itself is no narrowing */
+            if (open_c == 0) {
+              sols++;
+              if (sols == 1 && io.solutions != nullptr) {
+#pragma unroll
+                for (int r = 0; r < R; r++)
+                  if (live[r]) io.solutions[rrow + lane + r * CS_WAVE] = rlo[r] + b0[r];
+              }
+              if (!io.all) break;
+            } else {
+              descend = true;
+            }
+          }
+          if ((nodes & 63) == 0) { props += cs_wave_sum(acc_props); acc_props = 0; }
+          if (descend) {
+            if (!last) { /* the node comes back for its next value */
+              if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames >= n - 1): never write past the slice */
+              cs_val *f = stack + (size_t)depth * fstride;
+#pragma unroll
+              for (int r = 0; r < R; r++)
+                if (live[r]) f[lane + r * CS_WAVE] = cs_interval(plo[r], phi[r]);
+              if (lane == 0) f[n] = cs_interval(bv, value + 1);
+              depth++;
+            }
+#pragma unroll
+            for (int r = 0; r < R; r++) { plo[r] = rlo[r]; phi[r] = rhi[r]; }
+            CS_DIVE_SELECT();
+            CS_DIVE_ENTER();
+            nv = xlo;
+          } else if (last) { /* the node's values are used up */
+            if (depth == 0) break;
+            depth--;
+            const cs_val *f = stack + (size_t)depth * fstride;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+              plo[r] = 0; phi[r] = 0;
+              if (live[r]) {
+                const cs_val d = f[lane + r * CS_WAVE];
+                plo[r] = d.lo; phi[r] = d.hi;
+              }
+            }
+            cs_val meta = cs_interval(0, 0);
+            if (lane == 0) meta = f[n];
+            bv = __builtin_amdgcn_readfirstlane(meta.lo);
+            nv = __builtin_amdgcn_readfirstlane(meta.hi);
+            CS_DIVE_ENTER();
+          } else {
+            nv = value + 1;
+          }
+        }
+      }
+    }
+    props += cs_wave_sum(acc_props);
+    if (lane == 0) {
+      cs_dive_result res;
+      res.status = status; res.root_props = root_props;
+      res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
+      io.results[inst] = res;
+#if CS_DIVE_CK
+      ck.slots[inst] = kept;
+#endif
+    }
+  }
+#undef CS_DIVE_SELECT
+#undef CS_DIVE_ENTER

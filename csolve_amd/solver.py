@@ -209,13 +209,16 @@ class Model:
     # ---- many instances of this model in one call (csgpu_solve_many) -------------------------------
     MANY_OBJECTIVES = {"ANY": 0, "ALL": 1, "MIN": 2, "MAX": 3}
 
-    def solve_many(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None) -> dict:
+    def solve_many(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
         """K instances of this model, a depth-first search per wavefront (csgpu_solve_many; the model must qualify for
         kernel 7).  roots: int32 [K, n_vars, 2] root rows inside the model's root domains, a torch tensor on the device
         (a numpy array is uploaded).  max_nodes: the budget per instance (children tried); there is no "unlimited".
         -> dict of device tensors [K]: status (0 done, 1 stopped at max_nodes, 2 bad root row), root_props, nodes, cuts,
         props, solutions, and with solutions=True `first` [K, n_vars] int32: the first solution of every instance that
-        has one (zeros elsewhere).  Asynchronous on the stream; one call in flight per model."""
+        has one (zeros elsewhere).  Asynchronous on the stream; one call in flight per model.
+        checkpoints: a pool of many_checkpoints(): an instance that stops at max_nodes keeps its walk in a slot of it
+        (csgpu_solve_many_checkpointed); the answer then has `slot` [K] int32 (-1: no checkpoint) and is what
+        resume_many() continues.  Without it the call is csgpu_solve_many."""
         L = load_library()
         n = self.n_vars
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
@@ -236,19 +239,151 @@ class Model:
         res = buf[:K]
         first = torch.zeros((K, n), dtype=torch.int32, device=roots.device) if solutions else None
         # (an empty batch still goes through the library's checks: any non-null pointer stands for its rows)
-        check(L.csgpu_solve_many(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
-                                 first.data_ptr() if solutions and K else None, _stream_ptr(stream)))
+        if checkpoints is None:
+            check(L.csgpu_solve_many(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                                     first.data_ptr() if solutions and K else None, _stream_ptr(stream)))
+            return self._many_answer(buf, K, first)
+        slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
+        check(L.csgpu_solve_many_checkpointed(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
+                                              buf.data_ptr(), first.data_ptr() if solutions and K else None,
+                                              checkpoints._h, slots.data_ptr(), _stream_ptr(stream)))
+        return self._many_answer(buf, K, first, slots, checkpoints)
+
+    @staticmethod
+    def _many_answer(buf, K, first, slots=None, checkpoints=None) -> dict:
+        """views of the csgpu_many_result records in `buf` (the answer keeps the buffers a resume writes to)"""
+        res = buf[:K]
         head = res.view(torch.int32)  # [K, 10]: the two 32-bit fields lead the record
         out = {"status": head[:, 0], "root_props": head[:, 1], "nodes": res[:, 1], "cuts": res[:, 2], "props": res[:, 3],
                "solutions": res[:, 4]}
-        if solutions:
+        if first is not None:
             out["first"] = first
+        if slots is not None:
+            out["slot"] = slots[:K]
+            out["_records"], out["_slots"], out["_checkpoints"] = buf, slots, checkpoints
         return out
+
+    def many_checkpoints(self, capacity: int) -> "ManyCheckpoints":
+        """a pool of `capacity` checkpoint slots for solve_many(..., checkpoints=) (csgpu_many_checkpoints_create); a
+        slot stays with its instance until reset()"""
+        return ManyCheckpoints(self, capacity)
+
+    def checkpoint_bytes(self) -> int:
+        """bytes of one checkpoint slot, 0 if the model does not qualify (host only: after build_tables or finalize)"""
+        return int(load_library().csgpu_many_checkpoint_bytes(self._h))
+
+    def resume_many(self, result: dict, *, max_nodes, objective="ANY", stream=None) -> dict:
+        """continue, in place, the instances of a checkpointed solve_many answer that stopped with a checkpoint
+        (csgpu_solve_many_resume): `max_nodes` more nodes each; counters accumulate, `first` is written when an
+        instance's `solutions` goes from 0 to 1, rows of instances without a slot are not touched.  -> result"""
+        assert "_checkpoints" in result, "an answer of solve_many(..., checkpoints=pool)"
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        opt = ManyOptions(obj, 0, int(max_nodes))
+        first = result.get("first")
+        K = result["status"].shape[0]
+        check(load_library().csgpu_solve_many_resume(self._h, K, C.byref(opt), result["_records"].data_ptr(),
+                                                     first.data_ptr() if first is not None and K else None,
+                                                     result["_checkpoints"]._h, result["_slots"].data_ptr(),
+                                                     _stream_ptr(stream)))
+        return result
+
+    def checkpoint_states(self, checkpoints: "ManyCheckpoints", slot: int, stream=None) -> torch.Tensor:
+        """the open subtrees of the checkpoint in `slot` as states [depth + 1, n_vars, 2] int32 on the device, the
+        oldest frame (the largest subtree) first (csgpu_many_checkpoint_states).  They are not at the fixpoint yet:
+        see open_subtrees()."""
+        n = self.n_vars
+        out = torch.empty((n, n, 2), dtype=torch.int32, device="cuda")  # depth + 1 <= n
+        count = C.c_int64()
+        check(load_library().csgpu_many_checkpoint_states(checkpoints._h, int(slot), out.data_ptr(), n, C.byref(count),
+                                                          _stream_ptr(stream)))
+        return out[: count.value]
+
+    def open_subtrees(self, checkpoints: "ManyCheckpoints", slot: int):
+        """checkpoint_states() made ready for a Search: every state through the fixpoint as a `var < 0` node, the
+        inconsistent ones dropped.  -> (open states [m, n_vars, 2] for Search.put, complete states [s, n_vars, 2]: each
+        a solution of its own, which the engine must not be given -- it branches on an open variable)"""
+        states = self.checkpoint_states(checkpoints, slot)
+        nodes = torch.zeros((states.shape[0], 4), dtype=torch.int32, device=states.device)
+        nodes[:, 0] = -1
+        nodes[:, 3] = torch.arange(states.shape[0], dtype=torch.int32, device=states.device)
+        out, res = self.propagate(states.contiguous(), nodes)
+        alive = res[:, 0] >= 0
+        complete = (out[:, :, 0] == out[:, :, 1]).all(dim=1)
+        return out[alive & ~complete].contiguous(), out[alive & complete].contiguous()
+
+    def solve_many_sliced(self, roots, objective="ANY", *, budgets, finish="resume", solutions=True, pool_capacity=1 << 18,
+                          max_children=1 << 14) -> dict:
+        """solve_many in slices: a checkpointed call with budgets[0], then a resume with each following budget while
+        an instance is at LIMIT.  finish="resume": that is all (instances still at LIMIT stay so, with their slots).
+        finish="search": after the last budget every instance still at LIMIT hands its open subtrees to a Search of
+        its own (the whole device on one deep tree) and ends DONE: `solutions` is the sum (ALL) or 1 if either part
+        found one (ANY), `first` the dive's if it has one, else the search's; `nodes`, `cuts` and `props` of those
+        instances are the sum of both parts -- the engine walks the open subtrees in its own order and, for ANY, not
+        up to the same node, so they are NOT the single-wave walk's.  The engine walks with the model's own objective,
+        which must be the one asked for.  Synchronises between the slices.
+        -> the dict of solve_many plus `slot` and `sliced`: {"slices": calls made, "searched": instances finished by
+        a Search}"""
+        assert finish in ("resume", "search") and len(budgets) >= 1
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        if finish == "search" and obj != self.objective:
+            raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
+        K = roots.shape[0]
+        pool = self.many_checkpoints(max(K, 1))
+        out = self.solve_many(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+        slices = 1
+        for budget in budgets[1:]:
+            if not bool((out["status"] == 1).any()):
+                break
+            self.resume_many(out, max_nodes=budget, objective=objective)
+            slices += 1
+        searched = 0
+        if finish == "search":
+            left = torch.nonzero((out["status"] == 1) & (out["slot"] >= 0)).flatten().tolist()
+            if left:
+                search = Search(self, pool_capacity, max_children)
+                for i in left:
+                    self._finish_by_search(search, pool, out, i, obj)
+                    searched += 1
+                search.close()
+        out["sliced"] = {"slices": slices, "searched": searched}
+        return out
+
+    def _finish_by_search(self, search: "Search", pool, out: dict, i: int, obj: int):
+        """instance i of `out`, stopped with a checkpoint: its open subtrees through `search`, the totals added"""
+        states, complete = self.open_subtrees(pool, int(out["slot"][i]))
+        found = int(complete.shape[0])
+        first = complete[0, :, 0] if found else None
+        nodes = cuts = props = 0
+        if states.shape[0] and not (obj == 0 and found):
+            search.reset()
+            search.put(states)
+            st = search.run()
+            assert st["done"] == 1
+            nodes, cuts, props = st["nodes"], st["cuts"], st["props"]
+            if st["solutions"] and first is None:
+                first = torch.from_numpy(search.solutions(1)[0].astype(np.int32)).to(states.device)
+            found += st["solutions"]
+        if obj == 0:
+            found = min(found, 1)
+        if found and int(out["solutions"][i]) == 0 and "first" in out:
+            out["first"][i] = first
+        out["solutions"][i] += found
+        out["nodes"][i] += nodes
+        out["cuts"][i] += cuts
+        out["props"][i] += props
+        out["status"][i] = 0
+        out["slot"][i] = -1
 
     def many_kernel(self):
         """the cs_dive_shave instantiation solve_many launches for this model (template-id), None if it does not qualify"""
         buf = C.create_string_buffer(1024)
         check(load_library().csgpu_internal_many_symbol(self._h, buf, len(buf)))
+        return demangle(buf.value.decode()) if buf.value else None
+
+    def many_resume_kernel(self):
+        """the cs_dive_resume instantiation the checkpointed calls launch (template-id), None if the model does not qualify"""
+        buf = C.create_string_buffer(1024)
+        check(load_library().csgpu_internal_many_resume_symbol(self._h, buf, len(buf)))
         return demangle(buf.value.decode()) if buf.value else None
 
     def many_waves(self, count: int) -> int:
@@ -401,6 +536,32 @@ class Model:
         st, rounds = C.c_int32(), C.c_int32()
         check(load_library().csgpu_model_root_propagate_limit(self._h, limit, C.byref(st), C.byref(rounds)))
         return st.value, rounds.value
+
+
+class ManyCheckpoints:
+    """A pool of checkpoint slots of one finalized model (csgpu_many_checkpoints); it holds the model."""
+
+    def __init__(self, model: Model, capacity: int):
+        self.model = model
+        self.capacity = int(capacity)
+        self._h = C.c_void_p()
+        check(load_library().csgpu_many_checkpoints_create(model._h, self.capacity, C.byref(self._h)))
+
+    def reset(self, stream=None):
+        """every slot free again (asynchronous on the stream)"""
+        check(load_library().csgpu_many_checkpoints_reset(self._h, _stream_ptr(stream)))
+        return self
+
+    def close(self):
+        if self._h:
+            load_library().csgpu_many_checkpoints_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def set_linear_fast_paths(on: bool):

@@ -230,7 +230,8 @@ int csgpu_propagate_batch_fb(const csgpu_model *m, const csgpu_val *d_states_in,
  *   options->objective  0 ANY: stop at an instance's first solution; 1 ALL: walk its whole tree and count
  *   options->max_nodes  budget per instance (children tried), > 0: there is no "unlimited".  An instance that would
  *                       need one more node stops with status CSGPU_MANY_LIMIT, nodes == max_nodes and the counters
- *                       of what it did; the caller re-runs such an instance through a csgpu_search
+ *                       of what it did; the caller re-runs such an instance through a csgpu_search, or uses
+ *                       csgpu_solve_many_checkpointed (below), which lets it go on from where it stopped
  *   d_results[i]        status; nodes = children tried (a value that a valued neighbour forbids is a node and a cut),
  *                       cuts = inconsistent children, props = narrowings of the consistent children (the reference's
  *                       PROPS on such networks), solutions; root_props = narrowings of the root node (0 when the root
@@ -262,6 +263,51 @@ typedef struct csgpu_many_options {
 } csgpu_many_options;
 int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
                      csgpu_many_result *d_results, int32_t *d_solutions, void *stream);
+
+/* ---- checkpoints: csgpu_solve_many in slices ----
+ * An instance that stops at max_nodes with work left keeps what it walked: it draws a slot of a pool and leaves there its
+ * frame stack, its current node and {branching variable, next value}.  From the slot it goes on in two ways:
+ *   csgpu_solve_many_resume        on a wavefront again, with a budget for THIS call (nodes tried in the call); the
+ *                                  counters accumulate and the first solution is stored when `solutions` goes from 0 to
+ *                                  1, so a walk in slices gives, field for field, the one call with the summed budget
+ *   csgpu_many_checkpoint_states   its open subtrees as states, for a csgpu_search that puts the whole device on them
+ * csgpu_solve_many_checkpointed is csgpu_solve_many plus the pool: d_slots[i] receives the slot of an instance that stopped
+ * with a checkpoint, and -1 for every other one (DONE, BAD_ROOT, or LIMIT while the pool had no slot left -- such an
+ * instance ends exactly as in csgpu_solve_many).  csgpu_solve_many_resume takes the same d_results / d_solutions /
+ * d_slots rows: an instance with d_slots[i] < 0 is left untouched (nothing of it is written); one with a slot reads its
+ * counters from d_results[i], goes on, and ends DONE (d_slots[i] = -1) or LIMIT (the checkpoint goes back into the SAME
+ * slot).  A slot number outside [0, capacity), or a slot that holds no checkpoint, gives status CSGPU_MANY_BAD_SLOT and
+ * nothing else of the instance is touched (the kernel compares before it reads).
+ * Slots are not recycled one by one: a slot stays with its instance until csgpu_many_checkpoints_reset makes every slot
+ * free again.  A caller that runs K instances in slices creates the pool with as many slots as it will let stop, K at
+ * the most.  A slot is csgpu_many_checkpoint_bytes(m) bytes: (n_vars + 1) frames of (n_vars + 1) 8-byte entries.
+ * Concurrency: "one call in flight per model" holds for these calls too (they share the model's ticket counters); the
+ * same slot number twice in one resume call is undefined; the pool must outlive the calls queued on it and is freed
+ * before its model.
+ * Errors before any HIP call, as csgpu_solve_many: a null pointer (d_solutions may be null), count < 0, max_nodes <= 0,
+ * capacity < 1 -> CSGPU_E_ARG; MIN / MAX -> CSGPU_E_LIMIT; model not finalized -> CSGPU_E_STATE; model does not qualify
+ * -> CSGPU_E_LIMIT; a pool created for another model -> CSGPU_E_ARG.
+ * csgpu_many_checkpoint_states: the open subtrees of one checkpoint, the oldest frame (the largest subtree) first: a
+ * frame {row, bv, next} becomes row with bv narrowed to [next, row[bv].hi], the current node the same with its next
+ * value.  *count = depth + 1; CSGPU_E_LIMIT (and *count set) if cap is smaller; CSGPU_E_STATE if the slot holds no
+ * checkpoint.  It reads the slot's header on `stream` and waits for it.  The states are NOT at the fixpoint yet: `next`
+ * has not been pushed, and when it is the variable's last value the state has a new valued variable.  Run them through
+ * csgpu_propagate_batch as `var < 0` nodes and drop the inconsistent ones before csgpu_search_put; a state that is fully
+ * valued after that is a solution of its own and must not be put (the engine branches on an open variable): count it. */
+#define CSGPU_MANY_BAD_SLOT 3 /* csgpu_solve_many_resume: d_slots[i] names no checkpoint of the pool: not touched */
+typedef struct csgpu_many_checkpoints csgpu_many_checkpoints; /* device pool, belongs to one finalized model */
+size_t csgpu_many_checkpoint_bytes(const csgpu_model *m); /* bytes per slot; 0 if the model does not qualify.  No HIP call:
+                                                             after finalize, or after csgpu_model_build_tables alone */
+int csgpu_many_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out);
+int csgpu_many_checkpoints_reset(csgpu_many_checkpoints *ck, void *stream); /* every slot free again */
+void csgpu_many_checkpoints_free(csgpu_many_checkpoints *ck);
+int csgpu_solve_many_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                                  csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                  int32_t *d_slots, void *stream);
+int csgpu_solve_many_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options, csgpu_many_result *d_results,
+                            int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap, int64_t *count,
+                                 void *stream);
 
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */

@@ -8,6 +8,11 @@ time as a function of max_nodes (bulk against tail), and a seeded sample of the 
 oracle walk (tests/many_walk.py).
 
   python tools/time_solve_many.py --set sudoku9 [--count 65536] [--reps 5] [--loop-sample 256] [--check 32]
+                                  [--sliced B0,B1,... [--finish resume|search]]
+  --sliced: the same instances through Model.solve_many_sliced as well (a checkpointed call with budget B0, a resume
+  with every following budget; --finish search: what is left after the last budget through one Search per instance):
+  the time of the whole, the time until the answers of the first slice are there, and whether it found what the one
+  call found.
   sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY)
 """
 import argparse
@@ -60,6 +65,8 @@ def main():
     ap.add_argument("--loop-sample", type=int, default=256)
     ap.add_argument("--check", type=int, default=32)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sliced", default=None, help="budgets of the slices, e.g. 256,4096")
+    ap.add_argument("--finish", default="resume", choices=("resume", "search"))
     args = ap.parse_args()
     count = args.count or {"sudoku9": 65536, "queens12": 16384, "sudoku16": 4096}[args.set]
     text, roots, objective, budget = instances(args.set, count)
@@ -88,6 +95,46 @@ def main():
     for b in sorted({16, 64, 256, 1024, 4096, max(1, largest)}):
         if b <= budget:
             per_budget[b] = round(statistics.median(many(b)[0] for _ in range(3)) * 1e3, 3)
+
+    sliced = None
+    if args.sliced:
+        budgets = tuple(int(b) for b in args.sliced.split(","))
+
+        def first_slice():
+            pool = model.many_checkpoints(count)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            model.solve_many(dev, objective, max_nodes=budgets[0], checkpoints=pool)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t
+
+        def whole():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = model.solve_many_sliced(dev, objective, budgets=budgets, finish=args.finish)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, res
+
+        first_slice()
+        whole()  # warm-up: the pool, the engine's buffers
+        firsts = [first_slice() for _ in range(args.reps)]
+        wholes = []
+        for _ in range(args.reps):
+            dt, res = whole()
+            wholes.append(dt)
+        left = res["status"] == 1
+        found = bool(((res["solutions"] > 0) == (out["solutions"] > 0))[~left].all())
+        same = all(bool((res[f] == out[f])[~left].all()) for f in ("nodes", "cuts", "props", "solutions"))
+        sliced = {"budgets": list(budgets), "finish": args.finish, "calls": res["sliced"]["slices"],
+                  "searched": res["sliced"]["searched"], "still_at_limit": int(left.sum()),
+                  "ms": {"median": round(statistics.median(wholes) * 1e3, 3), "min": round(min(wholes) * 1e3, 3),
+                         "max": round(max(wholes) * 1e3, 3), "reps": args.reps},
+                  "first_slice_ms": {"median": round(statistics.median(firsts) * 1e3, 3), "min": round(min(firsts) * 1e3, 3),
+                                     "max": round(max(firsts) * 1e3, 3)},
+                  "finds_what_one_call_finds": found,
+                  # finish=search: the engine's own walk below the checkpoints, so only finish=resume can say yes
+                  "counters_equal_one_call": same, "kernel": model.many_resume_kernel(),
+                  "slot_bytes": model.checkpoint_bytes()}
 
     # the per-instance loop: one Search, reset and seeded per instance
     rng = np.random.default_rng(args.seed)
@@ -141,6 +188,7 @@ def main():
         "loop_instances_per_s": round(loop_rate), "loop_nodes_per_s": round(loop_nodes / t_loop),
         "ratio_instances_per_s": round(many_rate / loop_rate, 1),
         "oracle_checked": len(picks), "oracle_ok": checked_ok,
+        **({"sliced": sliced} if sliced else {}),
     }))
     return 0 if checked_ok else 1
 
