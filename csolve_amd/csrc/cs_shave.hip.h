@@ -60,16 +60,46 @@ __device__ __forceinline__ unsigned long long cs_bitset0(unsigned long long m, i
   return m;
 }
 
-/* x + (x == f) and x - (x == f): a compare into VCC and an add / subtract with carry-in */
-__device__ __forceinline__ int cs_inc_if_eq(int x, int f) {
-  int r;
-  asm("v_cmp_eq_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, 0, %1, vcc" : "=v"(r) : "v"(x), "v"(f) : "vcc");
-  return r;
+/* One slot of a PUSH on one register of bounds: lo += (lo == f), hi -= (hi == f), in place.  Each is a compare into a
+ * scalar pair and an add / subtract with that pair as carry-in; the two pairs are interleaved, so that an independent
+ * instruction stands between every compare and the carry instruction that reads it.  ONE statement: the compiler pads
+ * every asm statement with a wait state (one `s_nop 0` per compare/carry pair it was, six per push on queens). */
+__device__ __forceinline__ void cs_shift_if_eq(int &lo, int &hi, int f) {
+  unsigned long long c;
+  asm("v_cmp_eq_u32 vcc, %0, %3\n\t"
+      "v_cmp_eq_u32 %2, %1, %3\n\t"
+      "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+      "v_subb_co_u32 %1, %2, %1, 0, %2"
+      : "+v"(lo), "+v"(hi), "=&s"(c) : "v"(f) : "vcc");
 }
-__device__ __forceinline__ int cs_dec_if_eq(int x, int f) {
-  int r;
-  asm("v_cmp_eq_u32 vcc, %1, %2\n\tv_subb_co_u32 %0, vcc, %1, 0, vcc" : "=v"(r) : "v"(x), "v"(f) : "vcc");
-  return r;
+/* three slots, one after the other on the bounds as they stand (queens) */
+__device__ __forceinline__ void cs_shift_if_eq3(int &lo, int &hi, int f0, int f1, int f2) {
+  unsigned long long c;
+  asm("v_cmp_eq_u32 vcc, %0, %3\n\t"
+      "v_cmp_eq_u32 %2, %1, %3\n\t"
+      "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+      "v_subb_co_u32 %1, %2, %1, 0, %2\n\t"
+      "v_cmp_eq_u32 vcc, %0, %4\n\t"
+      "v_cmp_eq_u32 %2, %1, %4\n\t"
+      "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+      "v_subb_co_u32 %1, %2, %1, 0, %2\n\t"
+      "v_cmp_eq_u32 vcc, %0, %5\n\t"
+      "v_cmp_eq_u32 %2, %1, %5\n\t"
+      "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+      "v_subb_co_u32 %1, %2, %1, 0, %2"
+      : "+v"(lo), "+v"(hi), "=&s"(c) : "v"(f0), "v"(f1), "v"(f2) : "vcc");
+}
+
+/* the lanes where a != b and where c != d, as scalar masks.  (From `__ballot(a != b)` behind a loop that may not run
+ * the compiler makes a select into a vector register and a second compare per mask.) */
+__device__ __forceinline__ void cs_lanes_ne2(unsigned long long &m0, int a, int b, unsigned long long &m1, int c, int d) {
+  asm("v_cmp_ne_u32 %0, %2, %3\n\tv_cmp_ne_u32 %1, %4, %5" : "=&s"(m0), "=s"(m1) : "v"(a), "v"(b), "v"(c), "v"(d));
+}
+
+/* bits set in two wave-uniform masks, 32-bit scalars (the compiler's count is 64 bits wide, and comparing two of them
+ * goes through the vector unit) */
+__device__ __forceinline__ void cs_popc64x2(int &c0, unsigned long long m0, int &c1, unsigned long long m1) {
+  asm("s_bcnt1_i32_b64 %0, %2\n\ts_bcnt1_i32_b64 %1, %3" : "=&s"(c0), "=s"(c1) : "s"(m0), "s"(m1) : "scc");
 }
 
 /* v with lane L replaced by the wave-uniform x */
@@ -121,46 +151,76 @@ struct cs_shave_core {
   }
 
   /* PUSH(u): the variable `ul` of register r is the value cd + dmin; every lane moves a bound that equals the
-   * value u forbids for it by one and is dirty then */
+   * value u forbids for it by one, in place.  Which bounds moved is found once per phase (push_phase): bounds only
+   * move inwards, so "moved by some push of the phase" is "differs from the start of the phase".  The tracing variant
+   * needs the lanes per push (the cause of a record is the pusher) and compares per push. */
   __device__ __forceinline__ void push_var(int r, int ul, int cd, int (&rlo)[R], int (&rhi)[R], u64 (&dl)[R], u64 (&dh)[R],
                                            int &revisions) {
     revisions += __builtin_amdgcn_readlane(deg[r], ul);
     const E *row = s_tab + (size_t)(ul + r * CS_WAVE) * slots * W + lane;
     /* The slots are applied one after the other to the bounds as they stand (a bound moved by slot k may be moved
-     * again by slot k + 1: both values are forbidden by u, each move is one narrowing); `bound += (f == bound)` is
-     * a compare into VCC and an add with carry-in, and which bounds moved is ONE compare per bound at the end --
-     * the scalar unit merges nothing. */
+     * again by slot k + 1: both values are forbidden by u, each move is one narrowing). */
     int plo[R], phi[R];
+    if (TRACE) {
 #pragma unroll
-    for (int r2 = 0; r2 < R; r2++) { plo[r2] = rlo[r2]; phi[r2] = rhi[r2]; }
-    if (SL != 0) {
+      for (int r2 = 0; r2 < R; r2++) { plo[r2] = rlo[r2]; phi[r2] = rhi[r2]; }
+    }
+    if (SL == 3) {
+#pragma unroll
+      for (int r2 = 0; r2 < R; r2++) {
+        const int f0 = cd - (int)row[r2 * CS_WAVE]; /* the value of w that u forbids (sentinel: < 0) */
+        const int f1 = cd - (int)row[W + r2 * CS_WAVE];
+        const int f2 = cd - (int)row[2 * W + r2 * CS_WAVE];
+        cs_shift_if_eq3(rlo[r2], rhi[r2], f0, f1, f2);
+      }
+    } else if (SL != 0) {
 #pragma unroll
       for (int k = 0; k < (SL ? SL : 1); k++) {
 #pragma unroll
-        for (int r2 = 0; r2 < R; r2++) {
-          const int f = cd - (int)row[k * W + r2 * CS_WAVE]; /* the value of w that u forbids (sentinel: < 0) */
-          rlo[r2] = cs_inc_if_eq(rlo[r2], f);
-          rhi[r2] = cs_dec_if_eq(rhi[r2], f);
-        }
+        for (int r2 = 0; r2 < R; r2++) cs_shift_if_eq(rlo[r2], rhi[r2], cd - (int)row[k * W + r2 * CS_WAVE]);
       }
     } else {
       for (int k = 0; k < slots; k++) {
 #pragma unroll
-        for (int r2 = 0; r2 < R; r2++) {
-          const int f = cd - (int)row[k * W + r2 * CS_WAVE];
-          rlo[r2] = cs_inc_if_eq(rlo[r2], f);
-          rhi[r2] = cs_dec_if_eq(rhi[r2], f);
-        }
+        for (int r2 = 0; r2 < R; r2++) cs_shift_if_eq(rlo[r2], rhi[r2], cd - (int)row[k * W + r2 * CS_WAVE]);
       }
     }
+    if (TRACE) {
 #pragma unroll
-    for (int r2 = 0; r2 < R; r2++) {
-      const u64 ml = __ballot(rlo[r2] != plo[r2]), mh = __ballot(rhi[r2] != phi[r2]);
-      dl[r2] |= ml;
-      dh[r2] |= mh;
-      if (TRACE) {
+      for (int r2 = 0; r2 < R; r2++) {
+        const u64 ml = __ballot(rlo[r2] != plo[r2]), mh = __ballot(rhi[r2] != phi[r2]);
+        dl[r2] |= ml;
+        dh[r2] |= mh;
         trace_lanes(ml, r2, 0, rlo[r2], ul + r * CS_WAVE);
         trace_lanes(mh, r2, 1, rhi[r2], ul + r * CS_WAVE);
+      }
+    }
+  }
+
+  /* every variable of `who` pushes, ascending.  A valued variable's bounds do not change any more, so
+   * "value - dmin" of every pusher of the phase is taken from one register. */
+  __device__ __forceinline__ void push_phase(const u64 (&who)[R], int (&rlo)[R], int (&rhi)[R], u64 (&pushed)[R], u64 (&dl)[R],
+                                             u64 (&dh)[R], int &revisions) {
+    int cdv[R], plo[R], phi[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) { cdv[r] = rlo[r] + kb[r]; plo[r] = rlo[r]; phi[r] = rhi[r]; }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      u64 bits = who[r];
+      pushed[r] |= bits;
+      while (bits != 0ull) {
+        const int ul = __builtin_ctzll(bits);
+        bits = cs_bitset0(bits, ul);
+        push_var(r, ul, __builtin_amdgcn_readlane(cdv[r], ul), rlo, rhi, dl, dh, revisions);
+      }
+    }
+    if (!TRACE) {
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        u64 ml, mh;
+        cs_lanes_ne2(ml, rlo[r], plo[r], mh, rhi[r], phi[r]);
+        dl[r] |= ml;
+        dh[r] |= mh;
       }
     }
   }
@@ -174,159 +234,171 @@ struct cs_shave_core {
       if (c != 0ull) bad = __builtin_ctzll(c) + r * CS_WAVE;
       val[r] = __ballot(rlo[r] == rhi[r]) & livemask[r];
     }
-    return bad;
+    return __builtin_amdgcn_readfirstlane(bad);
+  }
+
+  /* more moved bounds than valued variables?  (two 32-bit scalars) */
+  __device__ __forceinline__ bool sweep_pays(const u64 (&dl)[R], const u64 (&dh)[R], const u64 (&val)[R]) const {
+    int n_dirty = 0, n_val = 0;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      int d, v;
+      cs_popc64x2(d, dl[r] | dh[r], v, val[r]);
+      n_dirty += d;
+      n_val += v;
+    }
+    return n_dirty > n_val;
+  }
+
+  /* the valued lanes that forbid the value c of the variable whose table row is `row` (ckw = c + kb[w]).  Lane u holds
+   * the table entry e of (w, k, u); its own value forbids the value rlo[u] + e - kb[w] of w, i.e. c is forbidden iff
+   * e == c + kb[w] - rlo[u]: one subtraction per register, the compares run on the raw table bytes.  With a
+   * compile-time slot count the entries are in registers (e), with a run-time one the row is re-read. */
+  template <bool CAUSE>
+  __device__ __forceinline__ u64 forbidders(const E *row, const int (&e)[SL ? SL : 1][R], int ckw, const int (&rlo)[R],
+                                            const u64 (&val)[R], int &cause) const {
+    u64 hit = 0ull;
+    if (SL != 0) {
+#pragma unroll
+      for (int r2 = 0; r2 < R; r2++) {
+        const int t = ckw - rlo[r2];
+        u64 h = 0ull;
+#pragma unroll
+        for (int k = 0; k < (SL ? SL : 1); k++) h |= __ballot(e[k][r2] == t);
+        hit |= h & val[r2];
+        if (TRACE && CAUSE && cause < 0 && (h & val[r2]) != 0ull) cause = __builtin_ctzll(h & val[r2]) + r2 * CS_WAVE;
+      }
+    } else {
+      for (int k = 0; k < slots; k++) {
+#pragma unroll
+        for (int r2 = 0; r2 < R; r2++) {
+          const u64 h = __ballot((int)row[k * W + r2 * CS_WAVE] == ckw - rlo[r2]) & val[r2];
+          hit |= h;
+          if (TRACE && CAUSE && cause < 0 && h != 0ull) cause = __builtin_ctzll(h) + r2 * CS_WAVE;
+        }
+      }
+    }
+    return hit;
+  }
+
+  /* VERIFY one side (0: lower bounds, 1: upper bounds), ascending: a moved bound stops at the first value no valued
+   * variable forbids.  Mostly the bound is supported and nothing is written: the iteration is straight code, the
+   * walk hangs off it.  A bound that passes the other one is the failure (fail_v; the loops run to their end). */
+  template <int SIDE>
+  __device__ __forceinline__ void verify_side(int (&rlo)[R], int (&rhi)[R], u64 (&dirty)[R], u64 (&val)[R], int &revisions,
+                                              int &fail_v) {
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      u64 bits = dirty[r];
+      dirty[r] = 0ull;
+      while (bits != 0ull) {
+        const int wl = __builtin_ctzll(bits);
+        bits = cs_bitset0(bits, wl);
+        int cand = __builtin_amdgcn_readlane(SIDE == 0 ? rlo[r] : rhi[r], wl);
+        const int ckw = cand + __builtin_amdgcn_readlane(kb[r], wl);
+        revisions += __builtin_amdgcn_readlane(deg[r], wl);
+        const E *row = s_tab + (size_t)(wl + r * CS_WAVE) * slots * W + lane;
+        int e[SL ? SL : 1][R];
+        if (SL != 0) {
+#pragma unroll
+          for (int k = 0; k < (SL ? SL : 1); k++)
+#pragma unroll
+            for (int r2 = 0; r2 < R; r2++) e[k][r2] = (int)row[k * W + r2 * CS_WAVE];
+        }
+        int cause = -1; /* TRACE: a valued variable that forbids the candidate */
+        if (forbidders<true>(row, e, ckw, rlo, val, cause) != 0ull) {
+          /* the bound moves on, one value (one PROPS) at a time, until it is supported or passes the other */
+          const int other = __builtin_amdgcn_readlane(SIDE == 0 ? rhi[r] : rlo[r], wl);
+          int step = 0;
+          bool on;
+          do {
+            step++;
+            on = SIDE == 0 ? cand + step <= other : cand - step >= other;
+            if (on) on = forbidders<false>(row, e, ckw + (SIDE == 0 ? step : -step), rlo, val, cause) != 0ull;
+          } while (on);
+          cand += SIDE == 0 ? step : -step;
+          if (lane == wl) { if (SIDE == 0) rlo[r] = cand; else rhi[r] = cand; }
+          if (TRACE) trace_lanes(1ull << wl, r, SIDE, cand, cause);
+          if (SIDE == 0 ? cand > other : cand < other) fail_v = wl + r * CS_WAVE;
+          if (cand == other) val[r] |= 1ull << wl; /* counts for the verifications that follow */
+        }
+      }
+    }
+  }
+
+  /* One round: (1) PUSH, every variable of `push` moves the bounds it sits on; (2a) sweeps; (2) VERIFY; (3) who pushes
+   * next.  Returns -1, or a variable whose domain has become empty; `more` says that `push` holds the next round's
+   * variables.  Straight code: every failure is an `if` around the rest of the round, no exit from inside a loop. */
+  __device__ __forceinline__ int round(int (&rlo)[R], int (&rhi)[R], u64 (&pushed)[R], u64 (&push)[R], u64 (&dl)[R],
+                                       u64 (&dh)[R], u64 (&val)[R], int &revisions, bool &more) {
+    more = false;
+    push_phase(push, rlo, rhi, pushed, dl, dh, revisions);
+    int fail_v = settle(rlo, rhi, val);
+    if (fail_v < 0) {
+      /* (2a) Many moved bounds, few valued variables (an assignment on a bound of the root domains moves a bound
+       * of every other queen): cheaper than verifying each moved bound against all valued variables is to let
+       * every valued variable push again -- each sweep moves the bounds that are still forbidden by one more
+       * value -- until the moved bounds are fewer than the valued variables.  Rare (deep nodes never sweep). */
+      if (sweep_pays(dl, dh, val)) {
+        bool again;
+        do {
+          u64 who[R];
+#pragma unroll
+          for (int r = 0; r < R; r++) { who[r] = val[r]; dl[r] = 0ull; dh[r] = 0ull; }
+          push_phase(who, rlo, rhi, pushed, dl, dh, revisions);
+          fail_v = settle(rlo, rhi, val);
+          again = fail_v < 0;
+          if (again) again = sweep_pays(dl, dh, val);
+        } while (again);
+      }
+      if (fail_v < 0) {
+        verify_side<0>(rlo, rhi, dl, val, revisions, fail_v);
+        verify_side<1>(rlo, rhi, dh, val, revisions, fail_v);
+        fail_v = __builtin_amdgcn_readfirstlane(fail_v);
+        if (fail_v < 0) {
+          /* (3) variables that became values (and are supported) push next */
+          u64 any_push = 0ull;
+#pragma unroll
+          for (int r = 0; r < R; r++) {
+            push[r] = val[r] & ~pushed[r];
+            any_push |= push[r];
+          }
+          more = any_push != 0ull;
+        }
+      }
+    }
+    return fail_v;
   }
 
   /* the fixpoint; returns -1, or a variable whose domain has become empty (what the reference's
    * propagate_term_confl would be called for, propagate.c:33-41).  push: the variables that push first; pushed: those
-   * that have pushed already; dl / dh: bounds to be verified; val: the variables that are single values now. */
+   * that have pushed already; dl / dh: bounds to be verified; val: the variables that are single values now.
+   * The first round, which is the only one of most nodes, is peeled: the loop is entered by the nodes that cascade. */
   __device__ __forceinline__ int fixpoint(int (&rlo)[R], int (&rhi)[R], u64 (&pushed)[R], u64 (&push)[R], u64 (&dl)[R],
                                           u64 (&dh)[R], u64 (&val)[R], int &rounds, int &revisions) {
-    int fail_v = -1;
-    for (;;) {
-      /* (1) PUSH: every newly valued variable moves the bounds it sits on.  A valued variable's bounds do
-       * not change any more, so "value - dmin" of every pusher of this round is taken from one register. */
-      int cdv[R];
-#pragma unroll
-      for (int r = 0; r < R; r++) cdv[r] = rlo[r] + kb[r];
-#pragma unroll
-      for (int r = 0; r < R; r++) {
-        u64 bits = push[r];
-        pushed[r] |= bits;
-        while (bits != 0ull) {
-          const int ul = __builtin_ctzll(bits);
-          bits = cs_bitset0(bits, ul);
-          push_var(r, ul, __builtin_amdgcn_readlane(cdv[r], ul), rlo, rhi, dl, dh, revisions);
+    bool more;
+    int fail_v;
+    if (TRACE) { /* single-node launches: one copy of the round is enough */
+      do {
+        fail_v = round(rlo, rhi, pushed, push, dl, dh, val, revisions, more);
+        if (more) {
+          if (rounds == 0) __builtin_amdgcn_s_setprio(3);
+          rounds++;
         }
-      }
-      fail_v = settle(rlo, rhi, val);
-      if (fail_v >= 0) return fail_v;
-      /* (2a) Many moved bounds, few valued variables (an assignment on a bound of the root domains moves a bound
-       * of every other queen): cheaper than verifying each moved bound against all valued variables is to let
-       * every valued variable push again -- each sweep moves the bounds that are still forbidden by one more
-       * value -- until the moved bounds are fewer than the valued variables. */
-      for (;;) {
-        int n_dirty = 0, n_val = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) { n_dirty += __popcll(dl[r] | dh[r]); n_val += __popcll(val[r]); }
-        if (n_dirty <= n_val) break;
-#pragma unroll
-        for (int r = 0; r < R; r++) { cdv[r] = rlo[r] + kb[r]; dl[r] = 0ull; dh[r] = 0ull; }
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-          u64 bits = val[r];
-          pushed[r] |= bits;
-          while (bits != 0ull) {
-            const int ul = __builtin_ctzll(bits);
-            bits = cs_bitset0(bits, ul);
-            push_var(r, ul, __builtin_amdgcn_readlane(cdv[r], ul), rlo, rhi, dl, dh, revisions);
-          }
-        }
-        fail_v = settle(rlo, rhi, val);
-        if (fail_v >= 0) return fail_v;
-      }
-      /* (2) VERIFY: a moved bound stops at the first value no valued variable forbids.  Lane u holds the
-       * table entry e of (w, k, u); its own value forbids the value rlo[u] + e - kb[w] of w, i.e. the
-       * candidate c is forbidden iff e == c + kb[w] - rlo[u]: one subtraction per register, the compares run
-       * on the raw table bytes.  Mostly the candidate is supported and nothing is written. */
-#pragma unroll
-      for (int side = 0; side < 2; side++) {
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-          u64 bits = side == 0 ? dl[r] : dh[r];
-          if (side == 0) dl[r] = 0ull; else dh[r] = 0ull;
-          while (bits != 0ull) {
-            const int wl = __builtin_ctzll(bits);
-            bits = cs_bitset0(bits, wl);
-            int cand = __builtin_amdgcn_readlane(side == 0 ? rlo[r] : rhi[r], wl);
-            const int ckw = cand + __builtin_amdgcn_readlane(kb[r], wl);
-            revisions += __builtin_amdgcn_readlane(deg[r], wl);
-            const E *row = s_tab + (size_t)(wl + r * CS_WAVE) * slots * W + lane;
-            u64 hit = 0ull;
-            if (SL != 0) {
-              int e[SL ? SL : 1][R];
-#pragma unroll
-              for (int k = 0; k < (SL ? SL : 1); k++)
-#pragma unroll
-                for (int r2 = 0; r2 < R; r2++) e[k][r2] = (int)row[k * W + r2 * CS_WAVE];
-              int cause = -1; /* TRACE: a valued variable that forbids the candidate */
-#pragma unroll
-              for (int r2 = 0; r2 < R; r2++) {
-                const int t = ckw - rlo[r2];
-                u64 h = 0ull;
-#pragma unroll
-                for (int k = 0; k < (SL ? SL : 1); k++) h |= __ballot(e[k][r2] == t);
-                hit |= h & val[r2];
-                if (TRACE && cause < 0 && (h & val[r2]) != 0ull) cause = __builtin_ctzll(h & val[r2]) + r2 * CS_WAVE;
-              }
-              if (hit == 0ull) continue; /* supported: the common case */
-              /* the bound moves on, one value (one PROPS) at a time, until it is supported or passes the other */
-              const int other = __builtin_amdgcn_readlane(side == 0 ? rhi[r] : rlo[r], wl);
-              int step = 0;
-              for (;;) {
-                step++;
-                if (side == 0 ? cand + step > other : cand - step < other) break;
-                hit = 0ull;
-#pragma unroll
-                for (int r2 = 0; r2 < R; r2++) {
-                  const int t = ckw + (side == 0 ? step : -step) - rlo[r2];
-                  u64 h = 0ull;
-#pragma unroll
-                  for (int k = 0; k < (SL ? SL : 1); k++) h |= __ballot(e[k][r2] == t);
-                  hit |= h & val[r2];
-                }
-                if (hit == 0ull) break;
-              }
-              cand += side == 0 ? step : -step;
-              if (lane == wl) { if (side == 0) rlo[r] = cand; else rhi[r] = cand; }
-              if (TRACE) trace_lanes(1ull << wl, r, side, cand, cause);
-              /* a bound that passed the other one is the failure: noticed after the loops (no exit from in here) */
-              if (side == 0 ? cand > other : cand < other) fail_v = wl + r * CS_WAVE;
-              if (cand == other) val[r] |= 1ull << wl; /* counts for the verifications that follow */
-            } else {
-              /* run-time slot count: the row is re-read per candidate */
-              const int other = __builtin_amdgcn_readlane(side == 0 ? rhi[r] : rlo[r], wl);
-              int step = 0;
-              int cause = -1;
-              for (;;) {
-                hit = 0ull;
-                for (int k = 0; k < slots; k++) {
-#pragma unroll
-                  for (int r2 = 0; r2 < R; r2++) {
-                    const u64 h = __ballot((int)row[k * W + r2 * CS_WAVE] == ckw + (side == 0 ? step : -step) - rlo[r2]) & val[r2];
-                    hit |= h;
-                    if (TRACE && cause < 0 && h != 0ull) cause = __builtin_ctzll(h) + r2 * CS_WAVE;
-                  }
-                }
-                if (hit == 0ull) break;
-                step++;
-                if (side == 0 ? cand + step > other : cand - step < other) break;
-              }
-              if (step != 0) {
-                cand += side == 0 ? step : -step;
-                if (lane == wl) { if (side == 0) rlo[r] = cand; else rhi[r] = cand; }
-                if (TRACE) trace_lanes(1ull << wl, r, side, cand, cause);
-                if (side == 0 ? cand > other : cand < other) fail_v = wl + r * CS_WAVE;
-                if (cand == other) val[r] |= 1ull << wl;
-              }
-            }
-          }
-        }
-      }
-      if (fail_v >= 0) return fail_v;
-      /* (3) variables that became values (and are supported) push next */
-      u64 any_push = 0ull;
-#pragma unroll
-      for (int r = 0; r < R; r++) {
-        push[r] = val[r] & ~pushed[r];
-        any_push |= push[r];
-      }
-      if (any_push == 0ull) return -1;
+      } while (more);
+      return fail_v;
+    }
+    fail_v = round(rlo, rhi, pushed, push, dl, dh, val, revisions, more);
+    if (more) {
       /* a node that goes on cascading is a candidate for the tail of the launch (a few nodes cost 50 times the
        * average): from its second round on its wave is served first by the SIMD's arbiter */
       if (rounds == 0) __builtin_amdgcn_s_setprio(3);
-      rounds++;
+      do {
+        rounds++;
+        fail_v = round(rlo, rhi, pushed, push, dl, dh, val, revisions, more);
+      } while (more);
     }
+    return fail_v;
   }
 };
 

@@ -1,10 +1,10 @@
 #!/bin/bash
 # A/B of builds of libcsolve_hip.so on the SAME box: tools/ab/libcsolve_hip_base.so and every tools/ab/libcsolve_hip_var*.so
-# against the in-tree one, alternating, three rounds of the headline bench each (state_only leg: kernel_ms of
+# against the in-tree one, alternating, ROUNDS (default five) rounds of the headline bench each (state_only leg: kernel_ms of
 # queens-64 and queens-128).  Rank builds only by runs on one device (cdna_hip_programming.md rule 24).
 set -e
 mkdir -p gpurun_out
-for round in 1 2 3; do
+for round in $(seq ${ROUNDS:-5}); do
   for lib in tools/ab/libcsolve_hip_base.so tools/ab/libcsolve_hip_var*.so new; do
     [ "$lib" != new ] && [ ! -e "$lib" ] && continue
     path=""; [ "$lib" != new ] && path="$PWD/$lib"
