@@ -58,6 +58,11 @@ class ManyOptions(C.Structure):
     _fields_ = [("objective", C.c_int32), ("reserved", C.c_int32), ("max_nodes", C.c_int64)]
 
 
+class ManyUptoOptions(C.Structure):
+    """csgpu_many_upto_options: an instance stops at its max_solutions-th solution"""
+    _fields_ = [("max_solutions", C.c_int32), ("reserved", C.c_int32), ("max_nodes", C.c_int64)]
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Names of every function declared in include/csolve_gpu.h."""
     text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
@@ -220,6 +225,10 @@ def load_library():
     L.csgpu_solve_many_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
     L.csgpu_solve_many_resume.argtypes = [vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
     L.csgpu_many_checkpoint_states.argtypes = [vp, C.c_int32, vp, i64, C.POINTER(i64), vp]
+    L.csgpu_solve_many_upto.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp]
+    L.csgpu_solve_many_upto_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_upto_resume.argtypes = [vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
+    L.csgpu_internal_many_upto_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L

@@ -70,6 +70,7 @@ struct cs_kernel_plan {
   cs_planned step_shave, step_packed, step_import;
   cs_planned dive;                 /* cs_dive_shave (csgpu_solve_many): not one of csgpu_internal_plan_symbol's families */
   cs_planned dive_ck;              /* cs_dive_resume (csgpu_solve_many_checkpointed / _resume): the same */
+  cs_planned dive_upto;            /* cs_dive_upto (csgpu_solve_many_upto and its two checkpoint calls): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -816,6 +817,19 @@ static const void *dive_resume_kernel(int width, int n_vars) {
 #undef CS_PICK
 }
 
+/* the same loop leaving an instance at its k-th solution (csgpu_solve_many_upto / _upto_checkpointed / _upto_resume) */
+static const void *dive_upto_kernel(int width, int n_vars) {
+#define CS_PICK(E)                                                                                 \
+  switch (cs_dense_strides(n_vars)) {                                                              \
+  case 1: return (const void *)cs_dive_upto<E, 1>;                                                  \
+  case 2: return (const void *)cs_dive_upto<E, 2>;                                                  \
+  default: return (const void *)cs_dive_upto<E, 4>;                                                 \
+  }
+  if (width == 1) { CS_PICK(unsigned char) }
+  CS_PICK(unsigned short)
+#undef CS_PICK
+}
+
 /* ---- the resident single-node server (cs_shave.hip.h) ---- */
 static const void *shave_server_kernel(int width, int n_vars, int slots) {
   const int r = cs_dense_strides(n_vars);
@@ -1124,6 +1138,7 @@ static int plan_dense_table(csgpu_model *m) {
   /* cs_dive_shave: the table alone; the upper bounds of the root domains for its check of the root rows */
   if ((rc = plan_kernel(&m->plan.dive, dive_kernel(width, n), table, waves))) return rc;
   if ((rc = plan_kernel(&m->plan.dive_ck, dive_resume_kernel(width, n), table, waves))) return rc;
+  if ((rc = plan_kernel(&m->plan.dive_upto, dive_upto_kernel(width, n), table, waves))) return rc;
   {
     int *hi = (int *)malloc((size_t)n * sizeof(int));
     if (hi == NULL) return set_err(CSGPU_E_ARG, "out of memory");
@@ -1268,12 +1283,12 @@ extern "C" int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char
 }
 
 /* the same for cs_dive_shave, which is no family of the list above (the plan dictionary stays what it was) */
-static int many_symbol(const csgpu_model *m, int checkpointed, char *buf, size_t len) {
+static int many_symbol(const csgpu_model *m, int which, char *buf, size_t len) {
   if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
   buf[0] = '\0';
-  const void *fn = checkpointed ? m->plan.dive_ck.fn : m->plan.dive.fn;
-  const char *name = checkpointed ? "cs_dive_resume" : "cs_dive_shave";
+  const void *fn = which == 2 ? m->plan.dive_upto.fn : which == 1 ? m->plan.dive_ck.fn : m->plan.dive.fn;
+  const char *name = which == 2 ? "cs_dive_upto" : which == 1 ? "cs_dive_resume" : "cs_dive_shave";
   if (fn == NULL) return CSGPU_OK;
   Dl_info info;
   if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
@@ -1288,6 +1303,11 @@ extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_
 /* and for cs_dive_resume, the kernel of csgpu_solve_many_checkpointed and csgpu_solve_many_resume */
 extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t len) {
   return many_symbol(m, 1, buf, len);
+}
+
+/* and for cs_dive_upto, the kernel of csgpu_solve_many_upto, _upto_checkpointed and _upto_resume */
+extern "C" int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_symbol(m, 2, buf, len);
 }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
@@ -1776,6 +1796,85 @@ extern "C" int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, in
                      (cs_val *)d_states);
   HIP_TRY(hipGetLastError());
   return CSGPU_OK;
+}
+
+/* ---- up to k solutions per instance (cs_dive_upto): csgpu_solve_many, stopped at the k-th solution, all k rows kept ---- */
+
+/* the checks the three calls share, in csgpu_solve_many's order; nothing here touches the device.  `pooled`: the call
+ * has a pool and slot numbers */
+static int many_upto_args(const csgpu_model *m, const void *d_roots, int64_t count, const csgpu_many_upto_options *options,
+                          const void *d_results, int pooled, const csgpu_many_checkpoints *ck, const int32_t *d_slots) {
+  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL || (pooled && (ck == NULL || d_slots == NULL)))
+    return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every instance has a budget");
+  if (options->max_solutions < 1) return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (m->plan.dive_upto.fn == NULL)
+    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
+                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
+  if (pooled && ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
+  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  return CSGPU_OK;
+}
+
+/* ck == NULL: the plain call, a pool of capacity 0 that the kernel does not touch */
+static int many_upto_launch(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_upto_options *options,
+                            csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                            int resume, void *stream) {
+  if (count == 0) return CSGPU_OK;
+  csgpu_model *mm = const_cast<csgpu_model *>(m);
+  const cs_planned *k = &m->plan.dive_upto;
+  const int n = m->host->n_vars;
+  const int64_t waves = csgpu_internal_many_waves(m, count);
+  const int frames = n; /* as csgpu_solve_many; a resumed instance walks on the n frames of its slot */
+  int rc;
+  if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
+  cs_dive_io io;
+  io.roots = (const cs_val *)d_roots;
+  io.count = (int)count;
+  io.all = 1; /* not read: the walk is the ALL walk, left at the k-th solution */
+  io.max_nodes = (long long)options->max_nodes;
+  io.results = (cs_dive_result *)d_results;
+  io.solutions = d_solutions;
+  io.stack = resume ? NULL : (cs_val *)mm->d_many_stack;
+  io.frames = frames;
+  io.tickets = mm->d_many_tickets;
+  cs_dive_ck dk;
+  dk.pool = ck != NULL ? ck->d_pool : NULL;
+  dk.next = ck != NULL ? ck->d_next : NULL;
+  dk.capacity = ck != NULL ? (int)ck->capacity : 0;
+  dk.resume = resume;
+  dk.slots = ck != NULL ? d_slots : NULL;
+  int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin, upto = options->max_solutions;
+  const void *tab_d = m->d_dense_tab;
+  const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
+  size_t tab_bytes = m->dense_bytes;
+  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io, &dk, &upto };
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_solve_many_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                     const csgpu_many_upto_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                     void *stream) {
+  const int rc = many_upto_args(m, d_roots, count, options, d_results, 0, NULL, NULL);
+  return rc != CSGPU_OK ? rc : many_upto_launch(m, d_roots, count, options, d_results, d_solutions, NULL, NULL, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                  const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                                  int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                                  void *stream) {
+  const int rc = many_upto_args(m, d_roots, count, options, d_results, 1, ck, d_slots);
+  return rc != CSGPU_OK ? rc : many_upto_launch(m, d_roots, count, options, d_results, d_solutions, ck, d_slots, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
+                                            csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                            int32_t *d_slots, void *stream) {
+  const int rc = many_upto_args(m, d_results /* no roots: any non-null pointer */, count, options, d_results, 1, ck, d_slots);
+  return rc != CSGPU_OK ? rc : many_upto_launch(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
 }
 
 #ifdef CS_SHAVE_TIMELINE

@@ -48,7 +48,14 @@
  * the first copies nothing in and, when it stops again, writes only the current node; it needs no workspace at all.  A
  * fresh instance walks in the wave's workspace slice and copies its depth frames out when it stops (every lane copies
  * the entries it wrote itself).  The budget of a resumed instance counts the nodes of this launch; everything else
- * accumulates, so a walk in slices gives, counter for counter, the walk with the summed budget. */
+ * accumulates, so a walk in slices gives, counter for counter, the walk with the summed budget.
+ *
+ * Up to k solutions (cs_dive_upto, csgpu_solve_many_upto / _upto_checkpointed / _upto_resume): the same loop a third
+ * time, with CS_DIVE_CK 1 and CS_DIVE_UPTO 1.  The instance walks the ALL walk and leaves right after its k-th solution,
+ * as ANY leaves after its first; solution j goes to row j of the instance's k rows ([count][k][n], the index in 64 bits).
+ * k and the row index are scalars.  The kernel is checkpoint-capable and serves all three entries: the plain call
+ * passes a pool of capacity 0, which the kernel then never touches.  A resumed instance whose record already counts k
+ * solutions (k is per call) ends DONE before it tries a node: only so the row index stays below k. */
 #ifndef CS_DIVE_HIP_H
 #define CS_DIVE_HIP_H
 
@@ -74,10 +81,11 @@ static __device__ __forceinline__ long long cs_dive_uniform(long long x) {
 struct cs_dive_io {
   const cs_val *roots;     /* [count][n] */
   int count;
-  int all;                 /* 0: stop at the first solution, 1: walk the whole tree */
+  int all;                 /* 0: stop at the first solution, 1: walk the whole tree (cs_dive_upto does not read it) */
   long long max_nodes;
   cs_dive_result *results; /* [count] */
-  int *solutions;          /* [count][n] or NULL: the first solution of an instance that has one */
+  int *solutions;          /* [count][n] or NULL: the first solution of an instance that has one; cs_dive_upto:
+                              [count][k][n] or NULL, the first k in walk order */
   cs_val *stack;           /* [waves][frames][n + 1] */
   int frames;
   unsigned *tickets;       /* CS_DIVE_SHARDS counters, zero between launches */
@@ -89,7 +97,7 @@ struct cs_dive_io {
 struct cs_dive_ck {
   cs_val *pool;              /* [capacity][n + 1][n + 1] */
   unsigned long long *next;  /* slots handed out since the last reset (it counts on past capacity) */
-  int capacity;
+  int capacity;              /* cs_dive_upto: 0 = no pool (pool, next and slots are not touched) */
   int resume;                /* 0: fresh instances from io.roots; 1: instance i goes on from slot slots[i] */
   int *slots;                /* [count]: the slot of an instance stopped with a checkpoint, else -1 */
 };
@@ -101,7 +109,9 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_shave(int n, c
                                                                         const int *__restrict__ sym_off, size_t tab_bytes,
                                                                         cs_dive_io io) {
 #define CS_DIVE_CK 0
+#define CS_DIVE_UPTO 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
 }
 
@@ -113,7 +123,23 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_resume(int n, 
                                                                          const int *__restrict__ sym_off, size_t tab_bytes,
                                                                          cs_dive_io io, cs_dive_ck ck) {
 #define CS_DIVE_CK 1
+#define CS_DIVE_UPTO 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_UPTO
+#undef CS_DIVE_CK
+}
+
+/* the same again, leaving an instance right after its `upto`-th solution and keeping all of them (upto >= 1) */
+template <typename E, int R>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_upto(int n, const E *__restrict__ tab_g, int slots, int dmin,
+                                                                       const int *__restrict__ root_lo,
+                                                                       const int *__restrict__ root_hi,
+                                                                       const int *__restrict__ sym_off, size_t tab_bytes,
+                                                                       cs_dive_io io, cs_dive_ck ck, int upto) {
+#define CS_DIVE_CK 1
+#define CS_DIVE_UPTO 1
+#include "cs_dive_body.hip.h"
+#undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
 }
 

@@ -1,7 +1,11 @@
-/* cs_dive_body.hip.h -- the body of cs_dive_shave (CS_DIVE_CK 0) and of cs_dive_resume (CS_DIVE_CK 1), included by
- * cs_dive.hip.h inside either kernel.  Text, not a __device__ function: inlined from a function, the loop of
- * cs_dive_shave<E, 2> takes 42 vector registers instead of 39.  With CS_DIVE_CK 0 the text is the kernel as it was before
- * there were checkpoints, and compiles to the same instructions. */
+/* cs_dive_body.hip.h -- the body of cs_dive_shave (CS_DIVE_CK 0), of cs_dive_resume (CS_DIVE_CK 1) and of cs_dive_upto
+ * (CS_DIVE_CK 1, CS_DIVE_UPTO 1), included by cs_dive.hip.h inside each kernel.  Text, not a __device__ function: inlined
+ * from a function, the loop of cs_dive_shave<E, 2> takes 42 vector registers instead of 39.  With CS_DIVE_CK 0 the text is
+ * the kernel as it was before there were checkpoints, and compiles to the same instructions; every line of cs_dive_upto
+ * stands under `#if CS_DIVE_UPTO`, so the other two see the text they saw before there was a third.
+ * CS_DIVE_UPTO: the kernel has one more argument, `upto` (k >= 1, a scalar): the instance stops right after its k-th
+ * solution, solution j goes to row j of the instance's k rows, and io.all is not read.  A pool of capacity 0 means "no
+ * pool": ck.next, ck.pool and ck.slots are then never touched (csgpu_solve_many_upto). */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   typedef unsigned long long u64;
   const int lane = threadIdx.x & (CS_WAVE - 1);
@@ -145,6 +149,18 @@
         nodes = nodes0;
       }
     }
+#if CS_DIVE_UPTO
+    /* a resumed instance that holds its k solutions already (a smaller k than the slice before): DONE before it tries a
+     * node, nothing of it is written but this.  It is what keeps the row index below k; unsigned, so that a negative
+     * count in the caller's record ends here as well. */
+    if (resumed && (unsigned long long)sols >= (unsigned long long)upto) {
+      if (lane == 0) {
+        io.results[inst].status = 0; /* CSGPU_MANY_DONE */
+        ck.slots[inst] = -1;
+      }
+      continue;
+    }
+#endif
 #else
     const long long nodes0 = 0;
 #endif
@@ -184,9 +200,16 @@
       } else if (open_vars == 0) {
         sols = 1;
         if (io.solutions != nullptr) {
+#if CS_DIVE_UPTO
+          const size_t row0 = (size_t)inst * (size_t)upto * (size_t)n; /* row 0 of the instance's k rows */
+#pragma unroll
+          for (int r = 0; r < R; r++)
+            if (live[r]) io.solutions[row0 + lane + r * CS_WAVE] = plo[r] + b0[r];
+#else
 #pragma unroll
           for (int r = 0; r < R; r++)
             if (live[r]) io.solutions[rrow + lane + r * CS_WAVE] = plo[r] + b0[r];
+#endif
         }
       } else {
         int depth = 0, bv, br, bl, xlo = 0, bhi = 0, nv;
@@ -211,6 +234,9 @@
             status = 1; /* CSGPU_MANY_LIMIT */
 #if CS_DIVE_CK
             { /* leave a checkpoint, if the pool has a slot */
+#if CS_DIVE_UPTO
+              if (ck.capacity > 0) /* no pool: no slot is drawn, the instance ends as without checkpoints */
+#endif
               if (!resumed) {
                 unsigned long long drawn = 0ull;
                 if (lane == 0) drawn = __hip_atomic_fetch_add(ck.next, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -279,12 +305,22 @@
             props -= bhi - xlo; /* the assignment itself is no narrowing */
             if (open_c == 0) {
               sols++;
+#if CS_DIVE_UPTO
+              if (io.solutions != nullptr) { /* 1 <= sols <= upto here: a fresh count starts at 0, a resumed one below upto */
+                const size_t srow = ((size_t)inst * (size_t)upto + (size_t)(sols - 1)) * (size_t)n;
+#pragma unroll
+                for (int r = 0; r < R; r++)
+                  if (live[r]) io.solutions[srow + lane + r * CS_WAVE] = rlo[r] + b0[r];
+              }
+              if (sols >= (long long)upto) break;
+#else
               if (sols == 1 && io.solutions != nullptr) {
 #pragma unroll
                 for (int r = 0; r < R; r++)
                   if (live[r]) io.solutions[rrow + lane + r * CS_WAVE] = rlo[r] + b0[r];
               }
               if (!io.all) break;
+#endif
             } else {
               descend = true;
             }
@@ -334,6 +370,9 @@
       res.status = status; res.root_props = root_props;
       res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
       io.results[inst] = res;
+#if CS_DIVE_UPTO
+      if (ck.capacity > 0)
+#endif
 #if CS_DIVE_CK
       ck.slots[inst] = kept;
 #endif

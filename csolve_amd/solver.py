@@ -5,13 +5,14 @@ parent state), `propagate` (propagate_clauses for every node of a batch), `eval_
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
 import torch
 
-from ._lib import (PLAN_FAMILIES, CsolveError, ManyOptions, ManyResult, Node, Result, SearchStats, Val, check, demangle,
-                   load_library)
+from ._lib import (PLAN_FAMILIES, CsolveError, ManyOptions, ManyResult, ManyUptoOptions, Node, Result, SearchStats, Val,
+                   check, demangle, load_library)
 
 STATUS_FAIL = -1
 
@@ -263,6 +264,62 @@ class Model:
             out["_records"], out["_slots"], out["_checkpoints"] = buf, slots, checkpoints
         return out
 
+    def solve_many_upto(self, roots, k, *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
+        """solve_many that leaves an instance right after its k-th solution and keeps all k (csgpu_solve_many_upto): the
+        ALL walk, stopped as ANY stops after the first.  k = 1 is ANY, an instance with fewer than k solutions ends as
+        under ALL; status DONE means solutions == min(k, solutions of the tree).  roots, max_nodes, stream, checkpoints:
+        as solve_many.  -> the dict of solve_many with `rows` [K, k, n_vars] int32 in place of `first`: row j of instance
+        i is its j-th solution in walk order, rows >= solutions[i] are not written.  solutions: True (a zeroed buffer),
+        False (no rows), or an int32 device tensor [K, k, n_vars] to write into.  With a pool the answer has `slot` and
+        is what resume_many() continues (csgpu_solve_many_upto_checkpointed)."""
+        L = load_library()
+        n, k = self.n_vars, int(k)
+        opt = ManyUptoOptions(k, 0, int(max_nodes))
+        if not torch.is_tensor(roots):
+            roots = np.ascontiguousarray(roots, dtype=np.int32)
+            assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
+            if not self.qualifies(7) or k < 1:
+                # as solve_many: the library says what is wrong before any device call, nothing is uploaded for it
+                check(L.csgpu_solve_many_upto(self._h, roots.ctypes.data, roots.shape[0], C.byref(opt), roots.ctypes.data,
+                                              None, None))
+            roots = torch.from_numpy(roots).cuda()
+        assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
+        assert roots.dim() == 3 and tuple(roots.shape[1:]) == (n, 2), "roots is [K, n_vars, 2]"
+        K = roots.shape[0]
+        buf = torch.zeros((max(K, 1), 5), dtype=torch.int64, device=roots.device)  # csgpu_many_result: 40 bytes
+        rows = None
+        if torch.is_tensor(solutions):
+            rows = solutions
+            assert rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and tuple(rows.shape) == (K, k, n), \
+                "solutions is [K, k, n_vars] int32 on the device"
+        elif solutions:
+            rows = torch.zeros((K, max(k, 0), n), dtype=torch.int32, device=roots.device)
+        rows_ptr = rows.data_ptr() if rows is not None and K and k >= 1 else None
+        if checkpoints is None:
+            check(L.csgpu_solve_many_upto(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                                          rows_ptr, _stream_ptr(stream)))
+            out = self._many_answer(buf, K, None)
+        else:
+            slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
+            check(L.csgpu_solve_many_upto_checkpointed(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
+                                                       buf.data_ptr(), rows_ptr, checkpoints._h, slots.data_ptr(),
+                                                       _stream_ptr(stream)))
+            out = self._many_answer(buf, K, None, slots, checkpoints)
+            out["_upto"] = k  # resume_many goes on through csgpu_solve_many_upto_resume, with this k unless told another
+        if rows is not None:
+            out["rows"] = rows
+        return out
+
+    def classify_many(self, roots, *, max_nodes, stream=None) -> torch.Tensor:
+        """is the solution unique?  -> int8 [K] on the device: 0 no solution, 1 exactly one, 2 several, -1 undecided
+        within max_nodes (LIMIT), -2 bad root row.  A solve_many_upto with k = 2 and no rows."""
+        out = self.solve_many_upto(roots, 2, max_nodes=max_nodes, solutions=False, stream=stream)
+        status, found = out["status"], out["solutions"]
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+        with ctx:
+            cls = torch.where(status == 2, torch.full_like(found, -2), torch.where(status == 1, torch.full_like(found, -1), found))
+            return cls.to(torch.int8)
+
     def many_checkpoints(self, capacity: int) -> "ManyCheckpoints":
         """a pool of `capacity` checkpoint slots for solve_many(..., checkpoints=) (csgpu_many_checkpoints_create); a
         slot stays with its instance until reset()"""
@@ -272,11 +329,18 @@ class Model:
         """bytes of one checkpoint slot, 0 if the model does not qualify (host only: after build_tables or finalize)"""
         return int(load_library().csgpu_many_checkpoint_bytes(self._h))
 
-    def resume_many(self, result: dict, *, max_nodes, objective="ANY", stream=None) -> dict:
+    def resume_many(self, result: dict, *, max_nodes, objective="ANY", stream=None, max_solutions=None) -> dict:
         """continue, in place, the instances of a checkpointed solve_many answer that stopped with a checkpoint
         (csgpu_solve_many_resume): `max_nodes` more nodes each; counters accumulate, `first` is written when an
-        instance's `solutions` goes from 0 to 1, rows of instances without a slot are not touched.  -> result"""
+        instance's `solutions` goes from 0 to 1, rows of instances without a slot are not touched.  -> result
+        An answer of solve_many_upto(..., checkpoints=pool) goes on through csgpu_solve_many_upto_resume (`objective`
+        does not apply): its rows continue at index `solutions`.  max_solutions: the k of THIS slice, by default the
+        answer's; an instance that already holds that many ends DONE untouched; with another k the rows are laid out
+        anew for the call ([K, max(k), n_vars] stays or grows)."""
         assert "_checkpoints" in result, "an answer of solve_many(..., checkpoints=pool)"
+        if "_upto" in result:
+            return self._resume_many_upto(result, int(max_nodes), max_solutions, stream)
+        assert max_solutions is None, "max_solutions continues an answer of solve_many_upto"
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         opt = ManyOptions(obj, 0, int(max_nodes))
         first = result.get("first")
@@ -285,6 +349,34 @@ class Model:
                                                      first.data_ptr() if first is not None and K else None,
                                                      result["_checkpoints"]._h, result["_slots"].data_ptr(),
                                                      _stream_ptr(stream)))
+        return result
+
+    def _resume_many_upto(self, result: dict, max_nodes: int, max_solutions, stream) -> dict:
+        had = result["_upto"]
+        k = had if max_solutions is None else int(max_solutions)
+        opt = ManyUptoOptions(k, 0, max_nodes)
+        rows = result.get("rows")
+        K = result["status"].shape[0]
+        L = load_library()
+
+        def call(buf):
+            check(L.csgpu_solve_many_upto_resume(self._h, K, C.byref(opt), result["_records"].data_ptr(),
+                                                 buf.data_ptr() if buf is not None and K and k >= 1 else None,
+                                                 result["_checkpoints"]._h, result["_slots"].data_ptr(), _stream_ptr(stream)))
+
+        if rows is None or k == had or k < 1:
+            call(rows)
+            return result
+        # the kernel indexes rows with the k of the call: a buffer laid out for this k, carrying the rows there are
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            laid = torch.zeros((K, k, rows.shape[2]), dtype=torch.int32, device=rows.device)
+            keep = min(k, had)
+            laid[:, :keep] = rows[:, :keep]
+            call(laid)
+            if k < had:
+                rows[:, :k] = laid
+            else:
+                result["rows"], result["_upto"] = laid, k
         return result
 
     def checkpoint_states(self, checkpoints: "ManyCheckpoints", slot: int, stream=None) -> torch.Tensor:
@@ -312,7 +404,7 @@ class Model:
         return out[alive & ~complete].contiguous(), out[alive & complete].contiguous()
 
     def solve_many_sliced(self, roots, objective="ANY", *, budgets, finish="resume", solutions=True, pool_capacity=1 << 18,
-                          max_children=1 << 14) -> dict:
+                          max_children=1 << 14, max_solutions=None) -> dict:
         """solve_many in slices: a checkpointed call with budgets[0], then a resume with each following budget while
         an instance is at LIMIT.  finish="resume": that is all (instances still at LIMIT stay so, with their slots).
         finish="search": after the last budget every instance still at LIMIT hands its open subtrees to a Search of
@@ -322,8 +414,25 @@ class Model:
         up to the same node, so they are NOT the single-wave walk's.  The engine walks with the model's own objective,
         which must be the one asked for.  Synchronises between the slices.
         -> the dict of solve_many plus `slot` and `sliced`: {"slices": calls made, "searched": instances finished by
-        a Search}"""
+        a Search}
+        max_solutions=k: the slices are solve_many_upto calls (`objective` does not apply, the answer has `rows`), with
+        finish="resume" only."""
         assert finish in ("resume", "search") and len(budgets) >= 1
+        if max_solutions is not None:
+            if finish == "search":
+                raise ValueError("finish=\"search\" with max_solutions: an engine search cannot stop at a k-th solution "
+                                 "per instance")
+            K = roots.shape[0]
+            pool = self.many_checkpoints(max(K, 1))
+            out = self.solve_many_upto(roots, max_solutions, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+            slices = 1
+            for budget in budgets[1:]:
+                if not bool((out["status"] == 1).any()):
+                    break
+                self.resume_many(out, max_nodes=budget)
+                slices += 1
+            out["sliced"] = {"slices": slices, "searched": 0}
+            return out
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         if finish == "search" and obj != self.objective:
             raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
@@ -384,6 +493,13 @@ class Model:
         """the cs_dive_resume instantiation the checkpointed calls launch (template-id), None if the model does not qualify"""
         buf = C.create_string_buffer(1024)
         check(load_library().csgpu_internal_many_resume_symbol(self._h, buf, len(buf)))
+        return demangle(buf.value.decode()) if buf.value else None
+
+    def many_upto_kernel(self):
+        """the cs_dive_upto instantiation solve_many_upto and its checkpoint calls launch (template-id), None if the model
+        does not qualify"""
+        buf = C.create_string_buffer(1024)
+        check(load_library().csgpu_internal_many_upto_symbol(self._h, buf, len(buf)))
         return demangle(buf.value.decode()) if buf.value else None
 
     def many_waves(self, count: int) -> int:

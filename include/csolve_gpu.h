@@ -309,6 +309,42 @@ int csgpu_solve_many_resume(const csgpu_model *m, int64_t count, const csgpu_man
 int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap, int64_t *count,
                                  void *stream);
 
+/* ---- up to k solutions per instance: csgpu_solve_many, left at an instance's k-th solution ----
+ * "Is the solution unique?", "give me the first k": the instance walks exactly the ALL walk (same branching rule, same
+ * value order, same counters) and stops right after accepting its k-th solution, as ANY stops after its first.
+ * max_solutions = 1 is ANY, field for field; an instance whose whole tree holds fewer than k solutions ends as under
+ * ALL, field for field.  d_results is csgpu_many_result as above.  CSGPU_MANY_DONE: the k-th solution was reached or the
+ * tree is exhausted, and solutions == min(k, solutions of the tree) -- with k = 2, "unique" is DONE && solutions == 1,
+ * "several" DONE && solutions == 2, "none" DONE && solutions == 0.  LIMIT, BAD_ROOT and BAD_SLOT are as above.
+ *   d_solutions   NULL, or [count][max_solutions][n_vars] int32: row j of instance i is its j-th solution in walk order
+ *                 (a root row that is a solution already is row 0); rows >= solutions of an instance are not touched
+ * The three entries are csgpu_solve_many, csgpu_solve_many_checkpointed and csgpu_solve_many_resume with this stop; pool,
+ * slots, csgpu_many_checkpoint_states and csgpu_many_checkpoints_reset are those above, unchanged, and a checkpoint
+ * written here exports its open subtrees like any other.  A resumed instance reads its counters from its record and
+ * continues its rows at index `solutions`: a walk in slices gives, field for field and row for row, the one call with
+ * the summed budget.  max_solutions is per call: a resumed instance whose record already has solutions >= max_solutions
+ * ends DONE before it tries a node, and nothing of it is written but its status and d_slots[i] = -1 (rows are indexed
+ * with the max_solutions of the call that writes them: give every slice the k the buffer was laid out for, or a buffer
+ * laid out for the new k).  "One call in flight per model" covers these calls (same workspace, same ticket counters);
+ * calls of both families may be queued behind each other on one stream without the host in between.
+ * Errors before any HIP call, in csgpu_solve_many's order: a null pointer (d_solutions may be null), count < 0,
+ * max_nodes <= 0, max_solutions < 1 -> CSGPU_E_ARG; model not finalized -> CSGPU_E_STATE; model does not qualify for
+ * kernel 7 -> CSGPU_E_LIMIT; a pool created for another model -> CSGPU_E_ARG.  count == 0 -> CSGPU_OK, nothing is
+ * launched. */
+typedef struct csgpu_many_upto_options {
+  int32_t max_solutions; /* k >= 1: an instance stops at its k-th solution */
+  int32_t reserved;      /* 0 */
+  int64_t max_nodes;     /* as csgpu_many_options */
+} csgpu_many_upto_options;
+int csgpu_solve_many_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_upto_options *options,
+                          csgpu_many_result *d_results, int32_t *d_solutions, void *stream);
+int csgpu_solve_many_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                       const csgpu_many_upto_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                       csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_solve_many_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
+                                 csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                 void *stream);
+
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */
 int csgpu_eval_batch(const csgpu_model *m, const csgpu_val *d_states, int32_t *d_truth, int64_t batch,

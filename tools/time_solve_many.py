@@ -8,11 +8,15 @@ time as a function of max_nodes (bulk against tail), and a seeded sample of the 
 oracle walk (tests/many_walk.py).
 
   python tools/time_solve_many.py --set sudoku9 [--count 65536] [--reps 5] [--loop-sample 256] [--check 32]
-                                  [--sliced B0,B1,... [--finish resume|search]]
+                                  [--sliced B0,B1,... [--finish resume|search]] [--upto K]
   --sliced: the same instances through Model.solve_many_sliced as well (a checkpointed call with budget B0, a resume
   with every following budget; --finish search: what is left after the last budget through one Search per instance):
   the time of the whole, the time until the answers of the first slice are there, and whether it found what the one
   call found.
+  --upto K: Model.solve_many_upto (an instance stops at its K-th solution, all K rows kept) on the same instances beside
+  the ANY and the ALL call of solve_many, all three in this process after a warm-up, same budget: medians and ranges of
+  --reps, what each call decided, the share of instances a k = 2 call classifies as unique / several / none / undecided,
+  and the sampled answers (fields and rows) re-checked against the host walk of tests/many_walk_upto.py.
   sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY)
 """
 import argparse
@@ -67,6 +71,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--sliced", default=None, help="budgets of the slices, e.g. 256,4096")
     ap.add_argument("--finish", default="resume", choices=("resume", "search"))
+    ap.add_argument("--upto", type=int, default=None, help="K: time solve_many_upto beside the ANY and the ALL call")
     args = ap.parse_args()
     count = args.count or {"sudoku9": 65536, "queens12": 16384, "sudoku16": 4096}[args.set]
     text, roots, objective, budget = instances(args.set, count)
@@ -136,8 +141,53 @@ def main():
                   "counters_equal_one_call": same, "kernel": model.many_resume_kernel(),
                   "slot_bytes": model.checkpoint_bytes()}
 
-    # the per-instance loop: one Search, reset and seeded per instance
     rng = np.random.default_rng(args.seed)
+    upto = None
+    if args.upto is not None:
+        import many_walk_upto
+
+        def timed(call):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = call()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, res
+
+        calls = {"any": lambda: model.solve_many(dev, "ANY", max_nodes=budget),
+                 "all": lambda: model.solve_many(dev, "ALL", max_nodes=budget),
+                 "upto": lambda: model.solve_many_upto(dev, args.upto, max_nodes=budget)}
+        for call in calls.values():  # warm-up: code load, workspace, the allocator's blocks
+            timed(call)
+            timed(call)
+        series = {name: [] for name in calls}
+        answers = {}
+        for _ in range(args.reps):  # interleaved: a drift of the machine falls on all three alike
+            for name, call in calls.items():
+                dt, answers[name] = timed(call)
+                series[name].append(dt)
+
+        def summary(name):
+            ts, res = series[name], answers[name]
+            return {"ms": {"median": round(statistics.median(ts) * 1e3, 3), "min": round(min(ts) * 1e3, 3),
+                           "max": round(max(ts) * 1e3, 3), "reps": args.reps},
+                    "status_counts": torch.bincount(res["status"].long(), minlength=3).tolist(),
+                    "nodes": int(res["nodes"].sum()), "largest_tree": int(res["nodes"].max()),
+                    "solutions": int(res["solutions"].sum())}
+
+        cls = model.classify_many(dev, max_nodes=budget)
+        share = {name: int((cls == value).sum()) for name, value in (("none", 0), ("unique", 1), ("several", 2),
+                                                                      ("limit", -1), ("bad_root", -2))}
+        picks_u = rng.choice(count, size=min(args.check, count), replace=False)
+        want_u = many_walk_upto.dive_many_upto(text, roots[picks_u], args.upto, budget)
+        got_u = {k: v[torch.from_numpy(picks_u).cuda()].cpu().numpy() for k, v in answers["upto"].items() if torch.is_tensor(v)}
+        upto_ok = all((got_u[f] == want_u[f]).all() for f in many_walk_upto.FIELDS) and bool((got_u["rows"] == want_u["rows"]).all())
+        same_as_any = all(bool((answers["upto"][f] == answers["any"][f]).all()) for f in many_walk_upto.FIELDS)
+        upto = {"k": args.upto, "kernel": model.many_upto_kernel(), "max_nodes": budget,
+                "any": summary("any"), "all": summary("all"), "upto": summary("upto"),
+                "classes_k2": share, "every_field_equals_any": same_as_any,
+                "oracle_checked": len(picks_u), "oracle_ok": bool(upto_ok)}
+
+    # the per-instance loop: one Search, reset and seeded per instance
     sample = np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
     search = Search(model, 1 << 18, 1 << 14)
     node = torch.tensor([[-1, 0, 0, 0]], dtype=torch.int32, device="cuda")
@@ -189,8 +239,9 @@ def main():
         "ratio_instances_per_s": round(many_rate / loop_rate, 1),
         "oracle_checked": len(picks), "oracle_ok": checked_ok,
         **({"sliced": sliced} if sliced else {}),
+        **({"upto": upto} if upto else {}),
     }))
-    return 0 if checked_ok else 1
+    return 0 if checked_ok and (upto is None or upto["oracle_ok"]) else 1
 
 
 if __name__ == "__main__":
