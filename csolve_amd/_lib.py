@@ -63,6 +63,14 @@ class ManyUptoOptions(C.Structure):
     _fields_ = [("max_solutions", C.c_int32), ("reserved", C.c_int32), ("max_nodes", C.c_int64)]
 
 
+MANY_ROTATE_FIRST = 1  # CSGPU_MANY_ROTATE_FIRST
+
+
+class ManyRestartOptions(C.Structure):
+    """csgpu_many_restart_options: Luby restarts (restart_base x 1 1 2 1 1 2 4 ... failures) with a seeded value order"""
+    _fields_ = [("max_nodes", C.c_int64), ("restart_base", C.c_int64), ("seed", C.c_uint32), ("flags", C.c_int32)]
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Names of every function declared in include/csolve_gpu.h."""
     text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
@@ -229,6 +237,10 @@ def load_library():
     L.csgpu_solve_many_upto_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
     L.csgpu_solve_many_upto_resume.argtypes = [vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
     L.csgpu_internal_many_upto_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many_restarts.argtypes = [vp, vp, vp, i64, C.POINTER(ManyRestartOptions), vp, vp, vp, vp]
+    L.csgpu_internal_many_restart_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_many_value.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, Val, C.c_uint32, C.c_int32]
+    L.csgpu_many_value.restype = C.c_int32
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L

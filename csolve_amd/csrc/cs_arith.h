@@ -149,7 +149,7 @@ CS_HD static inline int32_t cs_objective_best(int sense, cs_val d, int32_t best)
 }
 
 /* fail_threshold_next (csolve.c:76-83): Knuth's formulation of the Luby sequence 1 1 2 1 1 2 4 ... */
-static inline void cs_luby_next(uint64_t *threshold, uint64_t *counter) {
+CS_HD static inline void cs_luby_next(uint64_t *threshold, uint64_t *counter) {
   if ((*counter & (0 - *counter)) == *threshold) {
     (*counter)++;
     *threshold = 1;
@@ -165,6 +165,35 @@ CS_HD static inline int cs_step_check(cs_val bounds, uint32_t iter) {
 }
 CS_HD static inline int32_t cs_step_val(cs_val bounds, uint32_t iter, uint32_t seed) {
   return ((iter ^ seed) & 1u) ? (int32_t)((uint32_t)bounds.hi - (iter >> 1)) : (int32_t)((uint32_t)bounds.lo + (iter >> 1));
+}
+
+/* The value order of csgpu_solve_many_restarts (csolve_gpu.h): a node that branches on variable `var` with `width`
+ * values tries value(j) = lo + ((start + j) mod width), j = 0 .. width - 1 -- a rotation of the ascending order.  start
+ * is 0 in run 0 unless CSGPU_MANY_ROTATE_FIRST (flag bit 0) is set, else the high word of key * width, key a murmur3
+ * finalizer of (seed, run, var): one multiply-high, no division.  All of it wraps in 32 bits.  cs_many_start is computed
+ * once per entered node, cs_many_rotated once per value (start < width and j < width: one conditional subtraction). */
+CS_HD static inline uint32_t cs_fmix32(uint32_t x) {
+  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+  return x;
+}
+CS_HD static inline uint32_t cs_many_start(uint32_t seed, uint32_t run, int32_t var, uint32_t width, int32_t flags) {
+  if (run == 0u && !(flags & 1)) return 0u;
+  const uint32_t key = cs_fmix32(seed ^ cs_fmix32(run * 0x9E3779B1u + (uint32_t)var + 1u));
+  return (uint32_t)(((uint64_t)key * width) >> 32);
+}
+CS_HD static inline int32_t cs_many_rotated(int32_t lo, uint32_t width, uint32_t start, uint32_t j) {
+  const uint32_t s = start + j;
+  return (int32_t)((uint32_t)lo + (s >= width ? s - width : s));
+}
+/* the whole definition for one (node, j); j is taken mod width.  An interval of all 2^32 values (width wraps to 0)
+ * rotates by the key itself */
+CS_HD static inline int32_t cs_many_value(uint32_t seed, uint32_t run, int32_t var, cs_val bounds, uint32_t j, int32_t flags) {
+  const uint32_t width = (uint32_t)bounds.hi - (uint32_t)bounds.lo + 1u;
+  if (width == 0u) {
+    const uint32_t key = run == 0u && !(flags & 1) ? 0u : cs_fmix32(seed ^ cs_fmix32(run * 0x9E3779B1u + (uint32_t)var + 1u));
+    return (int32_t)((uint32_t)bounds.lo + key + j);
+  }
+  return cs_many_rotated(bounds.lo, width, cs_many_start(seed, run, var, width, flags), j % width);
 }
 
 /* The branching rule's key (strategy_var_cmp, reference src/strategy.c:79-121): the variable with the SMALLEST key is

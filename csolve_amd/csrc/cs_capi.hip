@@ -71,6 +71,7 @@ struct cs_kernel_plan {
   cs_planned dive;                 /* cs_dive_shave (csgpu_solve_many): not one of csgpu_internal_plan_symbol's families */
   cs_planned dive_ck;              /* cs_dive_resume (csgpu_solve_many_checkpointed / _resume): the same */
   cs_planned dive_upto;            /* cs_dive_upto (csgpu_solve_many_upto and its two checkpoint calls): the same */
+  cs_planned dive_restart;         /* cs_dive_restart (csgpu_solve_many_restarts): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -209,6 +210,9 @@ extern "C" uint64_t csgpu_branch_key(int order, int prefer_failing, csgpu_val va
 }
 extern "C" int32_t csgpu_step_val(csgpu_val bounds, uint32_t iter, uint32_t seed) {
   return cs_step_val(cs_interval(bounds.lo, bounds.hi), iter, seed);
+}
+extern "C" int32_t csgpu_many_value(uint32_t seed, uint32_t run, int32_t var, csgpu_val bounds, uint32_t j, int32_t flags) {
+  return cs_many_value(seed, run, var, cs_interval(bounds.lo, bounds.hi), j, flags);
 }
 
 /* ---- host model ------------------------------------------------------------------ */
@@ -830,6 +834,19 @@ static const void *dive_upto_kernel(int width, int n_vars) {
 #undef CS_PICK
 }
 
+/* the ANY loop with a seeded value order and Luby restarts (csgpu_solve_many_restarts) */
+static const void *dive_restart_kernel(int width, int n_vars) {
+#define CS_PICK(E)                                                                                 \
+  switch (cs_dense_strides(n_vars)) {                                                              \
+  case 1: return (const void *)cs_dive_restart<E, 1>;                                               \
+  case 2: return (const void *)cs_dive_restart<E, 2>;                                               \
+  default: return (const void *)cs_dive_restart<E, 4>;                                              \
+  }
+  if (width == 1) { CS_PICK(unsigned char) }
+  CS_PICK(unsigned short)
+#undef CS_PICK
+}
+
 /* ---- the resident single-node server (cs_shave.hip.h) ---- */
 static const void *shave_server_kernel(int width, int n_vars, int slots) {
   const int r = cs_dense_strides(n_vars);
@@ -1139,6 +1156,7 @@ static int plan_dense_table(csgpu_model *m) {
   if ((rc = plan_kernel(&m->plan.dive, dive_kernel(width, n), table, waves))) return rc;
   if ((rc = plan_kernel(&m->plan.dive_ck, dive_resume_kernel(width, n), table, waves))) return rc;
   if ((rc = plan_kernel(&m->plan.dive_upto, dive_upto_kernel(width, n), table, waves))) return rc;
+  if ((rc = plan_kernel(&m->plan.dive_restart, dive_restart_kernel(width, n), table, waves))) return rc;
   {
     int *hi = (int *)malloc((size_t)n * sizeof(int));
     if (hi == NULL) return set_err(CSGPU_E_ARG, "out of memory");
@@ -1287,8 +1305,11 @@ static int many_symbol(const csgpu_model *m, int which, char *buf, size_t len) {
   if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
   buf[0] = '\0';
-  const void *fn = which == 2 ? m->plan.dive_upto.fn : which == 1 ? m->plan.dive_ck.fn : m->plan.dive.fn;
-  const char *name = which == 2 ? "cs_dive_upto" : which == 1 ? "cs_dive_resume" : "cs_dive_shave";
+  const void *fn = which == 3   ? m->plan.dive_restart.fn
+                   : which == 2 ? m->plan.dive_upto.fn
+                   : which == 1 ? m->plan.dive_ck.fn
+                                : m->plan.dive.fn;
+  const char *name = which == 3 ? "cs_dive_restart" : which == 2 ? "cs_dive_upto" : which == 1 ? "cs_dive_resume" : "cs_dive_shave";
   if (fn == NULL) return CSGPU_OK;
   Dl_info info;
   if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
@@ -1308,6 +1329,11 @@ extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf
 /* and for cs_dive_upto, the kernel of csgpu_solve_many_upto, _upto_checkpointed and _upto_resume */
 extern "C" int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len) {
   return many_symbol(m, 2, buf, len);
+}
+
+/* and for cs_dive_restart, the kernel of csgpu_solve_many_restarts */
+extern "C" int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_symbol(m, 3, buf, len);
 }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
@@ -1875,6 +1901,56 @@ extern "C" int csgpu_solve_many_upto_resume(const csgpu_model *m, int64_t count,
                                             int32_t *d_slots, void *stream) {
   const int rc = many_upto_args(m, d_results /* no roots: any non-null pointer */, count, options, d_results, 1, ck, d_slots);
   return rc != CSGPU_OK ? rc : many_upto_launch(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
+}
+
+/* ---- Luby restarts with a seeded value order for ANY (cs_dive_restart) ---- */
+
+static_assert(sizeof(csgpu_many_restart_options) == 24, "csgpu_many_restart_options layout");
+
+extern "C" int csgpu_solve_many_restarts(const csgpu_model *m, const csgpu_val *d_roots, const uint32_t *d_seeds, int64_t count,
+                                         const csgpu_many_restart_options *options, csgpu_many_result *d_results,
+                                         int32_t *d_solutions, int32_t *d_restarts, void *stream) {
+  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every instance has a budget");
+  if (options->restart_base < 0) return set_err(CSGPU_E_ARG, "restart_base must not be negative (0: no restarts)");
+  if ((options->flags & ~CSGPU_MANY_ROTATE_FIRST) != 0) return set_err(CSGPU_E_ARG, "unknown flags 0x%x", (unsigned)options->flags);
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (m->plan.dive_restart.fn == NULL)
+    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
+                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
+  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  if (count == 0) return CSGPU_OK;
+  csgpu_model *mm = const_cast<csgpu_model *>(m);
+  const cs_planned *k = &m->plan.dive_restart;
+  const int n = m->host->n_vars;
+  const int64_t waves = csgpu_internal_many_waves(m, count);
+  const int frames = n; /* as csgpu_solve_many: at most n - 1 are in use, the n-th keeps the root node's fixpoint */
+  int rc;
+  if ((rc = many_workspace(mm, waves, frames))) return rc;
+  cs_dive_io io;
+  io.roots = (const cs_val *)d_roots;
+  io.count = (int)count;
+  io.all = 0;
+  io.max_nodes = (long long)options->max_nodes;
+  io.results = (cs_dive_result *)d_results;
+  io.solutions = d_solutions;
+  io.stack = (cs_val *)mm->d_many_stack;
+  io.frames = frames;
+  io.tickets = mm->d_many_tickets;
+  cs_dive_rs rs;
+  rs.seeds = d_seeds;
+  rs.restarts = d_restarts;
+  rs.restart_base = (long long)options->restart_base;
+  rs.seed = options->seed;
+  rs.flags = options->flags;
+  int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
+  const void *tab_d = m->d_dense_tab;
+  const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
+  size_t tab_bytes = m->dense_bytes;
+  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io, &rs };
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
+  return CSGPU_OK;
 }
 
 #ifdef CS_SHAVE_TIMELINE

@@ -55,7 +55,16 @@
  * as ANY leaves after its first; solution j goes to row j of the instance's k rows ([count][k][n], the index in 64 bits).
  * k and the row index are scalars.  The kernel is checkpoint-capable and serves all three entries: the plain call
  * passes a pool of capacity 0, which the kernel then never touches.  A resumed instance whose record already counts k
- * solutions (k is per call) ends DONE before it tries a node: only so the row index stays below k. */
+ * solutions (k is per call) ends DONE before it tries a node: only so the row index stays below k.
+ *
+ * Restarts (cs_dive_restart, csgpu_solve_many_restarts): the same loop a fourth time, CS_DIVE_CK 0 and CS_DIVE_RESTART 1,
+ * ANY only and without checkpoints.  The deep walks of a batch are the heavy tail of a depth-first search with a fixed
+ * value order; the reference cures it with Luby restarts and a seeded value order (csolve.c:76-83, 264-276, 331-338).
+ * Here a node tries its values in a rotation of the ascending order that depends on (seed of the instance, run,
+ * variable), cs_many_start / cs_many_rotated of cs_arith.h, and after more than threshold x restart_base failed children
+ * the walk starts again from the root node's fixpoint with run + 1 and the next Luby threshold.  Counters and the budget
+ * run over all runs; a restart costs no node.  The root fixpoint is kept in the wave's n-th frame, which the walk never
+ * uses.  Everything new is a scalar. */
 #ifndef CS_DIVE_HIP_H
 #define CS_DIVE_HIP_H
 
@@ -102,6 +111,15 @@ struct cs_dive_ck {
   int *slots;                /* [count]: the slot of an instance stopped with a checkpoint, else -1 */
 };
 
+/* the restart walk of a call (cs_dive_restart) */
+struct cs_dive_rs {
+  const unsigned *seeds;  /* [count], or NULL: `seed` for every instance */
+  int *restarts;          /* [count] or NULL: the restarts of an instance, written by lane 0 with its record */
+  long long restart_base; /* a run ends after more than threshold x base failures (Luby thresholds); 0: no restarts */
+  unsigned seed;
+  int flags;              /* bit 0: CSGPU_MANY_ROTATE_FIRST, run 0 rotates as well */
+};
+
 template <typename E, int R>
 __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_shave(int n, const E *__restrict__ tab_g, int slots, int dmin,
                                                                         const int *__restrict__ root_lo,
@@ -110,7 +128,9 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_shave(int n, c
                                                                         cs_dive_io io) {
 #define CS_DIVE_CK 0
 #define CS_DIVE_UPTO 0
+#define CS_DIVE_RESTART 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_RESTART
 #undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
 }
@@ -124,7 +144,9 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_resume(int n, 
                                                                          cs_dive_io io, cs_dive_ck ck) {
 #define CS_DIVE_CK 1
 #define CS_DIVE_UPTO 0
+#define CS_DIVE_RESTART 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_RESTART
 #undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
 }
@@ -138,7 +160,26 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_upto(int n, co
                                                                        cs_dive_io io, cs_dive_ck ck, int upto) {
 #define CS_DIVE_CK 1
 #define CS_DIVE_UPTO 1
+#define CS_DIVE_RESTART 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_RESTART
+#undef CS_DIVE_UPTO
+#undef CS_DIVE_CK
+}
+
+/* the ANY walk with a seeded rotation of every node's value order and Luby restarts (csgpu_solve_many_restarts); io.all
+ * is 0 */
+template <typename E, int R>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_restart(int n, const E *__restrict__ tab_g, int slots, int dmin,
+                                                                          const int *__restrict__ root_lo,
+                                                                          const int *__restrict__ root_hi,
+                                                                          const int *__restrict__ sym_off, size_t tab_bytes,
+                                                                          cs_dive_io io, cs_dive_rs rs) {
+#define CS_DIVE_CK 0
+#define CS_DIVE_UPTO 0
+#define CS_DIVE_RESTART 1
+#include "cs_dive_body.hip.h"
+#undef CS_DIVE_RESTART
 #undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
 }

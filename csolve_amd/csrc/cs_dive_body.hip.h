@@ -5,7 +5,14 @@
  * stands under `#if CS_DIVE_UPTO`, so the other two see the text they saw before there was a third.
  * CS_DIVE_UPTO: the kernel has one more argument, `upto` (k >= 1, a scalar): the instance stops right after its k-th
  * solution, solution j goes to row j of the instance's k rows, and io.all is not read.  A pool of capacity 0 means "no
- * pool": ck.next, ck.pool and ck.slots are then never touched (csgpu_solve_many_upto). */
+ * pool": ck.next, ck.pool and ck.slots are then never touched (csgpu_solve_many_upto).
+ * CS_DIVE_RESTART (with CS_DIVE_CK 0): cs_dive_restart, the ANY walk with a seeded rotation of every node's value order
+ * and Luby restarts (csgpu_solve_many_restarts; the walk is defined in csolve_gpu.h).  One more argument, `rs`.  Every
+ * line of it stands under `#if CS_DIVE_RESTART`; the three older inclusions define it 0 and see the text they saw.  A
+ * frame's 8-byte entry is {variable, next j} instead of {variable, next value}; the root node's fixpoint is kept in
+ * frame `frames - 1`, which the walk never uses (at most n - 1 of the n frames), and a restart reads it back, every
+ * lane the entries it wrote itself.  A restart stays inside the instance's loop: it is no `continue` of the ticket
+ * loop.  New per-wave state is scalars only: run, fails, threshold, counter, seed, restarts, start (and width). */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   typedef unsigned long long u64;
   const int lane = threadIdx.x & (CS_WAVE - 1);
@@ -70,6 +77,14 @@
       }                                                                                                              \
     }                                                                                                                \
   } while (0)
+#if CS_DIVE_RESTART
+  /* where the value order of the entered node starts: from scalars, once per node (cs_arith.h) */
+#define CS_DIVE_START()                                                                                              \
+  do {                                                                                                               \
+    width = (unsigned)(bhi - xlo) + 1u;                                                                              \
+    start = cs_many_start(rs_seed, run, bv, width, rs.flags);                                                        \
+  } while (0)
+#endif
 
   for (;;) {
     /* The wave meets here before lane 0 draws.  Without this convergent no-op the compiler joins the `lane == 0` of
@@ -84,6 +99,12 @@
     const int inst = (int)t * nsh + shard;
     const size_t rrow = (size_t)inst * (size_t)n;
 
+#if CS_DIVE_RESTART
+    unsigned run = 0u, rs_seed = rs.seed, start = 0u, width = 1u; /* scalars, as everything the restarts add */
+    int restarts = 0;
+    uint64_t fails = 0u, threshold = 1u, counter = 1u;
+    if (rs.seeds != nullptr) rs_seed = (unsigned)__builtin_amdgcn_readfirstlane((int)rs.seeds[inst]);
+#endif
     int plo[R], phi[R]; /* the current node, relative to the root lower bounds; a lane without a variable is the value 0 */
     bool bad_l = false;
 #if CS_DIVE_CK
@@ -224,8 +245,22 @@
         } else {
           CS_DIVE_SELECT();
           CS_DIVE_ENTER();
+#if CS_DIVE_RESTART
+          CS_DIVE_START();
+          nv = 0; /* j, not a value */
+#else
           nv = xlo;
+#endif
         }
+#if CS_DIVE_RESTART
+        /* the root node's fixpoint, for the restarts: the frame the walk leaves alone */
+        cs_val *const root_f = stack + (size_t)(io.frames - 1) * fstride;
+        if (rs.restart_base > 0) {
+#pragma unroll
+          for (int r = 0; r < R; r++)
+            if (live[r]) root_f[lane + r * CS_WAVE] = cs_interval(plo[r], phi[r]);
+        }
+#endif
         for (;;) {
           depth = __builtin_amdgcn_readfirstlane(depth);
           nv = __builtin_amdgcn_readfirstlane(nv);
@@ -272,8 +307,13 @@
 #endif
             break;
           }
+#if CS_DIVE_RESTART
+          const int value = cs_many_rotated(xlo, width, start, (unsigned)nv);
+          const bool last = (unsigned)nv == width - 1u;
+#else
           const int value = nv;
           const bool last = value == bhi;
+#endif
           int rlo[R], rhi[R];
           u64 pushed[R], push[R], dl[R], dh[R], val[R];
 #pragma unroll
@@ -326,21 +366,63 @@
             }
           }
           if ((nodes & 63) == 0) { props += cs_wave_sum(acc_props); acc_props = 0; }
+#if CS_DIVE_RESTART
+          /* a failed child (ANY: whatever does not descend here has failed), unless it ends the whole tree: one more
+           * failure of this run, and past threshold x base the walk starts again from the root node's fixpoint, with
+           * the next run's rotation.  No node, no ticket: the instance's own loop goes on. */
+          bool again = false;
+          if (!descend && !(last && depth == 0) && rs.restart_base > 0) {
+            fails++;
+            again = fails > threshold * (uint64_t)rs.restart_base;
+          }
+          if (again) {
+            fails = 0u;
+            cs_luby_next(&threshold, &counter);
+            run++;
+            restarts++;
+            depth = 0;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+              plo[r] = 0; phi[r] = 0;
+              if (live[r]) {
+                const cs_val d = root_f[lane + r * CS_WAVE];
+                plo[r] = d.lo; phi[r] = d.hi;
+              }
+            }
+            CS_DIVE_SELECT();
+            CS_DIVE_ENTER();
+            CS_DIVE_START();
+            nv = 0;
+          } else
+#endif
           if (descend) {
             if (!last) { /* the node comes back for its next value */
+#if CS_DIVE_RESTART
+              if (depth >= io.frames - 1) { status = 1; break; } /* cannot happen; the last frame is the root node's */
+#else
               if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames >= n - 1): never write past the slice */
+#endif
               cs_val *f = stack + (size_t)depth * fstride;
 #pragma unroll
               for (int r = 0; r < R; r++)
                 if (live[r]) f[lane + r * CS_WAVE] = cs_interval(plo[r], phi[r]);
+#if CS_DIVE_RESTART
+              if (lane == 0) f[n] = cs_interval(bv, nv + 1);
+#else
               if (lane == 0) f[n] = cs_interval(bv, value + 1);
+#endif
               depth++;
             }
 #pragma unroll
             for (int r = 0; r < R; r++) { plo[r] = rlo[r]; phi[r] = rhi[r]; }
             CS_DIVE_SELECT();
             CS_DIVE_ENTER();
+#if CS_DIVE_RESTART
+            CS_DIVE_START();
+            nv = 0;
+#else
             nv = xlo;
+#endif
           } else if (last) { /* the node's values are used up */
             if (depth == 0) break;
             depth--;
@@ -358,8 +440,15 @@
             bv = __builtin_amdgcn_readfirstlane(meta.lo);
             nv = __builtin_amdgcn_readfirstlane(meta.hi);
             CS_DIVE_ENTER();
+#if CS_DIVE_RESTART
+            CS_DIVE_START(); /* the run is the one that pushed the frame: a restart empties the stack */
+#endif
           } else {
+#if CS_DIVE_RESTART
+            nv = nv + 1;
+#else
             nv = value + 1;
+#endif
           }
         }
       }
@@ -370,6 +459,9 @@
       res.status = status; res.root_props = root_props;
       res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
       io.results[inst] = res;
+#if CS_DIVE_RESTART
+      if (rs.restarts != nullptr) rs.restarts[inst] = restarts;
+#endif
 #if CS_DIVE_UPTO
       if (ck.capacity > 0)
 #endif
@@ -380,3 +472,6 @@
   }
 #undef CS_DIVE_SELECT
 #undef CS_DIVE_ENTER
+#if CS_DIVE_RESTART
+#undef CS_DIVE_START
+#endif

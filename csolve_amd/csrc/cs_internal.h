@@ -62,6 +62,7 @@ int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char *buf, size
 int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len);
 int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t len); /* cs_dive_resume */
 int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len);   /* cs_dive_upto */
+int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len); /* cs_dive_restart */
 int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count);
 
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */

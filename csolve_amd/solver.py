@@ -11,8 +11,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import (PLAN_FAMILIES, CsolveError, ManyOptions, ManyResult, ManyUptoOptions, Node, Result, SearchStats, Val,
-                   check, demangle, load_library)
+from ._lib import (MANY_ROTATE_FIRST, PLAN_FAMILIES, CsolveError, ManyOptions, ManyRestartOptions, ManyResult,
+                   ManyUptoOptions, Node, Result, SearchStats, Val, check, demangle, load_library)
 
 STATUS_FAIL = -1
 
@@ -310,6 +310,57 @@ class Model:
             out["rows"] = rows
         return out
 
+    def solve_many_restarts(self, roots, *, max_nodes, restart_base=32, seed=0, seeds=None, rotate_first=False,
+                            solutions=True, restarts=True, stream=None) -> dict:
+        """solve_many under ANY with Luby restarts and a seeded value order (csgpu_solve_many_restarts): a node tries its
+        values in a rotation of the ascending order that depends on (seed of the instance, run, variable), and after
+        more than threshold x restart_base failed children -- thresholds 1 1 2 1 1 2 4 ... -- the walk starts again from
+        the root node's fixpoint with the next run's rotations.  The first run is the ascending walk of solve_many unless
+        rotate_first.  restart_base=0: no restarts (with rotate_first: one seeded walk, a sampler).  seeds: uint32 [K]
+        (int32 / int64 tensors and arrays are converted), one per instance, else `seed` for all: an instance's answer
+        depends on its row, its seed and the options only.  max_nodes is the total over an instance's runs; a LIMIT
+        instance can be run again with a larger budget, the walk is deterministic.  The default base of 32 comes from
+        node counts of 9x9 sudokus on the host.  roots, solutions, stream: as solve_many.
+        -> the dict of solve_many plus `restarts` [K] int32 (restarts=False: not counted, d_restarts is NULL); solutions
+        may be an int32 device tensor [K, n_vars] to write into."""
+        L = load_library()
+        n = self.n_vars
+        opt = ManyRestartOptions(int(max_nodes), int(restart_base), int(seed) & 0xffffffff,
+                                 MANY_ROTATE_FIRST if rotate_first else 0)
+        if not torch.is_tensor(roots):
+            roots = np.ascontiguousarray(roots, dtype=np.int32)
+            assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
+            if not self.qualifies(7) or restart_base < 0:
+                # as solve_many: the library says what is wrong before any device call, nothing is uploaded for it
+                check(L.csgpu_solve_many_restarts(self._h, roots.ctypes.data, None, roots.shape[0], C.byref(opt),
+                                                  roots.ctypes.data, None, None, None))
+            roots = torch.from_numpy(roots).cuda()
+        assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
+        assert roots.dim() == 3 and tuple(roots.shape[1:]) == (n, 2), "roots is [K, n_vars, 2]"
+        K = roots.shape[0]
+        if seeds is not None:
+            if not torch.is_tensor(seeds):
+                seeds = torch.from_numpy((np.asarray(seeds).astype(np.int64) & 0xffffffff).astype(np.uint32).view(np.int32))
+            seeds = seeds.to(device=roots.device, dtype=torch.int32).contiguous()  # the 32 bits are what counts
+            assert tuple(seeds.shape) == (K,), "seeds is [K]"
+        buf = torch.zeros((max(K, 1), 5), dtype=torch.int64, device=roots.device)  # csgpu_many_result: 40 bytes
+        first = None
+        if torch.is_tensor(solutions):
+            first = solutions
+            assert first.is_cuda and first.dtype == torch.int32 and first.is_contiguous() and tuple(first.shape) == (K, n), \
+                "solutions is [K, n_vars] int32 on the device"
+        elif solutions:
+            first = torch.zeros((K, n), dtype=torch.int32, device=roots.device)
+        count = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if restarts else None
+        check(L.csgpu_solve_many_restarts(self._h, roots.data_ptr() if K else buf.data_ptr(),
+                                          seeds.data_ptr() if seeds is not None and K else None, K, C.byref(opt),
+                                          buf.data_ptr(), first.data_ptr() if first is not None and K else None,
+                                          count.data_ptr() if restarts else None, _stream_ptr(stream)))
+        out = self._many_answer(buf, K, first)
+        if restarts:
+            out["restarts"] = count[:K]
+        return out
+
     def classify_many(self, roots, *, max_nodes, stream=None) -> torch.Tensor:
         """is the solution unique?  -> int8 [K] on the device: 0 no solution, 1 exactly one, 2 several, -1 undecided
         within max_nodes (LIMIT), -2 bad root row.  A solve_many_upto with k = 2 and no rows."""
@@ -500,6 +551,12 @@ class Model:
         does not qualify"""
         buf = C.create_string_buffer(1024)
         check(load_library().csgpu_internal_many_upto_symbol(self._h, buf, len(buf)))
+        return demangle(buf.value.decode()) if buf.value else None
+
+    def many_restart_kernel(self):
+        """the cs_dive_restart instantiation solve_many_restarts launches (template-id), None if the model does not qualify"""
+        buf = C.create_string_buffer(1024)
+        check(load_library().csgpu_internal_many_restart_symbol(self._h, buf, len(buf)))
         return demangle(buf.value.decode()) if buf.value else None
 
     def many_waves(self, count: int) -> int:

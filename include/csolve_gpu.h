@@ -345,6 +345,54 @@ int csgpu_solve_many_upto_resume(const csgpu_model *m, int64_t count, const csgp
                                  csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                  void *stream);
 
+/* ---- Luby restarts with a seeded value order, for ANY: csgpu_solve_many whose deep walks are cut short ----
+ * The deep instances of a batch are the heavy tail of a depth-first search with a fixed value order.  This call walks
+ * the ANY walk of csgpu_solve_many with two changes, both per instance; everything not mentioned (the root check and
+ * BAD_ROOT, the root node, the branching rule, the counters and props, the budget compared before a child is tried, at
+ * most n_vars - 1 frames) is csgpu_solve_many's.  State: run = 0, fails = 0, Luby state threshold = 1, counter = 1
+ * (csgpu_luby_next).
+ *   value order   a node that branches on variable v with the interval [lo, hi], width = hi - lo + 1, tries
+ *                 value(j) = lo + ((start + j) mod width) for j = 0 .. width - 1.  start = 0 when run == 0 and
+ *                 CSGPU_MANY_ROTATE_FIRST is not set; otherwise start = (uint64_t)key * width >> 32 with
+ *                 key = fmix32(seed_i ^ fmix32(run * 0x9E3779B1u + (uint32_t)v + 1u)), all in wrapping uint32_t, and
+ *                 fmix32(x): x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16.
+ *                 seed_i = d_seeds[i], or options->seed for every instance when d_seeds is NULL: an instance's answer
+ *                 depends on its row, its seed and the options, not on its position in the batch.  start is computed
+ *                 once per entered node (and again when a node comes back from its frame, which holds {v, next j}).
+ *   restart       after a child fails and the cut is counted: if it was the node's last value and no frame is left,
+ *                 this run has walked the whole tree -- DONE with 0 solutions, proven, no restart.  Otherwise, when
+ *                 restart_base > 0: fails++, and if fails > threshold * restart_base (in 64 bits): fails = 0,
+ *                 csgpu_luby_next(&threshold, &counter), run++, restarts++, and the walk starts again from the root
+ *                 node's fixpoint at depth 0, the branching variable selected anew, j = 0.  A restart costs no node;
+ *                 root_props is counted once; nodes / cuts / props accumulate over the runs and max_nodes is their
+ *                 total.  Thresholds grow without bound, so an instance without a solution is still proven so.
+ * restart_base = 0 with flags 0 is csgpu_solve_many under ANY, field for field and row for row, and so is every instance
+ * whose first run ends before its first restart.  restart_base = 0 with CSGPU_MANY_ROTATE_FIRST is one seeded walk (a
+ * sampler of solutions; it has the heavy tail).  There are no checkpoints: the walk is deterministic, an instance that
+ * ends LIMIT can be run again with a larger budget.
+ *   d_seeds       NULL, or [count] uint32
+ *   d_solutions   NULL, or [count][n_vars] int32: the solution of an instance that found one, else not touched
+ *   d_restarts    NULL, or [count] int32: the restarts of every instance (0 for a BAD_ROOT row)
+ * The call uses the model's workspace and ticket counters like the calls above: one call in flight per model, calls of
+ * all families may be queued behind each other on one stream without the host in between.
+ * Errors before any HIP call, in csgpu_solve_many's order: a null model / roots / results / options, count < 0,
+ * max_nodes <= 0, restart_base < 0, a flag bit other than CSGPU_MANY_ROTATE_FIRST -> CSGPU_E_ARG; model not finalized ->
+ * CSGPU_E_STATE; model does not qualify for kernel 7 -> CSGPU_E_LIMIT.  count == 0 -> CSGPU_OK, nothing is launched. */
+#define CSGPU_MANY_ROTATE_FIRST 1
+typedef struct csgpu_many_restart_options {
+  int64_t max_nodes;     /* > 0, over all runs of an instance */
+  int64_t restart_base;  /* >= 0; 0: no restarts */
+  uint32_t seed;         /* used where d_seeds is NULL */
+  int32_t flags;         /* 0 or CSGPU_MANY_ROTATE_FIRST; any other bit: CSGPU_E_ARG */
+} csgpu_many_restart_options;   /* 24 bytes */
+int csgpu_solve_many_restarts(const csgpu_model *m, const csgpu_val *d_roots, const uint32_t *d_seeds, int64_t count,
+                              const csgpu_many_restart_options *options, csgpu_many_result *d_results,
+                              int32_t *d_solutions /* NULL or [count][n_vars] */, int32_t *d_restarts /* NULL or [count] */,
+                              void *stream);
+/* host, no device: the value a node tries j-th -- the definition above, exported so it can be pinned (j is taken mod
+ * width) */
+int32_t csgpu_many_value(uint32_t seed, uint32_t run, int32_t var, csgpu_val bounds, uint32_t j, int32_t flags);
+
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */
 int csgpu_eval_batch(const csgpu_model *m, const csgpu_val *d_states, int32_t *d_truth, int64_t batch,

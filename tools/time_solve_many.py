@@ -9,6 +9,7 @@ oracle walk (tests/many_walk.py).
 
   python tools/time_solve_many.py --set sudoku9 [--count 65536] [--reps 5] [--loop-sample 256] [--check 32]
                                   [--sliced B0,B1,... [--finish resume|search]] [--upto K]
+                                  [--restarts BASE [--seed S]] [--revealed R]
   --sliced: the same instances through Model.solve_many_sliced as well (a checkpointed call with budget B0, a resume
   with every following budget; --finish search: what is left after the last budget through one Search per instance):
   the time of the whole, the time until the answers of the first slice are there, and whether it found what the one
@@ -17,6 +18,12 @@ oracle walk (tests/many_walk.py).
   the ANY and the ALL call of solve_many, all three in this process after a warm-up, same budget: medians and ranges of
   --reps, what each call decided, the share of instances a k = 2 call classifies as unique / several / none / undecided,
   and the sampled answers (fields and rows) re-checked against the host walk of tests/many_walk_upto.py.
+  --restarts BASE: Model.solve_many_restarts (Luby restarts x BASE failures, seeded value order, seed --seed) beside the
+  ANY call of solve_many on the same instances, both in this process after a warm-up, interleaved, same budget: medians
+  and ranges of --reps, sum and largest `nodes` of both calls, the share of instances that restarted, and --check sampled
+  answers re-checked against the host walk of tests/many_walk_restarts.py.
+  --revealed R: the sudoku sets with this share of givens for every instance instead of the set's own (the deep tails
+  of 9x9 sudokus are at 0.30 and 0.25).
   sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY)
 """
 import argparse
@@ -38,7 +45,12 @@ from csolve_amd import problems  # noqa: E402
 from csolve_amd.solver import Search, solve_root  # noqa: E402
 
 
-def instances(which, count):
+def instances(which, count, revealed=None):
+    if revealed is not None:
+        if which not in ("sudoku9", "sudoku16"):
+            raise SystemExit("--revealed applies to the sudoku sets")
+        text, rows = problems.sudoku_roots(3 if which == "sudoku9" else 4, revealed, list(range(1, count + 1)))
+        return text, rows, "ANY", 1 << 18
     if which == "sudoku9":
         parts, per = [], -(-count // 11)
         for i in range(11):  # revealed 0.35, 0.36, ... 0.45
@@ -72,9 +84,11 @@ def main():
     ap.add_argument("--sliced", default=None, help="budgets of the slices, e.g. 256,4096")
     ap.add_argument("--finish", default="resume", choices=("resume", "search"))
     ap.add_argument("--upto", type=int, default=None, help="K: time solve_many_upto beside the ANY and the ALL call")
+    ap.add_argument("--restarts", type=int, default=None, help="BASE: time solve_many_restarts beside the ANY call")
+    ap.add_argument("--revealed", type=float, default=None, help="share of givens of every sudoku (default: the set's own)")
     args = ap.parse_args()
     count = args.count or {"sudoku9": 65536, "queens12": 16384, "sudoku16": 4096}[args.set]
-    text, roots, objective, budget = instances(args.set, count)
+    text, roots, objective, budget = instances(args.set, count, args.revealed)
     model = solve_root(text)
     dev = torch.from_numpy(roots).cuda()
 
@@ -187,6 +201,53 @@ def main():
                 "classes_k2": share, "every_field_equals_any": same_as_any,
                 "oracle_checked": len(picks_u), "oracle_ok": bool(upto_ok)}
 
+    restarts = None
+    if args.restarts is not None:
+        import many_walk_restarts
+
+        def timed_r(call):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = call()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, res
+
+        calls_r = {"any": lambda: model.solve_many(dev, "ANY", max_nodes=budget),
+                   "restarts": lambda: model.solve_many_restarts(dev, max_nodes=budget, restart_base=args.restarts,
+                                                                 seed=args.seed)}
+        for call in calls_r.values():  # warm-up: code load, workspace, the allocator's blocks
+            timed_r(call)
+            timed_r(call)
+        series_r = {name: [] for name in calls_r}
+        answers_r = {}
+        for _ in range(args.reps):  # interleaved: a drift of the machine falls on both alike
+            for name, call in calls_r.items():
+                dt, answers_r[name] = timed_r(call)
+                series_r[name].append(dt)
+
+        def summary_r(name):
+            ts, res = series_r[name], answers_r[name]
+            return {"ms": {"median": round(statistics.median(ts) * 1e3, 3), "min": round(min(ts) * 1e3, 3),
+                           "max": round(max(ts) * 1e3, 3), "reps": args.reps},
+                    "status_counts": torch.bincount(res["status"].long(), minlength=3).tolist(),
+                    "nodes": int(res["nodes"].sum()), "largest_walk": int(res["nodes"].max()),
+                    "solutions": int(res["solutions"].sum())}
+
+        picks_r = rng.choice(count, size=min(args.check, count), replace=False)
+        want_r = many_walk_restarts.dive_many_restarts(text, roots[picks_r], args.restarts, seed=args.seed, max_nodes=budget)
+        got_r = {k: v[torch.from_numpy(picks_r).cuda()].cpu().numpy() for k, v in answers_r["restarts"].items() if torch.is_tensor(v)}
+        has_r = want_r["solutions"] > 0
+        restarts_ok = all((got_r[f] == want_r[f]).all() for f in many_walk_restarts.FIELDS + ("restarts",)) and \
+            bool((got_r["first"][has_r] == want_r["first"][has_r]).all())
+        both = (answers_r["any"]["status"] == 0) & (answers_r["restarts"]["status"] == 0)
+        restarts = {"base": args.restarts, "seed": args.seed, "revealed": args.revealed, "kernel": model.many_restart_kernel(),
+                    "max_nodes": budget, "any": summary_r("any"), "restarts": summary_r("restarts"),
+                    "restarted_instances": int((answers_r["restarts"]["restarts"] > 0).sum()),
+                    "restarted_share": round(float((answers_r["restarts"]["restarts"] > 0).float().mean()), 4),
+                    "most_restarts": int(answers_r["restarts"]["restarts"].max()),
+                    "same_verdict_where_both_done": bool((answers_r["any"]["solutions"] == answers_r["restarts"]["solutions"])[both].all()),
+                    "oracle_checked": len(picks_r), "oracle_ok": bool(restarts_ok)}
+
     # the per-instance loop: one Search, reset and seeded per instance
     sample = np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
     search = Search(model, 1 << 18, 1 << 14)
@@ -240,8 +301,9 @@ def main():
         "oracle_checked": len(picks), "oracle_ok": checked_ok,
         **({"sliced": sliced} if sliced else {}),
         **({"upto": upto} if upto else {}),
+        **({"restarts": restarts} if restarts else {}),
     }))
-    return 0 if checked_ok and (upto is None or upto["oracle_ok"]) else 1
+    return 0 if checked_ok and (upto is None or upto["oracle_ok"]) and (restarts is None or restarts["oracle_ok"]) else 1
 
 
 if __name__ == "__main__":
