@@ -55,6 +55,10 @@ struct cs_planned {
   int per_cu;     /* resident workgroups per CU */
 };
 
+/* the kernels of the csgpu_solve_many family (cs_dive.hip.h): one loop, compiled four times */
+enum { MANY_PLAIN, MANY_CK, MANY_UPTO, MANY_RESTART, MANY_FAMILIES };
+static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "cs_dive_resume", "cs_dive_upto", "cs_dive_restart" };
+
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
 struct cs_kernel_plan {
   cs_planned events, traced;       /* kernel 1; its tracing variant (one node) */
@@ -68,10 +72,7 @@ struct cs_kernel_plan {
   cs_planned shave, shave_trace;   /* kernel 7 (the instantiation whose FULL matches the model); its tracing variant */
   cs_planned server;               /* the resident single-node server */
   cs_planned step_shave, step_packed, step_import;
-  cs_planned dive;                 /* cs_dive_shave (csgpu_solve_many): not one of csgpu_internal_plan_symbol's families */
-  cs_planned dive_ck;              /* cs_dive_resume (csgpu_solve_many_checkpointed / _resume): the same */
-  cs_planned dive_upto;            /* cs_dive_upto (csgpu_solve_many_upto and its two checkpoint calls): the same */
-  cs_planned dive_restart;         /* cs_dive_restart (csgpu_solve_many_restarts): the same */
+  cs_planned dive[MANY_FAMILIES];  /* by MANY_*: all four or none; not among csgpu_internal_plan_symbol's families */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -796,55 +797,18 @@ static const void *step_shave_kernel(int width, int n_vars, int slots, int full)
 }
 
 /* ---- cs_dive.hip.h: a depth-first search per wave (csgpu_solve_many); the slot count is always a run-time value ---- */
-static const void *dive_kernel(int width, int n_vars) {
-#define CS_PICK(E)                                                                                 \
-  switch (cs_dense_strides(n_vars)) {                                                              \
-  case 1: return (const void *)cs_dive_shave<E, 1>;                                                 \
-  case 2: return (const void *)cs_dive_shave<E, 2>;                                                 \
-  default: return (const void *)cs_dive_shave<E, 4>;                                                \
+static const void *dive_kernel(int family, int width, int n_vars) {
+  const int r = cs_dense_strides(n_vars);
+#define CS_PICK_R(K, E) (r == 1 ? (const void *)K<E, 1> : r == 2 ? (const void *)K<E, 2> : (const void *)K<E, 4>)
+#define CS_PICK(K) return width == 1 ? CS_PICK_R(K, unsigned char) : CS_PICK_R(K, unsigned short);
+  switch (family) {
+  case MANY_CK: CS_PICK(cs_dive_resume)       /* with checkpoints (csgpu_solve_many_checkpointed / _resume) */
+  case MANY_UPTO: CS_PICK(cs_dive_upto)       /* leaving at the k-th solution (csgpu_solve_many_upto and its two checkpoint calls) */
+  case MANY_RESTART: CS_PICK(cs_dive_restart) /* ANY with a seeded value order and Luby restarts (csgpu_solve_many_restarts) */
+  default: CS_PICK(cs_dive_shave)
   }
-  if (width == 1) { CS_PICK(unsigned char) }
-  CS_PICK(unsigned short)
 #undef CS_PICK
-}
-
-/* the same loop with checkpoints (csgpu_solve_many_checkpointed / _resume) */
-static const void *dive_resume_kernel(int width, int n_vars) {
-#define CS_PICK(E)                                                                                 \
-  switch (cs_dense_strides(n_vars)) {                                                              \
-  case 1: return (const void *)cs_dive_resume<E, 1>;                                                \
-  case 2: return (const void *)cs_dive_resume<E, 2>;                                                \
-  default: return (const void *)cs_dive_resume<E, 4>;                                               \
-  }
-  if (width == 1) { CS_PICK(unsigned char) }
-  CS_PICK(unsigned short)
-#undef CS_PICK
-}
-
-/* the same loop leaving an instance at its k-th solution (csgpu_solve_many_upto / _upto_checkpointed / _upto_resume) */
-static const void *dive_upto_kernel(int width, int n_vars) {
-#define CS_PICK(E)                                                                                 \
-  switch (cs_dense_strides(n_vars)) {                                                              \
-  case 1: return (const void *)cs_dive_upto<E, 1>;                                                  \
-  case 2: return (const void *)cs_dive_upto<E, 2>;                                                  \
-  default: return (const void *)cs_dive_upto<E, 4>;                                                 \
-  }
-  if (width == 1) { CS_PICK(unsigned char) }
-  CS_PICK(unsigned short)
-#undef CS_PICK
-}
-
-/* the ANY loop with a seeded value order and Luby restarts (csgpu_solve_many_restarts) */
-static const void *dive_restart_kernel(int width, int n_vars) {
-#define CS_PICK(E)                                                                                 \
-  switch (cs_dense_strides(n_vars)) {                                                              \
-  case 1: return (const void *)cs_dive_restart<E, 1>;                                               \
-  case 2: return (const void *)cs_dive_restart<E, 2>;                                               \
-  default: return (const void *)cs_dive_restart<E, 4>;                                              \
-  }
-  if (width == 1) { CS_PICK(unsigned char) }
-  CS_PICK(unsigned short)
-#undef CS_PICK
+#undef CS_PICK_R
 }
 
 /* ---- the resident single-node server (cs_shave.hip.h) ---- */
@@ -1152,11 +1116,9 @@ static int plan_dense_table(csgpu_model *m) {
     m->plan.server = m->plan.shave_trace;
     m->plan.server.fn = shave_server_kernel(width, n, slots);
   }
-  /* cs_dive_shave: the table alone; the upper bounds of the root domains for its check of the root rows */
-  if ((rc = plan_kernel(&m->plan.dive, dive_kernel(width, n), table, waves))) return rc;
-  if ((rc = plan_kernel(&m->plan.dive_ck, dive_resume_kernel(width, n), table, waves))) return rc;
-  if ((rc = plan_kernel(&m->plan.dive_upto, dive_upto_kernel(width, n), table, waves))) return rc;
-  if ((rc = plan_kernel(&m->plan.dive_restart, dive_restart_kernel(width, n), table, waves))) return rc;
+  /* the cs_dive_* kernels: the table alone; the upper bounds of the root domains for its check of the root rows */
+  for (int family = 0; family < MANY_FAMILIES; family++)
+    if ((rc = plan_kernel(&m->plan.dive[family], dive_kernel(family, width, n), table, waves))) return rc;
   {
     int *hi = (int *)malloc((size_t)n * sizeof(int));
     if (hi == NULL) return set_err(CSGPU_E_ARG, "out of memory");
@@ -1300,16 +1262,13 @@ extern "C" int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char
   return CSGPU_OK;
 }
 
-/* the same for cs_dive_shave, which is no family of the list above (the plan dictionary stays what it was) */
-static int many_symbol(const csgpu_model *m, int which, char *buf, size_t len) {
+/* the same for the cs_dive_* kernels, which are no families of the list above (the plan dictionary stays what it was) */
+static int many_symbol(const csgpu_model *m, int family, char *buf, size_t len) {
   if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
   buf[0] = '\0';
-  const void *fn = which == 3   ? m->plan.dive_restart.fn
-                   : which == 2 ? m->plan.dive_upto.fn
-                   : which == 1 ? m->plan.dive_ck.fn
-                                : m->plan.dive.fn;
-  const char *name = which == 3 ? "cs_dive_restart" : which == 2 ? "cs_dive_upto" : which == 1 ? "cs_dive_resume" : "cs_dive_shave";
+  const void *fn = m->plan.dive[family].fn;
+  const char *name = many_kernel_name[family];
   if (fn == NULL) return CSGPU_OK;
   Dl_info info;
   if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
@@ -1319,22 +1278,10 @@ static int many_symbol(const csgpu_model *m, int which, char *buf, size_t len) {
   return CSGPU_OK;
 }
 
-extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, 0, buf, len); }
-
-/* and for cs_dive_resume, the kernel of csgpu_solve_many_checkpointed and csgpu_solve_many_resume */
-extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_symbol(m, 1, buf, len);
-}
-
-/* and for cs_dive_upto, the kernel of csgpu_solve_many_upto, _upto_checkpointed and _upto_resume */
-extern "C" int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_symbol(m, 2, buf, len);
-}
-
-/* and for cs_dive_restart, the kernel of csgpu_solve_many_restarts */
-extern "C" int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_symbol(m, 3, buf, len);
-}
+extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_PLAIN, buf, len); }
+extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_CK, buf, len); }
+extern "C" int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_UPTO, buf, len); }
+extern "C" int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_RESTART, buf, len); }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
   if (m != NULL) const_cast<csgpu_model *>(m)->engines += delta;
@@ -1596,13 +1543,25 @@ static int launch_shave(const csgpu_model *m, const csgpu_val *d_states_in, cons
   return CSGPU_OK;
 }
 
-/* ---- csgpu_solve_many: a depth-first search per wavefront (cs_dive.hip.h) ---- */
+/* ---- the csgpu_solve_many family: a depth-first search per wavefront (cs_dive.hip.h) ---- */
 
 static_assert(sizeof(csgpu_many_result) == sizeof(cs_dive_result) && sizeof(csgpu_many_result) == 40, "csgpu_many_result layout");
+static_assert(sizeof(csgpu_many_restart_options) == 24, "csgpu_many_restart_options layout");
+
+#define MANY_NOT_QUALIFIED "model does not qualify for the interval-only shaving kernel"
+
+struct csgpu_many_checkpoints {
+  const csgpu_model *m;
+  int64_t capacity;
+  size_t slot_bytes;
+  cs_val *d_pool;
+  unsigned long long *d_next; /* slots handed out since the last reset */
+  int counted;                /* the model counts this pool among the objects that hold its device tables */
+};
 
 extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count) {
-  if (m == NULL || !m->finalized || m->plan.dive.fn == NULL || count < 1) return 0;
-  const cs_planned *k = &m->plan.dive;
+  if (m == NULL || !m->finalized || m->plan.dive[MANY_PLAIN].fn == NULL || count < 1) return 0;
+  const cs_planned *k = &m->plan.dive[MANY_PLAIN]; /* the four are planned alike */
   int64_t grid = (int64_t)m->n_cus * k->per_cu;
   const int64_t by_count = (count + k->waves - 1) / k->waves;
   if (grid > by_count) grid = by_count;
@@ -1628,61 +1587,93 @@ static int many_workspace(csgpu_model *mm, int64_t waves, int frames) {
   return CSGPU_OK;
 }
 
-extern "C" int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
-                                csgpu_many_result *d_results, int32_t *d_solutions, void *stream) {
-  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL) return set_err(CSGPU_E_ARG, "null argument");
+/* The checks of every entry point, none of which touches the device: many_check_head, then the call's own checks of its
+ * options, then many_check_tail.  `null_arg`: some required pointer is NULL (max_nodes is then not looked at). */
+static int many_check_head(int null_arg, int64_t count, int64_t max_nodes, const char *budgeted) {
+  if (null_arg) return set_err(CSGPU_E_ARG, "null argument");
   if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
-  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every instance has a budget");
-  if (options->objective == CS_OBJ_MIN || options->objective == CS_OBJ_MAX)
+  if (max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every %s has a budget", budgeted);
+  return CSGPU_OK;
+}
+
+static int many_check_objective(int objective) {
+  if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX)
     return set_err(CSGPU_E_LIMIT, "csgpu_solve_many searches with ANY or ALL: MIN / MAX are not supported");
-  if (options->objective != CS_OBJ_ANY && options->objective != CS_OBJ_ALL) return set_err(CSGPU_E_ARG, "no objective %d", options->objective);
+  if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL) return set_err(CSGPU_E_ARG, "no objective %d", objective);
+  return CSGPU_OK;
+}
+
+/* `ck`: the pool of a call that has one, else NULL */
+static int many_check_tail(const csgpu_model *m, int family, const csgpu_many_checkpoints *ck, int64_t count) {
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (m->plan.dive.fn == NULL)
-    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
-                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
+  if (m->plan.dive[family].fn == NULL)
+    return set_err(CSGPU_E_LIMIT, MANY_NOT_QUALIFIED " (a pure != network of at most 256 variables whose dense pair table "
+                                                     "fits LDS), which csgpu_solve_many is built on");
+  if (ck != NULL && ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
   if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  return CSGPU_OK;
+}
+
+/* The one launch of a cs_dive_* kernel, after the checks.  `tail0`, `tail1`: the family's own kernel arguments after the
+ * nine common ones (NULL where it has fewer).  `resume`: the instances go on in the frames of their checkpoint slots, so
+ * the call brings no roots and needs no stacks. */
+static int many_launch(const csgpu_model *m, int family, const csgpu_val *d_roots, int64_t count, int64_t max_nodes, int all,
+                       csgpu_many_result *d_results, int32_t *d_solutions, int resume, void *stream, void *tail0, void *tail1) {
   if (count == 0) return CSGPU_OK;
   csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = &m->plan.dive;
+  const cs_planned *k = &m->plan.dive[family];
   const int n = m->host->n_vars;
   const int64_t waves = csgpu_internal_many_waves(m, count);
-  const int frames = n; /* open levels + 1: at most n - 1 frames are ever in use (cs_dive.hip.h) */
+  const int frames = n; /* open levels + 1: at most n - 1 frames are in use, the n-th keeps the root node's fixpoint */
   int rc;
-  if ((rc = many_workspace(mm, waves, frames))) return rc;
+  if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
   cs_dive_io io;
   io.roots = (const cs_val *)d_roots;
   io.count = (int)count;
-  io.all = options->objective == CS_OBJ_ALL;
-  io.max_nodes = (long long)options->max_nodes;
+  io.all = all;
+  io.max_nodes = (long long)max_nodes;
   io.results = (cs_dive_result *)d_results;
   io.solutions = d_solutions;
-  io.stack = (cs_val *)mm->d_many_stack;
+  io.stack = resume ? NULL : (cs_val *)mm->d_many_stack;
   io.frames = frames;
   io.tickets = mm->d_many_tickets;
   int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
   const void *tab_d = m->d_dense_tab;
   const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
   size_t tab_bytes = m->dense_bytes;
-  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io };
+  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io, tail0, tail1 };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
 
+/* the pool and slot numbers as the kernels take them; ck == NULL: a pool of capacity 0 that cs_dive_upto does not touch */
+static cs_dive_ck many_ck_arg(const csgpu_many_checkpoints *ck, int32_t *d_slots, int resume) {
+  cs_dive_ck dk;
+  dk.pool = ck != NULL ? ck->d_pool : NULL;
+  dk.next = ck != NULL ? ck->d_next : NULL;
+  dk.capacity = ck != NULL ? (int)ck->capacity : 0;
+  dk.resume = resume;
+  dk.slots = ck != NULL ? d_slots : NULL;
+  return dk;
+}
+
+extern "C" int csgpu_solve_many(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                                csgpu_many_result *d_results, int32_t *d_solutions, void *stream) {
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance")) ||
+      (rc = many_check_objective(options->objective)) || (rc = many_check_tail(m, MANY_PLAIN, NULL, count)))
+    return rc;
+  return many_launch(m, MANY_PLAIN, d_roots, count, options->max_nodes, options->objective == CS_OBJ_ALL, d_results, d_solutions,
+                     0, stream, NULL, NULL);
+}
+
 /* ---- checkpoints: csgpu_solve_many in slices (cs_dive_resume) ---- */
 
-struct csgpu_many_checkpoints {
-  const csgpu_model *m;
-  int64_t capacity;
-  size_t slot_bytes;
-  cs_val *d_pool;
-  unsigned long long *d_next; /* slots handed out since the last reset */
-  int counted;                /* the model counts this pool among the objects that hold its device tables */
-};
-
-/* does the model run cs_dive_shave?  What finalize planned; before finalize, the same rules on the host tables
+/* does the model run the cs_dive_* kernels?  What finalize planned; before finalize, the same rules on the host tables
  * (csgpu_model_build_tables), which is all they depend on */
 static int many_qualifies(const csgpu_model *m) {
-  if (m->finalized) return m->plan.dive.fn != NULL;
+  if (m->finalized) return m->plan.dive[MANY_PLAIN].fn != NULL;
   if (m->img == NULL) return 0;
   int fw = 0;
   size_t bytes = 0;
@@ -1699,8 +1690,7 @@ extern "C" int csgpu_many_checkpoints_create(const csgpu_model *m, int64_t capac
   if (m == NULL || out == NULL) return set_err(CSGPU_E_ARG, "null argument");
   if (capacity < 1) return set_err(CSGPU_E_ARG, "a checkpoint pool has at least one slot");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (m->plan.dive_ck.fn == NULL)
-    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel, which csgpu_solve_many is built on");
+  if (m->plan.dive[MANY_CK].fn == NULL) return set_err(CSGPU_E_LIMIT, MANY_NOT_QUALIFIED ", which csgpu_solve_many is built on");
   if (capacity > 0x7fffffff) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 1 slots");
   csgpu_many_checkpoints *ck = (csgpu_many_checkpoints *)calloc(1, sizeof *ck);
   if (ck == NULL) return set_err(CSGPU_E_LIMIT, "out of memory");
@@ -1735,73 +1725,30 @@ extern "C" void csgpu_many_checkpoints_free(csgpu_many_checkpoints *ck) {
   free(ck);
 }
 
-/* the checks both calls share, in csgpu_solve_many's order; nothing here touches the device */
-static int many_ck_args(const csgpu_model *m, const void *d_roots, int64_t count, const csgpu_many_options *options,
-                        const void *d_results, const csgpu_many_checkpoints *ck, const int32_t *d_slots) {
-  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL || ck == NULL || d_slots == NULL)
-    return set_err(CSGPU_E_ARG, "null argument");
-  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
-  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every slice has a budget");
-  if (options->objective == CS_OBJ_MIN || options->objective == CS_OBJ_MAX)
-    return set_err(CSGPU_E_LIMIT, "csgpu_solve_many searches with ANY or ALL: MIN / MAX are not supported");
-  if (options->objective != CS_OBJ_ANY && options->objective != CS_OBJ_ALL) return set_err(CSGPU_E_ARG, "no objective %d", options->objective);
-  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (m->plan.dive_ck.fn == NULL)
-    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
-                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
-  if (ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
-  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
-  return CSGPU_OK;
-}
-
-static int many_ck_launch(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
-                          csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
-                          int resume, void *stream) {
-  if (count == 0) return CSGPU_OK;
-  csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = &m->plan.dive_ck;
-  const int n = m->host->n_vars;
-  const int64_t waves = csgpu_internal_many_waves(m, count);
-  const int frames = n; /* as csgpu_solve_many; a resumed instance walks on the n frames of its slot */
+/* csgpu_solve_many_checkpointed, and with `resume` (and no roots) csgpu_solve_many_resume */
+static int many_ck_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                        csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                        int resume, void *stream) {
+  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || options == NULL || ck == NULL || d_slots == NULL;
   int rc;
-  if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
-  cs_dive_io io;
-  io.roots = (const cs_val *)d_roots;
-  io.count = (int)count;
-  io.all = options->objective == CS_OBJ_ALL;
-  io.max_nodes = (long long)options->max_nodes;
-  io.results = (cs_dive_result *)d_results;
-  io.solutions = d_solutions;
-  io.stack = resume ? NULL : (cs_val *)mm->d_many_stack;
-  io.frames = frames;
-  io.tickets = mm->d_many_tickets;
-  cs_dive_ck dk;
-  dk.pool = ck->d_pool;
-  dk.next = ck->d_next;
-  dk.capacity = (int)ck->capacity;
-  dk.resume = resume;
-  dk.slots = d_slots;
-  int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
-  const void *tab_d = m->d_dense_tab;
-  const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
-  size_t tab_bytes = m->dense_bytes;
-  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io, &dk };
-  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
-  return CSGPU_OK;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "slice")) ||
+      (rc = many_check_objective(options->objective)) || (rc = many_check_tail(m, MANY_CK, ck, count)))
+    return rc;
+  cs_dive_ck dk = many_ck_arg(ck, d_slots, resume);
+  return many_launch(m, MANY_CK, d_roots, count, options->max_nodes, options->objective == CS_OBJ_ALL, d_results, d_solutions,
+                     resume, stream, &dk, NULL);
 }
 
 extern "C" int csgpu_solve_many_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                              const csgpu_many_options *options, csgpu_many_result *d_results,
                                              int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  const int rc = many_ck_args(m, d_roots, count, options, d_results, ck, d_slots);
-  return rc != CSGPU_OK ? rc : many_ck_launch(m, d_roots, count, options, d_results, d_solutions, ck, d_slots, 0, stream);
+  return many_ck_call(m, d_roots, count, options, d_results, d_solutions, ck, d_slots, 0, stream);
 }
 
 extern "C" int csgpu_solve_many_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
                                        csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
                                        int32_t *d_slots, void *stream) {
-  const int rc = many_ck_args(m, d_results /* no roots: any non-null pointer */, count, options, d_results, ck, d_slots);
-  return rc != CSGPU_OK ? rc : many_ck_launch(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
+  return many_ck_call(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
 }
 
 extern "C" int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
@@ -1826,131 +1773,59 @@ extern "C" int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, in
 
 /* ---- up to k solutions per instance (cs_dive_upto): csgpu_solve_many, stopped at the k-th solution, all k rows kept ---- */
 
-/* the checks the three calls share, in csgpu_solve_many's order; nothing here touches the device.  `pooled`: the call
- * has a pool and slot numbers */
-static int many_upto_args(const csgpu_model *m, const void *d_roots, int64_t count, const csgpu_many_upto_options *options,
-                          const void *d_results, int pooled, const csgpu_many_checkpoints *ck, const int32_t *d_slots) {
-  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL || (pooled && (ck == NULL || d_slots == NULL)))
-    return set_err(CSGPU_E_ARG, "null argument");
-  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
-  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every instance has a budget");
-  if (options->max_solutions < 1) return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
-  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (m->plan.dive_upto.fn == NULL)
-    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
-                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
-  if (pooled && ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
-  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
-  return CSGPU_OK;
-}
-
-/* ck == NULL: the plain call, a pool of capacity 0 that the kernel does not touch */
-static int many_upto_launch(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_upto_options *options,
-                            csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
-                            int resume, void *stream) {
-  if (count == 0) return CSGPU_OK;
-  csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = &m->plan.dive_upto;
-  const int n = m->host->n_vars;
-  const int64_t waves = csgpu_internal_many_waves(m, count);
-  const int frames = n; /* as csgpu_solve_many; a resumed instance walks on the n frames of its slot */
+/* the three calls.  `pooled`: the call has a pool and slot numbers; `resume` (pooled, and no roots): it goes on in them */
+static int many_upto_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_upto_options *options,
+                          csgpu_many_result *d_results, int32_t *d_solutions, int pooled, csgpu_many_checkpoints *ck,
+                          int32_t *d_slots, int resume, void *stream) {
+  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || options == NULL ||
+                       (pooled && (ck == NULL || d_slots == NULL));
   int rc;
-  if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
-  cs_dive_io io;
-  io.roots = (const cs_val *)d_roots;
-  io.count = (int)count;
-  io.all = 1; /* not read: the walk is the ALL walk, left at the k-th solution */
-  io.max_nodes = (long long)options->max_nodes;
-  io.results = (cs_dive_result *)d_results;
-  io.solutions = d_solutions;
-  io.stack = resume ? NULL : (cs_val *)mm->d_many_stack;
-  io.frames = frames;
-  io.tickets = mm->d_many_tickets;
-  cs_dive_ck dk;
-  dk.pool = ck != NULL ? ck->d_pool : NULL;
-  dk.next = ck != NULL ? ck->d_next : NULL;
-  dk.capacity = ck != NULL ? (int)ck->capacity : 0;
-  dk.resume = resume;
-  dk.slots = ck != NULL ? d_slots : NULL;
-  int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin, upto = options->max_solutions;
-  const void *tab_d = m->d_dense_tab;
-  const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
-  size_t tab_bytes = m->dense_bytes;
-  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io, &dk, &upto };
-  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
-  return CSGPU_OK;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance"))) return rc;
+  if (options->max_solutions < 1) return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
+  if ((rc = many_check_tail(m, MANY_UPTO, ck, count))) return rc;
+  cs_dive_ck dk = many_ck_arg(ck, d_slots, resume);
+  int upto = options->max_solutions;
+  return many_launch(m, MANY_UPTO, d_roots, count, options->max_nodes, 1 /* not read: the ALL walk, left at the k-th solution */,
+                     d_results, d_solutions, resume, stream, &dk, &upto);
 }
 
 extern "C" int csgpu_solve_many_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                      const csgpu_many_upto_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
                                      void *stream) {
-  const int rc = many_upto_args(m, d_roots, count, options, d_results, 0, NULL, NULL);
-  return rc != CSGPU_OK ? rc : many_upto_launch(m, d_roots, count, options, d_results, d_solutions, NULL, NULL, 0, stream);
+  return many_upto_call(m, d_roots, count, options, d_results, d_solutions, 0, NULL, NULL, 0, stream);
 }
 
 extern "C" int csgpu_solve_many_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                                   const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                                   int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                                   void *stream) {
-  const int rc = many_upto_args(m, d_roots, count, options, d_results, 1, ck, d_slots);
-  return rc != CSGPU_OK ? rc : many_upto_launch(m, d_roots, count, options, d_results, d_solutions, ck, d_slots, 0, stream);
+  return many_upto_call(m, d_roots, count, options, d_results, d_solutions, 1, ck, d_slots, 0, stream);
 }
 
 extern "C" int csgpu_solve_many_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
                                             csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
                                             int32_t *d_slots, void *stream) {
-  const int rc = many_upto_args(m, d_results /* no roots: any non-null pointer */, count, options, d_results, 1, ck, d_slots);
-  return rc != CSGPU_OK ? rc : many_upto_launch(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
+  return many_upto_call(m, NULL, count, options, d_results, d_solutions, 1, ck, d_slots, 1, stream);
 }
 
 /* ---- Luby restarts with a seeded value order for ANY (cs_dive_restart) ---- */
 
-static_assert(sizeof(csgpu_many_restart_options) == 24, "csgpu_many_restart_options layout");
-
 extern "C" int csgpu_solve_many_restarts(const csgpu_model *m, const csgpu_val *d_roots, const uint32_t *d_seeds, int64_t count,
                                          const csgpu_many_restart_options *options, csgpu_many_result *d_results,
                                          int32_t *d_solutions, int32_t *d_restarts, void *stream) {
-  if (m == NULL || d_roots == NULL || d_results == NULL || options == NULL) return set_err(CSGPU_E_ARG, "null argument");
-  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
-  if (options->max_nodes <= 0) return set_err(CSGPU_E_ARG, "max_nodes must be positive: every instance has a budget");
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance"))) return rc;
   if (options->restart_base < 0) return set_err(CSGPU_E_ARG, "restart_base must not be negative (0: no restarts)");
   if ((options->flags & ~CSGPU_MANY_ROTATE_FIRST) != 0) return set_err(CSGPU_E_ARG, "unknown flags 0x%x", (unsigned)options->flags);
-  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (m->plan.dive_restart.fn == NULL)
-    return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel (a pure != network of at most 256 "
-                                  "variables whose dense pair table fits LDS), which csgpu_solve_many is built on");
-  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
-  if (count == 0) return CSGPU_OK;
-  csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = &m->plan.dive_restart;
-  const int n = m->host->n_vars;
-  const int64_t waves = csgpu_internal_many_waves(m, count);
-  const int frames = n; /* as csgpu_solve_many: at most n - 1 are in use, the n-th keeps the root node's fixpoint */
-  int rc;
-  if ((rc = many_workspace(mm, waves, frames))) return rc;
-  cs_dive_io io;
-  io.roots = (const cs_val *)d_roots;
-  io.count = (int)count;
-  io.all = 0;
-  io.max_nodes = (long long)options->max_nodes;
-  io.results = (cs_dive_result *)d_results;
-  io.solutions = d_solutions;
-  io.stack = (cs_val *)mm->d_many_stack;
-  io.frames = frames;
-  io.tickets = mm->d_many_tickets;
+  if ((rc = many_check_tail(m, MANY_RESTART, NULL, count))) return rc;
   cs_dive_rs rs;
   rs.seeds = d_seeds;
   rs.restarts = d_restarts;
   rs.restart_base = (long long)options->restart_base;
   rs.seed = options->seed;
   rs.flags = options->flags;
-  int nn = n, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
-  const void *tab_d = m->d_dense_tab;
-  const int *root_lo_d = m->d_root_lo, *root_hi_d = m->d_root_hi, *sym_off = m->d_sym_off;
-  size_t tab_bytes = m->dense_bytes;
-  void *args[] = { &nn, &tab_d, &slots, &dmin_d, &root_lo_d, &root_hi_d, &sym_off, &tab_bytes, &io, &rs };
-  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
-  return CSGPU_OK;
+  return many_launch(m, MANY_RESTART, d_roots, count, options->max_nodes, 0, d_results, d_solutions, 0, stream, &rs, NULL);
 }
 
 #ifdef CS_SHAVE_TIMELINE

@@ -1,18 +1,18 @@
-/* cs_dive_body.hip.h -- the body of cs_dive_shave (CS_DIVE_CK 0), of cs_dive_resume (CS_DIVE_CK 1) and of cs_dive_upto
- * (CS_DIVE_CK 1, CS_DIVE_UPTO 1), included by cs_dive.hip.h inside each kernel.  Text, not a __device__ function: inlined
- * from a function, the loop of cs_dive_shave<E, 2> takes 42 vector registers instead of 39.  With CS_DIVE_CK 0 the text is
- * the kernel as it was before there were checkpoints, and compiles to the same instructions; every line of cs_dive_upto
- * stands under `#if CS_DIVE_UPTO`, so the other two see the text they saw before there was a third.
- * CS_DIVE_UPTO: the kernel has one more argument, `upto` (k >= 1, a scalar): the instance stops right after its k-th
- * solution, solution j goes to row j of the instance's k rows, and io.all is not read.  A pool of capacity 0 means "no
- * pool": ck.next, ck.pool and ck.slots are then never touched (csgpu_solve_many_upto).
- * CS_DIVE_RESTART (with CS_DIVE_CK 0): cs_dive_restart, the ANY walk with a seeded rotation of every node's value order
- * and Luby restarts (csgpu_solve_many_restarts; the walk is defined in csolve_gpu.h).  One more argument, `rs`.  Every
- * line of it stands under `#if CS_DIVE_RESTART`; the three older inclusions define it 0 and see the text they saw.  A
- * frame's 8-byte entry is {variable, next j} instead of {variable, next value}; the root node's fixpoint is kept in
- * frame `frames - 1`, which the walk never uses (at most n - 1 of the n frames), and a restart reads it back, every
- * lane the entries it wrote itself.  A restart stays inside the instance's loop: it is no `continue` of the ticket
- * loop.  New per-wave state is scalars only: run, fails, threshold, counter, seed, restarts, start (and width). */
+/* cs_dive_body.hip.h -- the body of the four kernels of cs_dive.hip.h, which includes it inside each of them under three
+ * switches:            CS_DIVE_CK  CS_DIVE_UPTO  CS_DIVE_RESTART
+ *   cs_dive_shave          0           0              0        csgpu_solve_many
+ *   cs_dive_resume         1           0              0        one more argument, `ck`: the pool and the slots of the call
+ *   cs_dive_upto           1           1              0        and `upto` (k >= 1, a scalar)
+ *   cs_dive_restart        0           0              1        one more argument, `rs` (the walk is defined in csolve_gpu.h)
+ * Text, not a __device__ function: inlined from a function, the loop of cs_dive_shave<E, 2> takes 42 vector registers
+ * instead of 39.  Every line of a switch stands under its `#if`, so a kernel that defines it 0 sees the text it saw before
+ * the switch was there and compiles to the same instructions.
+ * CS_DIVE_UPTO: the instance stops right after its k-th solution, solution j goes to row j of the instance's k rows, and
+ * io.all is not read.  A pool of capacity 0 means "no pool": ck.next, ck.pool and ck.slots are then never touched.
+ * CS_DIVE_RESTART: the ANY walk with a seeded rotation of every node's value order and Luby restarts.  A frame's 8-byte
+ * entry is {variable, next j} instead of {variable, next value}; the root node's fixpoint is kept in frame `frames - 1`,
+ * which the walk never uses, and a restart reads it back, every lane the entries it wrote itself.  A restart is no
+ * `continue` of the ticket loop.  New per-wave state is scalars only: run, fails, threshold, counter, seed, restarts, start. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   typedef unsigned long long u64;
   const int lane = threadIdx.x & (CS_WAVE - 1);

@@ -210,6 +210,37 @@ class Model:
     # ---- many instances of this model in one call (csgpu_solve_many) -------------------------------
     MANY_OBJECTIVES = {"ANY": 0, "ALL": 1, "MIN": 2, "MAX": 3}
 
+    def _many_roots(self, roots, bad_option, probe):
+        """the root rows of a call of the solve_many family on the device -> (roots, K); a numpy array is uploaded.  On a
+        model that is not finalized or not one of kernel 7, or with `bad_option`, probe(host pointer, K) makes the call
+        itself first: the library says what is wrong before any device call (it touches no buffer), and nothing is
+        uploaded for it"""
+        n = self.n_vars
+        if not torch.is_tensor(roots):
+            roots = np.ascontiguousarray(roots, dtype=np.int32)
+            assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
+            if not self.qualifies(7) or bad_option:
+                probe(roots.ctypes.data, roots.shape[0])
+            roots = torch.from_numpy(roots).cuda()
+        assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
+        assert roots.dim() == 3 and tuple(roots.shape[1:]) == (n, 2), "roots is [K, n_vars, 2]"
+        return roots, roots.shape[0]
+
+    @staticmethod
+    def _many_records(K, device) -> torch.Tensor:
+        """K zeroed csgpu_many_result records of 40 bytes (one for an empty batch: the library wants a pointer)"""
+        return torch.zeros((max(K, 1), 5), dtype=torch.int64, device=device)
+
+    @staticmethod
+    def _many_rows(solutions, shape, named, device):
+        """the buffer for the solution rows: `solutions` True -> a zeroed int32 one of `shape`, False -> None, an int32
+        device tensor of that shape -> itself"""
+        if torch.is_tensor(solutions):
+            assert solutions.is_cuda and solutions.dtype == torch.int32 and solutions.is_contiguous() and \
+                tuple(solutions.shape) == shape, f"solutions is {named} int32 on the device"
+            return solutions
+        return torch.zeros(tuple(max(d, 0) for d in shape), dtype=torch.int32, device=device) if solutions else None
+
     def solve_many(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
         """K instances of this model, a depth-first search per wavefront (csgpu_solve_many; the model must qualify for
         kernel 7).  roots: int32 [K, n_vars, 2] root rows inside the model's root domains, a torch tensor on the device
@@ -224,21 +255,10 @@ class Model:
         n = self.n_vars
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         opt = ManyOptions(obj, 0, int(max_nodes))
-        if not torch.is_tensor(roots):
-            roots = np.ascontiguousarray(roots, dtype=np.int32)
-            assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
-            if not self.qualifies(7):
-                # not finalized, or not a model of kernel 7: the library says which, before any device call (it
-                # touches neither buffer), and nothing is uploaded for it
-                check(L.csgpu_solve_many(self._h, roots.ctypes.data, roots.shape[0], C.byref(opt), roots.ctypes.data,
-                                         None, None))
-            roots = torch.from_numpy(roots).cuda()
-        assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
-        assert roots.dim() == 3 and tuple(roots.shape[1:]) == (n, 2), "roots is [K, n_vars, 2]"
-        K = roots.shape[0]
-        buf = torch.zeros((max(K, 1), 5), dtype=torch.int64, device=roots.device)  # csgpu_many_result: 40 bytes
-        res = buf[:K]
-        first = torch.zeros((K, n), dtype=torch.int32, device=roots.device) if solutions else None
+        roots, K = self._many_roots(roots, False, lambda ptr, count: check(
+            L.csgpu_solve_many(self._h, ptr, count, C.byref(opt), ptr, None, None)))
+        buf = self._many_records(K, roots.device)
+        first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
         # (an empty batch still goes through the library's checks: any non-null pointer stands for its rows)
         if checkpoints is None:
             check(L.csgpu_solve_many(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
@@ -275,25 +295,10 @@ class Model:
         L = load_library()
         n, k = self.n_vars, int(k)
         opt = ManyUptoOptions(k, 0, int(max_nodes))
-        if not torch.is_tensor(roots):
-            roots = np.ascontiguousarray(roots, dtype=np.int32)
-            assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
-            if not self.qualifies(7) or k < 1:
-                # as solve_many: the library says what is wrong before any device call, nothing is uploaded for it
-                check(L.csgpu_solve_many_upto(self._h, roots.ctypes.data, roots.shape[0], C.byref(opt), roots.ctypes.data,
-                                              None, None))
-            roots = torch.from_numpy(roots).cuda()
-        assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
-        assert roots.dim() == 3 and tuple(roots.shape[1:]) == (n, 2), "roots is [K, n_vars, 2]"
-        K = roots.shape[0]
-        buf = torch.zeros((max(K, 1), 5), dtype=torch.int64, device=roots.device)  # csgpu_many_result: 40 bytes
-        rows = None
-        if torch.is_tensor(solutions):
-            rows = solutions
-            assert rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and tuple(rows.shape) == (K, k, n), \
-                "solutions is [K, k, n_vars] int32 on the device"
-        elif solutions:
-            rows = torch.zeros((K, max(k, 0), n), dtype=torch.int32, device=roots.device)
+        roots, K = self._many_roots(roots, k < 1, lambda ptr, count: check(
+            L.csgpu_solve_many_upto(self._h, ptr, count, C.byref(opt), ptr, None, None)))
+        buf = self._many_records(K, roots.device)
+        rows = self._many_rows(solutions, (K, k, n), "[K, k, n_vars]", roots.device)
         rows_ptr = rows.data_ptr() if rows is not None and K and k >= 1 else None
         if checkpoints is None:
             check(L.csgpu_solve_many_upto(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
@@ -327,30 +332,15 @@ class Model:
         n = self.n_vars
         opt = ManyRestartOptions(int(max_nodes), int(restart_base), int(seed) & 0xffffffff,
                                  MANY_ROTATE_FIRST if rotate_first else 0)
-        if not torch.is_tensor(roots):
-            roots = np.ascontiguousarray(roots, dtype=np.int32)
-            assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
-            if not self.qualifies(7) or restart_base < 0:
-                # as solve_many: the library says what is wrong before any device call, nothing is uploaded for it
-                check(L.csgpu_solve_many_restarts(self._h, roots.ctypes.data, None, roots.shape[0], C.byref(opt),
-                                                  roots.ctypes.data, None, None, None))
-            roots = torch.from_numpy(roots).cuda()
-        assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
-        assert roots.dim() == 3 and tuple(roots.shape[1:]) == (n, 2), "roots is [K, n_vars, 2]"
-        K = roots.shape[0]
+        roots, K = self._many_roots(roots, restart_base < 0, lambda ptr, count: check(
+            L.csgpu_solve_many_restarts(self._h, ptr, None, count, C.byref(opt), ptr, None, None, None)))
         if seeds is not None:
             if not torch.is_tensor(seeds):
                 seeds = torch.from_numpy((np.asarray(seeds).astype(np.int64) & 0xffffffff).astype(np.uint32).view(np.int32))
             seeds = seeds.to(device=roots.device, dtype=torch.int32).contiguous()  # the 32 bits are what counts
             assert tuple(seeds.shape) == (K,), "seeds is [K]"
-        buf = torch.zeros((max(K, 1), 5), dtype=torch.int64, device=roots.device)  # csgpu_many_result: 40 bytes
-        first = None
-        if torch.is_tensor(solutions):
-            first = solutions
-            assert first.is_cuda and first.dtype == torch.int32 and first.is_contiguous() and tuple(first.shape) == (K, n), \
-                "solutions is [K, n_vars] int32 on the device"
-        elif solutions:
-            first = torch.zeros((K, n), dtype=torch.int32, device=roots.device)
+        buf = self._many_records(K, roots.device)
+        first = self._many_rows(solutions, (K, n), "[K, n_vars]", roots.device)
         count = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if restarts else None
         check(L.csgpu_solve_many_restarts(self._h, roots.data_ptr() if K else buf.data_ptr(),
                                           seeds.data_ptr() if seeds is not None and K else None, K, C.byref(opt),
@@ -473,28 +463,24 @@ class Model:
             if finish == "search":
                 raise ValueError("finish=\"search\" with max_solutions: an engine search cannot stop at a k-th solution "
                                  "per instance")
-            K = roots.shape[0]
-            pool = self.many_checkpoints(max(K, 1))
-            out = self.solve_many_upto(roots, max_solutions, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
-            slices = 1
-            for budget in budgets[1:]:
-                if not bool((out["status"] == 1).any()):
-                    break
-                self.resume_many(out, max_nodes=budget)
-                slices += 1
-            out["sliced"] = {"slices": slices, "searched": 0}
-            return out
-        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
-        if finish == "search" and obj != self.objective:
-            raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
-        K = roots.shape[0]
-        pool = self.many_checkpoints(max(K, 1))
-        out = self.solve_many(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+            obj, more = None, {}  # resume_many takes the k from the answer
+
+            def first_slice(pool):
+                return self.solve_many_upto(roots, max_solutions, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+        else:
+            obj, more = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective), {"objective": objective}
+            if finish == "search" and obj != self.objective:
+                raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
+
+            def first_slice(pool):
+                return self.solve_many(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+        pool = self.many_checkpoints(max(roots.shape[0], 1))
+        out = first_slice(pool)
         slices = 1
         for budget in budgets[1:]:
             if not bool((out["status"] == 1).any()):
                 break
-            self.resume_many(out, max_nodes=budget, objective=objective)
+            self.resume_many(out, max_nodes=budget, **more)
             slices += 1
         searched = 0
         if finish == "search":
@@ -534,30 +520,28 @@ class Model:
         out["status"][i] = 0
         out["slot"][i] = -1
 
-    def many_kernel(self):
-        """the cs_dive_shave instantiation solve_many launches for this model (template-id), None if it does not qualify"""
+    def _many_symbol(self, export: str):
+        """the instantiation a family of solve_many launches for this model (template-id), by the library's `export`;
+        None if the model does not qualify"""
         buf = C.create_string_buffer(1024)
-        check(load_library().csgpu_internal_many_symbol(self._h, buf, len(buf)))
+        check(getattr(load_library(), export)(self._h, buf, len(buf)))
         return demangle(buf.value.decode()) if buf.value else None
+
+    def many_kernel(self):
+        """the cs_dive_shave instantiation solve_many launches"""
+        return self._many_symbol("csgpu_internal_many_symbol")
 
     def many_resume_kernel(self):
-        """the cs_dive_resume instantiation the checkpointed calls launch (template-id), None if the model does not qualify"""
-        buf = C.create_string_buffer(1024)
-        check(load_library().csgpu_internal_many_resume_symbol(self._h, buf, len(buf)))
-        return demangle(buf.value.decode()) if buf.value else None
+        """the cs_dive_resume instantiation the checkpointed calls launch"""
+        return self._many_symbol("csgpu_internal_many_resume_symbol")
 
     def many_upto_kernel(self):
-        """the cs_dive_upto instantiation solve_many_upto and its checkpoint calls launch (template-id), None if the model
-        does not qualify"""
-        buf = C.create_string_buffer(1024)
-        check(load_library().csgpu_internal_many_upto_symbol(self._h, buf, len(buf)))
-        return demangle(buf.value.decode()) if buf.value else None
+        """the cs_dive_upto instantiation solve_many_upto and its checkpoint calls launch"""
+        return self._many_symbol("csgpu_internal_many_upto_symbol")
 
     def many_restart_kernel(self):
-        """the cs_dive_restart instantiation solve_many_restarts launches (template-id), None if the model does not qualify"""
-        buf = C.create_string_buffer(1024)
-        check(load_library().csgpu_internal_many_restart_symbol(self._h, buf, len(buf)))
-        return demangle(buf.value.decode()) if buf.value else None
+        """the cs_dive_restart instantiation solve_many_restarts launches"""
+        return self._many_symbol("csgpu_internal_many_restart_symbol")
 
     def many_waves(self, count: int) -> int:
         """waves a solve_many of `count` instances launches"""

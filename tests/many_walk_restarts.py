@@ -12,9 +12,8 @@ nodes / cuts / props and the budget run over all runs; the budget is compared be
 import numpy as np
 
 import many_walk
-from many_walk import BAD_ROOT, DONE, LIMIT  # noqa: F401
+from many_walk import BAD_ROOT, DONE, FIELDS, LIMIT  # noqa: F401
 
-FIELDS = ("status", "root_props", "nodes", "cuts", "props", "solutions")
 M32 = 0xffffffff
 ROTATE_FIRST = 1
 
@@ -119,19 +118,6 @@ def dive_restarts(text, row, restart_base, seed, rotate_first=False, max_nodes=1
 def dive_many_restarts(text, roots, restart_base, seed=0, seeds=None, rotate_first=False, max_nodes=1 << 62):
     """dive_restarts() of every row (seeds[i], or `seed` for all) -> dict of arrays shaped like
     Model.solve_many_restarts's answer (first: zeros where there is none); equal (row, seed) pairs are walked once"""
-    roots = np.ascontiguousarray(roots, dtype=np.int32)
-    K, n = roots.shape[0], roots.shape[1]
-    res = {k: np.zeros(K, dtype=np.int64) for k in FIELDS + ("restarts",)}
-    res["first"] = np.zeros((K, n), dtype=np.int32)
-    seen = {}
-    for i in range(K):
-        s = int(seeds[i]) & M32 if seeds is not None else int(seed) & M32
-        key = (roots[i].tobytes(), s)
-        if key not in seen:
-            seen[key] = dive_restarts(text, roots[i], restart_base, s, rotate_first, max_nodes)
-        d = seen[key]
-        for k in FIELDS + ("restarts",):
-            res[k][i] = d[k]
-        if d["first"] is not None:
-            res["first"][i] = d["first"]
-    return res
+    tags = [int(seeds[i]) & M32 if seeds is not None else int(seed) & M32 for i in range(len(roots))]
+    results = many_walk.walk_each(roots, lambda row, s: dive_restarts(text, row, restart_base, s, rotate_first, max_nodes), tags)
+    return many_walk.gather(results, np.shape(roots)[1], FIELDS + ("restarts",))

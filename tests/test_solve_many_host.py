@@ -214,3 +214,60 @@ def test_no_instance_of_a_set_reaches_its_budget(name):
     sample = np.concatenate([roots[:8], roots[-4:]])
     res = many_walk.dive_many(text, sample, objective, budget)
     assert (res["status"] == many_walk.DONE).all() and res["nodes"].max() <= largest
+
+
+def _plain(x):
+    """a walk's answer as JSON holds it"""
+    if isinstance(x, dict):
+        return {k: _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_plain(v) for v in x]
+    if isinstance(x, np.ndarray):
+        return x.tolist()
+    return None if x is None else int(x)
+
+
+def _walk_calls(text, row):
+    """every call the recorded walks pin, on one root row: the whole result dict of each, and the open subtrees of every
+    walk that stops at LIMIT"""
+    import many_resume_walk
+    import many_walk_upto
+    calls = {}
+    for objective in ("ANY", "ALL"):
+        for budget in (1, 7, 1 << 62):
+            calls[f"dive {objective} {budget}"] = many_walk.dive(text, row, objective, budget)
+    w, parts = many_resume_walk.Walk(text, row, "ALL"), []
+    while not parts or parts[-1][0]["status"] == many_walk.LIMIT:
+        part = w.run(5)
+        stopped = part["status"] == many_walk.LIMIT
+        parts.append([part, w.open_subtrees() if stopped else None, w.has_last_value_frame() if stopped else None])
+    calls["Walk ALL by 5"] = parts
+    for k in (1, 2, 3, 1 << 40):
+        calls[f"WalkUpto {k}"] = many_walk_upto.WalkUpto(text, row).run(1 << 62, k)
+    slices = [(5, 2), (9, 1), (1 << 62, 3)]
+    w, parts = many_walk_upto.WalkUpto(text, row), []
+    for budget, k in slices:
+        part = w.run(budget, k)
+        parts.append([part, w.open_subtrees() if part["status"] == many_walk.LIMIT else None])
+    calls["WalkUpto by slices"] = parts
+    calls["dive_sliced"] = many_walk_upto.dive_sliced(text, row, slices)
+    return _plain(calls)
+
+
+def test_the_walks_give_what_the_three_separate_walks_gave():
+    """tests/golden/many_walk/recorded.json holds what many_walk.dive, many_resume_walk.Walk and many_walk_upto.WalkUpto
+    / dive_sliced answered while each had a loop of its own (recorded by _walk_calls at the last commit that had them):
+    every field and every row of every call is still that, on queens-7 and four 9x9 sudokus under ALL and on three root
+    rows that are not searched"""
+    import json
+    recorded = json.load(open(golden("many_walk", "recorded.json")))
+    texts = {"queens7": problems.queens(7, "ALL"), "sudoku9": problems.sudoku_roots(3, 0.40, [1, 2, 3, 4], "ALL")[0]}
+    sudoku_rows = problems.sudoku_roots(3, 0.40, [1, 2, 3, 4], "ALL")[1]
+    assert [c["what"] for c in recorded] == ["root domains", "a solution", "lo > hi", "inconsistent at the root"] + ["sudoku row"] * 4
+    assert recorded[0]["row"] == many_walk.oracle_for(texts["queens7"])[1].tolist()
+    assert [c["row"] for c in recorded[4:]] == sudoku_rows[:4].tolist()
+    for case in recorded:
+        got = _walk_calls(texts[case["model"]], np.array(case["row"], dtype=np.int32))
+        assert sorted(got) == sorted(case["calls"])
+        for call, want in case["calls"].items():
+            assert got[call] == want, (case["model"], case["what"], call)
