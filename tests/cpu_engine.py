@@ -27,6 +27,10 @@ class OracleEngine:
                        best=INT32_MAX if self.objective == OBJ_MIN else (INT32_MIN if self.objective == OBJ_MAX else 0),
                        done=0)
         self.found = []
+        # counters of the walk that the statistics of the GPU engine have no field for (they change nothing it computes)
+        self.halvings = 0  # parents split in two
+        self.halved = []  # their branching intervals (lo, hi)
+        self.complete_false = 0  # complete consistent children whose root evaluates false
 
     def put(self, states):
         for s in states.cpu().numpy():
@@ -77,7 +81,9 @@ class OracleEngine:
                 v = int(np.argmin(width))
                 lo, hi = int(state[v, 0]), int(state[v, 1])
                 if hi - lo + 1 > SPLIT_WIDTH:
-                    mid = (lo + hi) >> 1
+                    mid = self._middle(lo, hi)
+                    self.halvings += 1
+                    self.halved.append((lo, hi))
                     kids = [(lo, mid), (mid + 1, hi)]
                 else:
                     kids = [(x, x) for x in range(lo, hi + 1)]
@@ -97,6 +103,8 @@ class OracleEngine:
                                 self.st["best"] = min(self.st["best"], int(out[self.obj_var, 0]))
                             if self.objective == OBJ_MAX:
                                 self.st["best"] = max(self.st["best"], int(out[self.obj_var, 1]))
+                        else:
+                            self.complete_false += 1
                     else:
                         self.pool.append(out)
             self.st["pool_peak"] = max(self.st["pool_peak"], len(self.pool))
@@ -106,6 +114,11 @@ class OracleEngine:
         self.st["pool"] = len(self.pool)
         self.st["done"] = int(not self.pool or (self.objective == OBJ_ANY and self.st["solutions"] > 0))
         return dict(self.st)
+
+    @staticmethod
+    def _middle(lo, hi):
+        """the last value of the lower half of a halved interval: rounded down, whatever the signs (cs_emit_seg)"""
+        return (lo + hi) >> 1
 
     def orc_eval_true(self, state):
         self.orc.set_domains(state)
