@@ -324,8 +324,9 @@ __device__ inline void cs_tree_revise(const cs_tables &T, int tree, cs_ctx &cx, 
     case CS_OP_VAR:
       cx.narrow(n.y, w);
       break;
-    case CS_OP_CONST: /* terminal without variable: only a conflict is observable */
-      if (n.y > w.hi || n.z < w.lo) cx.fail = 1;
+    case CS_OP_CONST: /* terminal without variable: only a conflict is observable; the trail names it as a failure
+                       * at no variable (csolve_gpu.h: -1) */
+      if (n.y > w.hi || n.z < w.lo) cx.failed_at(-1);
       break;
     case CS_OP_EQ: {
       cs_val lv = S.val[n.y], rv = S.val[n.z];
@@ -372,7 +373,7 @@ __device__ inline void cs_tree_revise(const cs_tables &T, int tree, cs_ctx &cx, 
           if (!cs_is_value(cv)) continue;
           const int c = cv.lo;
           if (((w.lo > 0 || w.hi < 0) && c == 0) || (cs_is_value(w) && c != 0 && (w.lo % c) != 0)) {
-            cx.fail = 1;
+            cx.failed_at(-1); /* PROP_ERROR of propagate_mul_lr: no variable emptied, the trail still ends in a failure */
             break;
           }
           if (c != 0) {
