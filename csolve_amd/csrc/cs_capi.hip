@@ -18,6 +18,7 @@
 #include "cs_shave.hip.h"
 #include "cs_step.hip.h"
 #include "cs_dive.hip.h"
+#include "cs_walk.hip.h"
 #include "cs_chain.hip.h"
 #include "cs_internal.h"
 
@@ -73,6 +74,7 @@ struct cs_kernel_plan {
   cs_planned server;               /* the resident single-node server */
   cs_planned step_shave, step_packed, step_import;
   cs_planned dive[MANY_FAMILIES];  /* by MANY_*: all four or none; not among csgpu_internal_plan_symbol's families */
+  cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -111,6 +113,7 @@ struct csgpu_model {
   void *d_many_stack;
   int64_t many_stack_waves;
   unsigned *d_many_tickets;
+  cs_val *d_walk_root; /* csgpu_solve_many_clauses: the root domains, which a root row must lie inside */
   int *d_sym_off;
   void *d_sym_packed;
   int n_cus;
@@ -309,6 +312,8 @@ static void free_device(csgpu_model *m) {
   (void)hipFree(m->d_root_hi);
   (void)hipFree(m->d_many_stack);
   (void)hipFree(m->d_many_tickets);
+  (void)hipFree(m->d_walk_root);
+  m->d_walk_root = NULL;
   m->d_root_hi = NULL;
   m->d_many_stack = NULL;
   m->d_many_tickets = NULL;
@@ -973,6 +978,22 @@ static int plan_general(csgpu_model *m) {
     m->plan.rounds.lds = ((((size_t)h->n_vars * sizeof(cs_val) + 16 + 15) & ~(size_t)15)) * CS_WAVES_PER_BLOCK;
     m->plan.rounds.waves = CS_WAVES_PER_BLOCK;
     m->plan.rounds.per_cu = 8;
+    /* cs_walk_clauses: kernel 6's slices; planned when a workgroup's fit a CU (csgpu_solve_many_clauses says so otherwise) */
+    if (m->plan.rounds.lds <= CS_CU_LDS) {
+#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_clauses<CPL, true> : (const void *)cs_walk_clauses<CPL, false>)
+      const int cpl = m->plan.rounds_cpl;
+      const void *fn = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
+#undef CS_PICKW
+      if ((rc = plan_kernel(&m->plan.walk, fn, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
+      { /* persistent waves: no more workgroups than stay resident with the instantiation's registers and scratch */
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, CS_BLOCK, m->plan.walk.lds) == hipSuccess && occ >= 1 &&
+            occ < m->plan.walk.per_cu)
+          m->plan.walk.per_cu = occ;
+        if (m->plan.walk.per_cu < 1) m->plan.walk.per_cu = 1;
+      }
+      if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
+    }
   }
   m->plan.max_width = 2;
   for (int32_t v = 0; v < h->n_vars; v++) {
@@ -1826,6 +1847,95 @@ extern "C" int csgpu_solve_many_restarts(const csgpu_model *m, const csgpu_val *
   rs.seed = options->seed;
   rs.flags = options->flags;
   return many_launch(m, MANY_RESTART, d_roots, count, options->max_nodes, 0, d_results, d_solutions, 0, stream, &rs, NULL);
+}
+
+/* ---- clause models: csgpu_solve_many_clauses, a depth-first search per wavefront on kernel 6's fixpoint (cs_walk.hip.h) ---- */
+
+#define MANY_CLAUSES_STACK_MAX ((size_t)1 << 30) /* bytes of frames a call keeps: fewer waves rather than more memory */
+
+extern "C" int csgpu_model_qualifies_many_clauses(const csgpu_model *m) {
+  return m != NULL && m->finalized && m->plan.walk.fn != NULL;
+}
+
+extern "C" int csgpu_internal_many_clauses_symbol(const csgpu_model *m, char *buf, size_t len) {
+  if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  buf[0] = '\0';
+  const void *fn = m->plan.walk.fn;
+  if (fn == NULL) return CSGPU_OK;
+  Dl_info info;
+  if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
+    return set_err(CSGPU_E_STATE, "cs_walk_clauses: the kernel handle has no dynamic symbol");
+  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "cs_walk_clauses: symbol longer than the buffer");
+  strcpy(buf, info.dli_sname);
+  return CSGPU_OK;
+}
+
+/* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
+ * whose frames fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices fit a CU) */
+extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64_t count) {
+  if (!csgpu_model_qualifies_many_clauses(m) || count < 1) return 0;
+  const cs_planned *k = &m->plan.walk;
+  const size_t n = (size_t)m->host->n_vars;
+  int64_t grid = (int64_t)m->n_cus * k->per_cu;
+  const int64_t by_count = (count + k->waves - 1) / k->waves;
+  const int64_t by_stack = (int64_t)(MANY_CLAUSES_STACK_MAX / ((size_t)k->waves * n * (n + 1) * sizeof(cs_val)));
+  if (grid > by_count) grid = by_count;
+  if (grid > by_stack) grid = by_stack;
+  if (grid < 1) grid = 1;
+  return grid * k->waves;
+}
+
+extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                        const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                        int32_t *d_best, void *stream) {
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance"))) return rc;
+  const int objective = options->objective;
+  if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
+    return set_err(CSGPU_E_ARG, "no objective %d", objective);
+  if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX) {
+    if (m->host->obj_var < 0 || m->host->obj_var >= m->host->n_vars)
+      return set_err(CSGPU_E_ARG, "MIN / MAX need a model with an objective: this one has none");
+    if (m->host->objective != objective)
+      return set_err(CSGPU_E_ARG, "the model's objective is %s: it cannot be searched with %s",
+                     m->host->objective == CS_OBJ_MIN ? "MIN" : "MAX", objective == CS_OBJ_MIN ? "MIN" : "MAX");
+  }
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (m->plan.walk.fn == NULL) {
+    if (m->plan.rounds_cpl == 0)
+      return set_err(CSGPU_E_LIMIT, "model does not qualify for the clause-resident kernel (at most 512 clauses; this one has %d), "
+                                    "which csgpu_solve_many_clauses is built on", (int)m->img->n_clauses);
+    return set_err(CSGPU_E_LIMIT, "csgpu_solve_many_clauses: %d variables make LDS slices of %zu bytes for the %d waves of a "
+                                  "workgroup, more than the 160 KiB of a CU", (int)m->host->n_vars, m->plan.rounds.lds, CS_WAVES_PER_BLOCK);
+  }
+  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  if (count == 0) return CSGPU_OK;
+  csgpu_model *mm = const_cast<csgpu_model *>(m);
+  const cs_planned *k = &m->plan.walk;
+  const int n = m->host->n_vars;
+  const int64_t waves = csgpu_internal_many_clauses_waves(m, count);
+  const int frames = n; /* at most n - 1 pushed frames and the current node's */
+  if ((rc = many_workspace(mm, waves, frames))) return rc;
+  cs_walk_io io;
+  io.roots = (const cs_val *)d_roots;
+  io.root_dom = m->d_walk_root;
+  io.count = (int)count;
+  io.all = objective != CS_OBJ_ANY;
+  io.sense = objective_sense(objective);
+  io.obj_var = io.sense != 0 ? m->host->obj_var : -1;
+  io.max_nodes = (long long)options->max_nodes;
+  io.results = (cs_dive_result *)d_results;
+  io.solutions = d_solutions;
+  io.best = io.sense != 0 ? d_best : NULL;
+  io.stack = (cs_val *)mm->d_many_stack;
+  io.frames = frames;
+  io.tickets = mm->d_many_tickets;
+  cs_tables tab = m->tab;
+  void *args[] = { &tab, &io };
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
+  return CSGPU_OK;
 }
 
 #ifdef CS_SHAVE_TIMELINE

@@ -210,16 +210,16 @@ class Model:
     # ---- many instances of this model in one call (csgpu_solve_many) -------------------------------
     MANY_OBJECTIVES = {"ANY": 0, "ALL": 1, "MIN": 2, "MAX": 3}
 
-    def _many_roots(self, roots, bad_option, probe):
+    def _many_roots(self, roots, bad_option, probe, qualifies=None):
         """the root rows of a call of the solve_many family on the device -> (roots, K); a numpy array is uploaded.  On a
-        model that is not finalized or not one of kernel 7, or with `bad_option`, probe(host pointer, K) makes the call
-        itself first: the library says what is wrong before any device call (it touches no buffer), and nothing is
-        uploaded for it"""
+        model that is not finalized or not one of kernel 7 (`qualifies`: the entry's own rule instead), or with
+        `bad_option`, probe(host pointer, K) makes the call itself first: the library says what is wrong before any
+        device call (it touches no buffer), and nothing is uploaded for it"""
         n = self.n_vars
         if not torch.is_tensor(roots):
             roots = np.ascontiguousarray(roots, dtype=np.int32)
             assert roots.ndim == 3 and roots.shape[1:] == (n, 2), "roots is [K, n_vars, 2]"
-            if not self.qualifies(7) or bad_option:
+            if not (self.qualifies(7) if qualifies is None else qualifies) or bad_option:
                 probe(roots.ctypes.data, roots.shape[0])
             roots = torch.from_numpy(roots).cuda()
         assert roots.is_cuda and roots.dtype == torch.int32 and roots.is_contiguous()
@@ -350,6 +350,45 @@ class Model:
         if restarts:
             out["restarts"] = count[:K]
         return out
+
+    def solve_many_clauses(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None) -> dict:
+        """solve_many for clause models (csgpu_solve_many_clauses: `=`, `<`, disjunctions, expression trees; the model
+        must satisfy qualifies_many_clauses()), a depth-first search per wavefront on kernel 6's fixpoint, also under
+        "MIN" / "MAX": the model's own sense, each instance with a private incumbent, walked to the end of its tree.
+        roots, max_nodes, solutions, stream: as solve_many.  -> the dict of solve_many; `first` is the stored row (ANY /
+        ALL: the first solution; MIN / MAX: the best one found, the optimum when status is 0), and under MIN / MAX
+        `best` [K] int32, meaningful where solutions > 0.  An instance that stops at max_nodes under MIN / MAX keeps the
+        best found so far: an anytime answer."""
+        L = load_library()
+        n = self.n_vars
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        opt = ManyOptions(obj, 0, int(max_nodes))
+        bad = obj not in (0, 1) and (obj not in (2, 3) or self.objective != obj or self.objective_var < 0)
+        roots, K = self._many_roots(roots, bad, lambda ptr, count: check(
+            L.csgpu_solve_many_clauses(self._h, ptr, count, C.byref(opt), ptr, None, None, None)),
+            qualifies=self.qualifies_many_clauses())
+        buf = self._many_records(K, roots.device)
+        first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
+        best = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if obj in (2, 3) else None
+        check(L.csgpu_solve_many_clauses(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                                         first.data_ptr() if solutions and K else None,
+                                         best.data_ptr() if best is not None else None, _stream_ptr(stream)))
+        out = self._many_answer(buf, K, first)
+        if best is not None:
+            out["best"] = best[:K]
+        return out
+
+    def qualifies_many_clauses(self) -> bool:
+        """may solve_many_clauses run this model (finalized, kernel 6 planned, its LDS slices fit a CU)?"""
+        return bool(load_library().csgpu_model_qualifies_many_clauses(self._h))
+
+    def many_clauses_kernel(self):
+        """the cs_walk_clauses instantiation solve_many_clauses launches, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_symbol")
+
+    def many_clauses_waves(self, count: int) -> int:
+        """waves a solve_many_clauses of `count` instances launches"""
+        return int(load_library().csgpu_internal_many_clauses_waves(self._h, int(count)))
 
     def classify_many(self, roots, *, max_nodes, stream=None) -> torch.Tensor:
         """is the solution unique?  -> int8 [K] on the device: 0 no solution, 1 exactly one, 2 several, -1 undecided

@@ -393,6 +393,50 @@ int csgpu_solve_many_restarts(const csgpu_model *m, const csgpu_val *d_roots, co
  * width) */
 int32_t csgpu_many_value(uint32_t seed, uint32_t run, int32_t var, csgpu_val bounds, uint32_t j, int32_t flags);
 
+/* ---- many instances of one CLAUSE model in one call: a depth-first search per wavefront, also under MIN / MAX ----
+ * csgpu_solve_many for the models it refuses: `=`, `<`, disjunctions, expression trees, an objective -- the scheduling
+ * models with other release times, windows or deadlines per row.  Built on kernel 6 (csgpu_model_qualifies(m, 6): at
+ * most 512 clauses, resident in registers).  csgpu_many_options and csgpu_many_result are those of csgpu_solve_many;
+ * options->objective also takes 2 MIN and 3 MAX, on this entry only.
+ *
+ * The walk.  One wavefront takes an instance from its root row to its answer.
+ *   Root.       A row with lo > hi, or outside the model's root domains, gives CSGPU_MANY_BAD_ROOT and is not searched.
+ *               Otherwise the root node runs, a `var < 0` node of kernel 6: rounds over all clauses until nothing
+ *               changes.  An inconsistent root gives CSGPU_MANY_DONE with 0 nodes.  A root with every variable valued is
+ *               the one solution.
+ *   Branching.  The branching variable is the open variable with the smallest hi - lo, ties to the lowest index, over
+ *               all variables including "<obj>".  Values are tried in ascending order.  A child is the assignment
+ *               followed by the fixpoint.  A consistent child with open variables is entered at once; its parent is
+ *               pushed only if it has values left.  max_nodes is compared before a child is tried.
+ *   Counters.   nodes = children tried, cuts = inconsistent children, solutions = children with every variable valued,
+ *               props / root_props = kernel 6's props of the consistent children / of the root.
+ *   MIN / MAX.  Each instance has a private incumbent, none at the start, so its tree is deterministic.  Before a
+ *               child's fixpoint, and only once the instance has a solution, dom[obj] becomes the objective bound of
+ *               csgpu_objective_bound(objective, dom[obj], best): what kernel 6 does at node entry, so a frame popped
+ *               from the stack is bounded again when its next child is made.  If the bound empties dom[obj], the child
+ *               is a node and a cut.  A solution sets best to "<obj>"'s value and overwrites the instance's row in
+ *               d_solutions; the search goes on to the end of the tree.  CSGPU_MANY_DONE means the optimum is proven, or
+ *               that there is no solution.  CSGPU_MANY_LIMIT leaves the best found so far in d_best and d_solutions: an
+ *               anytime answer.
+ *   ANY / ALL.  Exactly csgpu_solve_many's meaning: ANY leaves at the first solution, and the row stored is the first
+ *               solution.  The model's "<obj>" variable, if it has one, is then an ordinary variable.
+ *   d_best      NULL, or [count] int32: written only for instances with at least one solution under MIN / MAX.
+ * Which models qualify (csgpu_model_qualifies_many_clauses): finalized, kernel 6 planned, and the per-wave LDS slice
+ * (n_vars * 8 + 16 bytes) times the four waves of a workgroup fits the 160 KiB of a CU.
+ * Workspace and tickets are the model's, shared with csgpu_solve_many: ONE call of the whole family in flight per
+ * model; a call may be queued behind another on the same stream without the host in between.  A frame holds absolute
+ * bounds; a wave has n_vars frames of (n_vars + 1) x 8 bytes, and a call launches min(count, resident waves) waves, fewer
+ * where their frames would pass 1 GiB.
+ * Errors before any HIP call, in csgpu_solve_many's order: null model / roots / results / options, count < 0,
+ * max_nodes <= 0 -> CSGPU_E_ARG; an objective other than 0-3, MIN / MAX on a model without an objective variable or
+ * with the other sense -> CSGPU_E_ARG; model not finalized -> CSGPU_E_STATE; more than 512 clauses, or slices that do
+ * not fit -> CSGPU_E_LIMIT, the message says which; count > 2^31 - 65 -> CSGPU_E_LIMIT.  count == 0 -> CSGPU_OK, nothing
+ * is launched. */
+int csgpu_model_qualifies_many_clauses(const csgpu_model *m);
+int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                             csgpu_many_result *d_results, int32_t *d_solutions /* NULL or [count][n_vars] */,
+                             int32_t *d_best /* NULL or [count] */, void *stream);
+
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */
 int csgpu_eval_batch(const csgpu_model *m, const csgpu_val *d_states, int32_t *d_truth, int64_t batch,

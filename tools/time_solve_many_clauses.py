@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""K instances of one clause model through Model.solve_many_clauses, and the SAME instances through the per-instance loop
+that was the only route for such models: one Search, reset and seeded per instance (the instance's root fixpoint, put,
+run), one after the other -- on a sample of the instances when all K would take minutes (the output says how many).
+Both routes run in this process after a warm-up, interleaved, so that a drift of the machine falls on both alike.
+
+Prints one JSON line: medians and ranges of both routes, instances/s and their ratio, what the call decided, and a
+seeded sample of the device's answers re-checked against the host walk (tests/many_walk_objective.py).  Under MIN / MAX
+the optimum of every DONE instance of the loop's sample is compared with the engine's as well.
+
+  python tools/time_solve_many_clauses.py --set schedule5_min [--count 4096] [--reps 5] [--loop-sample 128] [--check 16]
+  sets: the names of tests/many_clause_sets.py; the set's rows are repeated with other seeds up to --count."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from csolve_amd.solver import Search, solve_root  # noqa: E402
+
+
+def commit():
+    try:
+        return open(os.path.join(ROOT, "csolve_amd", "csrc", "build", "COMMIT")).read().strip()
+    except OSError:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+
+
+def spread(ts, scale=1e3):
+    return {"median": round(statistics.median(ts) * scale, 3), "min": round(min(ts) * scale, 3), "max": round(max(ts) * scale, 3),
+            "reps": len(ts)}
+
+
+def main():
+    import many_clause_sets as sets
+    import many_walk_objective as W
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--set", default="schedule5_min", choices=sorted(sets.SETS))
+    ap.add_argument("--count", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--loop-sample", type=int, default=128)
+    ap.add_argument("--check", type=int, default=16)
+    ap.add_argument("--seed", type=int, default=1)
+    args = ap.parse_args()
+    text, base, objective, budget = sets.build(args.set)
+    roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
+    count = len(roots)
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+    rng = np.random.default_rng(args.seed)
+    sample = np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
+    search = Search(model, 1 << 18, 1 << 14)
+    node = torch.tensor([[-1, 0, 0, 0]], dtype=torch.int32, device="cuda")
+
+    def many():
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = model.solve_many_clauses(dev, objective, max_nodes=budget)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    def loop():
+        total, bests = 0, {}
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for i in sample:
+            state, res = model.propagate(dev[i:i + 1], node)
+            if int(res[0, 0]) <= 0:  # inconsistent, or solved by the root node
+                continue
+            search.reset()
+            search.put(state)
+            st = search.run()
+            total += st["nodes"]
+            bests[int(i)] = (st["best"], st["solutions"])
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, total, bests
+
+    for _ in range(2):  # warm-up: code load, workspace, the engine's buffers
+        many()
+    loop()
+    many_times, loop_times = [], []
+    for _ in range(args.reps):
+        dt, out = many()
+        many_times.append(dt)
+        dt, loop_nodes, bests = loop()
+        loop_times.append(dt)
+    host = {k: v.cpu().numpy() for k, v in out.items() if torch.is_tensor(v)}
+
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    want = W.walk_many(text, roots[picks], objective, budget)
+    has = want["solutions"] > 0
+    ok = all((host[f][picks] == want[f]).all() for f in W.FIELDS) and bool((host["first"][picks][has] == want["first"][has]).all())
+    if objective in ("MIN", "MAX"):
+        ok = ok and bool((host["best"][picks][has] == want["best"][has]).all())
+        done = [i for i in bests if host["status"][i] == 0 and host["solutions"][i] > 0]
+        same_optimum = all(bests[i][0] == host["best"][i] for i in done)
+    else:
+        done, same_optimum = [], None
+
+    t_many, t_loop = statistics.median(many_times), statistics.median(loop_times)
+    many_rate, loop_rate = count / t_many, len(sample) / t_loop
+    print(json.dumps({
+        "tool": "time_solve_many_clauses", "commit": commit(), "command": " ".join(sys.argv), "set": args.set,
+        "objective": objective, "instances": count, "max_nodes": budget, "n_vars": model.n_vars, "clauses": model.n_clauses,
+        "kernel": model.many_clauses_kernel(), "waves": model.many_clauses_waves(count),
+        "status_counts": np.bincount(host["status"], minlength=3).tolist(), "nodes": int(host["nodes"].sum()),
+        "largest_tree": int(host["nodes"].max()), "solutions": int(host["solutions"].sum()),
+        "solve_many_clauses_ms": spread(many_times), "solve_many_clauses_instances_per_s": round(many_rate),
+        "solve_many_clauses_nodes_per_s": round(int(host["nodes"].sum()) / t_many),
+        "loop_instances": len(sample), "loop_nodes": loop_nodes, "loop_s": spread(loop_times, 1.0),
+        "loop_instances_per_s": round(loop_rate), "ratio_instances_per_s": round(many_rate / loop_rate, 1),
+        "optima_compared_with_the_engine": len(done), "same_optimum": same_optimum,
+        "oracle_checked": len(picks), "oracle_ok": bool(ok),
+    }))
+    return 0 if ok and same_optimum is not False else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
