@@ -102,7 +102,7 @@ struct cs_ctx {
   unsigned *mark;     /* LDS, next-round changed mask (events) or one flag word (sweeps) */
   int mark_is_flag;
   int fail, props, revisions;
-  int fail_var; /* a variable whose domain this lane saw become empty (-1: none / not attributable to one variable):
+  int fail_var; /* a variable whose domain this lane saw become empty (-1: none; <= -2: none, in tree -2 - fail_var):
                  * the reference bumps that variable's priority (propagate_term_confl, propagate.c:33-41) */
   /* trace (null unless the kernel was built with TRACE): which clause is being revised, and where narrowings are
    * recorded -- what the reference keeps as binding_t.clause on its trail (csolve.h:73-79) */
@@ -120,6 +120,14 @@ struct cs_ctx {
     if (!fail) record(v, 2, 0);
     fail = 1;
     fail_var = v;
+  }
+  /* a failure that empties no variable's interval: an expression tree's at a constant terminal or in a product's
+   * PROP_ERROR.  The trail names it as a failure at no variable (-1); the tree is kept, as fail_var = -2 - tree, so that
+   * the node's result can still name a variable of the clause that failed (cs_wave_fail_var) */
+  __device__ __forceinline__ void failed_in_tree(int tree) {
+    if (!fail) record(-1, 2, 0);
+    fail = 1;
+    fail_var = -2 - tree;
   }
 
   __device__ __forceinline__ void touched(int v) {
@@ -157,14 +165,27 @@ struct cs_ctx {
 };
 
 /* the variable a failed node reports in csgpu_result.rounds: the first lane that attributed its failure to a
- * variable, else a variable whose bounds have crossed in `dom`, else -1 */
-__device__ __forceinline__ int cs_wave_fail_var(const cs_ctx &cx, const cs_val *dom, int n, int lane) {
+ * variable, else a variable whose bounds have crossed in `dom`, else -- the failure is a tree's at a constant, which
+ * empties nothing (cs_ctx::failed_in_tree) -- the first variable of that tree in node order, else -1.  Runs once per
+ * failed node, after the fixpoint loop */
+__device__ __forceinline__ int cs_wave_fail_var(const cs_tables &T, const cs_ctx &cx, const cs_val *dom, int n, int lane) {
   const unsigned long long m = __ballot(cx.fail && cx.fail_var >= 0);
   if (m != 0ull) return __builtin_amdgcn_readlane(cx.fail_var, __builtin_ctzll(m));
   for (int v0 = 0; v0 < n; v0 += CS_WAVE) {
     const int v = v0 + lane;
     const unsigned long long c = __ballot(v < n && dom[v < n ? v : 0].lo > dom[v < n ? v : 0].hi);
     if (c != 0ull) return v0 + __builtin_ctzll(c);
+  }
+  const unsigned long long t = __ballot(cx.fail && cx.fail_var <= -2);
+  if (t != 0ull) {
+    const int tree = -2 - __builtin_amdgcn_readlane(cx.fail_var, __builtin_ctzll(t));
+    const int base = T.tree_off[tree], len = T.tree_off[tree + 1] - base;
+    for (int k0 = 0; k0 < len; k0 += CS_WAVE) {
+      const int k = k0 + lane;
+      const int4 nd = k < len ? T.tnode[base + k] : make_int4(-1, -1, 0, 0);
+      const unsigned long long c = __ballot(k < len && nd.x == CS_OP_VAR);
+      if (c != 0ull) return __builtin_amdgcn_readlane(nd.y, __builtin_ctzll(c));
+    }
   }
   return -1;
 }
@@ -326,7 +347,7 @@ __device__ inline void cs_tree_revise(const cs_tables &T, int tree, cs_ctx &cx, 
       break;
     case CS_OP_CONST: /* terminal without variable: only a conflict is observable; the trail names it as a failure
                        * at no variable (csolve_gpu.h: -1) */
-      if (n.y > w.hi || n.z < w.lo) cx.failed_at(-1);
+      if (n.y > w.hi || n.z < w.lo) cx.failed_in_tree(tree);
       break;
     case CS_OP_EQ: {
       cs_val lv = S.val[n.y], rv = S.val[n.z];
@@ -373,7 +394,7 @@ __device__ inline void cs_tree_revise(const cs_tables &T, int tree, cs_ctx &cx, 
           if (!cs_is_value(cv)) continue;
           const int c = cv.lo;
           if (((w.lo > 0 || w.hi < 0) && c == 0) || (cs_is_value(w) && c != 0 && (w.lo % c) != 0)) {
-            cx.failed_at(-1); /* PROP_ERROR of propagate_mul_lr: no variable emptied, the trail still ends in a failure */
+            cx.failed_in_tree(tree); /* PROP_ERROR of propagate_mul_lr: no variable emptied, the trail still ends in a failure */
             break;
           }
           if (c != 0) {
@@ -618,7 +639,7 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_propagate_events(cs_tables T, con
         open_vars += __popcll(__ballot(d.lo != d.hi));
       }
     } else {
-      rounds = cs_wave_fail_var(cx, dom, n, lane); /* an inconsistent node reports the failing variable here */
+      rounds = cs_wave_fail_var(T, cx, dom, n, lane); /* an inconsistent node reports the failing variable here */
     }
     if (lane == 0) {
       cs_node_out r;
@@ -705,7 +726,7 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_propagate_clause_rounds(cs_tables
         open_vars += __popcll(__ballot(d.lo != d.hi));
       }
     } else {
-      rounds = cs_wave_fail_var(cx, dom, n, lane); /* an inconsistent node reports the failing variable here */
+      rounds = cs_wave_fail_var(T, cx, dom, n, lane); /* an inconsistent node reports the failing variable here */
     }
     if (lane == 0) {
       cs_node_out r;

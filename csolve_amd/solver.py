@@ -207,6 +207,27 @@ class Model:
                                                    _stream_ptr(stream)))
         return states_out, results
 
+    def propagate_obj(self, states_in: torch.Tensor, nodes: torch.Tensor, obj_lo: int, obj_hi: int, stream=None):
+        """Batched propagate_clauses under an incumbent bound (csgpu_propagate_batch_obj): "<obj>" of every child is
+        intersected with [obj_lo, obj_hi] before the child is propagated, and if that moved a bound the clauses of
+        "<obj>" are propagated as well; (INT32_MIN, INT32_MAX) is no bound, and a model without an objective variable
+        ignores both.  Tensors and return values as propagate()."""
+        n = self.n_vars
+        obj_lo, obj_hi = int(obj_lo), int(obj_hi)
+        if not (-2**31 <= obj_lo <= 2**31 - 1 and -2**31 <= obj_hi <= 2**31 - 1):
+            raise ValueError("obj_lo and obj_hi are int32 values")
+        assert states_in.is_cuda and nodes.is_cuda, "device tensors required"
+        assert states_in.dtype == torch.int32 and nodes.dtype == torch.int32
+        assert states_in.is_contiguous() and nodes.is_contiguous()
+        assert states_in.shape[-2:] == (n, 2) and nodes.shape[-1] == 4
+        B = nodes.shape[0]
+        states_out = torch.empty((B, n, 2), dtype=torch.int32, device=nodes.device)
+        results = torch.empty((B, 4), dtype=torch.int32, device=nodes.device)
+        check(load_library().csgpu_propagate_batch_obj(self._h, states_in.data_ptr(), nodes.data_ptr(),
+                                                       states_out.data_ptr(), results.data_ptr(), B, obj_lo, obj_hi,
+                                                       _stream_ptr(stream)))
+        return states_out, results
+
     # ---- many instances of this model in one call (csgpu_solve_many) -------------------------------
     MANY_OBJECTIVES = {"ANY": 0, "ALL": 1, "MIN": 2, "MAX": 3}
 

@@ -64,7 +64,8 @@ typedef struct csgpu_node {
  * revisions = clause revisions performed, rounds = worklist rounds -- and for an INCONSISTENT node (status -1)
  * the index of a variable whose domain became empty, or -1 if the kernel does not attribute the failure (kernels
  * 1, 6, 7 do; the reference bumps that variable's priority, propagate_term_confl, propagate.c:33-41; which of
- * several emptied variables is reported depends on the revision order). */
+ * several emptied variables is reported depends on the revision order; where an expression tree fails at a constant
+ * and no domain is empty, kernels 1 and 6 report the first variable of that tree). */
 typedef struct csgpu_result {
   int32_t status, props, revisions, rounds;
 } csgpu_result;

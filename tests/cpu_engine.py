@@ -12,10 +12,21 @@ SPLIT_WIDTH = 256
 
 
 class OracleEngine:
-    def __init__(self, omodel, parents_per_iteration=4, shuffle_seed=None):
+    def __init__(self, omodel, parents_per_iteration=4, shuffle_seed=None, incumbent="immediate", lag=0):
         """shuffle_seed: permute the pool after every iteration with this seed -- the level kernels of the GPU engine
         (cs_step.hip.h) leave a frontier's survivors in an order that depends on timing, so two ranks that expand the same
-        root hold the same SET of open states in different orders"""
+        root hold the same SET of open states in different orders.
+        incumbent: "immediate" -- a solution bounds the very next child --, or "iteration", what the device engine does
+        (cs_expand_burst / cs_accept_block): all children of an iteration are bounded by the incumbent as it stood when
+        the iteration began, every true complete child counts as a solution, and `best` moves to the extreme of an
+        iteration's solutions at its end.  lag (with "iteration"): the solutions of iteration k bound the children of
+        iteration k + 1 + lag; 1 is the host-driven loop of the device engine (one_iteration reads an accept's results
+        only after the next iteration's fixpoints have been launched)."""
+        assert incumbent in ("immediate", "iteration") and lag >= 0 and (lag == 0 or incumbent == "iteration")
+        self.per_iteration = incumbent == "iteration"
+        self.lag = lag
+        self.waiting = []  # "iteration": the extremes of the last `lag` iterations' solutions, not yet in st["best"]
+        self.best_row = None  # "iteration": the first child, in child order, that attained `best`
         self.rng = None if shuffle_seed is None else np.random.default_rng(shuffle_seed)
         self.m = omodel
         self.orc = Oracle(omodel)
@@ -75,6 +86,7 @@ class OracleEngine:
             self.st["iterations"] += 1
             take = min(self.parents, len(self.pool))
             parents, self.pool = self.pool[-take:], self.pool[:-take]
+            mine = None  # "iteration": the first child of this iteration that attains the extreme of its solutions
             for state in parents:
                 width = (state[:, 1].astype(np.int64) - state[:, 0].astype(np.int64))
                 width[width == 0] = 1 << 40
@@ -99,6 +111,10 @@ class OracleEngine:
                         if self.orc_eval_true(out):
                             self.st["solutions"] += 1
                             self.found.append(out[:, 0].copy())
+                            if self.per_iteration:
+                                if self.obj_var >= 0 and self._better(int(out[self.obj_var, 0]), mine):
+                                    mine = out[:, 0].copy()
+                                continue
                             if self.objective == OBJ_MIN:
                                 self.st["best"] = min(self.st["best"], int(out[self.obj_var, 0]))
                             if self.objective == OBJ_MAX:
@@ -107,13 +123,34 @@ class OracleEngine:
                             self.complete_false += 1
                     else:
                         self.pool.append(out)
+            if self.per_iteration and self.obj_var >= 0:
+                self.waiting.append(mine)
+                if len(self.waiting) > self.lag:
+                    self._apply(self.waiting.pop(0))
             self.st["pool_peak"] = max(self.st["pool_peak"], len(self.pool))
             if self.rng is not None and len(self.pool) > 1:
                 order = self.rng.permutation(len(self.pool))
                 self.pool = [self.pool[i] for i in order]
+        while self.waiting:  # nothing is left waiting when a run ends (csgpu_search_run flushes the accept results)
+            self._apply(self.waiting.pop(0))
         self.st["pool"] = len(self.pool)
         self.st["done"] = int(not self.pool or (self.objective == OBJ_ANY and self.st["solutions"] > 0))
         return dict(self.st)
+
+    def _better(self, value, row):
+        """does `value` beat the objective value of `row` (None: no row yet) strictly"""
+        if row is None:
+            return True
+        return value < row[self.obj_var] if self.objective == OBJ_MIN else value > row[self.obj_var]
+
+    def _apply(self, row):
+        """an iteration's extreme solution becomes the incumbent if it beats it"""
+        if row is None:
+            return
+        value = int(row[self.obj_var])
+        if (self.objective == OBJ_MIN and value < self.st["best"]) or (self.objective == OBJ_MAX and value > self.st["best"]):
+            self.st["best"] = value
+            self.best_row = row
 
     @staticmethod
     def _middle(lo, hi):
