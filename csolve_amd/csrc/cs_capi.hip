@@ -75,6 +75,7 @@ struct cs_kernel_plan {
   cs_planned step_shave, step_packed, step_import;
   cs_planned dive[MANY_FAMILIES];  /* by MANY_*: all four or none; not among csgpu_internal_plan_symbol's families */
   cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
+  cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -992,6 +993,17 @@ static int plan_general(csgpu_model *m) {
           m->plan.walk.per_cu = occ;
         if (m->plan.walk.per_cu < 1) m->plan.walk.per_cu = 1;
       }
+      { /* cs_walk_resume: the same slices, its own registers */
+#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_resume<CPL, true> : (const void *)cs_walk_resume<CPL, false>)
+        const void *fn_ck = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
+#undef CS_PICKW
+        if ((rc = plan_kernel(&m->plan.walk_ck, fn_ck, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_ck, CS_BLOCK, m->plan.walk_ck.lds) == hipSuccess && occ >= 1 &&
+            occ < m->plan.walk_ck.per_cu)
+          m->plan.walk_ck.per_cu = occ;
+        if (m->plan.walk_ck.per_cu < 1) m->plan.walk_ck.per_cu = 1;
+      }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
   }
@@ -1578,7 +1590,12 @@ struct csgpu_many_checkpoints {
   cs_val *d_pool;
   unsigned long long *d_next; /* slots handed out since the last reset */
   int counted;                /* the model counts this pool among the objects that hold its device tables */
+  int kind;                   /* MANY_POOL_DIVE: of csgpu_many_checkpoints_create; MANY_POOL_WALK: of the clause one */
+  int *d_zero;                /* MANY_POOL_WALK: n_vars zeros, the offsets cs_dive_export adds to absolute bounds */
 };
+enum { MANY_POOL_DIVE, MANY_POOL_WALK };
+#define MANY_POOL_KIND "the checkpoint pool is of the other kind: csgpu_many_checkpoints_create makes the pools of csgpu_solve_many, " \
+                       "csgpu_many_clause_checkpoints_create those of csgpu_solve_many_clauses"
 
 extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count) {
   if (m == NULL || !m->finalized || m->plan.dive[MANY_PLAIN].fn == NULL || count < 1) return 0;
@@ -1631,6 +1648,7 @@ static int many_check_tail(const csgpu_model *m, int family, const csgpu_many_ch
     return set_err(CSGPU_E_LIMIT, MANY_NOT_QUALIFIED " (a pure != network of at most 256 variables whose dense pair table "
                                                      "fits LDS), which csgpu_solve_many is built on");
   if (ck != NULL && ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
+  if (ck != NULL && ck->kind != MANY_POOL_DIVE) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
   if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
   return CSGPU_OK;
 }
@@ -1707,22 +1725,28 @@ extern "C" size_t csgpu_many_checkpoint_bytes(const csgpu_model *m) {
   return (n + 1) * (n + 1) * sizeof(cs_val); /* the header frame, n - 1 stack frames at most, the current node */
 }
 
-extern "C" int csgpu_many_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out) {
+/* the pool of either kind, after the checks of its create call; `qualifies`: may the model's kernels of that kind run? */
+static int many_pool_create(const csgpu_model *m, int64_t capacity, int kind, int qualifies, const char *limit, size_t slot_bytes,
+                            csgpu_many_checkpoints **out) {
   if (m == NULL || out == NULL) return set_err(CSGPU_E_ARG, "null argument");
   if (capacity < 1) return set_err(CSGPU_E_ARG, "a checkpoint pool has at least one slot");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (m->plan.dive[MANY_CK].fn == NULL) return set_err(CSGPU_E_LIMIT, MANY_NOT_QUALIFIED ", which csgpu_solve_many is built on");
+  if (!qualifies) return set_err(CSGPU_E_LIMIT, "%s", limit);
   if (capacity > 0x7fffffff) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 1 slots");
   csgpu_many_checkpoints *ck = (csgpu_many_checkpoints *)calloc(1, sizeof *ck);
   if (ck == NULL) return set_err(CSGPU_E_LIMIT, "out of memory");
   ck->m = m;
   ck->capacity = capacity;
-  ck->slot_bytes = csgpu_many_checkpoint_bytes(m);
+  ck->slot_bytes = slot_bytes;
+  ck->kind = kind;
+  const size_t zero_bytes = (size_t)m->host->n_vars * sizeof(int);
   hipError_t e;
   if ((e = hipMalloc((void **)&ck->d_pool, (size_t)capacity * ck->slot_bytes)) != hipSuccess ||
       (e = hipMalloc((void **)&ck->d_next, sizeof *ck->d_next)) != hipSuccess ||
       (e = hipMemset(ck->d_pool, 0, (size_t)capacity * ck->slot_bytes)) != hipSuccess || /* no slot holds a checkpoint */
-      (e = hipMemset(ck->d_next, 0, sizeof *ck->d_next)) != hipSuccess) {
+      (e = hipMemset(ck->d_next, 0, sizeof *ck->d_next)) != hipSuccess ||
+      (kind == MANY_POOL_WALK && ((e = hipMalloc((void **)&ck->d_zero, zero_bytes)) != hipSuccess ||
+                                  (e = hipMemset(ck->d_zero, 0, zero_bytes)) != hipSuccess))) {
     csgpu_many_checkpoints_free(ck);
     return set_err(CSGPU_E_HIP, "checkpoint pool of %lld slots: %s", (long long)capacity, hipGetErrorString(e));
   }
@@ -1730,6 +1754,11 @@ extern "C" int csgpu_many_checkpoints_create(const csgpu_model *m, int64_t capac
   ck->counted = 1;
   *out = ck;
   return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out) {
+  return many_pool_create(m, capacity, MANY_POOL_DIVE, m != NULL && m->finalized && m->plan.dive[MANY_CK].fn != NULL,
+                          MANY_NOT_QUALIFIED ", which csgpu_solve_many is built on", csgpu_many_checkpoint_bytes(m), out);
 }
 
 extern "C" int csgpu_many_checkpoints_reset(csgpu_many_checkpoints *ck, void *stream) {
@@ -1743,6 +1772,7 @@ extern "C" void csgpu_many_checkpoints_free(csgpu_many_checkpoints *ck) {
   if (ck->counted) csgpu_internal_engine_ref(ck->m, -1);
   (void)hipFree(ck->d_pool);
   (void)hipFree(ck->d_next);
+  (void)hipFree(ck->d_zero);
   free(ck);
 }
 
@@ -1772,24 +1802,35 @@ extern "C" int csgpu_solve_many_resume(const csgpu_model *m, int64_t count, cons
   return many_ck_call(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
 }
 
-extern "C" int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
-                                            int64_t *count, void *stream) {
+/* the open subtrees of a slot of either kind: `head`, if wanted, receives the header's first two entries.  A clause pool
+ * holds absolute bounds: cs_dive_export adds the pool's zeros to them */
+static int many_pool_states(const csgpu_many_checkpoints *ck, int kind, int32_t slot, csgpu_val *d_states, int64_t cap,
+                            int64_t *count, cs_val *head2, void *stream) {
   if (ck == NULL || d_states == NULL || count == NULL || cap < 0) return set_err(CSGPU_E_ARG, "null argument");
+  if (ck->kind != kind) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
   if (slot < 0 || slot >= ck->capacity) return set_err(CSGPU_E_ARG, "no slot %d in a pool of %lld", slot, (long long)ck->capacity);
   const int n = ck->m->host->n_vars;
   const cs_val *base = ck->d_pool + (size_t)slot * ((size_t)n + 1) * ((size_t)n + 1);
-  cs_val head;
-  HIP_TRY(hipMemcpyAsync(&head, base, sizeof head, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  cs_val header[2];
+  HIP_TRY(hipMemcpyAsync(header, base, sizeof header, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  if (head.hi != CS_DIVE_CK_MAGIC || head.lo < 0 || head.lo >= n) return set_err(CSGPU_E_STATE, "slot %d holds no checkpoint", slot);
+  const cs_val head = header[0];
+  if (head.hi != (kind == MANY_POOL_WALK ? CS_WALK_CK_MAGIC : CS_DIVE_CK_MAGIC) || head.lo < 0 || head.lo >= n)
+    return set_err(CSGPU_E_STATE, "slot %d holds no checkpoint", slot);
+  if (head2 != NULL) { head2[0] = header[0]; head2[1] = header[1]; }
   *count = (int64_t)head.lo + 1;
   if (cap < *count)
     return set_err(CSGPU_E_LIMIT, "the checkpoint has %lld open subtrees, the buffer holds %lld", (long long)*count, (long long)cap);
-  const int *root_lo_d = ck->m->d_root_lo;
+  const int *root_lo_d = kind == MANY_POOL_WALK ? ck->d_zero : ck->m->d_root_lo;
   hipLaunchKernelGGL(cs_dive_export, dim3((unsigned)*count), dim3(CS_WAVE), 0, (hipStream_t)stream, n, root_lo_d, base,
                      (cs_val *)d_states);
   HIP_TRY(hipGetLastError());
   return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
+                                            int64_t *count, void *stream) {
+  return many_pool_states(ck, MANY_POOL_DIVE, slot, d_states, cap, count, NULL, stream);
 }
 
 /* ---- up to k solutions per instance (cs_dive_upto): csgpu_solve_many, stopped at the k-th solution, all k rows kept ---- */
@@ -1857,25 +1898,31 @@ extern "C" int csgpu_model_qualifies_many_clauses(const csgpu_model *m) {
   return m != NULL && m->finalized && m->plan.walk.fn != NULL;
 }
 
-extern "C" int csgpu_internal_many_clauses_symbol(const csgpu_model *m, char *buf, size_t len) {
+/* the instantiation of `k` by its dynamic symbol, for the tests ("" where the model plans none) */
+static int many_clauses_symbol(const csgpu_model *m, const cs_planned *k, const char *name, char *buf, size_t len) {
   if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
   buf[0] = '\0';
-  const void *fn = m->plan.walk.fn;
+  const void *fn = k->fn;
   if (fn == NULL) return CSGPU_OK;
   Dl_info info;
   if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
-    return set_err(CSGPU_E_STATE, "cs_walk_clauses: the kernel handle has no dynamic symbol");
-  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "cs_walk_clauses: symbol longer than the buffer");
+    return set_err(CSGPU_E_STATE, "%s: the kernel handle has no dynamic symbol", name);
+  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "%s: symbol longer than the buffer", name);
   strcpy(buf, info.dli_sname);
   return CSGPU_OK;
 }
 
+extern "C" int csgpu_internal_many_clauses_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_clauses_symbol(m, m != NULL ? &m->plan.walk : NULL, "cs_walk_clauses", buf, len);
+}
+extern "C" int csgpu_internal_many_clauses_resume_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_ck : NULL, "cs_walk_resume", buf, len);
+}
+
 /* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
  * whose frames fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices fit a CU) */
-extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64_t count) {
-  if (!csgpu_model_qualifies_many_clauses(m) || count < 1) return 0;
-  const cs_planned *k = &m->plan.walk;
+static int64_t many_clauses_waves(const csgpu_model *m, const cs_planned *k, int64_t count) {
   const size_t n = (size_t)m->host->n_vars;
   int64_t grid = (int64_t)m->n_cus * k->per_cu;
   const int64_t by_count = (count + k->waves - 1) / k->waves;
@@ -1886,12 +1933,20 @@ extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64
   return grid * k->waves;
 }
 
-extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
-                                        const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
-                                        int32_t *d_best, void *stream) {
-  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64_t count) {
+  if (!csgpu_model_qualifies_many_clauses(m) || count < 1) return 0;
+  return many_clauses_waves(m, &m->plan.walk, count);
+}
+
+/* The one path of the three entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
+ * has a pool and slot numbers and launches cs_walk_resume; `resume` (pooled, and no roots): the instances go on in their
+ * slots, so the call needs no workspace. */
+static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                             csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best, int pooled,
+                             csgpu_many_checkpoints *ck, int32_t *d_slots, int resume, void *stream) {
+  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || options == NULL;
   int rc;
-  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance"))) return rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, pooled ? "slice" : "instance"))) return rc;
   const int objective = options->objective;
   if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
     return set_err(CSGPU_E_ARG, "no objective %d", objective);
@@ -1911,13 +1966,18 @@ extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d
                                   "workgroup, more than the 160 KiB of a CU", (int)m->host->n_vars, m->plan.rounds.lds, CS_WAVES_PER_BLOCK);
   }
   if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  if (pooled) {
+    if (ck == NULL || d_slots == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
+    if (ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
+    if (ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  }
   if (count == 0) return CSGPU_OK;
   csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = &m->plan.walk;
+  const cs_planned *k = pooled ? &m->plan.walk_ck : &m->plan.walk;
   const int n = m->host->n_vars;
-  const int64_t waves = csgpu_internal_many_clauses_waves(m, count);
+  const int64_t waves = many_clauses_waves(m, k, count);
   const int frames = n; /* at most n - 1 pushed frames and the current node's */
-  if ((rc = many_workspace(mm, waves, frames))) return rc;
+  if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
   cs_walk_io io;
   io.roots = (const cs_val *)d_roots;
   io.root_dom = m->d_walk_root;
@@ -1929,13 +1989,74 @@ extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d
   io.results = (cs_dive_result *)d_results;
   io.solutions = d_solutions;
   io.best = io.sense != 0 ? d_best : NULL;
-  io.stack = (cs_val *)mm->d_many_stack;
+  io.stack = resume ? NULL : (cs_val *)mm->d_many_stack;
   io.frames = frames;
   io.tickets = mm->d_many_tickets;
+  cs_walk_ck wk;
+  wk.pool = pooled ? ck->d_pool : NULL;
+  wk.next = pooled ? ck->d_next : NULL;
+  wk.capacity = pooled ? (int)ck->capacity : 0;
+  wk.resume = resume;
+  wk.code = objective;
+  wk.slots = d_slots;
   cs_tables tab = m->tab;
-  void *args[] = { &tab, &io };
+  void *args[] = { &tab, &io, &wk }; /* cs_walk_clauses takes the first two */
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
+}
+
+extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                        const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                        int32_t *d_best, void *stream) {
+  return many_clauses_call(m, d_roots, count, options, d_results, d_solutions, d_best, 0, NULL, NULL, 0, stream);
+}
+
+/* ---- clause checkpoints: csgpu_solve_many_clauses in slices (cs_walk_resume) ---- */
+
+/* does the model run the cs_walk_* kernels?  What finalize planned; before finalize, the same rules on the host tables
+ * (csgpu_model_build_tables) as they stand */
+static int many_clauses_qualifies(const csgpu_model *m) {
+  if (m->finalized) return m->plan.walk.fn != NULL;
+  if (m->img == NULL) return 0;
+  const size_t slice = ((size_t)m->host->n_vars * sizeof(cs_val) + 16 + 15) & ~(size_t)15;
+  return m->img->n_clauses > 0 && m->img->n_clauses <= 8 * CS_WAVE && slice * CS_WAVES_PER_BLOCK <= CS_CU_LDS;
+}
+
+extern "C" size_t csgpu_many_clause_checkpoint_bytes(const csgpu_model *m) {
+  if (m == NULL || !many_clauses_qualifies(m)) return 0;
+  const size_t n = (size_t)m->host->n_vars;
+  return (n + 1) * (n + 1) * sizeof(cs_val); /* the header frame, n - 1 pushed frames at most, the current node */
+}
+
+extern "C" int csgpu_many_clause_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out) {
+  return many_pool_create(m, capacity, MANY_POOL_WALK, csgpu_model_qualifies_many_clauses(m),
+                          "model does not qualify for csgpu_solve_many_clauses (kernel 6 planned, its LDS slices fit a CU)",
+                          csgpu_many_clause_checkpoint_bytes(m), out);
+}
+
+extern "C" int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                     const csgpu_many_options *options, csgpu_many_result *d_results,
+                                                     int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
+                                                     int32_t *d_slots, void *stream) {
+  return many_clauses_call(m, d_roots, count, options, d_results, d_solutions, d_best, 1, ck, d_slots, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                               csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                               csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
+  return many_clauses_call(m, NULL, count, options, d_results, d_solutions, d_best, 1, ck, d_slots, 1, stream);
+}
+
+extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
+                                                   int64_t *count, int32_t *best, int32_t *have_best, void *stream) {
+  if (best == NULL || have_best == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  cs_val header[2] = { cs_interval(0, 0), cs_interval(0, 0) };
+  const int rc = many_pool_states(ck, MANY_POOL_WALK, slot, d_states, cap, count, header, stream);
+  if (rc == CSGPU_OK || rc == CSGPU_E_LIMIT) { /* (a buffer too small: *count and the incumbent are set all the same) */
+    *best = header[1].lo;
+    *have_best = header[1].hi & 1;
+  }
+  return rc;
 }
 
 #ifdef CS_SHAVE_TIMELINE

@@ -67,6 +67,8 @@ int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count);
 /* the same for cs_walk_clauses (csgpu_solve_many_clauses) */
 int csgpu_internal_many_clauses_symbol(const csgpu_model *m, char *buf, size_t len);
 int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64_t count);
+/* and for cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume) */
+int csgpu_internal_many_clauses_resume_symbol(const csgpu_model *m, char *buf, size_t len);
 
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */
 typedef struct csgpu_step_launch {

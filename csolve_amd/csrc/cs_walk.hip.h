@@ -34,7 +34,25 @@
  *
  * Work distribution: cs_dive_shave's tickets (cs_dive.hip.h), on the model's same counters; the wave barrier in front of
  * the draw is the one cs_dive_body.hip.h explains.  Device memory is written by plain vector stores and the one ticket
- * atomic. */
+ * atomic.
+ *
+ * Checkpoints (cs_walk_resume, csgpu_solve_many_clauses_checkpointed / _resume): the same loop -- both kernels include
+ * cs_walk_body.hip.h, with CS_WALK_CK 0 and 1 -- as cs_dive_resume is cs_dive_shave's.  An instance that stops at its
+ * budget draws a slot of a pool (one relaxed atomic add by lane 0) and leaves there what the loop needs to go on at "try
+ * value nv of variable bv on the node in frame depth":
+ *
+ *   slot = n + 1 frames of n + 1 entries (8 bytes each), bounds absolute as in the workspace
+ *   frame 0           the header, lane 0's: entry 0 = {depth, CS_WALK_CK_MAGIC}, entry 1 = {best, have_best | objective << 1}
+ *   frame 1 + d       pushed frame d (d < depth), exactly as in the workspace: the row, then {variable, next value}
+ *   frame 1 + depth   the current node as it was entered, with {bv, nv} behind it
+ *
+ * The counters go to the instance's record as always and are read back from there; the incumbent travels in the header,
+ * so a stopped MIN / MAX walk keeps the bound that makes the rest of its tree small.  A fresh instance walks in the wave's
+ * workspace slice and copies its depth + 1 frames out when it stops (every lane the entries it wrote itself); a resumed
+ * one uses the frames of its slot AS its stack, reads the current node back from frame depth (root = false, fresh =
+ * false), and when it stops again writes only the header and {bv, nv}.  A resume launch needs no workspace.  The budget
+ * of a resumed instance counts the nodes of this launch.  The header's objective must be the call's: a checkpoint made
+ * under ALL has no incumbent to go on with under MIN, and one made under ANY would never have been written. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
 
@@ -60,166 +78,29 @@ struct cs_walk_io {
 
 template <int CPL, bool HAS_TREE>
 __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk_io io) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
-  const int lane = threadIdx.x & (CS_WAVE - 1);
-  const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wave_global = (int)blockIdx.x * CS_WAVES_PER_BLOCK + wave_in_block;
-  const int n = T.n_vars;
-  const size_t slice_al = ((size_t)n * sizeof(cs_val) + 16 + 15) & ~(size_t)15;
-  cs_val *dom = (cs_val *)(cs_lds + wave_in_block * slice_al);
-  unsigned *flag = (unsigned *)(dom + n); /* [0]: something changed this round */
+#define CS_WALK_CK 0
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_CK
+}
 
-  int4 rec[CPL], lit0[CPL], lit1[CPL];
-#pragma unroll
-  for (int q = 0; q < CPL; q++) {
-    const int c = lane + q * CS_WAVE;
-    rec[q] = c < T.n_clauses ? T.clause_by_kind[c] : make_int4(CS_CL_SKIP, 0, 0, 0);
-    lit0[q] = rec[q].x == CS_CL_OR2 ? T.lit[rec[q].y] : make_int4(0, 0, 0, 0);
-    lit1[q] = rec[q].x == CS_CL_OR2 ? T.lit[rec[q].y + 1] : make_int4(0, 0, 0, 0);
-  }
+#define CS_WALK_CK_MAGIC 0x77636b70 /* header entry 0 .hi of a slot that holds a clause checkpoint (not CS_DIVE_CK_MAGIC) */
 
-  const int nsh = (int)gridDim.x < CS_DIVE_SHARDS ? (int)gridDim.x : CS_DIVE_SHARDS;
-  const int shard = (int)(blockIdx.x % nsh);
-  const unsigned count_x = io.count > shard ? (unsigned)((io.count - 1 - shard) / nsh + 1) : 0u; /* instances of this shard */
-  const unsigned waves_x = (unsigned)((((int)gridDim.x - 1 - shard) / nsh + 1) * CS_WAVES_PER_BLOCK);
-  unsigned *my_ticket = io.tickets + (size_t)shard * CS_DIVE_TICKET_STRIDE;
-  const size_t fstride = (size_t)n + 1;
-  cs_val *const wave_stack = io.stack + (size_t)wave_global * (size_t)io.frames * fstride;
+/* the checkpoint pool and the slot numbers of a call (cs_walk_resume) */
+struct cs_walk_ck {
+  cs_val *pool;             /* [capacity][n + 1][n + 1] */
+  unsigned long long *next; /* slots handed out since the last reset (it counts on past capacity) */
+  int capacity;
+  int resume;               /* 0: fresh instances from io.roots; 1: instance i goes on from slot slots[i] */
+  int code;                 /* the call's objective, 0 ANY .. 3 MAX: a checkpoint goes on under the one it was made under */
+  int *slots;               /* [count]: the slot of an instance stopped with a checkpoint, else -1 */
+};
 
-  for (;;) {
-    /* the wave meets here before lane 0 draws (cs_dive_body.hip.h: without it the launch never ends) */
-    __builtin_amdgcn_wave_barrier();
-    unsigned t = 0u;
-    if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-    if (t == count_x + waves_x - 1u && lane == 0) __hip_atomic_store(my_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t >= count_x) break;
-    const int inst = (int)t * nsh + shard;
-    const size_t rrow = (size_t)inst * (size_t)n;
-
-    /* the root row, into the LDS slice */
-    bool bad_l = false;
-    for (int v = lane; v < n; v += CS_WAVE) {
-      const cs_val d = io.roots[rrow + v], r = io.root_dom[v];
-      bad_l = bad_l || d.lo > d.hi || d.lo < r.lo || d.hi > r.hi;
-      dom[v] = d;
-    }
-    int status = 0 /* CSGPU_MANY_DONE */, root_props = 0;
-    long long nodes = 0, cuts = 0, sols = 0, props = 0; /* scalars */
-    int acc_props = 0;                                  /* per lane, added to props every 64 nodes */
-    int best = 0;
-    bool have_best = false;
-
-    if (__ballot(bad_l) != 0ull) {
-      status = 2; /* CSGPU_MANY_BAD_ROOT */
-    } else {
-      /* One loop for the root node and every child, so that the rounds stand in the kernel once.  `root`: the node in
-       * the slice is the root row itself, nothing is assigned and no node is counted.  f: the current node's frame. */
-      int depth = 0, bv = 0, nv = 0;
-      bool root = true, fresh = true; /* fresh: the slice holds the current node as it was entered */
-      cs_val *f = wave_stack;
-      for (;;) {
-        depth = __builtin_amdgcn_readfirstlane(depth);
-        bv = __builtin_amdgcn_readfirstlane(bv);
-        nv = __builtin_amdgcn_readfirstlane(nv);
-        bool last = false;
-        if (!root) {
-          if (nodes >= io.max_nodes) { status = 1; /* CSGPU_MANY_LIMIT */ break; }
-          if (!fresh) {
-            for (int v = lane; v < n; v += CS_WAVE) dom[v] = f[v];
-            cs_wave_sync();
-          }
-          last = nv == __builtin_amdgcn_readfirstlane(dom[bv].hi);
-          cs_wave_sync();
-          if (lane == 0) {
-            dom[bv] = cs_interval(nv, nv); /* the assignment: not counted in PROPS */
-            if (have_best) dom[io.obj_var] = cs_objective_bound(io.sense, dom[io.obj_var], best);
-          }
-        }
-        cs_wave_sync();
-
-#include "cs_rounds_body.hip.h"
-        (void)rounds;
-
-        /* the open variables of a consistent node, and this lane's candidate for the branching variable */
-        int open_vars = 0;
-        unsigned kw = 0xffffffffu, kv = 0xffffffffu;
-        if (!failed) {
-          for (int v0 = 0; v0 < n; v0 += CS_WAVE) { /* uniform trips: the ballot counts every lane */
-            const int v = v0 + lane;
-            const cs_val d = v < n ? dom[v] : cs_value(0);
-            const bool open = d.lo != d.hi;
-            const unsigned w = (unsigned)d.hi - (unsigned)d.lo;
-            if (open && w < kw) { kw = w; kv = (unsigned)v; }
-            open_vars += __popcll(__ballot(open));
-          }
-        }
-        bool descend = false;
-        const bool at_root = root;
-        if (root) {
-          if (failed) break; /* an inconsistent root: DONE, no node, no solution */
-          root_props = cs_wave_sum(cx.props);
-          root = false;
-          descend = open_vars != 0;
-        } else {
-          nodes++;
-          if (failed) {
-            cuts++;
-          } else {
-            acc_props += cx.props; /* consistent children only: kernel 6's props */
-            descend = open_vars != 0;
-          }
-          if ((nodes & 63) == 0) { props += cs_wave_sum(acc_props); acc_props = 0; }
-        }
-        if (!failed && open_vars == 0) { /* every variable valued: a solution (the root row itself may be the one) */
-          sols++;
-          if (io.sense != 0) {
-            best = __builtin_amdgcn_readfirstlane(dom[io.obj_var].lo);
-            have_best = true;
-          }
-          if ((sols == 1 || io.sense != 0) && io.solutions != nullptr)
-            for (int v = lane; v < n; v += CS_WAVE) io.solutions[rrow + v] = dom[v].lo;
-          if (!io.all || at_root) break; /* ANY, or the root node was the one solution */
-        }
-        if (descend) {
-          if (!at_root && !last) { /* the parent comes back for its next value */
-            if (lane == 0) f[n] = cs_interval(bv, nv + 1);
-            depth++;
-            f += fstride;
-          }
-          if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames = n): never write past the slice */
-          for (int v = lane; v < n; v += CS_WAVE) f[v] = dom[v];
-          const unsigned wmin = cs_wave_min_u32(kw);
-          bv = (int)cs_wave_min_u32(kw == wmin ? kv : 0xffffffffu);
-          /* cannot happen (an open variable exists): never index past the node */
-          if ((unsigned)bv >= (unsigned)n) { status = 1; break; }
-          nv = __builtin_amdgcn_readfirstlane(dom[bv].lo);
-          fresh = true;
-        } else if (last) { /* the node's values are used up */
-          if (depth == 0) break;
-          depth--;
-          f -= fstride;
-          cs_val meta = cs_interval(0, 0);
-          if (lane == 0) meta = f[n];
-          bv = __builtin_amdgcn_readfirstlane(meta.lo);
-          nv = __builtin_amdgcn_readfirstlane(meta.hi);
-          fresh = false;
-        } else {
-          nv = nv + 1;
-          fresh = false;
-        }
-      }
-    }
-    props += cs_wave_sum(acc_props);
-    if (lane == 0) {
-      cs_dive_result res;
-      res.status = status; res.root_props = root_props;
-      res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
-      io.results[inst] = res;
-      if (have_best && io.best != nullptr) io.best[inst] = best;
-    }
-    cs_wave_sync(); /* the next instance's root row goes into the slice only after every lane has left this one */
-  }
+/* the same with checkpoints: fresh instances (ck.resume == 0) or the instances of ck.slots going on */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_resume(cs_tables T, cs_walk_io io, cs_walk_ck ck) {
+#define CS_WALK_CK 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_CK
 }
 
 #endif

@@ -1,0 +1,267 @@
+/* cs_walk_body.hip.h -- the body of the two kernels of cs_walk.hip.h, which includes it inside each of them under one
+ * switch:              CS_WALK_CK
+ *   cs_walk_clauses        0        csgpu_solve_many_clauses
+ *   cs_walk_resume         1        one more argument, `ck`: the pool and the slots of the call
+ * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of the switch stands under its `#if`, so the kernel
+ * that defines it 0 sees the text it saw before the switch was there and compiles to the same instructions.
+ * CS_WALK_CK: an instance that stops at its budget leaves its frames, its current node, {bv, nv} and its incumbent in a
+ * slot of the pool (the layout is in cs_walk.hip.h); with ck.resume the instances of ck.slots go on in their slots, which
+ * are then their stacks.  New per-instance state is scalars only: slot, kept, depth0, nodes0, resumed, stack. */
+  extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
+  const int lane = threadIdx.x & (CS_WAVE - 1);
+  const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wave_global = (int)blockIdx.x * CS_WAVES_PER_BLOCK + wave_in_block;
+  const int n = T.n_vars;
+  const size_t slice_al = ((size_t)n * sizeof(cs_val) + 16 + 15) & ~(size_t)15;
+  cs_val *dom = (cs_val *)(cs_lds + wave_in_block * slice_al);
+  unsigned *flag = (unsigned *)(dom + n); /* [0]: something changed this round */
+
+  int4 rec[CPL], lit0[CPL], lit1[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; q++) {
+    const int c = lane + q * CS_WAVE;
+    rec[q] = c < T.n_clauses ? T.clause_by_kind[c] : make_int4(CS_CL_SKIP, 0, 0, 0);
+    lit0[q] = rec[q].x == CS_CL_OR2 ? T.lit[rec[q].y] : make_int4(0, 0, 0, 0);
+    lit1[q] = rec[q].x == CS_CL_OR2 ? T.lit[rec[q].y + 1] : make_int4(0, 0, 0, 0);
+  }
+
+  const int nsh = (int)gridDim.x < CS_DIVE_SHARDS ? (int)gridDim.x : CS_DIVE_SHARDS;
+  const int shard = (int)(blockIdx.x % nsh);
+  const unsigned count_x = io.count > shard ? (unsigned)((io.count - 1 - shard) / nsh + 1) : 0u; /* instances of this shard */
+  const unsigned waves_x = (unsigned)((((int)gridDim.x - 1 - shard) / nsh + 1) * CS_WAVES_PER_BLOCK);
+  unsigned *my_ticket = io.tickets + (size_t)shard * CS_DIVE_TICKET_STRIDE;
+  const size_t fstride = (size_t)n + 1;
+  cs_val *const wave_stack = io.stack + (size_t)wave_global * (size_t)io.frames * fstride;
+
+  for (;;) {
+    /* the wave meets here before lane 0 draws (cs_dive_body.hip.h: without it the launch never ends) */
+    __builtin_amdgcn_wave_barrier();
+    unsigned t = 0u;
+    if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+    if (t == count_x + waves_x - 1u && lane == 0) __hip_atomic_store(my_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t >= count_x) break;
+    const int inst = (int)t * nsh + shard;
+    const size_t rrow = (size_t)inst * (size_t)n;
+
+#if CS_WALK_CK
+    /* the instance's slot (-1: none yet), the slot a checkpoint was written to in this launch, the stack the instance
+     * walks on and, resuming, the checkpoint's depth and incumbent */
+    int slot = -1, kept = -1, depth0 = 0, best0 = 0;
+    bool resumed = false, have_best0 = false;
+    cs_val *stack = wave_stack;
+    if (ck.resume) {
+      slot = __builtin_amdgcn_readfirstlane(ck.slots[inst]);
+      if (slot < 0) continue; /* not stopped, or stopped without a checkpoint: nothing of it is written */
+      cs_val head = cs_interval(-1, 0), inc = cs_interval(0, -2);
+      if (slot < ck.capacity) { /* compared before it is read; the two header entries, nothing else of the slot yet */
+        const cs_val *base = ck.pool + (size_t)slot * (fstride * fstride);
+        head = base[0];
+        inc = base[1];
+      }
+      depth0 = __builtin_amdgcn_readfirstlane(head.lo);
+      const int word = __builtin_amdgcn_readfirstlane(inc.hi); /* have_best | objective code << 1 */
+      if (depth0 < 0 || depth0 >= n || __builtin_amdgcn_readfirstlane(head.hi) != CS_WALK_CK_MAGIC || (word >> 1) != ck.code) {
+        if (lane == 0) io.results[inst].status = 3; /* CSGPU_MANY_BAD_SLOT */
+        continue;
+      }
+      resumed = true;
+      best0 = __builtin_amdgcn_readfirstlane(inc.lo);
+      have_best0 = (word & 1) != 0;
+      stack = ck.pool + (size_t)slot * (fstride * fstride) + fstride;
+    }
+#endif
+    /* the root row, into the LDS slice */
+    bool bad_l = false;
+#if CS_WALK_CK
+    if (!resumed)
+#endif
+    for (int v = lane; v < n; v += CS_WAVE) {
+      const cs_val d = io.roots[rrow + v], r = io.root_dom[v];
+      bad_l = bad_l || d.lo > d.hi || d.lo < r.lo || d.hi > r.hi;
+      dom[v] = d;
+    }
+    int status = 0 /* CSGPU_MANY_DONE */, root_props = 0;
+    long long nodes = 0, cuts = 0, sols = 0, props = 0; /* scalars */
+    int acc_props = 0;                                  /* per lane, added to props every 64 nodes */
+    int best = 0;
+    bool have_best = false;
+#if CS_WALK_CK
+    long long nodes0 = 0; /* the nodes of earlier launches: the budget counts those of this one */
+    if (resumed) {        /* the counters go on from the instance's record, the incumbent from the header */
+      const cs_dive_result *was = io.results + inst;
+      root_props = __builtin_amdgcn_readfirstlane(was->root_props);
+      nodes0 = cs_dive_uniform(was->nodes);
+      cuts = cs_dive_uniform(was->cuts);
+      props = cs_dive_uniform(was->props);
+      sols = cs_dive_uniform(was->solutions);
+      nodes = nodes0;
+      best = best0;
+      have_best = have_best0;
+    }
+#endif
+
+    if (__ballot(bad_l) != 0ull) {
+      status = 2; /* CSGPU_MANY_BAD_ROOT */
+    } else {
+      /* One loop for the root node and every child, so that the rounds stand in the kernel once.  `root`: the node in
+       * the slice is the root row itself, nothing is assigned and no node is counted.  f: the current node's frame. */
+      int depth = 0, bv = 0, nv = 0;
+      bool root = true, fresh = true; /* fresh: the slice holds the current node as it was entered */
+      cs_val *f = wave_stack;
+#if CS_WALK_CK
+      if (resumed) { /* "try value nv of variable bv on the node in frame depth0", which is read into the slice */
+        depth = depth0;
+        f = stack + (size_t)depth0 * fstride;
+        cs_val meta = cs_interval(0, 0);
+        if (lane == 0) meta = f[n];
+        bv = __builtin_amdgcn_readfirstlane(meta.lo);
+        nv = __builtin_amdgcn_readfirstlane(meta.hi);
+        /* cannot happen (the kernel wrote the slot): never index past the node.  As every bad slot, the status alone */
+        if ((unsigned)bv >= (unsigned)n) {
+          if (lane == 0) io.results[inst].status = 3; /* CSGPU_MANY_BAD_SLOT */
+          continue;
+        }
+        root = false;
+        fresh = false;
+      }
+#endif
+      for (;;) {
+        depth = __builtin_amdgcn_readfirstlane(depth);
+        bv = __builtin_amdgcn_readfirstlane(bv);
+        nv = __builtin_amdgcn_readfirstlane(nv);
+        bool last = false;
+        if (!root) {
+#if CS_WALK_CK
+          if (nodes - nodes0 >= io.max_nodes) {
+            status = 1; /* CSGPU_MANY_LIMIT */
+            /* leave a checkpoint, if the pool has a slot */
+            if (!resumed) {
+              unsigned long long drawn = 0ull;
+              if (lane == 0) drawn = __hip_atomic_fetch_add(ck.next, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              const unsigned dlo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)drawn);
+              const unsigned dhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(drawn >> 32));
+              slot = dhi == 0u && dlo < (unsigned)ck.capacity ? (int)dlo : -1;
+            }
+            if (depth >= n) slot = -1; /* cannot happen (at most n frames in use): never write past the slot */
+            if (slot >= 0) {
+              cs_val *base = ck.pool + (size_t)slot * (fstride * fstride);
+              cs_val *frames = base + fstride;
+              if (!resumed) { /* the frames in use and the current node's, every lane the entries it wrote */
+                for (int d = 0; d <= depth; d++) {
+                  const cs_val *src = wave_stack + (size_t)d * fstride;
+                  cs_val *dst = frames + (size_t)d * fstride;
+                  for (int v = lane; v < n; v += CS_WAVE) dst[v] = src[v];
+                  if (lane == 0 && d < depth) dst[n] = src[n];
+                }
+              }
+              if (lane == 0) {
+                frames[(size_t)depth * fstride + n] = cs_interval(bv, nv);
+                base[0] = cs_interval(depth, CS_WALK_CK_MAGIC);
+                base[1] = cs_interval(best, (have_best ? 1 : 0) | (ck.code << 1));
+              }
+            }
+            kept = slot;
+            break;
+          }
+#else
+          if (nodes >= io.max_nodes) { status = 1; /* CSGPU_MANY_LIMIT */ break; }
+#endif
+          if (!fresh) {
+            for (int v = lane; v < n; v += CS_WAVE) dom[v] = f[v];
+            cs_wave_sync();
+          }
+          last = nv == __builtin_amdgcn_readfirstlane(dom[bv].hi);
+          cs_wave_sync();
+          if (lane == 0) {
+            dom[bv] = cs_interval(nv, nv); /* the assignment: not counted in PROPS */
+            if (have_best) dom[io.obj_var] = cs_objective_bound(io.sense, dom[io.obj_var], best);
+          }
+        }
+        cs_wave_sync();
+
+#include "cs_rounds_body.hip.h"
+        (void)rounds;
+
+        /* the open variables of a consistent node, and this lane's candidate for the branching variable */
+        int open_vars = 0;
+        unsigned kw = 0xffffffffu, kv = 0xffffffffu;
+        if (!failed) {
+          for (int v0 = 0; v0 < n; v0 += CS_WAVE) { /* uniform trips: the ballot counts every lane */
+            const int v = v0 + lane;
+            const cs_val d = v < n ? dom[v] : cs_value(0);
+            const bool open = d.lo != d.hi;
+            const unsigned w = (unsigned)d.hi - (unsigned)d.lo;
+            if (open && w < kw) { kw = w; kv = (unsigned)v; }
+            open_vars += __popcll(__ballot(open));
+          }
+        }
+        bool descend = false;
+        const bool at_root = root;
+        if (root) {
+          if (failed) break; /* an inconsistent root: DONE, no node, no solution */
+          root_props = cs_wave_sum(cx.props);
+          root = false;
+          descend = open_vars != 0;
+        } else {
+          nodes++;
+          if (failed) {
+            cuts++;
+          } else {
+            acc_props += cx.props; /* consistent children only: kernel 6's props */
+            descend = open_vars != 0;
+          }
+          if ((nodes & 63) == 0) { props += cs_wave_sum(acc_props); acc_props = 0; }
+        }
+        if (!failed && open_vars == 0) { /* every variable valued: a solution (the root row itself may be the one) */
+          sols++;
+          if (io.sense != 0) {
+            best = __builtin_amdgcn_readfirstlane(dom[io.obj_var].lo);
+            have_best = true;
+          }
+          if ((sols == 1 || io.sense != 0) && io.solutions != nullptr)
+            for (int v = lane; v < n; v += CS_WAVE) io.solutions[rrow + v] = dom[v].lo;
+          if (!io.all || at_root) break; /* ANY, or the root node was the one solution */
+        }
+        if (descend) {
+          if (!at_root && !last) { /* the parent comes back for its next value */
+            if (lane == 0) f[n] = cs_interval(bv, nv + 1);
+            depth++;
+            f += fstride;
+          }
+          if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames = n): never write past the slice */
+          for (int v = lane; v < n; v += CS_WAVE) f[v] = dom[v];
+          const unsigned wmin = cs_wave_min_u32(kw);
+          bv = (int)cs_wave_min_u32(kw == wmin ? kv : 0xffffffffu);
+          /* cannot happen (an open variable exists): never index past the node */
+          if ((unsigned)bv >= (unsigned)n) { status = 1; break; }
+          nv = __builtin_amdgcn_readfirstlane(dom[bv].lo);
+          fresh = true;
+        } else if (last) { /* the node's values are used up */
+          if (depth == 0) break;
+          depth--;
+          f -= fstride;
+          cs_val meta = cs_interval(0, 0);
+          if (lane == 0) meta = f[n];
+          bv = __builtin_amdgcn_readfirstlane(meta.lo);
+          nv = __builtin_amdgcn_readfirstlane(meta.hi);
+          fresh = false;
+        } else {
+          nv = nv + 1;
+          fresh = false;
+        }
+      }
+    }
+    props += cs_wave_sum(acc_props);
+    if (lane == 0) {
+      cs_dive_result res;
+      res.status = status; res.root_props = root_props;
+      res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
+      io.results[inst] = res;
+      if (have_best && io.best != nullptr) io.best[inst] = best;
+#if CS_WALK_CK
+      ck.slots[inst] = kept;
+#endif
+    }
+    cs_wave_sync(); /* the next instance's root row goes into the slice only after every lane has left this one */
+  }

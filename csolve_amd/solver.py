@@ -372,14 +372,17 @@ class Model:
             out["restarts"] = count[:K]
         return out
 
-    def solve_many_clauses(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None) -> dict:
+    def solve_many_clauses(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
         """solve_many for clause models (csgpu_solve_many_clauses: `=`, `<`, disjunctions, expression trees; the model
         must satisfy qualifies_many_clauses()), a depth-first search per wavefront on kernel 6's fixpoint, also under
         "MIN" / "MAX": the model's own sense, each instance with a private incumbent, walked to the end of its tree.
         roots, max_nodes, solutions, stream: as solve_many.  -> the dict of solve_many; `first` is the stored row (ANY /
         ALL: the first solution; MIN / MAX: the best one found, the optimum when status is 0), and under MIN / MAX
         `best` [K] int32, meaningful where solutions > 0.  An instance that stops at max_nodes under MIN / MAX keeps the
-        best found so far: an anytime answer."""
+        best found so far: an anytime answer.
+        checkpoints: a pool of many_clause_checkpoints(): an instance that stops at max_nodes keeps its walk and its
+        incumbent in a slot of it (csgpu_solve_many_clauses_checkpointed); the answer then has `slot` [K] int32 (-1: no
+        checkpoint) and is what resume_many_clauses() continues.  Without it nothing changes."""
         L = load_library()
         n = self.n_vars
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
@@ -391,13 +394,165 @@ class Model:
         buf = self._many_records(K, roots.device)
         first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
         best = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if obj in (2, 3) else None
-        check(L.csgpu_solve_many_clauses(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
-                                         first.data_ptr() if solutions and K else None,
-                                         best.data_ptr() if best is not None else None, _stream_ptr(stream)))
-        out = self._many_answer(buf, K, first)
+        if checkpoints is None:
+            check(L.csgpu_solve_many_clauses(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                                             first.data_ptr() if solutions and K else None,
+                                             best.data_ptr() if best is not None else None, _stream_ptr(stream)))
+            out = self._many_answer(buf, K, first)
+        else:
+            slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
+            check(L.csgpu_solve_many_clauses_checkpointed(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
+                                                          buf.data_ptr(), first.data_ptr() if solutions and K else None,
+                                                          best.data_ptr() if best is not None else None, checkpoints._h,
+                                                          slots.data_ptr(), _stream_ptr(stream)))
+            out = self._many_answer(buf, K, first, slots, checkpoints)
+            out["_objective"], out["_best"] = obj, best  # resume_many_clauses goes on under the same objective
         if best is not None:
             out["best"] = best[:K]
         return out
+
+    def resume_many_clauses(self, result: dict, *, max_nodes, stream=None) -> dict:
+        """continue, in place, the instances of a checkpointed solve_many_clauses answer that stopped with a checkpoint
+        (csgpu_solve_many_clauses_resume): `max_nodes` more nodes each, under the answer's objective.  Counters
+        accumulate; under MIN / MAX `first` / `best` are overwritten at every improvement, the incumbent travelling in
+        the slot; under ANY / ALL `first` is written when `solutions` goes from 0 to 1.  Rows of instances without a
+        slot are not touched.  -> result"""
+        assert "_checkpoints" in result and "_objective" in result, "an answer of solve_many_clauses(..., checkpoints=pool)"
+        opt = ManyOptions(result["_objective"], 0, int(max_nodes))
+        first, best = result.get("first"), result["_best"]
+        K = result["status"].shape[0]
+        check(load_library().csgpu_solve_many_clauses_resume(self._h, K, C.byref(opt), result["_records"].data_ptr(),
+                                                             first.data_ptr() if first is not None and K else None,
+                                                             best.data_ptr() if best is not None else None,
+                                                             result["_checkpoints"]._h, result["_slots"].data_ptr(),
+                                                             _stream_ptr(stream)))
+        return result
+
+    def many_clause_checkpoints(self, capacity: int) -> "ManyCheckpoints":
+        """a pool of `capacity` checkpoint slots for solve_many_clauses(..., checkpoints=)
+        (csgpu_many_clause_checkpoints_create): a ManyCheckpoints of the clause kind, which solve_many refuses as
+        solve_many_clauses refuses a pool of many_checkpoints()"""
+        return ManyCheckpoints(self, capacity, clauses=True)
+
+    def clause_checkpoint_bytes(self) -> int:
+        """bytes of one clause checkpoint slot, (n_vars + 1)^2 x 8, or 0 if the model does not qualify for
+        solve_many_clauses (host only: after build_tables or finalize)"""
+        return int(load_library().csgpu_many_clause_checkpoint_bytes(self._h))
+
+    def many_clauses_resume_kernel(self):
+        """the cs_walk_resume instantiation the checkpointed clause calls launch, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_resume_symbol")
+
+    def clause_checkpoint_states(self, checkpoints: "ManyCheckpoints", slot: int, stream=None):
+        """-> (states, best): the open subtrees of the clause checkpoint in `slot` as states [depth + 1, n_vars, 2] int32
+        on the device, the oldest frame (the largest subtree) first, and the instance's incumbent or None
+        (csgpu_many_clause_checkpoint_states).  The states are not at the fixpoint and not under the incumbent's bound
+        yet: see open_clause_subtrees()."""
+        n = self.n_vars
+        out = torch.empty((n, n, 2), dtype=torch.int32, device="cuda")  # depth + 1 <= n
+        count, best, have = C.c_int64(), C.c_int32(), C.c_int32()
+        check(load_library().csgpu_many_clause_checkpoint_states(checkpoints._h, int(slot), out.data_ptr(), n, C.byref(count),
+                                                                 C.byref(best), C.byref(have), _stream_ptr(stream)))
+        return out[: count.value], (int(best.value) if have.value else None)
+
+    def open_clause_subtrees(self, checkpoints: "ManyCheckpoints", slot: int):
+        """clause_checkpoint_states() made ready for a Search: every state through the fixpoint as a `var < 0` node, under
+        the incumbent's bound when there is one (propagate_obj), the inconsistent ones dropped.
+        -> (open states [m, n_vars, 2] for Search.put, complete states [s, n_vars, 2]: each a solution of its own -- under
+        an incumbent a better one -- which the engine must not be given, the incumbent or None for Search.set_best)"""
+        states, best = self.clause_checkpoint_states(checkpoints, slot)
+        nodes = torch.zeros((states.shape[0], 4), dtype=torch.int32, device=states.device)
+        nodes[:, 0] = -1
+        nodes[:, 3] = torch.arange(states.shape[0], dtype=torch.int32, device=states.device)
+        if best is None:
+            out, res = self.propagate(states.contiguous(), nodes)
+        else:
+            lo, hi = (-2**31, best - 1) if self.objective == 2 else (best + 1, 2**31 - 1)
+            out, res = self.propagate_obj(states.contiguous(), nodes, lo, hi)
+        alive = res[:, 0] >= 0
+        complete = (out[:, :, 0] == out[:, :, 1]).all(dim=1)
+        return out[alive & ~complete].contiguous(), out[alive & complete].contiguous(), best
+
+    def solve_many_clauses_sliced(self, roots, objective="ANY", *, budgets, finish="resume", solutions=True,
+                                  pool_capacity=1 << 18, max_children=1 << 14, checkpoints=None) -> dict:
+        """solve_many_clauses in slices: a checkpointed call with budgets[0], then a resume with each following budget
+        while an instance is at LIMIT -- a small budget for everybody, more for the few that need it.
+        finish="resume": that is all (instances still at LIMIT stay so, with their slots and the best found so far).
+        finish="search": after the last budget every instance still at LIMIT with a slot hands its open subtrees, and its
+        incumbent, to one reused Search (reset, set_best, put, run) and ends DONE.  Under MIN / MAX `best` / `first`
+        are the better of the walk's incumbent, the complete states and the engine's best_solution: the proven optimum;
+        the row may differ from the single-wave walk's where several rows attain it.  `solutions` is the sum (ALL, and
+        the improving solutions of MIN / MAX) or 1 if any part found one (ANY); `nodes`, `cuts` and `props` of those
+        instances are the sums of both parts and NOT the single-wave walk's: the engine walks the open subtrees in its
+        own order.  The engine walks with the model's own objective, which must be the one asked for.  Synchronises
+        between the slices.  checkpoints: a pool of many_clause_checkpoints() to use, which is reset first (a caller that
+        repeats the call saves making one); else a pool of K slots is made.
+        -> the dict of solve_many_clauses plus `slot` and `sliced`: {"slices": calls made, "searched": instances finished
+        by the Search}"""
+        assert finish in ("resume", "search") and len(budgets) >= 1
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        if finish == "search" and obj != self.objective:
+            raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
+        pool = checkpoints.reset() if checkpoints is not None else self.many_clause_checkpoints(max(roots.shape[0], 1))
+        out = self.solve_many_clauses(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+        slices = 1
+        for budget in budgets[1:]:
+            if not bool((out["status"] == 1).any()):
+                break
+            self.resume_many_clauses(out, max_nodes=budget)
+            slices += 1
+        searched = 0
+        if finish == "search":
+            left = torch.nonzero((out["status"] == 1) & (out["slot"] >= 0)).flatten().tolist()
+            if left:
+                search = Search(self, pool_capacity, max_children)
+                for i in left:
+                    self._finish_clauses_by_search(search, pool, out, i, obj)
+                    searched += 1
+                search.close()
+        out["sliced"] = {"slices": slices, "searched": searched}
+        return out
+
+    def _finish_clauses_by_search(self, search: "Search", pool, out: dict, i: int, obj: int):
+        """instance i of `out`, stopped with a clause checkpoint: its open subtrees through `search`, the totals added"""
+        states, complete, best = self.open_clause_subtrees(pool, int(out["slot"][i]))
+        found = int(complete.shape[0])
+        bounded, ov = obj in (2, 3), self.objective_var
+        first = None
+        if found and bounded:  # each complete state beats the walk's incumbent: the best of them
+            values = complete[:, ov, 0]
+            j = int(torch.argmin(values) if obj == 2 else torch.argmax(values))
+            best, first = int(values[j]), complete[j, :, 0]
+        elif found:
+            first = complete[0, :, 0]
+        nodes = cuts = props = 0
+        if states.shape[0] and not (obj == 0 and found):
+            search.reset()
+            if best is not None:
+                search.set_best(best)
+            search.put(states)
+            st = search.run()
+            assert st["done"] == 1
+            nodes, cuts, props = st["nodes"], st["cuts"], st["props"]
+            found += st["solutions"]
+            if bounded:
+                row = search.best_solution()
+                if row is not None and (best is None or (row[ov] < best if obj == 2 else row[ov] > best)):
+                    best, first = int(row[ov]), torch.from_numpy(row.astype(np.int32)).to(states.device)
+            elif st["solutions"] and first is None:
+                first = torch.from_numpy(search.solutions(1)[0].astype(np.int32)).to(states.device)
+        if obj == 0:
+            found = min(found, 1)
+        if first is not None and "first" in out and (bounded or int(out["solutions"][i]) == 0):
+            out["first"][i] = first
+        if bounded and best is not None:
+            out["best"][i] = best
+        out["solutions"][i] += found
+        out["nodes"][i] += nodes
+        out["cuts"][i] += cuts
+        out["props"][i] += props
+        out["status"][i] = 0
+        out["slot"][i] = -1
 
     def qualifies_many_clauses(self) -> bool:
         """may solve_many_clauses run this model (finalized, kernel 6 planned, its LDS slices fit a CU)?"""
@@ -756,13 +911,17 @@ class Model:
 
 
 class ManyCheckpoints:
-    """A pool of checkpoint slots of one finalized model (csgpu_many_checkpoints); it holds the model."""
+    """A pool of checkpoint slots of one finalized model (csgpu_many_checkpoints), of one of two kinds: for solve_many
+    (Model.many_checkpoints) or for solve_many_clauses (Model.many_clause_checkpoints).  It holds the model."""
 
-    def __init__(self, model: Model, capacity: int):
+    def __init__(self, model: Model, capacity: int, clauses: bool = False):
         self.model = model
         self.capacity = int(capacity)
+        self.clauses = bool(clauses)  # the kind: of solve_many_clauses (csgpu_many_clause_checkpoints_create), else of solve_many
         self._h = C.c_void_p()
-        check(load_library().csgpu_many_checkpoints_create(model._h, self.capacity, C.byref(self._h)))
+        L = load_library()
+        create = L.csgpu_many_clause_checkpoints_create if self.clauses else L.csgpu_many_checkpoints_create
+        check(create(model._h, self.capacity, C.byref(self._h)))
 
     def reset(self, stream=None):
         """every slot free again (asynchronous on the stream)"""

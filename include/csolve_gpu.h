@@ -432,11 +432,71 @@ int32_t csgpu_many_value(uint32_t seed, uint32_t run, int32_t var, csgpu_val bou
  * max_nodes <= 0 -> CSGPU_E_ARG; an objective other than 0-3, MIN / MAX on a model without an objective variable or
  * with the other sense -> CSGPU_E_ARG; model not finalized -> CSGPU_E_STATE; more than 512 clauses, or slices that do
  * not fit -> CSGPU_E_LIMIT, the message says which; count > 2^31 - 65 -> CSGPU_E_LIMIT.  count == 0 -> CSGPU_OK, nothing
- * is launched. */
+ * is launched.
+ * An instance that stops at max_nodes need not start again from its root row: see "clause checkpoints" below. */
 int csgpu_model_qualifies_many_clauses(const csgpu_model *m);
 int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
                              csgpu_many_result *d_results, int32_t *d_solutions /* NULL or [count][n_vars] */,
                              int32_t *d_best /* NULL or [count] */, void *stream);
+
+/* ---- clause checkpoints: csgpu_solve_many_clauses in slices ----
+ * What "checkpoints: csgpu_solve_many in slices" above is to csgpu_solve_many, for csgpu_solve_many_clauses, MIN / MAX
+ * included: an instance that stops at max_nodes with work left draws a slot of a pool and leaves there its pushed frames,
+ * its current node with {branching variable, next value}, and its incumbent.  The bound of a stopped MIN / MAX walk is
+ * what makes the rest of its tree small; it goes on with it.
+ *   csgpu_many_clause_checkpoints_create   a pool for these calls.  The type, csgpu_many_checkpoints_reset and
+ *                                  csgpu_many_checkpoints_free are those above; a pool remembers its kind, and every
+ *                                  call of either family answers CSGPU_E_ARG to a pool of the other kind
+ *   csgpu_solve_many_clauses_checkpointed   csgpu_solve_many_clauses plus the pool: d_slots[i] receives the slot of an
+ *                                  instance that stopped with a checkpoint and -1 for every other one (DONE, BAD_ROOT, or
+ *                                  LIMIT while the pool had no slot left: such an instance ends exactly as in
+ *                                  csgpu_solve_many_clauses)
+ *   csgpu_solve_many_clauses_resume   the same d_results / d_solutions / d_best / d_slots rows again, options->max_nodes
+ *                                  being the budget of THIS call (nodes tried in the call).  An instance with
+ *                                  d_slots[i] < 0 is left untouched: nothing of it is written.  One with a slot reads its
+ *                                  counters from d_results[i] and its incumbent from the slot, goes on in the slot's
+ *                                  frames, and ends DONE (d_slots[i] = -1) or LIMIT (header and {variable, next value}
+ *                                  go back into the SAME slot).  Counters accumulate; under MIN / MAX d_solutions /
+ *                                  d_best are overwritten at every improvement, under ANY / ALL the row is stored when
+ *                                  `solutions` becomes 1.  A walk in slices gives, field for field and row for row, the
+ *                                  one csgpu_solve_many_clauses call with the summed budget
+ *   csgpu_many_clause_checkpoint_states   the open subtrees of one checkpoint as states, the oldest frame (the largest
+ *                                  subtree) first: a frame {row, bv, next} becomes the row with bv narrowed to
+ *                                  [next, row[bv].hi], the current node likewise.  *count = depth + 1; *have_best and
+ *                                  *best are the incumbent.  The states are NOT at the fixpoint yet, and the incumbent's
+ *                                  bound is not in them: run them through csgpu_propagate_batch_obj as `var < 0` nodes
+ *                                  under the bound, drop the inconsistent ones and count the complete ones, then
+ *                                  csgpu_search_set_best and csgpu_search_put.  Errors as csgpu_many_checkpoint_states
+ *                                  (best / have_best must not be null); it reads the header on `stream` and waits
+ * The kernel gives CSGPU_MANY_BAD_SLOT, with nothing but the status word written, to an instance whose slot number is
+ * outside [0, capacity), whose slot holds no checkpoint (the magic word is missing or the depth is outside [0, n_vars)),
+ * or whose checkpoint was made under another objective than options->objective.  All of that is compared before
+ * anything else of the slot is read.
+ * A slot is csgpu_many_clause_checkpoint_bytes(m) bytes: (n_vars + 1) frames of (n_vars + 1) 8-byte entries in absolute
+ * bounds.  Frame 0 is the header: entry 0 {depth, magic}, entry 1 {best, have_best | objective << 1}.  Frames 1 .. depth
+ * are the pushed frames, the row and then {variable, next value}; frame 1 + depth is the current node as it was entered,
+ * with {variable, next value} behind it.  Slots are freed by csgpu_many_checkpoints_reset only.
+ * Concurrency: ONE call of the whole csgpu_solve_many family in flight per model, as before; calls may be queued on one
+ * stream without the host in between (a checkpointed call and its resumes, for instance).  The same slot number twice in
+ * one resume call is undefined.  The pool outlives the calls queued on it and is freed before its model.
+ * Errors before any HIP call, in csgpu_solve_many_clauses's order and with its codes; after them a null pool or d_slots,
+ * a pool created for another model, a pool of csgpu_many_checkpoints_create -> CSGPU_E_ARG; then count == 0 -> CSGPU_OK,
+ * nothing is launched.  csgpu_many_clause_checkpoints_create: as csgpu_many_checkpoints_create, CSGPU_E_LIMIT for a
+ * model that does not qualify for csgpu_solve_many_clauses.
+ * Not here: up to k solutions and restarts for clause models. */
+size_t csgpu_many_clause_checkpoint_bytes(const csgpu_model *m); /* bytes per slot; 0 if the model does not qualify (at most
+                                                                    512 clauses, slices that fit), and for NULL.  No HIP
+                                                                    call: after finalize, or after
+                                                                    csgpu_model_build_tables alone */
+int csgpu_many_clause_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out);
+int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                          const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                          int32_t *d_best, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                    csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                    csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
+                                        int64_t *count, int32_t *best, int32_t *have_best, void *stream);
 
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */

@@ -9,7 +9,14 @@ seeded sample of the device's answers re-checked against the host walk (tests/ma
 the optimum of every DONE instance of the loop's sample is compared with the engine's as well.
 
   python tools/time_solve_many_clauses.py --set schedule5_min [--count 4096] [--reps 5] [--loop-sample 128] [--check 16]
-  sets: the names of tests/many_clause_sets.py; the set's rows are repeated with other seeds up to --count."""
+  sets: the names of tests/many_clause_sets.py; the set's rows are repeated with other seeds up to --count.
+
+--sliced B1,B2,... [--finish resume|search] [--budget N] times, in place of the per-instance loop, the sliced route
+(Model.solve_many_clauses_sliced on one reused pool: a checkpointed call with B1, a resume per further budget while an
+instance is at LIMIT, then with --finish search one reused Search for every instance still stopped) beside the one call
+with the summed budget (or --budget), interleaved in this process; the first slice is timed on its own as well.  The
+sliced answers of the seeded sample are re-checked against the host walk: field for field with --finish resume; with
+--finish search every instance DONE and `best` the host walk's proven optimum where 32,768 more nodes prove one."""
 import argparse
 import json
 import os
@@ -50,8 +57,16 @@ def main():
     ap.add_argument("--loop-sample", type=int, default=128)
     ap.add_argument("--check", type=int, default=16)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sliced", default=None, help="B1,B2,...: the budgets of the sliced route")
+    ap.add_argument("--finish", default="resume", choices=("resume", "search"))
+    ap.add_argument("--budget", type=int, default=None, help="the one call's budget (default: the set's, or the sum of --sliced)")
     args = ap.parse_args()
     text, base, objective, budget = sets.build(args.set)
+    budgets = tuple(int(b) for b in args.sliced.split(",")) if args.sliced else None
+    if budgets:
+        budget = sum(budgets)
+    if args.budget:
+        budget = args.budget
     roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
     count = len(roots)
     model = solve_root(text)
@@ -84,6 +99,8 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t, total, bests
 
+    if budgets:
+        return sliced_route(args, model, text, roots, dev, objective, budget, budgets, many, rng, W)
     for _ in range(2):  # warm-up: code load, workspace, the engine's buffers
         many()
     loop()
@@ -122,6 +139,73 @@ def main():
         "oracle_checked": len(picks), "oracle_ok": bool(ok),
     }))
     return 0 if ok and same_optimum is not False else 1
+
+
+def sliced_route(args, model, text, roots, dev, objective, budget, budgets, many, rng, W):
+    count = len(roots)
+    pool = model.many_clause_checkpoints(count)
+
+    def first_slice():
+        pool.reset()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = model.solve_many_clauses(dev, objective, max_nodes=budgets[0], checkpoints=pool)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    def sliced():
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = model.solve_many_clauses_sliced(dev, objective, budgets=budgets, finish=args.finish, checkpoints=pool)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    many()  # warm-up: code load, workspace, the engine's buffers
+    first_slice()
+    sliced()
+    many_times, first_times, sliced_times = [], [], []
+    for _ in range(args.reps):
+        dt, one = many()
+        many_times.append(dt)
+        dt, part = first_slice()
+        first_times.append(dt)
+        stopped_first = int((part["status"] == 1).sum())
+        dt, out = sliced()
+        sliced_times.append(dt)
+    host = {k: v.cpu().numpy() for k, v in out.items() if torch.is_tensor(v) and not k.startswith("_")}
+    one = {k: v.cpu().numpy() for k, v in one.items() if torch.is_tensor(v)}
+
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    if args.finish == "resume":
+        want = W.walk_many(text, roots[picks], objective, sum(budgets))
+        has = want["solutions"] > 0
+        ok = all((host[f][picks] == want[f]).all() for f in W.FIELDS) and bool((host["first"][picks][has] == want["first"][has]).all())
+        if objective in ("MIN", "MAX"):
+            ok = ok and bool((host["best"][picks][has] == want["best"][has]).all())
+    else:
+        want = W.walk_many(text, roots[picks], objective, sum(budgets) + 32768)
+        proven = (want["status"] == 0) & (want["solutions"] > 0)
+        ok = bool((host["status"] == 0).all())
+        if objective in ("MIN", "MAX"):
+            ok = ok and bool((host["best"][picks][proven] == want["best"][proven]).all())
+        else:
+            ok = ok and bool((host["solutions"][picks][proven] == want["solutions"][proven]).all())
+    t_many, t_sliced = statistics.median(many_times), statistics.median(sliced_times)
+    print(json.dumps({
+        "tool": "time_solve_many_clauses", "route": "sliced", "commit": commit(), "command": " ".join(sys.argv), "set": args.set,
+        "objective": objective, "instances": count, "n_vars": model.n_vars, "clauses": model.n_clauses,
+        "kernel": model.many_clauses_kernel(), "resume_kernel": model.many_clauses_resume_kernel(),
+        "waves": model.many_clauses_waves(count), "slot_bytes": model.clause_checkpoint_bytes(),
+        "one_call_max_nodes": budget, "one_call_status_counts": np.bincount(one["status"], minlength=3).tolist(),
+        "one_call_nodes": int(one["nodes"].sum()), "one_call_largest_tree": int(one["nodes"].max()),
+        "one_call_ms": spread(many_times),
+        "budgets": list(budgets), "finish": args.finish, "sliced": out["sliced"], "stopped_after_the_first_slice": stopped_first,
+        "first_slice_ms": spread(first_times), "sliced_ms": spread(sliced_times),
+        "sliced_status_counts": np.bincount(host["status"], minlength=3).tolist(), "sliced_nodes": int(host["nodes"].sum()),
+        "sliced_over_one_call": round(t_sliced / t_many, 3),
+        "oracle_checked": len(picks), "oracle_ok": bool(ok),
+    }))
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
