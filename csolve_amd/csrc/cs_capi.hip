@@ -76,6 +76,7 @@ struct cs_kernel_plan {
   cs_planned dive[MANY_FAMILIES];  /* by MANY_*: all four or none; not among csgpu_internal_plan_symbol's families */
   cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
   cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
+  cs_planned walk_upto;            /* cs_walk_upto (csgpu_solve_many_clauses_upto and its two checkpoint calls): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -1004,6 +1005,17 @@ static int plan_general(csgpu_model *m) {
           m->plan.walk_ck.per_cu = occ;
         if (m->plan.walk_ck.per_cu < 1) m->plan.walk_ck.per_cu = 1;
       }
+      { /* cs_walk_upto: the same slices, its own registers */
+#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_upto<CPL, true> : (const void *)cs_walk_upto<CPL, false>)
+        const void *fn_upto = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
+#undef CS_PICKW
+        if ((rc = plan_kernel(&m->plan.walk_upto, fn_upto, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_upto, CS_BLOCK, m->plan.walk_upto.lds) == hipSuccess && occ >= 1 &&
+            occ < m->plan.walk_upto.per_cu)
+          m->plan.walk_upto.per_cu = occ;
+        if (m->plan.walk_upto.per_cu < 1) m->plan.walk_upto.per_cu = 1;
+      }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
   }
@@ -1919,6 +1931,9 @@ extern "C" int csgpu_internal_many_clauses_symbol(const csgpu_model *m, char *bu
 extern "C" int csgpu_internal_many_clauses_resume_symbol(const csgpu_model *m, char *buf, size_t len) {
   return many_clauses_symbol(m, m != NULL ? &m->plan.walk_ck : NULL, "cs_walk_resume", buf, len);
 }
+extern "C" int csgpu_internal_many_clauses_upto_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_upto : NULL, "cs_walk_upto", buf, len);
+}
 
 /* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
  * whose frames fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices fit a CU) */
@@ -1938,16 +1953,20 @@ extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64
   return many_clauses_waves(m, &m->plan.walk, count);
 }
 
-/* The one path of the three entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
+/* The one path of the six entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
  * has a pool and slot numbers and launches cs_walk_resume; `resume` (pooled, and no roots): the instances go on in their
- * slots, so the call needs no workspace. */
+ * slots, so the call needs no workspace.  An up-to-k entry brings `upto_options` in place of `options` (the other one is
+ * NULL): the ALL walk by cs_walk_upto, pooled or not, its rows [count][max_solutions][n_vars] in d_solutions. */
 static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
-                             csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best, int pooled,
-                             csgpu_many_checkpoints *ck, int32_t *d_slots, int resume, void *stream) {
-  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || options == NULL;
+                             const csgpu_many_upto_options *upto_options, csgpu_many_result *d_results, int32_t *d_solutions,
+                             int32_t *d_best, int pooled, csgpu_many_checkpoints *ck, int32_t *d_slots, int resume, void *stream) {
+  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || (options == NULL && upto_options == NULL);
+  const int64_t max_nodes = null_arg ? 0 : (upto_options != NULL ? upto_options->max_nodes : options->max_nodes);
   int rc;
-  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, pooled ? "slice" : "instance"))) return rc;
-  const int objective = options->objective;
+  if ((rc = many_check_head(null_arg, count, max_nodes, pooled ? "slice" : "instance"))) return rc;
+  if (upto_options != NULL && upto_options->max_solutions < 1)
+    return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
+  const int objective = upto_options != NULL ? CS_OBJ_ALL : options->objective;
   if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
     return set_err(CSGPU_E_ARG, "no objective %d", objective);
   if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX) {
@@ -1973,7 +1992,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   }
   if (count == 0) return CSGPU_OK;
   csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = pooled ? &m->plan.walk_ck : &m->plan.walk;
+  const cs_planned *k = upto_options != NULL ? &m->plan.walk_upto : (pooled ? &m->plan.walk_ck : &m->plan.walk);
   const int n = m->host->n_vars;
   const int64_t waves = many_clauses_waves(m, k, count);
   const int frames = n; /* at most n - 1 pushed frames and the current node's */
@@ -1985,7 +2004,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   io.all = objective != CS_OBJ_ANY;
   io.sense = objective_sense(objective);
   io.obj_var = io.sense != 0 ? m->host->obj_var : -1;
-  io.max_nodes = (long long)options->max_nodes;
+  io.max_nodes = (long long)max_nodes;
   io.results = (cs_dive_result *)d_results;
   io.solutions = d_solutions;
   io.best = io.sense != 0 ? d_best : NULL;
@@ -1995,12 +2014,13 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   cs_walk_ck wk;
   wk.pool = pooled ? ck->d_pool : NULL;
   wk.next = pooled ? ck->d_next : NULL;
-  wk.capacity = pooled ? (int)ck->capacity : 0;
+  wk.capacity = pooled ? (int)ck->capacity : 0; /* 0: the pool that cs_walk_upto does not touch */
   wk.resume = resume;
-  wk.code = objective;
-  wk.slots = d_slots;
+  wk.code = upto_options != NULL ? CS_WALK_CK_UPTO : objective;
+  wk.slots = pooled ? d_slots : NULL;
+  int upto = upto_options != NULL ? upto_options->max_solutions : 0;
   cs_tables tab = m->tab;
-  void *args[] = { &tab, &io, &wk }; /* cs_walk_clauses takes the first two */
+  void *args[] = { &tab, &io, &wk, &upto }; /* cs_walk_clauses takes the first two, cs_walk_resume the first three */
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
@@ -2008,7 +2028,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
 extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                         const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
                                         int32_t *d_best, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, d_results, d_solutions, d_best, 0, NULL, NULL, 0, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, stream);
 }
 
 /* ---- clause checkpoints: csgpu_solve_many_clauses in slices (cs_walk_resume) ---- */
@@ -2038,13 +2058,13 @@ extern "C" int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const
                                                      const csgpu_many_options *options, csgpu_many_result *d_results,
                                                      int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
                                                      int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, d_results, d_solutions, d_best, 1, ck, d_slots, 0, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
                                                csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
                                                csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, options, d_results, d_solutions, d_best, 1, ck, d_slots, 1, stream);
+  return many_clauses_call(m, NULL, count, options, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, stream);
 }
 
 extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
@@ -2057,6 +2077,27 @@ extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints 
     *have_best = header[1].hi & 1;
   }
   return rc;
+}
+
+/* ---- up to k solutions per instance of a clause model (cs_walk_upto) ---- */
+
+extern "C" int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                             const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                             int32_t *d_solutions, void *stream) {
+  return many_clauses_call(m, d_roots, count, NULL, options, d_results, d_solutions, NULL, 0, NULL, NULL, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_clauses_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                          const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                                          int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                                          void *stream) {
+  return many_clauses_call(m, d_roots, count, NULL, options, d_results, d_solutions, NULL, 1, ck, d_slots, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_clauses_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
+                                                    csgpu_many_result *d_results, int32_t *d_solutions,
+                                                    csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
+  return many_clauses_call(m, NULL, count, NULL, options, d_results, d_solutions, NULL, 1, ck, d_slots, 1, stream);
 }
 
 #ifdef CS_SHAVE_TIMELINE

@@ -52,7 +52,16 @@
  * one uses the frames of its slot AS its stack, reads the current node back from frame depth (root = false, fresh =
  * false), and when it stops again writes only the header and {bv, nv}.  A resume launch needs no workspace.  The budget
  * of a resumed instance counts the nodes of this launch.  The header's objective must be the call's: a checkpoint made
- * under ALL has no incumbent to go on with under MIN, and one made under ANY would never have been written. */
+ * under ALL has no incumbent to go on with under MIN, and one made under ANY would never have been written.
+ *
+ * Up to k solutions (cs_walk_upto, csgpu_solve_many_clauses_upto / _upto_checkpointed / _upto_resume): the same loop a
+ * third time, with CS_WALK_CK 1 and CS_WALK_UPTO 1.  The instance walks the ALL walk (sense 0, "<obj>" an ordinary
+ * variable, no incumbent) and leaves right after its k-th solution, DONE; solution j (0-based, walk order) goes to row
+ * (inst * k + j) of io.solutions, an index of 64 bits, every lane the variables it owns.  A root row that is a solution is
+ * row 0.  The header's code is CS_WALK_CK_UPTO, so a checkpoint of this kernel and one of cs_walk_resume refuse each
+ * other (CSGPU_MANY_BAD_SLOT).  A resumed instance continues its rows at index `solutions` of its record, with the k of
+ * the call; one that holds k already ends DONE before it tries a node, with only its status word and slot number
+ * written. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
 
@@ -64,12 +73,14 @@ struct cs_walk_io {
   const cs_val *roots;     /* [count][n] */
   const cs_val *root_dom;  /* [n]: the model's root domains, which a root row must lie inside */
   int count;
-  int all;                 /* 0: leave at the first solution (ANY), 1: walk the whole tree (ALL, MIN, MAX) */
+  int all;                 /* 0: leave at the first solution (ANY), 1: walk the whole tree (ALL, MIN, MAX); cs_walk_upto does
+                              not read it */
   int sense;               /* cs_objective_bound's: 0 none (ANY / ALL), 1 minimise, 2 maximise */
   int obj_var;             /* "<obj>" under MIN / MAX, else -1 */
   long long max_nodes;
   cs_dive_result *results; /* [count] */
-  int *solutions;          /* [count][n] or NULL: the first solution (ANY / ALL), the best one so far (MIN / MAX) */
+  int *solutions;          /* [count][n] or NULL: the first solution (ANY / ALL), the best one so far (MIN / MAX);
+                              cs_walk_upto: [count][k][n] or NULL, the first k in walk order */
   int *best;               /* [count] or NULL: MIN / MAX, instances with a solution */
   cs_val *stack;           /* [waves][frames][n + 1] */
   int frames;
@@ -79,19 +90,23 @@ struct cs_walk_io {
 template <int CPL, bool HAS_TREE>
 __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk_io io) {
 #define CS_WALK_CK 0
+#define CS_WALK_UPTO 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_UPTO
 #undef CS_WALK_CK
 }
 
 #define CS_WALK_CK_MAGIC 0x77636b70 /* header entry 0 .hi of a slot that holds a clause checkpoint (not CS_DIVE_CK_MAGIC) */
+#define CS_WALK_CK_UPTO 4           /* the header's code of an up-to-k checkpoint (cs_walk_upto): beside the objectives 0 .. 3 */
 
 /* the checkpoint pool and the slot numbers of a call (cs_walk_resume) */
 struct cs_walk_ck {
   cs_val *pool;             /* [capacity][n + 1][n + 1] */
   unsigned long long *next; /* slots handed out since the last reset (it counts on past capacity) */
-  int capacity;
+  int capacity;             /* cs_walk_upto: 0 = no pool (pool, next and slots are not touched) */
   int resume;               /* 0: fresh instances from io.roots; 1: instance i goes on from slot slots[i] */
-  int code;                 /* the call's objective, 0 ANY .. 3 MAX: a checkpoint goes on under the one it was made under */
+  int code;                 /* the call's objective, 0 ANY .. 3 MAX, or CS_WALK_CK_UPTO: a checkpoint goes on under the one it
+                               was made under */
   int *slots;               /* [count]: the slot of an instance stopped with a checkpoint, else -1 */
 };
 
@@ -99,7 +114,19 @@ struct cs_walk_ck {
 template <int CPL, bool HAS_TREE>
 __global__ __launch_bounds__(CS_BLOCK) void cs_walk_resume(cs_tables T, cs_walk_io io, cs_walk_ck ck) {
 #define CS_WALK_CK 1
+#define CS_WALK_UPTO 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+/* the same again, leaving an instance right after its `upto`-th solution and keeping all of them (upto >= 1) */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_upto(cs_tables T, cs_walk_io io, cs_walk_ck ck, int upto) {
+#define CS_WALK_CK 1
+#define CS_WALK_UPTO 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_UPTO
 #undef CS_WALK_CK
 }
 

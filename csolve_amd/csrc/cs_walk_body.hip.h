@@ -1,12 +1,16 @@
-/* cs_walk_body.hip.h -- the body of the two kernels of cs_walk.hip.h, which includes it inside each of them under one
- * switch:              CS_WALK_CK
- *   cs_walk_clauses        0        csgpu_solve_many_clauses
- *   cs_walk_resume         1        one more argument, `ck`: the pool and the slots of the call
- * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of the switch stands under its `#if`, so the kernel
+/* cs_walk_body.hip.h -- the body of the three kernels of cs_walk.hip.h, which includes it inside each of them under two
+ * switches:            CS_WALK_CK  CS_WALK_UPTO
+ *   cs_walk_clauses        0           0        csgpu_solve_many_clauses
+ *   cs_walk_resume         1           0        one more argument, `ck`: the pool and the slots of the call
+ *   cs_walk_upto           1           1        and `upto` (k >= 1, a scalar)
+ * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of a switch stands under its `#if`, so a kernel
  * that defines it 0 sees the text it saw before the switch was there and compiles to the same instructions.
  * CS_WALK_CK: an instance that stops at its budget leaves its frames, its current node, {bv, nv} and its incumbent in a
  * slot of the pool (the layout is in cs_walk.hip.h); with ck.resume the instances of ck.slots go on in their slots, which
- * are then their stacks.  New per-instance state is scalars only: slot, kept, depth0, nodes0, resumed, stack. */
+ * are then their stacks.  New per-instance state is scalars only: slot, kept, depth0, nodes0, resumed, stack.
+ * CS_WALK_UPTO: the ALL walk, left right after the k-th solution; solution j goes to row j of the instance's k rows, and
+ * ck.capacity == 0 means "no pool" (pool, next and slots are not touched), so the one kernel serves the plain, the
+ * checkpointed and the resume call.  It adds no per-instance state: the row index is inst, upto and sols, all scalar. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -98,7 +102,22 @@
       nodes = nodes0;
       best = best0;
       have_best = have_best0;
+#if CS_WALK_UPTO
+      have_best = false; /* an up-to-k walk has no incumbent, whatever the header says: obj_var is -1 */
+#endif
     }
+#if CS_WALK_UPTO
+    /* a resumed instance that holds its k solutions already (a smaller k than the slice before): DONE before it tries a
+     * node, nothing of it is written but this.  It is what keeps the row index below k; unsigned, so that a negative
+     * count in the caller's record ends here as well. */
+    if (resumed && (unsigned long long)sols >= (unsigned long long)upto) {
+      if (lane == 0) {
+        io.results[inst].status = 0; /* CSGPU_MANY_DONE */
+        ck.slots[inst] = -1;
+      }
+      continue;
+    }
+#endif
 #endif
 
     if (__ballot(bad_l) != 0ull) {
@@ -136,6 +155,9 @@
           if (nodes - nodes0 >= io.max_nodes) {
             status = 1; /* CSGPU_MANY_LIMIT */
             /* leave a checkpoint, if the pool has a slot */
+#if CS_WALK_UPTO
+            if (ck.capacity > 0) /* no pool: no slot is drawn, the instance ends as without checkpoints */
+#endif
             if (!resumed) {
               unsigned long long drawn = 0ull;
               if (lane == 0) drawn = __hip_atomic_fetch_add(ck.next, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -215,6 +237,13 @@
         }
         if (!failed && open_vars == 0) { /* every variable valued: a solution (the root row itself may be the one) */
           sols++;
+#if CS_WALK_UPTO
+          if (io.solutions != nullptr) { /* 1 <= sols <= upto here: a fresh count starts at 0, a resumed one below upto */
+            const size_t srow = ((size_t)inst * (size_t)upto + (size_t)(sols - 1)) * (size_t)n;
+            for (int v = lane; v < n; v += CS_WAVE) io.solutions[srow + v] = dom[v].lo;
+          }
+          if (sols >= (long long)upto || at_root) break; /* the k-th solution, or the root node was the one solution */
+#else
           if (io.sense != 0) {
             best = __builtin_amdgcn_readfirstlane(dom[io.obj_var].lo);
             have_best = true;
@@ -222,6 +251,7 @@
           if ((sols == 1 || io.sense != 0) && io.solutions != nullptr)
             for (int v = lane; v < n; v += CS_WAVE) io.solutions[rrow + v] = dom[v].lo;
           if (!io.all || at_root) break; /* ANY, or the root node was the one solution */
+#endif
         }
         if (descend) {
           if (!at_root && !last) { /* the parent comes back for its next value */
@@ -259,6 +289,9 @@
       res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
       io.results[inst] = res;
       if (have_best && io.best != nullptr) io.best[inst] = best;
+#if CS_WALK_UPTO
+      if (ck.capacity > 0)
+#endif
 #if CS_WALK_CK
       ck.slots[inst] = kept;
 #endif

@@ -313,25 +313,30 @@ class Model:
         i is its j-th solution in walk order, rows >= solutions[i] are not written.  solutions: True (a zeroed buffer),
         False (no rows), or an int32 device tensor [K, k, n_vars] to write into.  With a pool the answer has `slot` and
         is what resume_many() continues (csgpu_solve_many_upto_checkpointed)."""
+        return self._solve_many_upto("csgpu_solve_many_upto", None, roots, k, max_nodes, solutions, stream, checkpoints)
+
+    def _solve_many_upto(self, entry, qualifies, roots, k, max_nodes, solutions, stream, checkpoints) -> dict:
+        """solve_many_upto / solve_many_clauses_upto: `entry` and `entry`_checkpointed of the library, which take the same
+        arguments in both families; `qualifies` as _many_roots takes it"""
         L = load_library()
+        plain, pooled = getattr(L, entry), getattr(L, entry + "_checkpointed")
         n, k = self.n_vars, int(k)
         opt = ManyUptoOptions(k, 0, int(max_nodes))
         roots, K = self._many_roots(roots, k < 1, lambda ptr, count: check(
-            L.csgpu_solve_many_upto(self._h, ptr, count, C.byref(opt), ptr, None, None)))
+            plain(self._h, ptr, count, C.byref(opt), ptr, None, None)), qualifies=qualifies)
         buf = self._many_records(K, roots.device)
         rows = self._many_rows(solutions, (K, k, n), "[K, k, n_vars]", roots.device)
         rows_ptr = rows.data_ptr() if rows is not None and K and k >= 1 else None
         if checkpoints is None:
-            check(L.csgpu_solve_many_upto(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
-                                          rows_ptr, _stream_ptr(stream)))
+            check(plain(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(), rows_ptr,
+                        _stream_ptr(stream)))
             out = self._many_answer(buf, K, None)
         else:
             slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
-            check(L.csgpu_solve_many_upto_checkpointed(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
-                                                       buf.data_ptr(), rows_ptr, checkpoints._h, slots.data_ptr(),
-                                                       _stream_ptr(stream)))
+            check(pooled(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(), rows_ptr,
+                         checkpoints._h, slots.data_ptr(), _stream_ptr(stream)))
             out = self._many_answer(buf, K, None, slots, checkpoints)
-            out["_upto"] = k  # resume_many goes on through csgpu_solve_many_upto_resume, with this k unless told another
+            out["_upto"] = k  # the resume goes on through `entry`_resume, with this k unless told another
         if rows is not None:
             out["rows"] = rows
         return out
@@ -411,12 +416,19 @@ class Model:
             out["best"] = best[:K]
         return out
 
-    def resume_many_clauses(self, result: dict, *, max_nodes, stream=None) -> dict:
+    def resume_many_clauses(self, result: dict, *, max_nodes, stream=None, max_solutions=None) -> dict:
         """continue, in place, the instances of a checkpointed solve_many_clauses answer that stopped with a checkpoint
         (csgpu_solve_many_clauses_resume): `max_nodes` more nodes each, under the answer's objective.  Counters
         accumulate; under MIN / MAX `first` / `best` are overwritten at every improvement, the incumbent travelling in
         the slot; under ANY / ALL `first` is written when `solutions` goes from 0 to 1.  Rows of instances without a
-        slot are not touched.  -> result"""
+        slot are not touched.  -> result
+        An answer of solve_many_clauses_upto(..., checkpoints=pool) goes on through csgpu_solve_many_clauses_upto_resume:
+        its rows continue at index `solutions`.  max_solutions: the k of THIS slice, by default the answer's, exactly as
+        in resume_many()."""
+        if "_checkpoints" in result and "_upto" in result:
+            return self._resume_many_upto(result, int(max_nodes), max_solutions, stream,
+                                          entry="csgpu_solve_many_clauses_upto_resume")
+        assert max_solutions is None, "max_solutions continues an answer of solve_many_clauses_upto"
         assert "_checkpoints" in result and "_objective" in result, "an answer of solve_many_clauses(..., checkpoints=pool)"
         opt = ManyOptions(result["_objective"], 0, int(max_nodes))
         first, best = result.get("first"), result["_best"]
@@ -427,6 +439,29 @@ class Model:
                                                              result["_checkpoints"]._h, result["_slots"].data_ptr(),
                                                              _stream_ptr(stream)))
         return result
+
+    def solve_many_clauses_upto(self, roots, k, *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
+        """solve_many_clauses that leaves an instance right after its k-th solution and keeps all k
+        (csgpu_solve_many_clauses_upto): the ALL walk -- "<obj>" an ordinary variable, no incumbent -- stopped as ANY
+        stops after the first.  k = 1 is ANY, an instance with fewer than k solutions ends as under ALL; status DONE
+        means solutions == min(k, solutions of the tree).  roots, max_nodes, stream: as solve_many_clauses.  -> the dict
+        of solve_many_upto: `rows` [K, k, n_vars] int32, row j of instance i its j-th solution in walk order, rows >=
+        solutions[i] not written.  solutions: True (a zeroed buffer), False (no rows), or an int32 device tensor
+        [K, k, n_vars] to write into.  checkpoints: a pool of many_clause_checkpoints(); the answer then has `slot` and is
+        what resume_many_clauses() continues (csgpu_solve_many_clauses_upto_checkpointed)."""
+        return self._solve_many_upto("csgpu_solve_many_clauses_upto", self.qualifies_many_clauses(), roots, k, max_nodes,
+                                     solutions, stream, checkpoints)
+
+    def many_clauses_upto_kernel(self):
+        """the cs_walk_upto instantiation solve_many_clauses_upto and its checkpoint calls launch, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_upto_symbol")
+
+    def classify_many_clauses(self, roots, *, max_nodes, stream=None) -> torch.Tensor:
+        """classify_many for clause models: is the solution (the timetable of a schedule row) unique?  -> int8 [K] on
+        the device: 0 no solution, 1 exactly one, 2 several, -1 undecided within max_nodes (LIMIT), -2 bad root row.  A
+        solve_many_clauses_upto with k = 2 and no rows."""
+        return self._many_classes(self.solve_many_clauses_upto(roots, 2, max_nodes=max_nodes, solutions=False, stream=stream),
+                                  stream)
 
     def many_clause_checkpoints(self, capacity: int) -> "ManyCheckpoints":
         """a pool of `capacity` checkpoint slots for solve_many_clauses(..., checkpoints=)
@@ -474,7 +509,7 @@ class Model:
         return out[alive & ~complete].contiguous(), out[alive & complete].contiguous(), best
 
     def solve_many_clauses_sliced(self, roots, objective="ANY", *, budgets, finish="resume", solutions=True,
-                                  pool_capacity=1 << 18, max_children=1 << 14, checkpoints=None) -> dict:
+                                  pool_capacity=1 << 18, max_children=1 << 14, checkpoints=None, max_solutions=None) -> dict:
         """solve_many_clauses in slices: a checkpointed call with budgets[0], then a resume with each following budget
         while an instance is at LIMIT -- a small budget for everybody, more for the few that need it.
         finish="resume": that is all (instances still at LIMIT stay so, with their slots and the best found so far).
@@ -488,13 +523,21 @@ class Model:
         between the slices.  checkpoints: a pool of many_clause_checkpoints() to use, which is reset first (a caller that
         repeats the call saves making one); else a pool of K slots is made.
         -> the dict of solve_many_clauses plus `slot` and `sliced`: {"slices": calls made, "searched": instances finished
-        by the Search}"""
+        by the Search}
+        max_solutions=k: the slices are solve_many_clauses_upto calls (`objective` does not apply, the answer has
+        `rows`), with finish="resume" only."""
         assert finish in ("resume", "search") and len(budgets) >= 1
-        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        if max_solutions is not None and finish == "search":
+            raise ValueError("finish=\"search\" with max_solutions: an engine search cannot stop at a k-th solution "
+                             "per instance")
+        obj = None if max_solutions is not None else self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         if finish == "search" and obj != self.objective:
             raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
         pool = checkpoints.reset() if checkpoints is not None else self.many_clause_checkpoints(max(roots.shape[0], 1))
-        out = self.solve_many_clauses(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+        if max_solutions is not None:  # resume_many_clauses takes the k from the answer
+            out = self.solve_many_clauses_upto(roots, max_solutions, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+        else:
+            out = self.solve_many_clauses(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
         slices = 1
         for budget in budgets[1:]:
             if not bool((out["status"] == 1).any()):
@@ -569,7 +612,11 @@ class Model:
     def classify_many(self, roots, *, max_nodes, stream=None) -> torch.Tensor:
         """is the solution unique?  -> int8 [K] on the device: 0 no solution, 1 exactly one, 2 several, -1 undecided
         within max_nodes (LIMIT), -2 bad root row.  A solve_many_upto with k = 2 and no rows."""
-        out = self.solve_many_upto(roots, 2, max_nodes=max_nodes, solutions=False, stream=stream)
+        return self._many_classes(self.solve_many_upto(roots, 2, max_nodes=max_nodes, solutions=False, stream=stream), stream)
+
+    @staticmethod
+    def _many_classes(out: dict, stream) -> torch.Tensor:
+        """the classes of classify_many / classify_many_clauses from an up-to-2 answer"""
         status, found = out["status"], out["solutions"]
         ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         with ctx:
@@ -607,7 +654,9 @@ class Model:
                                                      _stream_ptr(stream)))
         return result
 
-    def _resume_many_upto(self, result: dict, max_nodes: int, max_solutions, stream) -> dict:
+    def _resume_many_upto(self, result: dict, max_nodes: int, max_solutions, stream,
+                          entry="csgpu_solve_many_upto_resume") -> dict:
+        """resume_many / resume_many_clauses on an up-to-k answer: `entry` is the family's resume call"""
         had = result["_upto"]
         k = had if max_solutions is None else int(max_solutions)
         opt = ManyUptoOptions(k, 0, max_nodes)
@@ -616,9 +665,9 @@ class Model:
         L = load_library()
 
         def call(buf):
-            check(L.csgpu_solve_many_upto_resume(self._h, K, C.byref(opt), result["_records"].data_ptr(),
-                                                 buf.data_ptr() if buf is not None and K and k >= 1 else None,
-                                                 result["_checkpoints"]._h, result["_slots"].data_ptr(), _stream_ptr(stream)))
+            check(getattr(L, entry)(self._h, K, C.byref(opt), result["_records"].data_ptr(),
+                                    buf.data_ptr() if buf is not None and K and k >= 1 else None,
+                                    result["_checkpoints"]._h, result["_slots"].data_ptr(), _stream_ptr(stream)))
 
         if rows is None or k == had or k < 1:
             call(rows)

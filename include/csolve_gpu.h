@@ -473,7 +473,8 @@ int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int
  * or whose checkpoint was made under another objective than options->objective.  All of that is compared before
  * anything else of the slot is read.
  * A slot is csgpu_many_clause_checkpoint_bytes(m) bytes: (n_vars + 1) frames of (n_vars + 1) 8-byte entries in absolute
- * bounds.  Frame 0 is the header: entry 0 {depth, magic}, entry 1 {best, have_best | objective << 1}.  Frames 1 .. depth
+ * bounds.  Frame 0 is the header: entry 0 {depth, magic}, entry 1 {best, have_best | objective << 1} (4 in place of the
+ * objective: a checkpoint of csgpu_solve_many_clauses_upto_checkpointed, below).  Frames 1 .. depth
  * are the pushed frames, the row and then {variable, next value}; frame 1 + depth is the current node as it was entered,
  * with {variable, next value} behind it.  Slots are freed by csgpu_many_checkpoints_reset only.
  * Concurrency: ONE call of the whole csgpu_solve_many family in flight per model, as before; calls may be queued on one
@@ -483,7 +484,8 @@ int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int
  * a pool created for another model, a pool of csgpu_many_checkpoints_create -> CSGPU_E_ARG; then count == 0 -> CSGPU_OK,
  * nothing is launched.  csgpu_many_clause_checkpoints_create: as csgpu_many_checkpoints_create, CSGPU_E_LIMIT for a
  * model that does not qualify for csgpu_solve_many_clauses.
- * Not here: up to k solutions and restarts for clause models. */
+ * Not here: restarts for clause models.  This note used to read "Not here: up to k solutions and restarts for clause
+ * models": its first half is closed, up to k solutions are the next section. */
 size_t csgpu_many_clause_checkpoint_bytes(const csgpu_model *m); /* bytes per slot; 0 if the model does not qualify (at most
                                                                     512 clauses, slices that fit), and for NULL.  No HIP
                                                                     call: after finalize, or after
@@ -497,6 +499,48 @@ int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const c
                                     csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
 int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
                                         int64_t *count, int32_t *best, int32_t *have_best, void *stream);
+
+/* ---- up to k solutions per instance of a clause model: csgpu_solve_many_clauses, left at the k-th solution ----
+ * "Which of these 10,000 schedule rows have a unique timetable?", "three alternatives per row": what "up to k solutions
+ * per instance" above is to csgpu_solve_many, for the clause models.  The instance walks exactly the ALL walk of
+ * csgpu_solve_many_clauses ("The walk" above: same root check, branching rule, value order and counters; "<obj>", if the
+ * model has one, is an ordinary variable and there is no incumbent) and stops right after accepting its k-th solution,
+ * as ANY stops after its first.  max_solutions = 1 is ANY, field for field and row for row; an instance whose whole tree
+ * holds fewer than k solutions ends as under ALL, field for field.  options is csgpu_many_upto_options and d_results
+ * csgpu_many_result, both as above.  CSGPU_MANY_DONE: the k-th solution was reached or the tree is exhausted, and
+ * solutions == min(k, solutions of the tree) -- with k = 2, "unique" is DONE && solutions == 1, "several" DONE &&
+ * solutions == 2, "none" DONE && solutions == 0.  LIMIT, BAD_ROOT and BAD_SLOT are as above.
+ *   d_solutions   NULL, or [count][max_solutions][n_vars] int32: row j of instance i is its j-th solution in walk order
+ *                 (a root row that is a solution already is row 0); rows >= solutions of an instance are not touched.
+ *                 count * max_solutions * n_vars may pass 2^31: the rows are indexed in 64 bits
+ * The three entries are csgpu_solve_many_clauses, csgpu_solve_many_clauses_checkpointed and
+ * csgpu_solve_many_clauses_resume with this stop.  The pool is one of csgpu_many_clause_checkpoints_create; slots, their
+ * layout, csgpu_many_clause_checkpoint_states (*have_best is 0) and csgpu_many_checkpoints_reset are those of "clause
+ * checkpoints", unchanged.  The header's code field (have_best | code << 1) holds 4, "up to k", where the other calls
+ * write their objective 0 .. 3: a checkpoint made here gives CSGPU_MANY_BAD_SLOT to csgpu_solve_many_clauses_resume
+ * under any objective, and one made there gives it to csgpu_solve_many_clauses_upto_resume, compared before anything
+ * else of the slot is read and with nothing but the status word written.  A resumed instance reads its counters from its
+ * record and continues its rows at index `solutions`: a walk in slices gives, field for field and row for row, the one
+ * call with the summed budget.  max_solutions is per call: a resumed instance whose record already has solutions >=
+ * max_solutions ends DONE before it tries a node, and nothing of it is written but its status and d_slots[i] = -1 (rows
+ * are indexed with the max_solutions of the call that writes them: give every slice the k the buffer was laid out for, or
+ * a buffer laid out for the new k).  ONE call of the whole csgpu_solve_many family in flight per model (same workspace,
+ * same ticket counters); calls of all families may be queued behind each other on one stream without the host in
+ * between.
+ * Errors before any HIP call, in csgpu_solve_many_clauses's order and with its codes: null model / roots / results /
+ * options (d_solutions may be null), count < 0, max_nodes <= 0, max_solutions < 1 -> CSGPU_E_ARG; model not finalized ->
+ * CSGPU_E_STATE; more than 512 clauses, or slices that do not fit -> CSGPU_E_LIMIT; count > 2^31 - 65 -> CSGPU_E_LIMIT;
+ * the checkpointed and the resume entry: a null pool or d_slots, a pool created for another model, a pool of
+ * csgpu_many_checkpoints_create -> CSGPU_E_ARG; then count == 0 -> CSGPU_OK, nothing is launched. */
+int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                  const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                  int32_t *d_solutions /* NULL or [count][max_solutions][n_vars] */, void *stream);
+int csgpu_solve_many_clauses_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                               const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                               int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_solve_many_clauses_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
+                                         csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                         int32_t *d_slots, void *stream);
 
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */

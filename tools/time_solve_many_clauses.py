@@ -16,7 +16,13 @@ the optimum of every DONE instance of the loop's sample is compared with the eng
 instance is at LIMIT, then with --finish search one reused Search for every instance still stopped) beside the one call
 with the summed budget (or --budget), interleaved in this process; the first slice is timed on its own as well.  The
 sliced answers of the seeded sample are re-checked against the host walk: field for field with --finish resume; with
---finish search every instance DONE and `best` the host walk's proven optimum where 32,768 more nodes prove one."""
+--finish search every instance DONE and `best` the host walk's proven optimum where 32,768 more nodes prove one.
+
+--upto K [--budget N] times, in place of the per-instance loop, Model.solve_many_clauses_upto(k=K) beside the ANY and the
+ALL call of the same rows and the same budget, the three interleaved in this process: what "is the timetable unique?"
+(K = 2) or "K alternatives per row" costs between the one row of ANY and the whole tree of ALL.  The seeded sample is
+re-checked against the host walk (tests/many_walk_clauses_upto.py), rows included.  With --sliced the slices are up-to-K
+calls (solve_many_clauses_sliced(max_solutions=K), --finish resume only) beside the one up-to-K call."""
 import argparse
 import json
 import os
@@ -59,8 +65,11 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--sliced", default=None, help="B1,B2,...: the budgets of the sliced route")
     ap.add_argument("--finish", default="resume", choices=("resume", "search"))
+    ap.add_argument("--upto", type=int, default=None, help="K: time solve_many_clauses_upto beside the ANY and the ALL call")
     ap.add_argument("--budget", type=int, default=None, help="the one call's budget (default: the set's, or the sum of --sliced)")
     args = ap.parse_args()
+    if args.upto is not None and (args.upto < 1 or args.finish == "search"):
+        ap.error("--upto K: K >= 1, and with --sliced --finish resume only")
     text, base, objective, budget = sets.build(args.set)
     budgets = tuple(int(b) for b in args.sliced.split(",")) if args.sliced else None
     if budgets:
@@ -79,7 +88,10 @@ def main():
     def many():
         torch.cuda.synchronize()
         t = time.perf_counter()
-        out = model.solve_many_clauses(dev, objective, max_nodes=budget)
+        if args.upto is not None:
+            out = model.solve_many_clauses_upto(dev, args.upto, max_nodes=budget)
+        else:
+            out = model.solve_many_clauses(dev, objective, max_nodes=budget)
         torch.cuda.synchronize()
         return time.perf_counter() - t, out
 
@@ -101,6 +113,8 @@ def main():
 
     if budgets:
         return sliced_route(args, model, text, roots, dev, objective, budget, budgets, many, rng, W)
+    if args.upto is not None:
+        return upto_route(args, model, text, roots, dev, budget, many, rng)
     for _ in range(2):  # warm-up: code load, workspace, the engine's buffers
         many()
     loop()
@@ -141,22 +155,74 @@ def main():
     return 0 if ok and same_optimum is not False else 1
 
 
+def upto_route(args, model, text, roots, dev, budget, upto, rng):
+    """the up-to-K call beside the ANY and the ALL call of the same rows, same budget, same build"""
+    import many_walk_clauses_upto as U
+    count = len(roots)
+
+    def under(objective):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = model.solve_many_clauses(dev, objective, max_nodes=budget)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    for _ in range(2):  # warm-up: code load, workspace
+        under("ANY"), upto(), under("ALL")
+    times = {"any": [], "upto": [], "all": []}
+    for _ in range(args.reps):
+        dt, first = under("ANY")
+        times["any"].append(dt)
+        dt, out = upto()
+        times["upto"].append(dt)
+        dt, every = under("ALL")
+        times["all"].append(dt)
+    host, first, every = ({k: v.cpu().numpy() for k, v in o.items() if torch.is_tensor(v)} for o in (out, first, every))
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    want = U.walk_many_upto(text, roots[picks], args.upto, budget)
+    ok = all((host[f][picks] == want[f]).all() for f in U.FIELDS) and bool((host["rows"][picks] == want["rows"]).all())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    found = np.minimum(host["solutions"], 2)
+    print(json.dumps({
+        "tool": "time_solve_many_clauses", "route": "upto", "commit": commit(), "command": " ".join(sys.argv), "set": args.set,
+        "instances": count, "max_nodes": budget, "max_solutions": args.upto, "n_vars": model.n_vars, "clauses": model.n_clauses,
+        "kernel": model.many_clauses_kernel(), "upto_kernel": model.many_clauses_upto_kernel(),
+        "waves": model.many_clauses_waves(count),
+        "any_ms": spread(times["any"]), "upto_ms": spread(times["upto"]), "all_ms": spread(times["all"]),
+        "upto_over_any": round(med["upto"] / med["any"], 3), "all_over_upto": round(med["all"] / med["upto"], 3),
+        "any_nodes": int(first["nodes"].sum()), "upto_nodes": int(host["nodes"].sum()), "all_nodes": int(every["nodes"].sum()),
+        "any_status_counts": np.bincount(first["status"], minlength=3).tolist(),
+        "upto_status_counts": np.bincount(host["status"], minlength=3).tolist(),
+        "all_status_counts": np.bincount(every["status"], minlength=3).tolist(),
+        "upto_largest_tree": int(host["nodes"].max()), "all_largest_tree": int(every["nodes"].max()),
+        "upto_solutions": int(host["solutions"].sum()), "all_solutions": int(every["solutions"].sum()),
+        "done_with_0_1_2_or_more_solutions": np.bincount(found[host["status"] == 0], minlength=3).tolist(),
+        "upto_instances_per_s": round(count / med["upto"]),
+        "oracle_checked": len(picks), "oracle_ok": bool(ok),
+    }))
+    return 0 if ok else 1
+
+
 def sliced_route(args, model, text, roots, dev, objective, budget, budgets, many, rng, W):
     count = len(roots)
     pool = model.many_clause_checkpoints(count)
+    upto = {} if args.upto is None else {"max_solutions": args.upto}
 
     def first_slice():
         pool.reset()
         torch.cuda.synchronize()
         t = time.perf_counter()
-        out = model.solve_many_clauses(dev, objective, max_nodes=budgets[0], checkpoints=pool)
+        if args.upto is not None:
+            out = model.solve_many_clauses_upto(dev, args.upto, max_nodes=budgets[0], checkpoints=pool)
+        else:
+            out = model.solve_many_clauses(dev, objective, max_nodes=budgets[0], checkpoints=pool)
         torch.cuda.synchronize()
         return time.perf_counter() - t, out
 
     def sliced():
         torch.cuda.synchronize()
         t = time.perf_counter()
-        out = model.solve_many_clauses_sliced(dev, objective, budgets=budgets, finish=args.finish, checkpoints=pool)
+        out = model.solve_many_clauses_sliced(dev, objective, budgets=budgets, finish=args.finish, checkpoints=pool, **upto)
         torch.cuda.synchronize()
         return time.perf_counter() - t, out
 
@@ -176,7 +242,11 @@ def sliced_route(args, model, text, roots, dev, objective, budget, budgets, many
     one = {k: v.cpu().numpy() for k, v in one.items() if torch.is_tensor(v)}
 
     picks = rng.choice(count, size=min(args.check, count), replace=False)
-    if args.finish == "resume":
+    if args.upto is not None:
+        import many_walk_clauses_upto as U
+        want = U.walk_many_upto(text, roots[picks], args.upto, sum(budgets))
+        ok = all((host[f][picks] == want[f]).all() for f in U.FIELDS) and bool((host["rows"][picks] == want["rows"]).all())
+    elif args.finish == "resume":
         want = W.walk_many(text, roots[picks], objective, sum(budgets))
         has = want["solutions"] > 0
         ok = all((host[f][picks] == want[f]).all() for f in W.FIELDS) and bool((host["first"][picks][has] == want["first"][has]).all())
@@ -193,8 +263,10 @@ def sliced_route(args, model, text, roots, dev, objective, budget, budgets, many
     t_many, t_sliced = statistics.median(many_times), statistics.median(sliced_times)
     print(json.dumps({
         "tool": "time_solve_many_clauses", "route": "sliced", "commit": commit(), "command": " ".join(sys.argv), "set": args.set,
-        "objective": objective, "instances": count, "n_vars": model.n_vars, "clauses": model.n_clauses,
+        "objective": objective if args.upto is None else None, "max_solutions": args.upto,
+        "instances": count, "n_vars": model.n_vars, "clauses": model.n_clauses,
         "kernel": model.many_clauses_kernel(), "resume_kernel": model.many_clauses_resume_kernel(),
+        "upto_kernel": model.many_clauses_upto_kernel(),
         "waves": model.many_clauses_waves(count), "slot_bytes": model.clause_checkpoint_bytes(),
         "one_call_max_nodes": budget, "one_call_status_counts": np.bincount(one["status"], minlength=3).tolist(),
         "one_call_nodes": int(one["nodes"].sum()), "one_call_largest_tree": int(one["nodes"].max()),
