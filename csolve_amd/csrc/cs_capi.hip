@@ -77,6 +77,7 @@ struct cs_kernel_plan {
   cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
   cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
   cs_planned walk_upto;            /* cs_walk_upto (csgpu_solve_many_clauses_upto and its two checkpoint calls): the same */
+  cs_planned walk_restart;         /* cs_walk_restart (csgpu_solve_many_clauses_restarts): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -110,10 +111,11 @@ struct csgpu_model {
   void *d_packed_tab; /* kernel 5: 16-bit table relative to the pushing variable */
   int *d_root_lo;
   int *d_root_hi;    /* csgpu_solve_many: a root row must lie inside the root domains */
-  /* csgpu_solve_many: the waves' stacks (sized at the first call, grown when a later call launches more waves) and the
-   * ticket counters of cs_dive_shave, which the kernel leaves at zero */
+  /* csgpu_solve_many: the waves' stacks (sized at the first call, grown when a later call needs more bytes: more waves,
+   * or the n + 1 frames per wave of cs_walk_restart after a call with n) and the ticket counters of cs_dive_shave, which
+   * the kernel leaves at zero */
   void *d_many_stack;
-  int64_t many_stack_waves;
+  size_t many_stack_bytes;
   unsigned *d_many_tickets;
   cs_val *d_walk_root; /* csgpu_solve_many_clauses: the root domains, which a root row must lie inside */
   int *d_sym_off;
@@ -319,7 +321,7 @@ static void free_device(csgpu_model *m) {
   m->d_root_hi = NULL;
   m->d_many_stack = NULL;
   m->d_many_tickets = NULL;
-  m->many_stack_waves = 0;
+  m->many_stack_bytes = 0;
   (void)hipFree(m->d_sym_off);
   (void)hipFree(m->d_sym_packed);
   (void)hipFree(m->d_dense_tab);
@@ -1016,6 +1018,17 @@ static int plan_general(csgpu_model *m) {
           m->plan.walk_upto.per_cu = occ;
         if (m->plan.walk_upto.per_cu < 1) m->plan.walk_upto.per_cu = 1;
       }
+      { /* cs_walk_restart: the same slices, its own registers */
+#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_restart<CPL, true> : (const void *)cs_walk_restart<CPL, false>)
+        const void *fn_rs = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
+#undef CS_PICKW
+        if ((rc = plan_kernel(&m->plan.walk_restart, fn_rs, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_rs, CS_BLOCK, m->plan.walk_restart.lds) == hipSuccess && occ >= 1 &&
+            occ < m->plan.walk_restart.per_cu)
+          m->plan.walk_restart.per_cu = occ;
+        if (m->plan.walk_restart.per_cu < 1) m->plan.walk_restart.per_cu = 1;
+      }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
   }
@@ -1618,21 +1631,23 @@ extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count
   return grid * k->waves;
 }
 
-/* the model's ticket counters and, for `waves` > 0, stacks for that many waves */
+/* the model's ticket counters and, for `waves` > 0, stacks of `frames` frames for that many waves.  The block is the
+ * whole family's and the families differ in their frames per wave: it grows by its bytes, not by its waves */
 static int many_workspace(csgpu_model *mm, int64_t waves, int frames) {
   const int n = mm->host->n_vars;
+  const size_t bytes = (size_t)waves * (size_t)frames * ((size_t)n + 1) * sizeof(cs_val);
   if (mm->d_many_tickets == NULL) {
     quiesce_servers();
     HIP_TRY(hipMalloc((void **)&mm->d_many_tickets, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
     HIP_TRY(hipMemset(mm->d_many_tickets, 0, (size_t)CS_DIVE_SHARDS * CS_DIVE_TICKET_STRIDE * sizeof(unsigned)));
   }
-  if (mm->many_stack_waves < waves) { /* one call in flight per model: nothing reads the old workspace */
+  if (mm->many_stack_bytes < bytes) { /* one call in flight per model: nothing reads the old workspace */
     quiesce_servers();
     if (mm->d_many_stack != NULL) (void)hipFree(mm->d_many_stack);
     mm->d_many_stack = NULL;
-    mm->many_stack_waves = 0;
-    HIP_TRY(hipMalloc(&mm->d_many_stack, (size_t)waves * (size_t)frames * ((size_t)n + 1) * sizeof(cs_val)));
-    mm->many_stack_waves = waves;
+    mm->many_stack_bytes = 0;
+    HIP_TRY(hipMalloc(&mm->d_many_stack, bytes));
+    mm->many_stack_bytes = bytes;
   }
   return CSGPU_OK;
 }
@@ -1934,14 +1949,18 @@ extern "C" int csgpu_internal_many_clauses_resume_symbol(const csgpu_model *m, c
 extern "C" int csgpu_internal_many_clauses_upto_symbol(const csgpu_model *m, char *buf, size_t len) {
   return many_clauses_symbol(m, m != NULL ? &m->plan.walk_upto : NULL, "cs_walk_upto", buf, len);
 }
+extern "C" int csgpu_internal_many_clauses_restart_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_restart : NULL, "cs_walk_restart", buf, len);
+}
 
 /* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
- * whose frames fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices fit a CU) */
-static int64_t many_clauses_waves(const csgpu_model *m, const cs_planned *k, int64_t count) {
+ * whose `frames` frames each fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices
+ * fit a CU) */
+static int64_t many_clauses_waves(const csgpu_model *m, const cs_planned *k, int64_t count, int frames) {
   const size_t n = (size_t)m->host->n_vars;
   int64_t grid = (int64_t)m->n_cus * k->per_cu;
   const int64_t by_count = (count + k->waves - 1) / k->waves;
-  const int64_t by_stack = (int64_t)(MANY_CLAUSES_STACK_MAX / ((size_t)k->waves * n * (n + 1) * sizeof(cs_val)));
+  const int64_t by_stack = (int64_t)(MANY_CLAUSES_STACK_MAX / ((size_t)k->waves * (size_t)frames * (n + 1) * sizeof(cs_val)));
   if (grid > by_count) grid = by_count;
   if (grid > by_stack) grid = by_stack;
   if (grid < 1) grid = 1;
@@ -1950,23 +1969,38 @@ static int64_t many_clauses_waves(const csgpu_model *m, const cs_planned *k, int
 
 extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64_t count) {
   if (!csgpu_model_qualifies_many_clauses(m) || count < 1) return 0;
-  return many_clauses_waves(m, &m->plan.walk, count);
+  return many_clauses_waves(m, &m->plan.walk, count, m->host->n_vars);
 }
 
-/* The one path of the six entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
+/* the restart entry's own arguments: its options in place of the other two, the seeds and the restart counts */
+struct many_clauses_rs {
+  const csgpu_many_restart_options *options;
+  const uint32_t *d_seeds;
+  int32_t *d_restarts;
+};
+
+/* The one path of the seven entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
  * has a pool and slot numbers and launches cs_walk_resume; `resume` (pooled, and no roots): the instances go on in their
  * slots, so the call needs no workspace.  An up-to-k entry brings `upto_options` in place of `options` (the other one is
- * NULL): the ALL walk by cs_walk_upto, pooled or not, its rows [count][max_solutions][n_vars] in d_solutions. */
+ * NULL): the ALL walk by cs_walk_upto, pooled or not, its rows [count][max_solutions][n_vars] in d_solutions.  The
+ * restart entry brings `rs` (else NULL) and neither of the two: the ANY walk by cs_walk_restart, one frame more per wave. */
 static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
-                             const csgpu_many_upto_options *upto_options, csgpu_many_result *d_results, int32_t *d_solutions,
-                             int32_t *d_best, int pooled, csgpu_many_checkpoints *ck, int32_t *d_slots, int resume, void *stream) {
-  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || (options == NULL && upto_options == NULL);
-  const int64_t max_nodes = null_arg ? 0 : (upto_options != NULL ? upto_options->max_nodes : options->max_nodes);
+                             const csgpu_many_upto_options *upto_options, const many_clauses_rs *rs, csgpu_many_result *d_results,
+                             int32_t *d_solutions, int32_t *d_best, int pooled, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                             int resume, void *stream) {
+  const csgpu_many_restart_options *rs_options = rs != NULL ? rs->options : NULL;
+  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL ||
+                       (options == NULL && upto_options == NULL && rs_options == NULL);
+  const int64_t max_nodes = null_arg ? 0 : (rs_options != NULL ? rs_options->max_nodes
+                                            : (upto_options != NULL ? upto_options->max_nodes : options->max_nodes));
   int rc;
   if ((rc = many_check_head(null_arg, count, max_nodes, pooled ? "slice" : "instance"))) return rc;
   if (upto_options != NULL && upto_options->max_solutions < 1)
     return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
-  const int objective = upto_options != NULL ? CS_OBJ_ALL : options->objective;
+  if (rs_options != NULL && rs_options->restart_base < 0) return set_err(CSGPU_E_ARG, "restart_base must not be negative (0: no restarts)");
+  if (rs_options != NULL && (rs_options->flags & ~CSGPU_MANY_ROTATE_FIRST) != 0)
+    return set_err(CSGPU_E_ARG, "unknown flags 0x%x", (unsigned)rs_options->flags);
+  const int objective = rs_options != NULL ? CS_OBJ_ANY : (upto_options != NULL ? CS_OBJ_ALL : options->objective);
   if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
     return set_err(CSGPU_E_ARG, "no objective %d", objective);
   if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX) {
@@ -1992,10 +2026,11 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   }
   if (count == 0) return CSGPU_OK;
   csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = upto_options != NULL ? &m->plan.walk_upto : (pooled ? &m->plan.walk_ck : &m->plan.walk);
+  const cs_planned *k = rs_options != NULL ? &m->plan.walk_restart
+                        : (upto_options != NULL ? &m->plan.walk_upto : (pooled ? &m->plan.walk_ck : &m->plan.walk));
   const int n = m->host->n_vars;
-  const int64_t waves = many_clauses_waves(m, k, count);
-  const int frames = n; /* at most n - 1 pushed frames and the current node's */
+  const int frames = rs_options != NULL ? n + 1 : n; /* at most n - 1 pushed frames and the current node's; cs_walk_restart: and the root node's */
+  const int64_t waves = many_clauses_waves(m, k, count, frames);
   if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
   cs_walk_io io;
   io.roots = (const cs_val *)d_roots;
@@ -2019,8 +2054,15 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   wk.code = upto_options != NULL ? CS_WALK_CK_UPTO : objective;
   wk.slots = pooled ? d_slots : NULL;
   int upto = upto_options != NULL ? upto_options->max_solutions : 0;
+  cs_dive_rs dr;
+  dr.seeds = rs != NULL ? rs->d_seeds : NULL;
+  dr.restarts = rs != NULL ? rs->d_restarts : NULL;
+  dr.restart_base = rs_options != NULL ? (long long)rs_options->restart_base : 0;
+  dr.seed = rs_options != NULL ? rs_options->seed : 0u;
+  dr.flags = rs_options != NULL ? rs_options->flags : 0;
   cs_tables tab = m->tab;
-  void *args[] = { &tab, &io, &wk, &upto }; /* cs_walk_clauses takes the first two, cs_walk_resume the first three */
+  /* cs_walk_clauses takes the first two, cs_walk_resume the first three; cs_walk_restart: the tables, io and `dr` */
+  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (void *)&wk, &upto };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
@@ -2028,7 +2070,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
 extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                         const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
                                         int32_t *d_best, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, stream);
 }
 
 /* ---- clause checkpoints: csgpu_solve_many_clauses in slices (cs_walk_resume) ---- */
@@ -2058,13 +2100,13 @@ extern "C" int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const
                                                      const csgpu_many_options *options, csgpu_many_result *d_results,
                                                      int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
                                                      int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
                                                csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
                                                csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, options, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, stream);
+  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, stream);
 }
 
 extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
@@ -2084,20 +2126,33 @@ extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints 
 extern "C" int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                              const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                              int32_t *d_solutions, void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, d_results, d_solutions, NULL, 0, NULL, NULL, 0, stream);
+  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 0, NULL, NULL, 0, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                                           const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                                           int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                                           void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, d_results, d_solutions, NULL, 1, ck, d_slots, 0, stream);
+  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 0, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
                                                     csgpu_many_result *d_results, int32_t *d_solutions,
                                                     csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, NULL, options, d_results, d_solutions, NULL, 1, ck, d_slots, 1, stream);
+  return many_clauses_call(m, NULL, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 1, stream);
+}
+
+/* ---- Luby restarts with a seeded value order for ANY instances of a clause model (cs_walk_restart) ---- */
+
+extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csgpu_val *d_roots, const uint32_t *d_seeds,
+                                                 int64_t count, const csgpu_many_restart_options *options,
+                                                 csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_restarts,
+                                                 void *stream) {
+  many_clauses_rs rs;
+  rs.options = options;
+  rs.d_seeds = d_seeds;
+  rs.d_restarts = d_restarts;
+  return many_clauses_call(m, d_roots, count, NULL, NULL, &rs, d_results, d_solutions, NULL, 0, NULL, NULL, 0, stream);
 }
 
 #ifdef CS_SHAVE_TIMELINE

@@ -71,6 +71,8 @@ int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64_t count);
 int csgpu_internal_many_clauses_resume_symbol(const csgpu_model *m, char *buf, size_t len);
 /* and for cs_walk_upto (csgpu_solve_many_clauses_upto / _upto_checkpointed / _upto_resume) */
 int csgpu_internal_many_clauses_upto_symbol(const csgpu_model *m, char *buf, size_t len);
+/* and for cs_walk_restart (csgpu_solve_many_clauses_restarts) */
+int csgpu_internal_many_clauses_restart_symbol(const csgpu_model *m, char *buf, size_t len);
 
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */
 typedef struct csgpu_step_launch {

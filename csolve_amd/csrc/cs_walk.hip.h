@@ -61,7 +61,15 @@
  * row 0.  The header's code is CS_WALK_CK_UPTO, so a checkpoint of this kernel and one of cs_walk_resume refuse each
  * other (CSGPU_MANY_BAD_SLOT).  A resumed instance continues its rows at index `solutions` of its record, with the k of
  * the call; one that holds k already ends DONE before it tries a node, with only its status word and slot number
- * written. */
+ * written.
+ *
+ * Restarts (cs_walk_restart, csgpu_solve_many_clauses_restarts): the same loop a fourth time, CS_WALK_RESTART 1, ANY only
+ * and without checkpoints; what cs_dive_restart is to cs_dive_shave.  A node tries its values in the rotation of
+ * cs_many_start / cs_many_rotated (cs_arith.h) that depends on (seed of the instance, run, variable), and after more than
+ * threshold x restart_base failed children the walk starts again from the root node's fixpoint with run + 1 and the next
+ * Luby threshold.  Counters and the budget run over all runs; a restart costs no node and no rounds.  Frame 0 cannot keep
+ * the root: a node's last-value child takes its parent's frame.  So the call has n + 1 frames per wave, the walk stays
+ * below frame n, and frame n holds the root fixpoint, every lane the entries it owns.  Everything new is a scalar. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
 
@@ -91,7 +99,9 @@ template <int CPL, bool HAS_TREE>
 __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk_io io) {
 #define CS_WALK_CK 0
 #define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
 #undef CS_WALK_CK
 }
@@ -115,7 +125,9 @@ template <int CPL, bool HAS_TREE>
 __global__ __launch_bounds__(CS_BLOCK) void cs_walk_resume(cs_tables T, cs_walk_io io, cs_walk_ck ck) {
 #define CS_WALK_CK 1
 #define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
 #undef CS_WALK_CK
 }
@@ -125,7 +137,22 @@ template <int CPL, bool HAS_TREE>
 __global__ __launch_bounds__(CS_BLOCK) void cs_walk_upto(cs_tables T, cs_walk_io io, cs_walk_ck ck, int upto) {
 #define CS_WALK_CK 1
 #define CS_WALK_UPTO 1
+#define CS_WALK_RESTART 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+/* the ANY walk with a seeded value order and Luby restarts (csgpu_solve_many_clauses_restarts): `rs` is cs_dive_restart's;
+ * io.frames is n + 1, the last frame the root node's fixpoint */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_restart(cs_tables T, cs_walk_io io, cs_dive_rs rs) {
+#define CS_WALK_CK 0
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
 #undef CS_WALK_CK
 }

@@ -1,8 +1,9 @@
-/* cs_walk_body.hip.h -- the body of the three kernels of cs_walk.hip.h, which includes it inside each of them under two
- * switches:            CS_WALK_CK  CS_WALK_UPTO
- *   cs_walk_clauses        0           0        csgpu_solve_many_clauses
- *   cs_walk_resume         1           0        one more argument, `ck`: the pool and the slots of the call
- *   cs_walk_upto           1           1        and `upto` (k >= 1, a scalar)
+/* cs_walk_body.hip.h -- the body of the four kernels of cs_walk.hip.h, which includes it inside each of them under three
+ * switches:            CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART
+ *   cs_walk_clauses        0           0              0        csgpu_solve_many_clauses
+ *   cs_walk_resume         1           0              0        one more argument, `ck`: the pool and the slots of the call
+ *   cs_walk_upto           1           1              0        and `upto` (k >= 1, a scalar)
+ *   cs_walk_restart        0           0              1        one more argument, `rs` (the walk is defined in csolve_gpu.h)
  * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of a switch stands under its `#if`, so a kernel
  * that defines it 0 sees the text it saw before the switch was there and compiles to the same instructions.
  * CS_WALK_CK: an instance that stops at its budget leaves its frames, its current node, {bv, nv} and its incumbent in a
@@ -10,7 +11,12 @@
  * are then their stacks.  New per-instance state is scalars only: slot, kept, depth0, nodes0, resumed, stack.
  * CS_WALK_UPTO: the ALL walk, left right after the k-th solution; solution j goes to row j of the instance's k rows, and
  * ck.capacity == 0 means "no pool" (pool, next and slots are not touched), so the one kernel serves the plain, the
- * checkpointed and the resume call.  It adds no per-instance state: the row index is inst, upto and sols, all scalar. */
+ * checkpointed and the resume call.  It adds no per-instance state: the row index is inst, upto and sols, all scalar.
+ * CS_WALK_RESTART: the ANY walk with a seeded rotation of every node's value order and Luby restarts, as CS_DIVE_RESTART
+ * of cs_dive_body.hip.h.  nv is j, not a value, and a frame's 8-byte entry {variable, next j}; the call has n + 1 frames
+ * per wave, the walk stays below frame n (io.frames - 1), and frame n keeps the root node's fixpoint, which a restart
+ * reads back into the slice and into frame 0, every lane the entries it wrote itself.  A restart is no `continue` of the
+ * ticket loop.  New per-instance state is scalars only: run, fails, threshold, counter, seed, restarts, start, width. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -48,6 +54,13 @@
     const int inst = (int)t * nsh + shard;
     const size_t rrow = (size_t)inst * (size_t)n;
 
+#if CS_WALK_RESTART
+    unsigned run = 0u, rs_seed = rs.seed, start = 0u, width = 1u; /* scalars, as everything the restarts add */
+    int restarts = 0;
+    uint64_t fails = 0u, threshold = 1u, counter = 1u;
+    if (rs.seeds != nullptr) rs_seed = (unsigned)__builtin_amdgcn_readfirstlane((int)rs.seeds[inst]);
+    cs_val *const root_f = wave_stack + (size_t)(io.frames - 1) * fstride; /* the frame the walk leaves alone */
+#endif
 #if CS_WALK_CK
     /* the instance's slot (-1: none yet), the slot a checkpoint was written to in this launch, the stack the instance
      * walks on and, resuming, the checkpoint's depth and incumbent */
@@ -193,10 +206,23 @@
             for (int v = lane; v < n; v += CS_WAVE) dom[v] = f[v];
             cs_wave_sync();
           }
+#if CS_WALK_RESTART
+          /* where the value order of this node starts, from scalars: the node as it was entered is in the slice */
+          const int xlo = __builtin_amdgcn_readfirstlane(dom[bv].lo), xhi = __builtin_amdgcn_readfirstlane(dom[bv].hi);
+          width = (unsigned)xhi - (unsigned)xlo + 1u;
+          start = (unsigned)cs_many_value(rs_seed, run, bv, cs_interval(xlo, xhi), 0u, rs.flags) - (unsigned)xlo;
+          last = (unsigned)nv == width - 1u;
+          const int value = cs_many_rotated(xlo, width, start, (unsigned)nv);
+#else
           last = nv == __builtin_amdgcn_readfirstlane(dom[bv].hi);
+#endif
           cs_wave_sync();
           if (lane == 0) {
+#if CS_WALK_RESTART
+            dom[bv] = cs_interval(value, value);
+#else
             dom[bv] = cs_interval(nv, nv); /* the assignment: not counted in PROPS */
+#endif
             if (have_best) dom[io.obj_var] = cs_objective_bound(io.sense, dom[io.obj_var], best);
           }
         }
@@ -253,19 +279,63 @@
           if (!io.all || at_root) break; /* ANY, or the root node was the one solution */
 #endif
         }
+#if CS_WALK_RESTART
+        /* the root node's fixpoint, for the restarts */
+        if (at_root && descend && rs.restart_base > 0)
+          for (int v = lane; v < n; v += CS_WAVE) root_f[v] = dom[v];
+        /* a failed child, unless it ends the whole tree: one more failure of this run, and past threshold x base the walk
+         * starts again from the root node's fixpoint, with the next run's rotation.  No node, no rounds, no ticket: the
+         * instance's own loop goes on. */
+        bool again = false;
+        if (!at_root && failed && !(last && depth == 0) && rs.restart_base > 0) {
+          fails++;
+          again = fails > threshold * (uint64_t)rs.restart_base;
+        }
+        if (again) {
+          fails = 0u;
+          cs_luby_next(&threshold, &counter);
+          run++;
+          restarts++;
+          depth = 0;
+          f = wave_stack;
+          cs_wave_sync(); /* every lane has left the failed child */
+          kw = 0xffffffffu; kv = 0xffffffffu;
+          for (int v = lane; v < n; v += CS_WAVE) { /* the root has an open variable, or it would not have been kept */
+            const cs_val d = root_f[v];
+            dom[v] = d;
+            f[v] = d;
+            const unsigned w = (unsigned)d.hi - (unsigned)d.lo;
+            if (d.lo != d.hi && w < kw) { kw = w; kv = (unsigned)v; }
+          }
+          cs_wave_sync();
+          const unsigned wmin = cs_wave_min_u32(kw);
+          bv = (int)cs_wave_min_u32(kw == wmin ? kv : 0xffffffffu);
+          if ((unsigned)bv >= (unsigned)n) { status = 1; break; } /* cannot happen: never index past the node */
+          nv = 0;
+          fresh = true;
+        } else
+#endif
         if (descend) {
           if (!at_root && !last) { /* the parent comes back for its next value */
             if (lane == 0) f[n] = cs_interval(bv, nv + 1);
             depth++;
             f += fstride;
           }
+#if CS_WALK_RESTART
+          if (depth >= io.frames - 1) { status = 1; break; } /* cannot happen (frames = n + 1); the last frame is the root node's */
+#else
           if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames = n): never write past the slice */
+#endif
           for (int v = lane; v < n; v += CS_WAVE) f[v] = dom[v];
           const unsigned wmin = cs_wave_min_u32(kw);
           bv = (int)cs_wave_min_u32(kw == wmin ? kv : 0xffffffffu);
           /* cannot happen (an open variable exists): never index past the node */
           if ((unsigned)bv >= (unsigned)n) { status = 1; break; }
+#if CS_WALK_RESTART
+          nv = 0; /* j, not a value */
+#else
           nv = __builtin_amdgcn_readfirstlane(dom[bv].lo);
+#endif
           fresh = true;
         } else if (last) { /* the node's values are used up */
           if (depth == 0) break;
@@ -289,6 +359,9 @@
       res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
       io.results[inst] = res;
       if (have_best && io.best != nullptr) io.best[inst] = best;
+#if CS_WALK_RESTART
+      if (rs.restarts != nullptr) rs.restarts[inst] = restarts;
+#endif
 #if CS_WALK_UPTO
       if (ck.capacity > 0)
 #endif

@@ -354,12 +354,19 @@ class Model:
         node counts of 9x9 sudokus on the host.  roots, solutions, stream: as solve_many.
         -> the dict of solve_many plus `restarts` [K] int32 (restarts=False: not counted, d_restarts is NULL); solutions
         may be an int32 device tensor [K, n_vars] to write into."""
-        L = load_library()
+        return self._solve_many_restarts("csgpu_solve_many_restarts", None, roots, max_nodes, restart_base, seed, seeds,
+                                         rotate_first, solutions, restarts, stream)
+
+    def _solve_many_restarts(self, entry, qualifies, roots, max_nodes, restart_base, seed, seeds, rotate_first, solutions,
+                             restarts, stream) -> dict:
+        """solve_many_restarts / solve_many_clauses_restarts: `entry` of the library, which takes the same arguments in
+        both families; `qualifies` as _many_roots takes it"""
+        call = getattr(load_library(), entry)
         n = self.n_vars
         opt = ManyRestartOptions(int(max_nodes), int(restart_base), int(seed) & 0xffffffff,
                                  MANY_ROTATE_FIRST if rotate_first else 0)
         roots, K = self._many_roots(roots, restart_base < 0, lambda ptr, count: check(
-            L.csgpu_solve_many_restarts(self._h, ptr, None, count, C.byref(opt), ptr, None, None, None)))
+            call(self._h, ptr, None, count, C.byref(opt), ptr, None, None, None)), qualifies=qualifies)
         if seeds is not None:
             if not torch.is_tensor(seeds):
                 seeds = torch.from_numpy((np.asarray(seeds).astype(np.int64) & 0xffffffff).astype(np.uint32).view(np.int32))
@@ -368,10 +375,9 @@ class Model:
         buf = self._many_records(K, roots.device)
         first = self._many_rows(solutions, (K, n), "[K, n_vars]", roots.device)
         count = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if restarts else None
-        check(L.csgpu_solve_many_restarts(self._h, roots.data_ptr() if K else buf.data_ptr(),
-                                          seeds.data_ptr() if seeds is not None and K else None, K, C.byref(opt),
-                                          buf.data_ptr(), first.data_ptr() if first is not None and K else None,
-                                          count.data_ptr() if restarts else None, _stream_ptr(stream)))
+        check(call(self._h, roots.data_ptr() if K else buf.data_ptr(), seeds.data_ptr() if seeds is not None and K else None,
+                   K, C.byref(opt), buf.data_ptr(), first.data_ptr() if first is not None and K else None,
+                   count.data_ptr() if restarts else None, _stream_ptr(stream)))
         out = self._many_answer(buf, K, first)
         if restarts:
             out["restarts"] = count[:K]
@@ -451,6 +457,25 @@ class Model:
         what resume_many_clauses() continues (csgpu_solve_many_clauses_upto_checkpointed)."""
         return self._solve_many_upto("csgpu_solve_many_clauses_upto", self.qualifies_many_clauses(), roots, k, max_nodes,
                                      solutions, stream, checkpoints)
+
+    def solve_many_clauses_restarts(self, roots, *, max_nodes, restart_base=1, seed=0, seeds=None, rotate_first=False,
+                                    solutions=True, restarts=True, stream=None) -> dict:
+        """solve_many_clauses under ANY with Luby restarts and a seeded value order (csgpu_solve_many_clauses_restarts):
+        what solve_many_restarts is to solve_many, for the clause models.  A node tries its values in a rotation of the
+        ascending order that depends on (seed of the instance, run, variable), and after more than threshold x
+        restart_base failed children -- thresholds 1 1 2 1 1 2 4 ... -- the walk starts again from the root node's
+        fixpoint with the next run's rotations.  The first run is the ascending walk of solve_many_clauses unless
+        rotate_first; restart_base=0 is that call under ANY, field for field.  ANY only: "<obj>" is an ordinary variable.
+        The default base of 1 has the fewest nodes in all of 1, 2, 4 .. 32 on three batches of schedule rows walked on
+        the host; the 32 of solve_many_restarts costs 3.5 times as many there.  roots, max_nodes, seed,
+        seeds, solutions, restarts, stream: as solve_many_restarts; the model must satisfy qualifies_many_clauses().
+        -> the dict of solve_many_clauses under ANY plus `restarts` [K] int32."""
+        return self._solve_many_restarts("csgpu_solve_many_clauses_restarts", self.qualifies_many_clauses(), roots, max_nodes,
+                                         restart_base, seed, seeds, rotate_first, solutions, restarts, stream)
+
+    def many_clauses_restart_kernel(self):
+        """the cs_walk_restart instantiation solve_many_clauses_restarts launches, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_restart_symbol")
 
     def many_clauses_upto_kernel(self):
         """the cs_walk_upto instantiation solve_many_clauses_upto and its checkpoint calls launch, or None"""

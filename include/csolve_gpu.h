@@ -484,8 +484,8 @@ int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int
  * a pool created for another model, a pool of csgpu_many_checkpoints_create -> CSGPU_E_ARG; then count == 0 -> CSGPU_OK,
  * nothing is launched.  csgpu_many_clause_checkpoints_create: as csgpu_many_checkpoints_create, CSGPU_E_LIMIT for a
  * model that does not qualify for csgpu_solve_many_clauses.
- * Not here: restarts for clause models.  This note used to read "Not here: up to k solutions and restarts for clause
- * models": its first half is closed, up to k solutions are the next section. */
+ * This note used to read "Not here: restarts for clause models", and before that "Not here: up to k solutions and restarts
+ * for clause models": both halves are closed, up to k solutions are the next section and restarts the one after it. */
 size_t csgpu_many_clause_checkpoint_bytes(const csgpu_model *m); /* bytes per slot; 0 if the model does not qualify (at most
                                                                     512 clauses, slices that fit), and for NULL.  No HIP
                                                                     call: after finalize, or after
@@ -541,6 +541,46 @@ int csgpu_solve_many_clauses_upto_checkpointed(const csgpu_model *m, const csgpu
 int csgpu_solve_many_clauses_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
                                          csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
                                          int32_t *d_slots, void *stream);
+
+/* ---- Luby restarts with a seeded value order for ANY instances of a clause model ----
+ * What "Luby restarts with a seeded value order, for ANY" above is to csgpu_solve_many, for the clause models: the deep
+ * instances of a batch of schedule rows are the heavy tail of a fixed ascending value order.  The walk is
+ * csgpu_solve_many_clauses under ANY ("The walk" above) with exactly the two changes of csgpu_solve_many_restarts, per
+ * instance.  State: run = 0, fails = 0, Luby state threshold = 1, counter = 1 (csgpu_luby_next).
+ *   value order   a node that branches on variable v with [lo, hi] tries
+ *                 csgpu_many_value(seed_i, run, v, {lo, hi}, j, flags) for j = 0 .. hi - lo: the rotation
+ *                 lo + ((start + j) mod width) defined above, its width-0 case included.  start = 0 in run 0 unless
+ *                 CSGPU_MANY_ROTATE_FIRST is set.  seed_i = d_seeds[i], or options->seed where d_seeds is NULL.  A
+ *                 frame's 8-byte entry holds {variable, next j}, not {variable, next value}; `last` is j == hi - lo of
+ *                 the node as it was entered.
+ *   restart       after a child fails and the cut is counted: if it was the node's last value and no frame is pushed
+ *                 (last && depth == 0): DONE with 0 solutions, proven, no restart.  Otherwise, when restart_base > 0:
+ *                 fails++, and if fails > threshold * restart_base (in 64 bits): fails = 0,
+ *                 csgpu_luby_next(&threshold, &counter), run++, restarts++, and the walk starts again from the root
+ *                 node's fixpoint at depth 0, the branching variable selected anew, j = 0.  No node is counted and no
+ *                 rounds are run for it: the stored root is at its fixpoint.  root_props is counted once; nodes, cuts
+ *                 and props accumulate over the runs and max_nodes is their total.
+ * Everything else is csgpu_solve_many_clauses's under ANY: the root check and BAD_ROOT, an inconsistent or all-valued
+ * root, the branching rule, the budget compared before a child is tried, and "<obj>" as an ordinary variable.
+ * restart_base = 0 with flags 0 is csgpu_solve_many_clauses under ANY, field for field and row for row, and so is every
+ * instance whose first run ends before its first restart.
+ * ANY only: under MIN / MAX only a run that walks the whole tree proves anything, and restarts make that proof dearer;
+ * ALL and up to k enumerate.  The options struct, csgpu_many_restart_options, cannot express another objective.  There
+ * are no checkpoints: the walk is deterministic, an instance that ends LIMIT is run again with a larger budget.
+ *   d_seeds       NULL, or [count] uint32
+ *   d_solutions   NULL, or [count][n_vars] int32: the solution of an instance that found one, else not touched
+ *   d_restarts    NULL, or [count] int32: the restarts of every instance (0 for a BAD_ROOT row)
+ * A wave has n_vars + 1 frames here: the walk's n_vars and one that keeps the root node's fixpoint.  Workspace and
+ * tickets are the model's: ONE call of the whole csgpu_solve_many family in flight per model; calls of all families may
+ * be queued behind each other on one stream without the host in between.
+ * Errors before any HIP call, in the family's order: null model / roots / results / options, count < 0, max_nodes <= 0,
+ * restart_base < 0, a flag bit other than CSGPU_MANY_ROTATE_FIRST -> CSGPU_E_ARG; model not finalized -> CSGPU_E_STATE;
+ * a model that does not qualify for csgpu_solve_many_clauses, or count > 2^31 - 65 -> CSGPU_E_LIMIT.  count == 0 ->
+ * CSGPU_OK, nothing is launched. */
+int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csgpu_val *d_roots, const uint32_t *d_seeds, int64_t count,
+                                      const csgpu_many_restart_options *options, csgpu_many_result *d_results,
+                                      int32_t *d_solutions /* NULL or [count][n_vars] */,
+                                      int32_t *d_restarts /* NULL or [count] */, void *stream);
 
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */

@@ -22,7 +22,14 @@ sliced answers of the seeded sample are re-checked against the host walk: field 
 ALL call of the same rows and the same budget, the three interleaved in this process: what "is the timetable unique?"
 (K = 2) or "K alternatives per row" costs between the one row of ANY and the whole tree of ALL.  The seeded sample is
 re-checked against the host walk (tests/many_walk_clauses_upto.py), rows included.  With --sliced the slices are up-to-K
-calls (solve_many_clauses_sliced(max_solutions=K), --finish resume only) beside the one up-to-K call."""
+calls (solve_many_clauses_sliced(max_solutions=K), --finish resume only) beside the one up-to-K call.
+
+--restarts BASE [--rotate-first] [--budget N] times Model.solve_many_clauses_restarts(restart_base=BASE) beside the ANY call
+of the same rows and the same budget (default 20,000), and the restart call with base 0 -- which is the ANY walk -- beside
+both, the three interleaved in this process.  The rows are not a set of the tests: --count windows of problems.schedule(10,
+1) as tests/many_clause_restart_sets.py draws its tail workload (width 30, at most 40 values for `end`, rows seed 11), walk
+seed 7.  A launch lasts as long as its deepest instance: the output has the deepest walk and the nodes in all of both
+calls.  The seeded sample is re-checked against the host walk (tests/many_walk_clauses_restarts.py)."""
 import argparse
 import json
 import os
@@ -67,7 +74,13 @@ def main():
     ap.add_argument("--finish", default="resume", choices=("resume", "search"))
     ap.add_argument("--upto", type=int, default=None, help="K: time solve_many_clauses_upto beside the ANY and the ALL call")
     ap.add_argument("--budget", type=int, default=None, help="the one call's budget (default: the set's, or the sum of --sliced)")
+    ap.add_argument("--restarts", type=int, default=None, help="BASE: time solve_many_clauses_restarts beside the ANY call")
+    ap.add_argument("--rotate-first", action="store_true", help="with --restarts: run 0 rotates as well")
     args = ap.parse_args()
+    if args.restarts is not None:
+        if args.restarts < 0 or args.sliced or args.upto is not None:
+            ap.error("--restarts BASE: BASE >= 0, without --sliced and --upto")
+        return restart_route(args)
     if args.upto is not None and (args.upto < 1 or args.finish == "search"):
         ap.error("--upto K: K >= 1, and with --sliced --finish resume only")
     text, base, objective, budget = sets.build(args.set)
@@ -153,6 +166,71 @@ def main():
         "oracle_checked": len(picks), "oracle_ok": bool(ok),
     }))
     return 0 if ok and same_optimum is not False else 1
+
+
+def restart_route(args):
+    """the restart call beside the ANY call of the same rows, same budget, same build; and base 0 beside both"""
+    import many_clause_restart_sets as rsets
+    import many_clause_sets as sets
+    import many_walk_clauses_restarts as R
+    from csolve_amd import problems
+    tasks, width, deadline, _ = rsets.TAIL["schedule10"]
+    text = problems.schedule(tasks, 1)
+    roots = np.ascontiguousarray(sets.windows(text, args.count, 11, width, sets._starts(deadline)), dtype=np.int32)
+    count, budget, seed = len(roots), args.budget or rsets.TAIL_BUDGET, rsets.TAIL_SEED
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+    rng = np.random.default_rng(args.seed)
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    calls = {
+        "any": lambda: model.solve_many_clauses(dev, "ANY", max_nodes=budget),
+        "base0": lambda: model.solve_many_clauses_restarts(dev, max_nodes=budget, restart_base=0, seed=seed),
+        "restarts": lambda: model.solve_many_clauses_restarts(dev, max_nodes=budget, restart_base=args.restarts, seed=seed,
+                                                              rotate_first=args.rotate_first),
+    }
+    for _ in range(2):  # warm-up: code load, workspace
+        for call in calls.values():
+            timed(call)
+    times, outs = {k: [] for k in calls}, {}
+    for _ in range(args.reps):
+        for k, call in calls.items():
+            dt, outs[k] = timed(call)
+            times[k].append(dt)
+    host = {k: {f: v.cpu().numpy() for f, v in o.items() if torch.is_tensor(v)} for k, o in outs.items()}
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    want = R.walk_many_restarts(text, roots[picks], args.restarts, seed=seed, rotate_first=args.rotate_first, max_nodes=budget)
+    has = want["solutions"] > 0
+    got = host["restarts"]
+    ok = all((got[f][picks] == want[f]).all() for f in ("status", "nodes", "cuts", "solutions", "restarts")) and \
+        bool((got["first"][picks][has] == want["first"][has]).all())
+    same = all(bool((host["base0"][f] == host["any"][f]).all()) for f in ("status", "root_props", "nodes", "cuts", "props", "solutions", "first"))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    record = {
+        "tool": "time_solve_many_clauses", "route": "restarts", "commit": commit(), "command": " ".join(sys.argv),
+        "rows": f"schedule({tasks},1), width {width}, deadline {deadline}, rows seed 11", "walk_seed": seed,
+        "restart_base": args.restarts, "rotate_first": bool(args.rotate_first), "instances": count, "max_nodes": budget,
+        "n_vars": model.n_vars, "clauses": model.n_clauses, "kernel": model.many_clauses_kernel(),
+        "restart_kernel": model.many_clauses_restart_kernel(), "waves": model.many_clauses_waves(count),
+        "any_ms": spread(times["any"]), "base0_ms": spread(times["base0"]), "restarts_ms": spread(times["restarts"]),
+        "any_over_restarts": round(med["any"] / med["restarts"], 2), "base0_over_any": round(med["base0"] / med["any"], 3),
+        "base0_equals_any": same,
+    }
+    for k in ("any", "restarts"):
+        h = host[k]
+        record.update({f"{k}_status_counts": np.bincount(h["status"], minlength=3).tolist(), f"{k}_nodes": int(h["nodes"].sum()),
+                       f"{k}_deepest": int(h["nodes"].max()), f"{k}_nodes_p50_p99_p999": [int(np.percentile(h["nodes"], q)) for q in (50, 99, 99.9)],
+                       f"{k}_solutions": int(h["solutions"].sum())})
+    record.update({"restarted": int((got["restarts"] > 0).sum()), "most_restarts": int(got["restarts"].max()),
+                   "oracle_checked": len(picks), "oracle_ok": bool(ok)})
+    print(json.dumps(record))
+    return 0 if ok and same else 1
 
 
 def upto_route(args, model, text, roots, dev, budget, upto, rng):
