@@ -71,6 +71,15 @@ class ManyRestartOptions(C.Structure):
     _fields_ = [("max_nodes", C.c_int64), ("restart_base", C.c_int64), ("seed", C.c_uint32), ("flags", C.c_int32)]
 
 
+MANY_FULL = 4         # CSGPU_MANY_FULL: stopped because the solution stream had no room
+MANY_SLOT_FRESH = -2  # CSGPU_MANY_SLOT_FRESH: d_slots[i] on entry, start instance i from its root row
+
+
+class ManyStream(C.Structure):
+    """csgpu_many_stream: the solution stream of csgpu_solve_many_stream, caller-owned device memory"""
+    _fields_ = [("d_rows", C.c_void_p), ("d_owner", C.c_void_p), ("d_count", C.c_void_p), ("capacity", C.c_int64)]
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Names of every function declared in include/csolve_gpu.h."""
     text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
@@ -241,6 +250,8 @@ def load_library():
     L.csgpu_internal_many_upto_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_restarts.argtypes = [vp, vp, vp, i64, C.POINTER(ManyRestartOptions), vp, vp, vp, vp]
     L.csgpu_internal_many_restart_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many_stream.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, C.POINTER(ManyStream), vp]
+    L.csgpu_internal_many_stream_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_clauses.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp]
     L.csgpu_model_qualifies_many_clauses.argtypes = [vp]
     L.csgpu_internal_many_clauses_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]

@@ -56,9 +56,10 @@ struct cs_planned {
   int per_cu;     /* resident workgroups per CU */
 };
 
-/* the kernels of the csgpu_solve_many family (cs_dive.hip.h): one loop, compiled four times */
-enum { MANY_PLAIN, MANY_CK, MANY_UPTO, MANY_RESTART, MANY_FAMILIES };
-static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "cs_dive_resume", "cs_dive_upto", "cs_dive_restart" };
+/* the kernels of the csgpu_solve_many family (cs_dive.hip.h): one loop, compiled five times */
+enum { MANY_PLAIN, MANY_CK, MANY_UPTO, MANY_RESTART, MANY_STREAM, MANY_FAMILIES };
+static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "cs_dive_resume", "cs_dive_upto", "cs_dive_restart",
+                                                             "cs_dive_stream" };
 
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
 struct cs_kernel_plan {
@@ -73,7 +74,7 @@ struct cs_kernel_plan {
   cs_planned shave, shave_trace;   /* kernel 7 (the instantiation whose FULL matches the model); its tracing variant */
   cs_planned server;               /* the resident single-node server */
   cs_planned step_shave, step_packed, step_import;
-  cs_planned dive[MANY_FAMILIES];  /* by MANY_*: all four or none; not among csgpu_internal_plan_symbol's families */
+  cs_planned dive[MANY_FAMILIES];  /* by MANY_*: all five or none; not among csgpu_internal_plan_symbol's families */
   cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
   cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
   cs_planned walk_upto;            /* cs_walk_upto (csgpu_solve_many_clauses_upto and its two checkpoint calls): the same */
@@ -814,6 +815,7 @@ static const void *dive_kernel(int family, int width, int n_vars) {
   case MANY_CK: CS_PICK(cs_dive_resume)       /* with checkpoints (csgpu_solve_many_checkpointed / _resume) */
   case MANY_UPTO: CS_PICK(cs_dive_upto)       /* leaving at the k-th solution (csgpu_solve_many_upto and its two checkpoint calls) */
   case MANY_RESTART: CS_PICK(cs_dive_restart) /* ANY with a seeded value order and Luby restarts (csgpu_solve_many_restarts) */
+  case MANY_STREAM: CS_PICK(cs_dive_stream)   /* ALL, every solution appended to a shared stream (csgpu_solve_many_stream) */
   default: CS_PICK(cs_dive_shave)
   }
 #undef CS_PICK
@@ -1340,6 +1342,7 @@ extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_
 extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_CK, buf, len); }
 extern "C" int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_UPTO, buf, len); }
 extern "C" int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_RESTART, buf, len); }
+extern "C" int csgpu_internal_many_stream_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_STREAM, buf, len); }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
   if (m != NULL) const_cast<csgpu_model *>(m)->engines += delta;
@@ -1624,7 +1627,7 @@ enum { MANY_POOL_DIVE, MANY_POOL_WALK };
 
 extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count) {
   if (m == NULL || !m->finalized || m->plan.dive[MANY_PLAIN].fn == NULL || count < 1) return 0;
-  const cs_planned *k = &m->plan.dive[MANY_PLAIN]; /* the four are planned alike */
+  const cs_planned *k = &m->plan.dive[MANY_PLAIN]; /* the five are planned alike */
   int64_t grid = (int64_t)m->n_cus * k->per_cu;
   const int64_t by_count = (count + k->waves - 1) / k->waves;
   if (grid > by_count) grid = by_count;
@@ -1915,6 +1918,29 @@ extern "C" int csgpu_solve_many_restarts(const csgpu_model *m, const csgpu_val *
   rs.seed = options->seed;
   rs.flags = options->flags;
   return many_launch(m, MANY_RESTART, d_roots, count, options->max_nodes, 0, d_results, d_solutions, 0, stream, &rs, NULL);
+}
+
+/* ---- every solution of every instance under ALL, through one bounded stream (cs_dive_stream) ---- */
+
+extern "C" int csgpu_solve_many_stream(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                       const csgpu_many_options *options, csgpu_many_result *d_results,
+                                       csgpu_many_checkpoints *ck, int32_t *d_slots, const csgpu_many_stream *out, void *stream) {
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL || ck == NULL || d_slots == NULL ||
+                       out == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "call"))) return rc;
+  if (options->objective != CS_OBJ_ALL)
+    return set_err(CSGPU_E_ARG, "csgpu_solve_many_stream walks under ALL (objective 1), not objective %d", options->objective);
+  if (out->capacity < 1) return set_err(CSGPU_E_ARG, "the solution stream has room for at least one row (capacity %lld)", (long long)out->capacity);
+  if (out->d_rows == NULL || out->d_owner == NULL || out->d_count == NULL) return set_err(CSGPU_E_ARG, "null pointer in the solution stream");
+  if ((rc = many_check_tail(m, MANY_STREAM, ck, count))) return rc;
+  cs_dive_ck dk = many_ck_arg(ck, d_slots, 0); /* fresh or resumed is d_slots[i]'s to say: the kernel does not read `resume` */
+  cs_dive_out ok;
+  ok.rows = out->d_rows;
+  ok.owner = out->d_owner;
+  ok.count = (unsigned long long *)out->d_count;
+  ok.capacity = (long long)out->capacity;
+  return many_launch(m, MANY_STREAM, d_roots, count, options->max_nodes, 1, d_results, NULL, 0, stream, &dk, &ok);
 }
 
 /* ---- clause models: csgpu_solve_many_clauses, a depth-first search per wavefront on kernel 6's fixpoint (cs_walk.hip.h) ---- */

@@ -64,7 +64,16 @@
  * variable), cs_many_start / cs_many_rotated of cs_arith.h, and after more than threshold x restart_base failed children
  * the walk starts again from the root node's fixpoint with run + 1 and the next Luby threshold.  Counters and the budget
  * run over all runs; a restart costs no node.  The root fixpoint is kept in the wave's n-th frame, which the walk never
- * uses.  Everything new is a scalar. */
+ * uses.  Everything new is a scalar.
+ *
+ * Every solution (cs_dive_stream, csgpu_solve_many_stream): the same loop a fifth time, CS_DIVE_CK 1 and CS_DIVE_STREAM 1,
+ * the ALL walk only.  A solution is appended to one output stream shared by all waves: lane 0 adds 1 to one 64-bit word
+ * (relaxed, agent scope), the old value is the row -- every lane stores its variables there, lane 0 the owner -- unless it
+ * is past the capacity: then the child is NOT counted and the instance stops with CSGPU_MANY_FULL and a checkpoint that
+ * stands before that very value, so the next call tries it again.  The fixpoint runs on copies, the parent node is intact.
+ * Whether an instance is fresh or goes on from a slot is a fact per instance here (slots[i] == -2 or >= 0): a fresh one
+ * walks in the wave's workspace slice and copies its frames out when it stops, a resumed one walks in its slot.  A wave
+ * that finds the stream full when it has drawn a ticket does not walk.  New per-wave state is scalars. */
 #ifndef CS_DIVE_HIP_H
 #define CS_DIVE_HIP_H
 
@@ -120,6 +129,14 @@ struct cs_dive_rs {
   int flags;              /* bit 0: CSGPU_MANY_ROTATE_FIRST, run 0 rotates as well */
 };
 
+/* the solution stream of a call (cs_dive_stream): csgpu_many_stream */
+struct cs_dive_out {
+  int *rows;                 /* [capacity][n] */
+  int *owner;                /* [capacity] */
+  unsigned long long *count; /* append attempts since the caller zeroed it: the kernel only adds */
+  long long capacity;        /* >= 1 */
+};
+
 template <typename E, int R>
 __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_shave(int n, const E *__restrict__ tab_g, int slots, int dmin,
                                                                         const int *__restrict__ root_lo,
@@ -129,7 +146,9 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_shave(int n, c
 #define CS_DIVE_CK 0
 #define CS_DIVE_UPTO 0
 #define CS_DIVE_RESTART 0
+#define CS_DIVE_STREAM 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_STREAM
 #undef CS_DIVE_RESTART
 #undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
@@ -145,7 +164,9 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_resume(int n, 
 #define CS_DIVE_CK 1
 #define CS_DIVE_UPTO 0
 #define CS_DIVE_RESTART 0
+#define CS_DIVE_STREAM 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_STREAM
 #undef CS_DIVE_RESTART
 #undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
@@ -161,7 +182,9 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_upto(int n, co
 #define CS_DIVE_CK 1
 #define CS_DIVE_UPTO 1
 #define CS_DIVE_RESTART 0
+#define CS_DIVE_STREAM 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_STREAM
 #undef CS_DIVE_RESTART
 #undef CS_DIVE_UPTO
 #undef CS_DIVE_CK
@@ -178,7 +201,28 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_restart(int n,
 #define CS_DIVE_CK 0
 #define CS_DIVE_UPTO 0
 #define CS_DIVE_RESTART 1
+#define CS_DIVE_STREAM 0
 #include "cs_dive_body.hip.h"
+#undef CS_DIVE_STREAM
+#undef CS_DIVE_RESTART
+#undef CS_DIVE_UPTO
+#undef CS_DIVE_CK
+}
+
+/* the ALL walk that appends every solution to `out` and steps back when there is no room; ck.resume and io.all are not
+ * read: ck.slots[i] says per instance whether it starts (-2), goes on (>= 0) or is finished (anything else) */
+template <typename E, int R>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_stream(int n, const E *__restrict__ tab_g, int slots, int dmin,
+                                                                         const int *__restrict__ root_lo,
+                                                                         const int *__restrict__ root_hi,
+                                                                         const int *__restrict__ sym_off, size_t tab_bytes,
+                                                                         cs_dive_io io, cs_dive_ck ck, cs_dive_out out) {
+#define CS_DIVE_CK 1
+#define CS_DIVE_UPTO 0
+#define CS_DIVE_RESTART 0
+#define CS_DIVE_STREAM 1
+#include "cs_dive_body.hip.h"
+#undef CS_DIVE_STREAM
 #undef CS_DIVE_RESTART
 #undef CS_DIVE_UPTO
 #undef CS_DIVE_CK

@@ -1,9 +1,10 @@
-/* cs_dive_body.hip.h -- the body of the four kernels of cs_dive.hip.h, which includes it inside each of them under three
- * switches:            CS_DIVE_CK  CS_DIVE_UPTO  CS_DIVE_RESTART
- *   cs_dive_shave          0           0              0        csgpu_solve_many
- *   cs_dive_resume         1           0              0        one more argument, `ck`: the pool and the slots of the call
- *   cs_dive_upto           1           1              0        and `upto` (k >= 1, a scalar)
- *   cs_dive_restart        0           0              1        one more argument, `rs` (the walk is defined in csolve_gpu.h)
+/* cs_dive_body.hip.h -- the body of the five kernels of cs_dive.hip.h, which includes it inside each of them under four
+ * switches:            CS_DIVE_CK  CS_DIVE_UPTO  CS_DIVE_RESTART  CS_DIVE_STREAM
+ *   cs_dive_shave          0           0              0              0       csgpu_solve_many
+ *   cs_dive_resume         1           0              0              0       one more argument, `ck`: the pool and the slots of the call
+ *   cs_dive_upto           1           1              0              0       and `upto` (k >= 1, a scalar)
+ *   cs_dive_restart        0           0              1              0       one more argument, `rs` (the walk is defined in csolve_gpu.h)
+ *   cs_dive_stream         1           0              0              1       `ck` and `out`, the solution stream of the call
  * Text, not a __device__ function: inlined from a function, the loop of cs_dive_shave<E, 2> takes 42 vector registers
  * instead of 39.  Every line of a switch stands under its `#if`, so a kernel that defines it 0 sees the text it saw before
  * the switch was there and compiles to the same instructions.
@@ -12,7 +13,11 @@
  * CS_DIVE_RESTART: the ANY walk with a seeded rotation of every node's value order and Luby restarts.  A frame's 8-byte
  * entry is {variable, next j} instead of {variable, next value}; the root node's fixpoint is kept in frame `frames - 1`,
  * which the walk never uses, and a restart reads it back, every lane the entries it wrote itself.  A restart is no
- * `continue` of the ticket loop.  New per-wave state is scalars only: run, fails, threshold, counter, seed, restarts, start. */
+ * `continue` of the ticket loop.  New per-wave state is scalars only: run, fails, threshold, counter, seed, restarts, start.
+ * CS_DIVE_STREAM: the ALL walk, every solution appended to `out` (io.all, io.solutions and ck.resume are not read).  Fresh
+ * or resumed is a fact per instance, its ck.slots entry (-2 / >= 0).  A child that is a solution asks for its row BEFORE it
+ * is counted: without room the walk goes round once more with `refused` set and leaves through the checkpoint code of the
+ * budget, status 4, nv still that value.  New per-wave state is scalars only: refused, room, the row index. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   typedef unsigned long long u64;
   const int lane = threadIdx.x & (CS_WAVE - 1);
@@ -85,6 +90,23 @@
     start = cs_many_start(rs_seed, run, bv, width, rs.flags);                                                        \
   } while (0)
 #endif
+#if CS_DIVE_STREAM
+  /* the solution LO (relative to the root lower bounds) asks for a row of the stream: one relaxed agent-scope add by
+   * lane 0, the old value broadcast; ROOM = it lies below the capacity, and then the row and its owner are stored */
+#define CS_DIVE_APPEND(LO, ROOM)                                                                                     \
+  do {                                                                                                               \
+    u64 at_ = 0ull;                                                                                                  \
+    if (lane == 0) at_ = __hip_atomic_fetch_add(out.count, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);        \
+    at_ = (u64)cs_dive_uniform((long long)at_);                                                                      \
+    ROOM = at_ < (u64)out.capacity;                                                                                  \
+    if (ROOM) {                                                                                                      \
+      int *row_ = out.rows + (size_t)at_ * (size_t)n;                                                                \
+      _Pragma("unroll") for (int r = 0; r < R; r++)                                                                  \
+        if (live[r]) row_[lane + r * CS_WAVE] = LO[r] + b0[r];                                                       \
+      if (lane == 0) out.owner[at_] = inst;                                                                          \
+    }                                                                                                                \
+  } while (0)
+#endif
 
   for (;;) {
     /* The wave meets here before lane 0 draws.  Without this convergent no-op the compiler joins the `lane == 0` of
@@ -114,9 +136,27 @@
     cs_val *stack = wave_stack;
     bool resumed = false;
     {
+#if CS_DIVE_STREAM
+      /* the stream as it stands now (a relaxed load: a hint, the append itself decides), then what the instance is */
+      const u64 appended = (u64)cs_dive_uniform((long long)__hip_atomic_load(out.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      slot = __builtin_amdgcn_readfirstlane(ck.slots[inst]);
+      if (slot < 0 && slot != -2) continue; /* finished: nothing of it is read or written */
+      if (appended >= (u64)out.capacity) { /* full already: no walk; an instance with a slot stays exactly as it is */
+        if (slot == -2 && lane == 0) {
+          cs_dive_result res;
+          res.status = 4; /* CSGPU_MANY_FULL */
+          res.root_props = 0;
+          res.nodes = 0; res.cuts = 0; res.props = 0; res.solutions = 0;
+          io.results[inst] = res;
+        }
+        continue;
+      }
+      if (slot >= 0) {
+#else
       if (ck.resume) {
         slot = __builtin_amdgcn_readfirstlane(ck.slots[inst]);
         if (slot < 0) continue; /* not stopped, or stopped without a checkpoint: nothing of it is written */
+#endif
         cs_val head = cs_interval(-1, 0);
         if (slot < ck.capacity) head = ck.pool[(size_t)slot * (fstride * fstride)]; /* compared before it is read */
         depth0 = __builtin_amdgcn_readfirstlane(head.lo);
@@ -136,6 +176,11 @@
           }
         }
       }
+#if CS_DIVE_STREAM
+      else {
+        slot = -1; /* a fresh instance: it draws its slot when it stops */
+      }
+#endif
     }
 #else
     cs_val *const stack = wave_stack;
@@ -219,6 +264,19 @@
       if (fail_var >= 0) {
         /* an inconsistent root: DONE, no node, no solution */
       } else if (open_vars == 0) {
+#if CS_DIVE_STREAM
+        /* the root row is itself the solution (a fresh instance: a checkpoint's node has an open variable).  Without
+         * room it is not started: status FULL, the other fields zero, its slot entry stays -2 */
+        bool room;
+        CS_DIVE_APPEND(plo, room);
+        if (room) {
+          sols = 1;
+        } else {
+          status = 4; /* CSGPU_MANY_FULL */
+          root_props = 0;
+          kept = -2;
+        }
+#else
         sols = 1;
         if (io.solutions != nullptr) {
 #if CS_DIVE_UPTO
@@ -232,8 +290,12 @@
             if (live[r]) io.solutions[rrow + lane + r * CS_WAVE] = plo[r] + b0[r];
 #endif
         }
+#endif
       } else {
         int depth = 0, bv, br, bl, xlo = 0, bhi = 0, nv;
+#if CS_DIVE_STREAM
+        bool refused = false; /* the child that was tried last is a solution the stream had no room for */
+#endif
         u64 pval[R];
         if (resumed) { /* "try value nv of variable bv on the node plo / phi" */
           depth = depth0;
@@ -265,8 +327,13 @@
           depth = __builtin_amdgcn_readfirstlane(depth);
           nv = __builtin_amdgcn_readfirstlane(nv);
           bv = __builtin_amdgcn_readfirstlane(bv);
+#if CS_DIVE_STREAM
+          if (refused || nodes - nodes0 >= io.max_nodes) {
+            status = refused ? 4 /* CSGPU_MANY_FULL: nv is the refused value, the node is as it was */ : 1;
+#else
           if (nodes - nodes0 >= io.max_nodes) {
             status = 1; /* CSGPU_MANY_LIMIT */
+#endif
 #if CS_DIVE_CK
             { /* leave a checkpoint, if the pool has a slot */
 #if CS_DIVE_UPTO
@@ -331,6 +398,22 @@
           int rounds = 0, revisions = 0;
           const int fail_var = C.fixpoint(rlo, rhi, pushed, push, dl, dh, val, rounds, revisions);
           if (rounds != 0) __builtin_amdgcn_s_setprio(0);
+#if CS_DIVE_STREAM
+          /* a child that is a solution takes its row before any counter moves: refused, it was not tried at all */
+          if (fail_var < 0) {
+            int open_s = 0;
+#pragma unroll
+            for (int r = 0; r < R; r++) open_s += __popcll(__ballot(rlo[r] != rhi[r]));
+            if (open_s == 0) {
+              bool room;
+              CS_DIVE_APPEND(rlo, room);
+              if (!room) {
+                refused = true;
+                continue;
+              }
+            }
+          }
+#endif
           nodes++;
           bool descend = false;
           if (fail_var >= 0) {
@@ -345,7 +428,9 @@
             props -= bhi - xlo; /* the assignment itself is no narrowing */
             if (open_c == 0) {
               sols++;
-#if CS_DIVE_UPTO
+#if CS_DIVE_STREAM
+              /* its row stands in the stream already; the walk goes on (ALL) */
+#elif CS_DIVE_UPTO
               if (io.solutions != nullptr) { /* 1 <= sols <= upto here: a fresh count starts at 0, a resumed one below upto */
                 const size_t srow = ((size_t)inst * (size_t)upto + (size_t)(sols - 1)) * (size_t)n;
 #pragma unroll
@@ -474,4 +559,7 @@
 #undef CS_DIVE_ENTER
 #if CS_DIVE_RESTART
 #undef CS_DIVE_START
+#endif
+#if CS_DIVE_STREAM
+#undef CS_DIVE_APPEND
 #endif

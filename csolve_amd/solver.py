@@ -11,8 +11,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import (MANY_ROTATE_FIRST, PLAN_FAMILIES, CsolveError, ManyOptions, ManyRestartOptions, ManyResult,
-                   ManyUptoOptions, Node, Result, SearchStats, Val, check, demangle, load_library)
+from ._lib import (MANY_ROTATE_FIRST, MANY_SLOT_FRESH, PLAN_FAMILIES, CsolveError, ManyOptions, ManyRestartOptions, ManyResult,
+                   ManyStream, ManyUptoOptions, Node, Result, SearchStats, Val, check, demangle, load_library)
 
 STATUS_FAIL = -1
 
@@ -340,6 +340,87 @@ class Model:
         if rows is not None:
             out["rows"] = rows
         return out
+
+    def many_stream(self, rows: int) -> "ManySolutionStream":
+        """a solution stream of `rows` rows for solve_many_stream: the three device tensors of csgpu_many_stream and
+        take()"""
+        return ManySolutionStream(self, rows)
+
+    def solve_many_stream(self, roots, out: "ManySolutionStream", pool: "ManyCheckpoints", slots=None, results=None, *,
+                          max_nodes, stream=None) -> dict:
+        """ONE call of csgpu_solve_many_stream: the ALL walk of solve_many, every solution appended to `out`; an instance
+        the stream has no room for steps back to before that solution and stops with status 4 (FULL).  roots: as
+        solve_many.  pool: many_checkpoints(); K slots never run out.  slots: int32 [K] on the device, per instance -2
+        start, -1 finished (not touched), >= 0 go on from that slot -- by default all -2; results: the record buffer of
+        the call before (the counters of a resumed instance are read from it), by default zeroed.  max_nodes: the budget
+        of THIS call per instance.  -> the dict of solve_many(..., checkpoints=pool) without `first`; its `_slots` and
+        `_records` are what the next call takes.  The rows are out.take()'s: take them before the next call."""
+        L = load_library()
+        opt = ManyOptions(1, 0, int(max_nodes))
+        desc = out.struct()
+        roots, K = self._many_roots(roots, out.capacity < 1, lambda ptr, count: check(
+            L.csgpu_solve_many_stream(self._h, ptr, count, C.byref(opt), ptr, pool._h if pool is not None else ptr, ptr,
+                                      C.byref(desc), None)))
+        buf = self._many_records(K, roots.device) if results is None else results
+        if slots is None:
+            slots = torch.full((max(K, 1),), MANY_SLOT_FRESH, dtype=torch.int32, device=roots.device)
+        assert buf.is_cuda and buf.dtype == torch.int64 and buf.is_contiguous() and tuple(buf.shape) == (max(K, 1), 5)
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[0] == max(K, 1)
+        check(L.csgpu_solve_many_stream(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                                        pool._h, slots.data_ptr(), C.byref(desc), _stream_ptr(stream)))
+        ans = self._many_answer(buf, K, None, slots, pool)
+        ans["_roots"] = roots
+        return ans
+
+    def solve_many_all(self, roots, *, max_nodes, stream_rows=65536, on_rows=None, max_calls=None) -> dict:
+        """every solution of every instance: solve_many_stream in a loop with a pool of K slots and a stream of
+        `stream_rows` rows -- call, take the rows, zero the count, until no instance has work left.  Every instance
+        then ends DONE with the record of solve_many(roots, "ALL") under an unlimited budget, whatever stream_rows and
+        max_nodes (the budget per instance and call) are.  Synchronises after every call.
+        -> the dict of solve_many without `first`, plus `calls`, and without on_rows `offsets` int64 [K + 1] and `rows`
+        int32 [total, n_vars] on the device: rows[offsets[i]:offsets[i + 1]] are the solutions of instance i in walk order.
+        on_rows(owner, rows): called with every drain that holds a row (device tensors int32 [m] and [m, n_vars], the
+        rows of one instance in walk order within and across drains); nothing is kept then.
+        max_calls: stop after that many calls; the answer then also has `slot`, `_slots`, `_records`, `_checkpoints`,
+        `_roots` and `stream`, which solve_many_stream takes to go on."""
+        out = self.many_stream(stream_rows)
+        K = int(roots.shape[0])
+        pool = slots = results = ans = None
+        kept, calls = [], 0
+        while True:
+            # (a numpy batch on a model that cannot run the call gets the library's error from the call's own probe,
+            # before anything is allocated for it)
+            if pool is None and (torch.is_tensor(roots) or self.qualifies(7)):
+                pool = self.many_checkpoints(max(K, 1))
+            ans = self.solve_many_stream(roots, out, pool, slots, results, max_nodes=max_nodes)
+            roots, slots, results = ans["_roots"], ans["_slots"], ans["_records"]
+            calls += 1
+            owner, rows = out.take()
+            if on_rows is None:
+                kept.append((owner, rows))
+            elif owner.shape[0]:
+                on_rows(owner, rows)
+            left = K > 0 and bool((ans["slot"] != -1).any())
+            if not left or (max_calls is not None and calls >= max_calls):
+                break
+        ans["calls"] = calls
+        if on_rows is None:
+            owner = torch.cat([o for o, _ in kept]).to(torch.int64)
+            order = torch.sort(owner, stable=True).indices
+            ans["rows"] = torch.cat([r for _, r in kept])[order]
+            ans["offsets"] = torch.cat([torch.zeros(1, dtype=torch.int64, device=owner.device),
+                                        torch.cumsum(torch.bincount(owner, minlength=K), 0)])
+        if left:
+            ans["stream"] = out
+        else:
+            for key in ("slot", "_slots", "_records", "_checkpoints", "_roots"):
+                ans.pop(key)
+            pool.close()
+        return ans
+
+    def many_stream_kernel(self):
+        """the cs_dive_stream instantiation solve_many_stream launches"""
+        return self._many_symbol("csgpu_internal_many_stream_symbol")
 
     def solve_many_restarts(self, roots, *, max_nodes, restart_base=32, seed=0, seeds=None, rotate_first=False,
                             solutions=True, restarts=True, stream=None) -> dict:
@@ -1012,6 +1093,30 @@ class ManyCheckpoints:
             self.close()
         except Exception:
             pass
+
+
+class ManySolutionStream:
+    """The solution stream of Model.solve_many_stream (csgpu_many_stream): `rows` int32 [capacity, n_vars], `owner` int32
+    [capacity] and `count`, one 64-bit device word that counts append attempts since it was last zeroed.  The kernel only
+    adds to it: after a call the valid rows are the first min(count, capacity)."""
+
+    def __init__(self, model: Model, rows: int):
+        self.capacity = int(rows)  # (below 1: kept as given, so that the library refuses the call)
+        cap = max(self.capacity, 1)
+        self.rows = torch.empty((cap, model.n_vars), dtype=torch.int32, device="cuda")
+        self.owner = torch.empty((cap,), dtype=torch.int32, device="cuda")
+        self.count = torch.zeros((1,), dtype=torch.int64, device="cuda")
+
+    def struct(self) -> ManyStream:
+        return ManyStream(self.rows.data_ptr(), self.owner.data_ptr(), self.count.data_ptr(), self.capacity)
+
+    def take(self):
+        """-> (owner int32 [m], rows int32 [m, n_vars]): copies of the valid part, in stream order; the counter is zeroed
+        on the current stream.  Waits for the calls queued before it."""
+        m = min(int(self.count.item()), max(self.capacity, 0))
+        owner, rows = self.owner[:m].clone(), self.rows[:m].clone()
+        self.count.zero_()
+        return owner, rows
 
 
 def set_linear_fast_paths(on: bool):

@@ -394,6 +394,60 @@ int csgpu_solve_many_restarts(const csgpu_model *m, const csgpu_val *d_roots, co
  * width) */
 int32_t csgpu_many_value(uint32_t seed, uint32_t run, int32_t var, csgpu_val bounds, uint32_t j, int32_t flags);
 
+/* ---- every solution of every instance under ALL: csgpu_solve_many whose solutions go to one bounded stream ----
+ * csgpu_solve_many under ALL counts an instance's solutions and keeps the first; csgpu_solve_many_upto keeps k rows per
+ * instance, k chosen in advance.  This call enumerates: the walk is csgpu_solve_many's ALL walk unchanged (the root check
+ * and BAD_ROOT, the root node, the branching rule, ascending values, the counters, the budget compared before a child is
+ * tried), and every solution is appended to ONE output stream that all instances share.  options->objective must be 1;
+ * options->max_nodes is the budget of THIS call per instance (nodes tried in the call), as in csgpu_solve_many_resume.
+ * One entry point starts and resumes instances, because with a bounded stream every call after the first does both.
+ *   appending     when a child, or the root node, has every variable valued, one relaxed agent-scope atomic adds 1 to
+ *                 *d_count; the old value idx is the row.  idx < capacity: d_rows[idx] receives the solution (absolute
+ *                 values), d_owner[idx] the instance, and the solution is counted.  idx >= capacity: it is refused (below).
+ *                 The kernel never zeroes *d_count: after a call the valid rows are the first min(*d_count, capacity), and
+ *                 the caller copies them out and zeroes the word on the same stream before the next call.  One wave walks
+ *                 an instance at a time and calls are ordered on the stream, so the rows of one instance appear in walk
+ *                 order: by index within a call, by call across calls.
+ *   refusal       a refused solution is not lost.  The child that produced it is not counted (nodes, cuts, props and
+ *                 solutions are what they were before it was tried), the instance stops with CSGPU_MANY_FULL, and its
+ *                 checkpoint stands at "try value nv of variable bv on this node" with nv that very value, in the slot
+ *                 layout above.  The next call tries the child again, and it is counted once.
+ *   d_slots[i]    on entry  -2 (CSGPU_MANY_SLOT_FRESH): start instance i from root row i.  -1, or anything below -2:
+ *                 finished, nothing of the instance is read or written.  >= 0: go on from that slot, the counters are read
+ *                 from d_results[i]; a number outside the pool, or a slot without a checkpoint, gives CSGPU_MANY_BAD_SLOT,
+ *                 compared before anything is read, and nothing else is touched.
+ *                 on exit   -2: not started -- the wave that drew it found the stream full already, or its root row is
+ *                 itself the solution and found no room; status FULL, the other fields zero.  -1: finished (DONE,
+ *                 BAD_ROOT), or stopped (LIMIT / FULL, with its counters) while the pool had no slot left: its walk is gone,
+ *                 exactly as in csgpu_solve_many_checkpointed.  >= 0: stopped with a checkpoint (LIMIT or FULL); a resumed
+ *                 instance goes back into the SAME slot.
+ *   full at the draw   a wave that has drawn a ticket first reads *d_count (relaxed); if it is >= capacity already the
+ *                 wave does not walk: a fresh instance stays -2 with status FULL, one with a slot is left exactly as it
+ *                 was.  So a full stream drains the remaining tickets quickly.
+ * The caller's loop:  slots = -2; do { call; take the rows; zero the count } while (any slot != -1).  A pool of `count`
+ * slots never runs out, and with such a pool every instance ends DONE with its record equal, field for field, to
+ * csgpu_solve_many under ALL with an unlimited budget, whatever capacity >= 1 and budget the calls had; the rows drained for
+ * the instance are its walk's solutions in walk order, each exactly once.
+ * The pool is that of csgpu_many_checkpoints_create with its slot layout; csgpu_many_checkpoint_states works unchanged on a
+ * slot written here.  "One call in flight per model" covers this call (same workspace, same ticket counters); calls of
+ * all families may be queued behind each other on one stream without the host in between.
+ * Errors before any HIP call, in csgpu_solve_many's order: a null m / d_roots / d_results / options / ck / d_slots / out,
+ * count < 0, max_nodes <= 0 -> CSGPU_E_ARG; an objective other than ALL -> CSGPU_E_ARG; capacity < 1 or a null pointer
+ * inside *out -> CSGPU_E_ARG; model not finalized -> CSGPU_E_STATE; model does not qualify for kernel 7 -> CSGPU_E_LIMIT; a
+ * pool of another model or of the clause kind -> CSGPU_E_ARG; count > 2^31 - 65 -> CSGPU_E_LIMIT.  count == 0 -> CSGPU_OK,
+ * nothing is launched. */
+#define CSGPU_MANY_FULL 4          /* stopped because the solution stream had no room */
+#define CSGPU_MANY_SLOT_FRESH (-2) /* d_slots[i] on entry: start instance i from its root row */
+typedef struct csgpu_many_stream {
+  int32_t  *d_rows;   /* [capacity][n_vars]: the solutions, absolute values */
+  int32_t  *d_owner;  /* [capacity]: the instance a row belongs to */
+  uint64_t *d_count;  /* ONE device word: append attempts since the caller last zeroed it */
+  int64_t   capacity; /* >= 1 */
+} csgpu_many_stream;   /* 32 bytes; caller-owned device memory */
+int csgpu_solve_many_stream(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                            csgpu_many_result *d_results, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                            const csgpu_many_stream *out, void *stream);
+
 /* ---- many instances of one CLAUSE model in one call: a depth-first search per wavefront, also under MIN / MAX ----
  * csgpu_solve_many for the models it refuses: `=`, `<`, disjunctions, expression trees, an objective -- the scheduling
  * models with other release times, windows or deadlines per row.  Built on kernel 6 (csgpu_model_qualifies(m, 6): at

@@ -9,7 +9,7 @@ oracle walk (tests/many_walk.py).
 
   python tools/time_solve_many.py --set sudoku9 [--count 65536] [--reps 5] [--loop-sample 256] [--check 32]
                                   [--sliced B0,B1,... [--finish resume|search]] [--upto K]
-                                  [--restarts BASE [--seed S]] [--revealed R]
+                                  [--restarts BASE [--seed S]] [--revealed R] [--stream ROWS]
   --sliced: the same instances through Model.solve_many_sliced as well (a checkpointed call with budget B0, a resume
   with every following budget; --finish search: what is left after the last budget through one Search per instance):
   the time of the whole, the time until the answers of the first slice are there, and whether it found what the one
@@ -24,7 +24,13 @@ oracle walk (tests/many_walk.py).
   answers re-checked against the host walk of tests/many_walk_restarts.py.
   --revealed R: the sudoku sets with this share of givens for every instance instead of the set's own (the deep tails
   of 9x9 sudokus are at 0.30 and 0.25).
-  sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY)
+  --stream ROWS: Model.solve_many_stream (ALL, every solution appended to one shared stream) beside the counting ALL call
+  of solve_many on the same instances, in this process after a warm-up, interleaved, same budget: (a) the ALL call, (b)
+  one stream call with room for every solution, (c) the loop call / take / zero with a stream of ROWS rows, which fills
+  (the output says how many calls it took); medians and ranges of --reps, whether every record of (b) and (c) equals (a)'s
+  and every solution arrived, and --check sampled instances' rows re-checked against the host walk of tests/many_walk.py.
+  sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY),
+  sparse40 (a sparse != network of 40 variables, 16-bit table, three of them open: nearly every node is a solution, ALL)
 """
 import argparse
 import json
@@ -63,6 +69,10 @@ def instances(which, count, revealed=None):
     if which == "queens12":
         import many_sets
         return problems.queens(12, "ALL"), many_sets.queens_two(12, count, 7), "ALL", 1 << 20
+    if which == "sparse40":
+        import many_sets
+        text = many_sets._sparse16(40, 3)
+        return text, many_sets.narrowed(text, count, 3, 2, 8), "ALL", 1 << 20
     raise SystemExit(f"no set {which}")
 
 
@@ -86,8 +96,9 @@ def main():
     ap.add_argument("--upto", type=int, default=None, help="K: time solve_many_upto beside the ANY and the ALL call")
     ap.add_argument("--restarts", type=int, default=None, help="BASE: time solve_many_restarts beside the ANY call")
     ap.add_argument("--revealed", type=float, default=None, help="share of givens of every sudoku (default: the set's own)")
+    ap.add_argument("--stream", type=int, default=None, help="ROWS: time solve_many_stream beside the counting ALL call")
     args = ap.parse_args()
-    count = args.count or {"sudoku9": 65536, "queens12": 16384, "sudoku16": 4096}[args.set]
+    count = args.count or {"sudoku9": 65536, "queens12": 16384, "sudoku16": 4096, "sparse40": 256}[args.set]
     text, roots, objective, budget = instances(args.set, count, args.revealed)
     model = solve_root(text)
     dev = torch.from_numpy(roots).cuda()
@@ -248,6 +259,75 @@ def main():
                     "same_verdict_where_both_done": bool((answers_r["any"]["solutions"] == answers_r["restarts"]["solutions"])[both].all()),
                     "oracle_checked": len(picks_r), "oracle_ok": bool(restarts_ok)}
 
+    streamed = None
+    if args.stream is not None:
+        import many_walk as walk_s
+        fields = ("status", "root_props", "nodes", "cuts", "props", "solutions")
+        counted = model.solve_many(dev, "ALL", max_nodes=budget)
+        total = int(counted["solutions"].sum())
+        pool = model.many_checkpoints(count)
+        roomy, small = model.many_stream(total + 1), model.many_stream(args.stream)
+
+        def one_call():  # (b): room for everything
+            pool.reset()
+            roomy.count.zero_()
+            return model.solve_many_stream(dev, roomy, pool, max_nodes=budget), 1, None
+
+        def loop_s():  # (c): call, take the rows, zero the count, while an instance has work left
+            pool.reset()
+            slots = results = None
+            calls, kept = 0, []
+            while True:
+                ans = model.solve_many_stream(dev, small, pool, slots, results, max_nodes=budget)
+                slots, results = ans["_slots"], ans["_records"]
+                calls += 1
+                kept.append(small.take())
+                if not bool((ans["slot"] != -1).any()):
+                    return ans, calls, kept
+
+        def timed_s(call):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = call()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, res
+
+        calls_s = {"all": lambda: (model.solve_many(dev, "ALL", max_nodes=budget), 1, None), "stream_roomy": one_call,
+                   "stream_loop": loop_s}
+        for call in calls_s.values():  # warm-up: code load, workspace, the allocator's blocks
+            timed_s(call)
+            timed_s(call)
+        series_s = {name: [] for name in calls_s}
+        answers_s = {}
+        for _ in range(args.reps):  # interleaved: a drift of the machine falls on all three alike
+            for name, call in calls_s.items():
+                dt, answers_s[name] = timed_s(call)
+                series_s[name].append(dt)
+
+        def summary_s(name):
+            ts, (res, calls, _) = series_s[name], answers_s[name]
+            return {"ms": {"median": round(statistics.median(ts) * 1e3, 3), "min": round(min(ts) * 1e3, 3),
+                           "max": round(max(ts) * 1e3, 3), "reps": args.reps}, "calls": calls,
+                    "records_equal_all": all(bool((res[f] == counted[f]).all()) for f in fields)}
+
+        # the rows of sampled instances, from the roomy call and from the loop, against the host walk
+        picks_s = rng.choice(count, size=min(args.check, count), replace=False)
+        n_roomy = int(roomy.count.item())
+        owner_b, rows_b = roomy.owner[:n_roomy].cpu().numpy(), roomy.rows[:n_roomy].cpu().numpy()
+        owner_c = torch.cat([o for o, _ in answers_s["stream_loop"][2]]).cpu().numpy()
+        rows_c = torch.cat([r for _, r in answers_s["stream_loop"][2]]).cpu().numpy()
+        rows_ok = n_roomy == total and len(owner_c) == total
+        for i in picks_s:
+            want_rows = walk_s.Walk(text, roots[i]).run(budget, None)["rows"]
+            for owner, rows in ((owner_b, rows_b), (owner_c, rows_c)):
+                mine = rows[owner == i]
+                rows_ok = rows_ok and len(mine) == len(want_rows) and all((a == b).all() for a, b in zip(mine, want_rows))
+        streamed = {"rows": args.stream, "kernel": model.many_stream_kernel(), "max_nodes": budget, "solutions": total,
+                    "nodes": int(counted["nodes"].sum()), "largest_tree": int(counted["nodes"].max()),
+                    "most_solutions_of_an_instance": int(counted["solutions"].max()),
+                    "all": summary_s("all"), "stream_roomy": summary_s("stream_roomy"), "stream_loop": summary_s("stream_loop"),
+                    "oracle_checked": len(picks_s), "oracle_ok": bool(rows_ok)}
+
     # the per-instance loop: one Search, reset and seeded per instance
     sample = np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
     search = Search(model, 1 << 18, 1 << 14)
@@ -302,8 +382,10 @@ def main():
         **({"sliced": sliced} if sliced else {}),
         **({"upto": upto} if upto else {}),
         **({"restarts": restarts} if restarts else {}),
+        **({"stream": streamed} if streamed else {}),
     }))
-    return 0 if checked_ok and (upto is None or upto["oracle_ok"]) and (restarts is None or restarts["oracle_ok"]) else 1
+    return 0 if checked_ok and (upto is None or upto["oracle_ok"]) and (restarts is None or restarts["oracle_ok"]) and \
+        (streamed is None or streamed["oracle_ok"]) else 1
 
 
 if __name__ == "__main__":
