@@ -271,6 +271,8 @@ def load_library():
     L.csgpu_internal_many_clauses_upto_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_clauses_restarts.argtypes = [vp, vp, vp, i64, C.POINTER(ManyRestartOptions), vp, vp, vp, vp]
     L.csgpu_internal_many_clauses_restart_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many_clauses_stream.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, C.POINTER(ManyStream), vp]
+    L.csgpu_internal_many_clauses_stream_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_many_value.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, Val, C.c_uint32, C.c_int32]
     L.csgpu_many_value.restype = C.c_int32
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -79,6 +79,7 @@ struct cs_kernel_plan {
   cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
   cs_planned walk_upto;            /* cs_walk_upto (csgpu_solve_many_clauses_upto and its two checkpoint calls): the same */
   cs_planned walk_restart;         /* cs_walk_restart (csgpu_solve_many_clauses_restarts): the same */
+  cs_planned walk_stream;          /* cs_walk_stream (csgpu_solve_many_clauses_stream): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -1031,6 +1032,17 @@ static int plan_general(csgpu_model *m) {
           m->plan.walk_restart.per_cu = occ;
         if (m->plan.walk_restart.per_cu < 1) m->plan.walk_restart.per_cu = 1;
       }
+      { /* cs_walk_stream: the same slices, its own registers */
+#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_stream<CPL, true> : (const void *)cs_walk_stream<CPL, false>)
+        const void *fn_st = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
+#undef CS_PICKW
+        if ((rc = plan_kernel(&m->plan.walk_stream, fn_st, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_st, CS_BLOCK, m->plan.walk_stream.lds) == hipSuccess && occ >= 1 &&
+            occ < m->plan.walk_stream.per_cu)
+          m->plan.walk_stream.per_cu = occ;
+        if (m->plan.walk_stream.per_cu < 1) m->plan.walk_stream.per_cu = 1;
+      }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
   }
@@ -1978,6 +1990,9 @@ extern "C" int csgpu_internal_many_clauses_upto_symbol(const csgpu_model *m, cha
 extern "C" int csgpu_internal_many_clauses_restart_symbol(const csgpu_model *m, char *buf, size_t len) {
   return many_clauses_symbol(m, m != NULL ? &m->plan.walk_restart : NULL, "cs_walk_restart", buf, len);
 }
+extern "C" int csgpu_internal_many_clauses_stream_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_stream : NULL, "cs_walk_stream", buf, len);
+}
 
 /* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
  * whose `frames` frames each fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices
@@ -2005,18 +2020,21 @@ struct many_clauses_rs {
   int32_t *d_restarts;
 };
 
-/* The one path of the seven entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
+/* The one path of the eight entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
  * has a pool and slot numbers and launches cs_walk_resume; `resume` (pooled, and no roots): the instances go on in their
  * slots, so the call needs no workspace.  An up-to-k entry brings `upto_options` in place of `options` (the other one is
  * NULL): the ALL walk by cs_walk_upto, pooled or not, its rows [count][max_solutions][n_vars] in d_solutions.  The
- * restart entry brings `rs` (else NULL) and neither of the two: the ANY walk by cs_walk_restart, one frame more per wave. */
+ * restart entry brings `rs` (else NULL) and neither of the two: the ANY walk by cs_walk_restart, one frame more per wave.
+ * The stream entry brings `out` (else NULL), is pooled and not `resume` -- d_slots says per instance whether it starts or
+ * goes on, so the workspace is a fresh call's: the ALL walk by cs_walk_stream, its rows in *out. */
 static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
                              const csgpu_many_upto_options *upto_options, const many_clauses_rs *rs, csgpu_many_result *d_results,
                              int32_t *d_solutions, int32_t *d_best, int pooled, csgpu_many_checkpoints *ck, int32_t *d_slots,
-                             int resume, void *stream) {
+                             int resume, int streamed, const csgpu_many_stream *out, void *stream) {
   const csgpu_many_restart_options *rs_options = rs != NULL ? rs->options : NULL;
   const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL ||
-                       (options == NULL && upto_options == NULL && rs_options == NULL);
+                       (options == NULL && upto_options == NULL && rs_options == NULL) ||
+                       (streamed && (ck == NULL || d_slots == NULL || out == NULL));
   const int64_t max_nodes = null_arg ? 0 : (rs_options != NULL ? rs_options->max_nodes
                                             : (upto_options != NULL ? upto_options->max_nodes : options->max_nodes));
   int rc;
@@ -2027,6 +2045,13 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   if (rs_options != NULL && (rs_options->flags & ~CSGPU_MANY_ROTATE_FIRST) != 0)
     return set_err(CSGPU_E_ARG, "unknown flags 0x%x", (unsigned)rs_options->flags);
   const int objective = rs_options != NULL ? CS_OBJ_ANY : (upto_options != NULL ? CS_OBJ_ALL : options->objective);
+  if (streamed) { /* before the model is looked at: ALL only, and a stream that can take a row */
+    if (objective != CS_OBJ_ALL)
+      return set_err(CSGPU_E_ARG, "csgpu_solve_many_clauses_stream walks under ALL (objective 1), not objective %d", objective);
+    if (out->capacity < 1)
+      return set_err(CSGPU_E_ARG, "the solution stream has room for at least one row (capacity %lld)", (long long)out->capacity);
+    if (out->d_rows == NULL || out->d_owner == NULL || out->d_count == NULL) return set_err(CSGPU_E_ARG, "null pointer in the solution stream");
+  }
   if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
     return set_err(CSGPU_E_ARG, "no objective %d", objective);
   if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX) {
@@ -2053,7 +2078,8 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   if (count == 0) return CSGPU_OK;
   csgpu_model *mm = const_cast<csgpu_model *>(m);
   const cs_planned *k = rs_options != NULL ? &m->plan.walk_restart
-                        : (upto_options != NULL ? &m->plan.walk_upto : (pooled ? &m->plan.walk_ck : &m->plan.walk));
+                        : (upto_options != NULL ? &m->plan.walk_upto
+                           : (streamed ? &m->plan.walk_stream : (pooled ? &m->plan.walk_ck : &m->plan.walk)));
   const int n = m->host->n_vars;
   const int frames = rs_options != NULL ? n + 1 : n; /* at most n - 1 pushed frames and the current node's; cs_walk_restart: and the root node's */
   const int64_t waves = many_clauses_waves(m, k, count, frames);
@@ -2077,7 +2103,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   wk.next = pooled ? ck->d_next : NULL;
   wk.capacity = pooled ? (int)ck->capacity : 0; /* 0: the pool that cs_walk_upto does not touch */
   wk.resume = resume;
-  wk.code = upto_options != NULL ? CS_WALK_CK_UPTO : objective;
+  wk.code = upto_options != NULL ? CS_WALK_CK_UPTO : (streamed ? CS_WALK_CK_STREAM : objective);
   wk.slots = pooled ? d_slots : NULL;
   int upto = upto_options != NULL ? upto_options->max_solutions : 0;
   cs_dive_rs dr;
@@ -2086,9 +2112,15 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   dr.restart_base = rs_options != NULL ? (long long)rs_options->restart_base : 0;
   dr.seed = rs_options != NULL ? rs_options->seed : 0u;
   dr.flags = rs_options != NULL ? rs_options->flags : 0;
+  cs_dive_out ok;
+  ok.rows = streamed ? out->d_rows : NULL;
+  ok.owner = streamed ? out->d_owner : NULL;
+  ok.count = streamed ? (unsigned long long *)out->d_count : NULL;
+  ok.capacity = streamed ? (long long)out->capacity : 0;
   cs_tables tab = m->tab;
-  /* cs_walk_clauses takes the first two, cs_walk_resume the first three; cs_walk_restart: the tables, io and `dr` */
-  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (void *)&wk, &upto };
+  /* cs_walk_clauses takes the first two, cs_walk_resume the first three; cs_walk_restart: the tables, io and `dr`;
+   * cs_walk_stream: the first three and `ok` */
+  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (void *)&wk, streamed ? (void *)&ok : (void *)&upto };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
@@ -2096,7 +2128,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
 extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                         const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
                                         int32_t *d_best, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, 0, NULL, stream);
 }
 
 /* ---- clause checkpoints: csgpu_solve_many_clauses in slices (cs_walk_resume) ---- */
@@ -2126,13 +2158,13 @@ extern "C" int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const
                                                      const csgpu_many_options *options, csgpu_many_result *d_results,
                                                      int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
                                                      int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, 0, NULL, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
                                                csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
                                                csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, stream);
+  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, 0, NULL, stream);
 }
 
 extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
@@ -2152,20 +2184,20 @@ extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints 
 extern "C" int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                              const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                              int32_t *d_solutions, void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 0, NULL, NULL, 0, stream);
+  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                                           const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                                           int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                                           void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 0, stream);
+  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 0, 0, NULL, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
                                                     csgpu_many_result *d_results, int32_t *d_solutions,
                                                     csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 1, stream);
+  return many_clauses_call(m, NULL, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 1, 0, NULL, stream);
 }
 
 /* ---- Luby restarts with a seeded value order for ANY instances of a clause model (cs_walk_restart) ---- */
@@ -2178,7 +2210,16 @@ extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csg
   rs.options = options;
   rs.d_seeds = d_seeds;
   rs.d_restarts = d_restarts;
-  return many_clauses_call(m, d_roots, count, NULL, NULL, &rs, d_results, d_solutions, NULL, 0, NULL, NULL, 0, stream);
+  return many_clauses_call(m, d_roots, count, NULL, NULL, &rs, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, stream);
+}
+
+/* ---- every solution of every instance of a clause model under ALL, through one bounded stream (cs_walk_stream) ---- */
+
+extern "C" int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                               const csgpu_many_options *options, csgpu_many_result *d_results,
+                                               csgpu_many_checkpoints *ck, int32_t *d_slots, const csgpu_many_stream *out,
+                                               void *stream) {
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, NULL, NULL, 1, ck, d_slots, 0, 1, out, stream);
 }
 
 #ifdef CS_SHAVE_TIMELINE

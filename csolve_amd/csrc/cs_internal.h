@@ -74,6 +74,8 @@ int csgpu_internal_many_clauses_resume_symbol(const csgpu_model *m, char *buf, s
 int csgpu_internal_many_clauses_upto_symbol(const csgpu_model *m, char *buf, size_t len);
 /* and for cs_walk_restart (csgpu_solve_many_clauses_restarts) */
 int csgpu_internal_many_clauses_restart_symbol(const csgpu_model *m, char *buf, size_t len);
+/* and for cs_walk_stream (csgpu_solve_many_clauses_stream) */
+int csgpu_internal_many_clauses_stream_symbol(const csgpu_model *m, char *buf, size_t len);
 
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */
 typedef struct csgpu_step_launch {

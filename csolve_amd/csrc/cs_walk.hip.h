@@ -69,7 +69,16 @@
  * threshold x restart_base failed children the walk starts again from the root node's fixpoint with run + 1 and the next
  * Luby threshold.  Counters and the budget run over all runs; a restart costs no node and no rounds.  Frame 0 cannot keep
  * the root: a node's last-value child takes its parent's frame.  So the call has n + 1 frames per wave, the walk stays
- * below frame n, and frame n holds the root fixpoint, every lane the entries it owns.  Everything new is a scalar. */
+ * below frame n, and frame n holds the root fixpoint, every lane the entries it owns.  Everything new is a scalar.
+ *
+ * Every solution (cs_walk_stream, csgpu_solve_many_clauses_stream): the same loop a fifth time, CS_WALK_CK 1 and
+ * CS_WALK_STREAM 1, the ALL walk of cs_walk_upto.  A solution is appended to one output stream shared by all waves
+ * (cs_dive_out, as cs_dive_stream): lane 0 adds 1 to one 64-bit word (relaxed, agent scope), the old value is the row --
+ * every lane stores the variables it owns there, lane 0 the owner -- unless it is past the capacity: then the child is NOT
+ * counted (the draw stands before nodes and props move) and the instance stops with CSGPU_MANY_FULL through the budget's
+ * checkpoint code, {bv, nv} with nv that very value, so the next call tries it again; the node is intact in its frame.
+ * Fresh or resumed is a fact per instance (slots[i] == -2 or >= 0).  The header's code is CS_WALK_CK_STREAM.  A wave that
+ * finds the stream full when it has drawn a ticket does not walk.  Three atomics: ticket, pool, stream. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
 
@@ -100,7 +109,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk
 #define CS_WALK_CK 0
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
 #undef CS_WALK_CK
@@ -108,6 +119,7 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk
 
 #define CS_WALK_CK_MAGIC 0x77636b70 /* header entry 0 .hi of a slot that holds a clause checkpoint (not CS_DIVE_CK_MAGIC) */
 #define CS_WALK_CK_UPTO 4           /* the header's code of an up-to-k checkpoint (cs_walk_upto): beside the objectives 0 .. 3 */
+#define CS_WALK_CK_STREAM 5         /* that of a stream checkpoint (cs_walk_stream) */
 
 /* the checkpoint pool and the slot numbers of a call (cs_walk_resume) */
 struct cs_walk_ck {
@@ -115,8 +127,8 @@ struct cs_walk_ck {
   unsigned long long *next; /* slots handed out since the last reset (it counts on past capacity) */
   int capacity;             /* cs_walk_upto: 0 = no pool (pool, next and slots are not touched) */
   int resume;               /* 0: fresh instances from io.roots; 1: instance i goes on from slot slots[i] */
-  int code;                 /* the call's objective, 0 ANY .. 3 MAX, or CS_WALK_CK_UPTO: a checkpoint goes on under the one it
-                               was made under */
+  int code;                 /* the call's objective, 0 ANY .. 3 MAX, CS_WALK_CK_UPTO or CS_WALK_CK_STREAM: a checkpoint goes on
+                               under the one it was made under */
   int *slots;               /* [count]: the slot of an instance stopped with a checkpoint, else -1 */
 };
 
@@ -126,7 +138,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_resume(cs_tables T, cs_walk_
 #define CS_WALK_CK 1
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
 #undef CS_WALK_CK
@@ -138,7 +152,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_upto(cs_tables T, cs_walk_io
 #define CS_WALK_CK 1
 #define CS_WALK_UPTO 1
 #define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
 #undef CS_WALK_CK
@@ -151,7 +167,25 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_restart(cs_tables T, cs_walk
 #define CS_WALK_CK 0
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 1
+#define CS_WALK_STREAM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_STREAM
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+/* the ALL walk that appends every solution to `out` (cs_dive_stream's descriptor) and steps back when there is no room;
+ * ck.resume and io.all are not read: ck.slots[i] says per instance whether it starts (-2), goes on (>= 0) or is finished
+ * (anything else) */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_stream(cs_tables T, cs_walk_io io, cs_walk_ck ck, cs_dive_out out) {
+#define CS_WALK_CK 1
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
 #undef CS_WALK_CK

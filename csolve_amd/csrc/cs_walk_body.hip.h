@@ -1,9 +1,10 @@
-/* cs_walk_body.hip.h -- the body of the four kernels of cs_walk.hip.h, which includes it inside each of them under three
- * switches:            CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART
- *   cs_walk_clauses        0           0              0        csgpu_solve_many_clauses
- *   cs_walk_resume         1           0              0        one more argument, `ck`: the pool and the slots of the call
- *   cs_walk_upto           1           1              0        and `upto` (k >= 1, a scalar)
- *   cs_walk_restart        0           0              1        one more argument, `rs` (the walk is defined in csolve_gpu.h)
+/* cs_walk_body.hip.h -- the body of the five kernels of cs_walk.hip.h, which includes it inside each of them under four
+ * switches:            CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART  CS_WALK_STREAM
+ *   cs_walk_clauses        0           0              0              0       csgpu_solve_many_clauses
+ *   cs_walk_resume         1           0              0              0       one more argument, `ck`: the pool and the slots of the call
+ *   cs_walk_upto           1           1              0              0       and `upto` (k >= 1, a scalar)
+ *   cs_walk_restart        0           0              1              0       one more argument, `rs` (the walk is defined in csolve_gpu.h)
+ *   cs_walk_stream         1           0              0              1       `ck` and `out`, the solution stream of the call
  * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of a switch stands under its `#if`, so a kernel
  * that defines it 0 sees the text it saw before the switch was there and compiles to the same instructions.
  * CS_WALK_CK: an instance that stops at its budget leaves its frames, its current node, {bv, nv} and its incumbent in a
@@ -16,7 +17,12 @@
  * of cs_dive_body.hip.h.  nv is j, not a value, and a frame's 8-byte entry {variable, next j}; the call has n + 1 frames
  * per wave, the walk stays below frame n (io.frames - 1), and frame n keeps the root node's fixpoint, which a restart
  * reads back into the slice and into frame 0, every lane the entries it wrote itself.  A restart is no `continue` of the
- * ticket loop.  New per-instance state is scalars only: run, fails, threshold, counter, seed, restarts, start, width. */
+ * ticket loop.  New per-instance state is scalars only: run, fails, threshold, counter, seed, restarts, start, width.
+ * CS_WALK_STREAM: the ALL walk, every solution appended to `out` (io.all, io.solutions and ck.resume are not read).  Fresh
+ * or resumed is a fact per instance, its ck.slots entry (-2 / >= 0).  A node without open variables asks for its row
+ * BEFORE it is counted: without room a child goes round once more with `refused` set and leaves through the checkpoint
+ * code of the budget, status 4, nv still that value; a root node leaves with zero fields and its slot entry -2.  New
+ * per-instance state is scalars only: refused, room, the row index. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -67,9 +73,29 @@
     int slot = -1, kept = -1, depth0 = 0, best0 = 0;
     bool resumed = false, have_best0 = false;
     cs_val *stack = wave_stack;
+#if CS_WALK_STREAM
+    /* the stream as it stands now (a relaxed load: a hint, the append itself decides), then what the instance is */
+    const unsigned long long appended = (unsigned long long)cs_dive_uniform(
+        (long long)__hip_atomic_load(out.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    slot = __builtin_amdgcn_readfirstlane(ck.slots[inst]);
+    if (slot < 0 && slot != -2) continue; /* finished: nothing of it is read or written */
+    if (appended >= (unsigned long long)out.capacity) { /* full already: no walk; an instance with a slot stays as it is */
+      if (slot == -2 && lane == 0) {
+        cs_dive_result res;
+        res.status = 4; /* CSGPU_MANY_FULL */
+        res.root_props = 0;
+        res.nodes = 0; res.cuts = 0; res.props = 0; res.solutions = 0;
+        io.results[inst] = res;
+      }
+      continue;
+    }
+    if (slot < 0) slot = -1; /* a fresh instance: it draws its slot when it stops */
+    if (slot >= 0) {
+#else
     if (ck.resume) {
       slot = __builtin_amdgcn_readfirstlane(ck.slots[inst]);
       if (slot < 0) continue; /* not stopped, or stopped without a checkpoint: nothing of it is written */
+#endif
       cs_val head = cs_interval(-1, 0), inc = cs_interval(0, -2);
       if (slot < ck.capacity) { /* compared before it is read; the two header entries, nothing else of the slot yet */
         const cs_val *base = ck.pool + (size_t)slot * (fstride * fstride);
@@ -118,6 +144,9 @@
 #if CS_WALK_UPTO
       have_best = false; /* an up-to-k walk has no incumbent, whatever the header says: obj_var is -1 */
 #endif
+#if CS_WALK_STREAM
+      have_best = false; /* nor has the stream's ALL walk */
+#endif
     }
 #if CS_WALK_UPTO
     /* a resumed instance that holds its k solutions already (a smaller k than the slice before): DONE before it tries a
@@ -141,6 +170,9 @@
       int depth = 0, bv = 0, nv = 0;
       bool root = true, fresh = true; /* fresh: the slice holds the current node as it was entered */
       cs_val *f = wave_stack;
+#if CS_WALK_STREAM
+      bool refused = false; /* the child that was tried last is a solution the stream had no room for */
+#endif
 #if CS_WALK_CK
       if (resumed) { /* "try value nv of variable bv on the node in frame depth0", which is read into the slice */
         depth = depth0;
@@ -165,8 +197,13 @@
         bool last = false;
         if (!root) {
 #if CS_WALK_CK
+#if CS_WALK_STREAM
+          if (refused || nodes - nodes0 >= io.max_nodes) {
+            status = refused ? 4 /* CSGPU_MANY_FULL: nv is the refused value, the node in its frame is as it was */ : 1;
+#else
           if (nodes - nodes0 >= io.max_nodes) {
             status = 1; /* CSGPU_MANY_LIMIT */
+#endif
             /* leave a checkpoint, if the pool has a slot */
 #if CS_WALK_UPTO
             if (ck.capacity > 0) /* no pool: no slot is drawn, the instance ends as without checkpoints */
@@ -244,6 +281,30 @@
             open_vars += __popcll(__ballot(open));
           }
         }
+#if CS_WALK_STREAM
+        /* a node that is a solution takes its row before any counter moves: one relaxed agent-scope add by lane 0, the
+         * old value broadcast.  Refused, a child was not tried at all; a root node is not started (status FULL, the other
+         * fields zero, its slot entry stays -2). */
+        if (!failed && open_vars == 0) {
+          __builtin_amdgcn_wave_barrier(); /* the wave meets before lane 0 adds, as in front of the ticket */
+          unsigned long long at = 0ull;
+          if (lane == 0) at =__hip_atomic_fetch_add(out.count, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          at = (unsigned long long)cs_dive_uniform((long long)at);
+          const bool room = at < (unsigned long long)out.capacity;
+          if (!room) {
+            if (root) {
+              status = 4; /* CSGPU_MANY_FULL */
+              kept = -2;
+              break;
+            }
+            refused = true;
+            continue;
+          }
+          int *row = out.rows + (size_t)at * (size_t)n;
+          for (int v = lane; v < n; v += CS_WAVE) row[v] = dom[v].lo;
+          if (lane == 0) out.owner[at] = inst;
+        }
+#endif
         bool descend = false;
         const bool at_root = root;
         if (root) {
@@ -263,7 +324,9 @@
         }
         if (!failed && open_vars == 0) { /* every variable valued: a solution (the root row itself may be the one) */
           sols++;
-#if CS_WALK_UPTO
+#if CS_WALK_STREAM
+          if (at_root) break; /* its row stands in the stream already; the root node was the one solution, else on (ALL) */
+#elif CS_WALK_UPTO
           if (io.solutions != nullptr) { /* 1 <= sols <= upto here: a fresh count starts at 0, a resumed one below upto */
             const size_t srow = ((size_t)inst * (size_t)upto + (size_t)(sols - 1)) * (size_t)n;
             for (int v = lane; v < n; v += CS_WAVE) io.solutions[srow + v] = dom[v].lo;

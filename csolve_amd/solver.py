@@ -355,19 +355,24 @@ class Model:
         the call before (the counters of a resumed instance are read from it), by default zeroed.  max_nodes: the budget
         of THIS call per instance.  -> the dict of solve_many(..., checkpoints=pool) without `first`; its `_slots` and
         `_records` are what the next call takes.  The rows are out.take()'s: take them before the next call."""
-        L = load_library()
+        return self._solve_many_stream("csgpu_solve_many_stream", self.qualifies(7), roots, out, pool, slots, results,
+                                       max_nodes, stream)
+
+    def _solve_many_stream(self, entry, qualifies, roots, out, pool, slots, results, max_nodes, stream) -> dict:
+        """solve_many_stream and solve_many_clauses_stream: `entry` is the library's call, `qualifies` its rule"""
+        call = getattr(load_library(), entry)
         opt = ManyOptions(1, 0, int(max_nodes))
         desc = out.struct()
         roots, K = self._many_roots(roots, out.capacity < 1, lambda ptr, count: check(
-            L.csgpu_solve_many_stream(self._h, ptr, count, C.byref(opt), ptr, pool._h if pool is not None else ptr, ptr,
-                                      C.byref(desc), None)))
+            call(self._h, ptr, count, C.byref(opt), ptr, pool._h if pool is not None else ptr, ptr, C.byref(desc), None)),
+            qualifies=qualifies)
         buf = self._many_records(K, roots.device) if results is None else results
         if slots is None:
             slots = torch.full((max(K, 1),), MANY_SLOT_FRESH, dtype=torch.int32, device=roots.device)
         assert buf.is_cuda and buf.dtype == torch.int64 and buf.is_contiguous() and tuple(buf.shape) == (max(K, 1), 5)
         assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[0] == max(K, 1)
-        check(L.csgpu_solve_many_stream(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
-                                        pool._h, slots.data_ptr(), C.byref(desc), _stream_ptr(stream)))
+        check(call(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(), pool._h,
+                   slots.data_ptr(), C.byref(desc), _stream_ptr(stream)))
         ans = self._many_answer(buf, K, None, slots, pool)
         ans["_roots"] = roots
         return ans
@@ -383,6 +388,12 @@ class Model:
         rows of one instance in walk order within and across drains); nothing is kept then.
         max_calls: stop after that many calls; the answer then also has `slot`, `_slots`, `_records`, `_checkpoints`,
         `_roots` and `stream`, which solve_many_stream takes to go on."""
+        return self._solve_many_all(self.solve_many_stream, self.many_checkpoints, self.qualifies(7), roots, max_nodes,
+                                    stream_rows, on_rows, max_calls)
+
+    def _solve_many_all(self, one_call, make_pool, qualifies, roots, max_nodes, stream_rows, on_rows, max_calls) -> dict:
+        """the loop of solve_many_all and solve_many_clauses_all: `one_call` is the family's stream call, `make_pool` its
+        pool and `qualifies` its rule"""
         out = self.many_stream(stream_rows)
         K = int(roots.shape[0])
         pool = slots = results = ans = None
@@ -390,9 +401,9 @@ class Model:
         while True:
             # (a numpy batch on a model that cannot run the call gets the library's error from the call's own probe,
             # before anything is allocated for it)
-            if pool is None and (torch.is_tensor(roots) or self.qualifies(7)):
-                pool = self.many_checkpoints(max(K, 1))
-            ans = self.solve_many_stream(roots, out, pool, slots, results, max_nodes=max_nodes)
+            if pool is None and (torch.is_tensor(roots) or qualifies):
+                pool = make_pool(max(K, 1))
+            ans = one_call(roots, out, pool, slots, results, max_nodes=max_nodes)
             roots, slots, results = ans["_roots"], ans["_slots"], ans["_records"]
             calls += 1
             owner, rows = out.take()
@@ -553,6 +564,29 @@ class Model:
         -> the dict of solve_many_clauses under ANY plus `restarts` [K] int32."""
         return self._solve_many_restarts("csgpu_solve_many_clauses_restarts", self.qualifies_many_clauses(), roots, max_nodes,
                                          restart_base, seed, seeds, rotate_first, solutions, restarts, stream)
+
+    def solve_many_clauses_stream(self, roots, out: "ManySolutionStream", pool: "ManyCheckpoints", slots=None, results=None,
+                                  *, max_nodes, stream=None) -> dict:
+        """ONE call of csgpu_solve_many_clauses_stream: solve_many_stream for the clause models.  The ALL walk of
+        solve_many_clauses_upto -- "<obj>" an ordinary variable, no incumbent -- with every solution appended to `out`
+        (many_stream()); an instance the stream has no room for steps back to before that solution and stops with status
+        4 (FULL).  pool: many_clause_checkpoints(); K slots never run out.  roots, slots, results, max_nodes, stream and
+        the answer: as solve_many_stream; the model must satisfy qualifies_many_clauses()."""
+        return self._solve_many_stream("csgpu_solve_many_clauses_stream", self.qualifies_many_clauses(), roots, out, pool,
+                                       slots, results, max_nodes, stream)
+
+    def solve_many_clauses_all(self, roots, *, max_nodes, stream_rows=65536, on_rows=None, max_calls=None) -> dict:
+        """every solution of every instance of a clause model ("every timetable of these windows"): the loop of
+        solve_many_all over solve_many_clauses_stream with a pool of K clause slots.  Every instance ends DONE with the
+        record of solve_many_clauses(roots, "ALL") under an unlimited budget, whatever stream_rows and max_nodes are.
+        The answer (`offsets`, `rows`, `calls`), on_rows and max_calls: exactly as solve_many_all; what max_calls leaves
+        is what solve_many_clauses_stream takes to go on."""
+        return self._solve_many_all(self.solve_many_clauses_stream, self.many_clause_checkpoints, self.qualifies_many_clauses(),
+                                    roots, max_nodes, stream_rows, on_rows, max_calls)
+
+    def many_clauses_stream_kernel(self):
+        """the cs_walk_stream instantiation solve_many_clauses_stream launches, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_stream_symbol")
 
     def many_clauses_restart_kernel(self):
         """the cs_walk_restart instantiation solve_many_clauses_restarts launches, or None"""

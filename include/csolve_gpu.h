@@ -636,6 +636,60 @@ int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csgpu_val *d_r
                                       int32_t *d_solutions /* NULL or [count][n_vars] */,
                                       int32_t *d_restarts /* NULL or [count] */, void *stream);
 
+/* ---- every solution of every instance of a clause model under ALL, through one bounded stream ----
+ * What "every solution of every instance under ALL" above is to csgpu_solve_many, for the clause models: "every timetable
+ * of these 10,000 windows", where one row has 8 and its neighbour a quarter of a million, so that no k of
+ * csgpu_solve_many_clauses_upto fits.  The walk is the ALL walk of csgpu_solve_many_clauses_upto ("The walk" above: same
+ * root check and BAD_ROOT, root node, branching rule, ascending values and counters; "<obj>", if the model has one, is an
+ * ordinary variable and there is no incumbent, so a model whose own objective is MIN or MAX is accepted), and every
+ * solution is appended to ONE output stream that all instances share.  csgpu_many_stream, CSGPU_MANY_FULL and
+ * CSGPU_MANY_SLOT_FRESH are those above.  options->objective must be 1; options->max_nodes is the budget of THIS call per
+ * instance (nodes tried in the call), as in csgpu_solve_many_clauses_resume; LIMIT behaves as there.  One entry point
+ * starts and resumes instances, because with a bounded stream every call after the first does both.
+ *   appending     when a child, or the root node after its fixpoint, has every variable valued, one relaxed agent-scope
+ *                 atomic adds 1 to *d_count; the old value idx is the row.  idx < capacity: d_rows[idx] receives the
+ *                 solution (absolute values, a row index of 64 bits), d_owner[idx] the instance, and the solution is
+ *                 counted.  idx >= capacity: it is refused (below).  The kernel never zeroes *d_count: after a call the
+ *                 valid rows are the first min(*d_count, capacity), and the caller copies them out and zeroes the word on
+ *                 the same stream before the next call.  One wave walks an instance at a time and calls are ordered on the
+ *                 stream, so the rows of one instance appear in walk order: by index within a call, by call across calls.
+ *   refusal       a refused solution is not lost.  The child that produced it is not counted (nodes, cuts, props and
+ *                 solutions are what they were before it was tried), the instance stops with CSGPU_MANY_FULL, and it
+ *                 writes the checkpoint a LIMIT stop writes: frames 0 .. depth and {variable, next value} with the next
+ *                 value that very value.  The next call tries the child again, and it is counted once.  A root node that
+ *                 is itself the solution and finds no room: status FULL, every other field zero, d_slots[i] stays -2, and
+ *                 the next call runs the root again.
+ *   d_slots[i]    on entry  -2 (CSGPU_MANY_SLOT_FRESH): start instance i from root row i.  -1, or anything below -2:
+ *                 finished, nothing of the instance is read or written.  >= 0: go on from that slot, the counters are read
+ *                 from d_results[i]; a number outside the pool, a slot without a checkpoint, or one whose header holds
+ *                 another code than 5 gives CSGPU_MANY_BAD_SLOT, compared before anything else of the slot is read, and
+ *                 only the status is written.
+ *                 on exit   -2: not started (see "full at the draw" and the root node above).  -1: finished (DONE,
+ *                 BAD_ROOT), or stopped (LIMIT / FULL, with its counters) while the pool had no slot left: its walk is
+ *                 gone, as in csgpu_solve_many_clauses_checkpointed, but no row of it is.  >= 0: stopped with a checkpoint
+ *                 (LIMIT or FULL); a resumed instance goes back into the SAME slot.
+ *   full at the draw   a wave that has drawn a ticket first reads *d_count (relaxed); if it is >= capacity already the
+ *                 wave does not walk: a fresh instance stays -2 with status FULL and zero fields, one with a slot is left
+ *                 exactly as it was.  So a full stream drains the remaining tickets quickly.
+ * The caller's loop:  slots = -2; do { call; take the rows; zero the count } while (any slot != -1).  The guarantee: a
+ * pool of `count` slots never runs out, and with such a pool every instance ends DONE with its record equal, field for
+ * field, to csgpu_solve_many_clauses under ALL with an unlimited budget, whatever capacity >= 1 and budget the calls had;
+ * the rows drained for the instance are its walk's solutions in walk order, each exactly once.
+ * The pool is one of csgpu_many_clause_checkpoints_create with its slot layout.  The header's code field holds 5, "stream":
+ * a checkpoint made here gives CSGPU_MANY_BAD_SLOT to csgpu_solve_many_clauses_resume and
+ * csgpu_solve_many_clauses_upto_resume, and theirs give it here.  csgpu_many_clause_checkpoint_states accepts a slot
+ * written here as it accepts an up-to-k one (*have_best is 0).  "One call in flight per model" covers this call (same
+ * workspace, sized as for a fresh call, same ticket counters); calls of all families may be queued behind each other on
+ * one stream without the host in between.
+ * Errors before any HIP call, in csgpu_solve_many_clauses's order: a null m / d_roots / d_results / options / ck /
+ * d_slots / out, count < 0, max_nodes <= 0 -> CSGPU_E_ARG; an objective other than ALL -> CSGPU_E_ARG; capacity < 1 or a
+ * null pointer inside *out -> CSGPU_E_ARG; model not finalized -> CSGPU_E_STATE; a model that does not qualify for
+ * csgpu_solve_many_clauses -> CSGPU_E_LIMIT; count > 2^31 - 65 -> CSGPU_E_LIMIT; a pool of another model or of
+ * csgpu_many_checkpoints_create -> CSGPU_E_ARG.  count == 0 -> CSGPU_OK, nothing is launched. */
+int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                    const csgpu_many_options *options, csgpu_many_result *d_results,
+                                    csgpu_many_checkpoints *ck, int32_t *d_slots, const csgpu_many_stream *out, void *stream);
+
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */
 int csgpu_eval_batch(const csgpu_model *m, const csgpu_val *d_states, int32_t *d_truth, int64_t batch,

@@ -29,7 +29,15 @@ of the same rows and the same budget (default 20,000), and the restart call with
 both, the three interleaved in this process.  The rows are not a set of the tests: --count windows of problems.schedule(10,
 1) as tests/many_clause_restart_sets.py draws its tail workload (width 30, at most 40 values for `end`, rows seed 11), walk
 seed 7.  A launch lasts as long as its deepest instance: the output has the deepest walk and the nodes in all of both
-calls.  The seeded sample is re-checked against the host walk (tests/many_walk_clauses_restarts.py)."""
+calls.  The seeded sample is re-checked against the host walk (tests/many_walk_clauses_restarts.py).
+
+--stream ROWS [--budget N] times three routes to every solution of every instance, interleaved in this process after a
+warm-up: the counting ALL call (solve_many_clauses, no rows at all), ONE solve_many_clauses_stream call into a stream with
+room for everything (pool and stream made once, reset per repetition), and the loop solve_many_clauses_all with a stream
+of ROWS rows (its pool and stream made per repetition, as a caller's would be).  The rows are those of
+tests/many_clause_stream_sets.py (--set one of its names, default wcet_max), repeated up to --count; every walk ends within
+the default budget of 16,000 nodes.  The records of both stream routes must equal the counting call's in every field, and
+the rows of the seeded sample the host walk's, in walk order."""
 import argparse
 import json
 import os
@@ -64,7 +72,8 @@ def main():
     import many_clause_sets as sets
     import many_walk_objective as W
     ap = argparse.ArgumentParser()
-    ap.add_argument("--set", default="schedule5_min", choices=sorted(sets.SETS))
+    ap.add_argument("--set", default=None, help="a set of tests/many_clause_sets.py (default schedule5_min); with --stream one "
+                                                "of tests/many_clause_stream_sets.py (default wcet_max)")
     ap.add_argument("--count", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop-sample", type=int, default=128)
@@ -76,7 +85,16 @@ def main():
     ap.add_argument("--budget", type=int, default=None, help="the one call's budget (default: the set's, or the sum of --sliced)")
     ap.add_argument("--restarts", type=int, default=None, help="BASE: time solve_many_clauses_restarts beside the ANY call")
     ap.add_argument("--rotate-first", action="store_true", help="with --restarts: run 0 rotates as well")
+    ap.add_argument("--stream", type=int, default=None, help="ROWS: time the counting ALL call, one stream call with room for "
+                                                             "everything and the loop with a stream of ROWS rows")
     args = ap.parse_args()
+    if args.stream is not None:
+        if args.stream < 1 or args.sliced or args.upto is not None or args.restarts is not None:
+            ap.error("--stream ROWS: ROWS >= 1, without --sliced, --upto and --restarts")
+        return stream_route(args)
+    args.set = args.set or "schedule5_min"
+    if args.set not in sets.SETS:
+        ap.error(f"--set: one of {sorted(sets.SETS)}")
     if args.restarts is not None:
         if args.restarts < 0 or args.sliced or args.upto is not None:
             ap.error("--restarts BASE: BASE >= 0, without --sliced and --upto")
@@ -230,6 +248,88 @@ def restart_route(args):
     record.update({"restarted": int((got["restarts"] > 0).sum()), "most_restarts": int(got["restarts"].max()),
                    "oracle_checked": len(picks), "oracle_ok": bool(ok)})
     print(json.dumps(record))
+    return 0 if ok and same else 1
+
+
+def stream_route(args):
+    """the counting ALL call, one stream call with room for everything, and the loop with a small stream"""
+    import many_clause_stream_sets as ssets
+    import many_walk_clauses_upto as U
+    name = args.set or "wcet_max"
+    if name not in ssets.TABLE:
+        raise SystemExit(f"--stream: --set is one of {sorted(ssets.TABLE)}")
+    text, base = ssets.build(name)
+    budget = args.budget or ssets.BUDGET
+    roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
+    count = len(roots)
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+    rng = np.random.default_rng(args.seed)
+    fields = ("status", "root_props", "nodes", "cuts", "props", "solutions")
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    counting = lambda: model.solve_many_clauses(dev, "ALL", max_nodes=budget, solutions=False)  # noqa: E731
+    total = int(timed(counting)[1]["solutions"].sum().item())
+    pool = model.many_clause_checkpoints(count)
+    out = model.many_stream(max(total, 1))
+
+    def streamed():
+        return model.solve_many_clauses_stream(dev, out, pool, max_nodes=budget)
+
+    def looped():
+        return model.solve_many_clauses_all(dev, max_nodes=budget, stream_rows=args.stream)
+
+    def fresh():  # between the repetitions, outside the timed part
+        pool.reset()
+        out.count.zero_()
+
+    for _ in range(2):  # warm-up: code load, workspace
+        timed(counting), fresh(), timed(streamed), timed(looped)
+    times = {"count": [], "stream": [], "loop": []}
+    for _ in range(args.reps):
+        dt, counted = timed(counting)
+        times["count"].append(dt)
+        fresh()
+        dt, one = timed(streamed)
+        times["stream"].append(dt)
+        dt, every = timed(looped)
+        times["loop"].append(dt)
+    host = lambda o: {k: v.cpu().numpy() for k, v in o.items() if torch.is_tensor(v) and not k.startswith("_")}  # noqa: E731
+    calls = int(every["calls"])
+    counted, one, every = host(counted), host(one), host(every)
+    attempts = int(out.count.item())
+    owner, rows = (a.cpu().numpy() for a in out.take())
+    same = all(bool((one[f] == counted[f]).all()) and bool((every[f] == counted[f]).all()) for f in fields)
+    same = same and attempts == total == int(every["offsets"][-1]) and bool((one["slot"] == -1).all())
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    ok = True
+    for i in picks:
+        want = U.Walk(text, roots[i]).run(budget, None)
+        mine = rows[owner == i]  # in stream order, which is walk order within one instance
+        lo, hi = int(every["offsets"][i]), int(every["offsets"][i + 1])
+        ok = ok and all(int(one[f][i]) == want[f] for f in U.FIELDS) and len(mine) == len(want["rows"]) == hi - lo
+        if ok and want["rows"]:
+            ok = bool((mine == np.stack(want["rows"])).all()) and bool((every["rows"][lo:hi] == np.stack(want["rows"])).all())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(json.dumps({
+        "tool": "time_solve_many_clauses", "route": "stream", "commit": commit(), "command": " ".join(sys.argv), "set": name,
+        "instances": count, "max_nodes": budget, "n_vars": model.n_vars, "clauses": model.n_clauses,
+        "kernel": model.many_clauses_kernel(), "stream_kernel": model.many_clauses_stream_kernel(),
+        "waves": model.many_clauses_waves(count), "slot_bytes": model.clause_checkpoint_bytes(),
+        "status_counts": np.bincount(counted["status"], minlength=5).tolist(), "nodes": int(counted["nodes"].sum()),
+        "largest_tree": int(counted["nodes"].max()), "solutions": total,
+        "solutions_per_node": round(total / max(int(counted["nodes"].sum()), 1), 3),
+        "count_ms": spread(times["count"]), "stream_ms": spread(times["stream"]), "loop_ms": spread(times["loop"]),
+        "stream_rows": args.stream, "loop_calls": calls,
+        "stream_over_count": round(med["stream"] / med["count"], 3), "loop_over_count": round(med["loop"] / med["count"], 3),
+        "records_equal_the_counting_call": bool(same), "oracle_checked": len(picks), "oracle_ok": bool(ok),
+    }))
     return 0 if ok and same else 1
 
 
