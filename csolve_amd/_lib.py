@@ -244,6 +244,9 @@ def load_library():
     L.csgpu_solve_many_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
     L.csgpu_solve_many_resume.argtypes = [vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
     L.csgpu_many_checkpoint_states.argtypes = [vp, C.c_int32, vp, i64, C.POINTER(i64), vp]
+    L.csgpu_many_checkpoint_children.argtypes = [vp, vp, i64, vp, vp]
+    L.csgpu_many_checkpoint_fanout.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
+    L.csgpu_many_fold.argtypes = [vp, vp, i64, vp, vp]
     L.csgpu_solve_many_upto.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp]
     L.csgpu_solve_many_upto_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
     L.csgpu_solve_many_upto_resume.argtypes = [vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]

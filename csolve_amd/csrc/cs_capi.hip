@@ -1875,6 +1875,57 @@ extern "C" int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, in
   return many_pool_states(ck, MANY_POOL_DIVE, slot, d_states, cap, count, NULL, stream);
 }
 
+/* ---- stopped ALL walks spread over the next launch: their children counted, fanned out as root rows, folded back ---- */
+
+#define MANY_FAN_LIMIT "more than 2^31 - 1 instances in one call"
+
+extern "C" int csgpu_many_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                              int64_t *d_children, void *stream) {
+  if (ck == NULL || d_slots == NULL || d_children == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (ck->kind != MANY_POOL_DIVE) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  if (count > 0x7fffffff) return set_err(CSGPU_E_LIMIT, MANY_FAN_LIMIT);
+  if (count == 0) return CSGPU_OK;
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  hipLaunchKernelGGL(cs_dive_children, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, m->host->n_vars,
+                     (const int *)m->d_root_lo, (const int *)m->d_root_hi, (const cs_val *)ck->d_pool, (int)ck->capacity,
+                     (const int *)d_slots, (long long)count, (long long *)d_children);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                            const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total,
+                                            void *stream) {
+  if (ck == NULL || d_slots == NULL || d_offsets == NULL || d_rows == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (total < 0) return set_err(CSGPU_E_ARG, "negative row count");
+  if (ck->kind != MANY_POOL_DIVE) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  if (count > 0x7fffffff) return set_err(CSGPU_E_LIMIT, MANY_FAN_LIMIT);
+  if (count == 0 || total == 0) return CSGPU_OK;
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  hipLaunchKernelGGL(cs_dive_fanout, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, m->host->n_vars,
+                     (const int *)m->d_root_lo, (const int *)m->d_root_hi, (const cs_val *)ck->d_pool, (int)ck->capacity,
+                     (const int *)d_slots, (long long)count, (const long long *)d_offsets, (long long)total, (cs_val *)d_rows,
+                     (int *)d_owner);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_fold(const csgpu_many_result *d_sub_results, const int32_t *d_owner, int64_t total,
+                               csgpu_many_result *d_results, void *stream) {
+  if (d_sub_results == NULL || d_owner == NULL || d_results == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (total < 0) return set_err(CSGPU_E_ARG, "negative record count");
+  if (total > 256ll * 0x7fffffff) return set_err(CSGPU_E_LIMIT, "more than 2^39 - 256 records in one call");
+  if (total == 0) return CSGPU_OK;
+  hipLaunchKernelGGL(cs_dive_fold, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const cs_dive_result *)d_sub_results, (const int *)d_owner, (long long)total, (cs_dive_result *)d_results);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
 /* ---- up to k solutions per instance (cs_dive_upto): csgpu_solve_many, stopped at the k-th solution, all k rows kept ---- */
 
 /* the three calls.  `pooled`: the call has a pool and slot numbers; `resume` (pooled, and no roots): it goes on in them */

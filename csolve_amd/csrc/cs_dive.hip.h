@@ -242,4 +242,125 @@ __global__ void cs_dive_export(int n, const int *__restrict__ root_lo, const cs_
   }
 }
 
+/* ---- a stopped ALL walk spread over the waves of the next launch (csgpu_many_checkpoint_children / _fanout, csgpu_many_fold)
+ *
+ * A checkpoint is a list of frames "node, branching variable bv, next value": the untried children of the walk are, in walk
+ * order, the values next .. node[bv].hi of the current node (frame `depth`), then those of frame depth - 1, down to frame
+ * 0.  Child (d, v) walked as a root row of its own -- the node in absolute bounds with bv = [v, v] -- gives its owner
+ * exactly what the one walk counts for that child and everything below it:
+ *
+ *   nodes     1 + sub.nodes
+ *   cuts      sub.cuts, plus 1 if the row was inconsistent as a root (DONE, no node, no solution)
+ *   props     sub.root_props + sub.props   (the fixpoint of a != network is unique, props counts units shaved, and the
+ *                                           assignment itself is counted on neither side)
+ *   solutions sub.solutions
+ *
+ * The kernels are not templated: a slot is 8-byte entries relative to the root lower bounds whatever E and R wrote it.
+ * One wave per instance, 64-bit row indices, no atomics in the count or the fan-out; the fold adds with relaxed
+ * agent-scope 64-bit atomics.  A slot is checked before anything that depends on it is read: a slot number outside the
+ * pool, a header without the magic, a depth outside [0, n), a frame whose bv is outside [0, n), whose node's bounds of bv
+ * are outside the root domain's width or whose next value is outside those bounds give -1, never a count. */
+#define CS_DIVE_FAN_WAVES 4 /* instances per workgroup */
+
+static __device__ __forceinline__ long long cs_dive_slot_children(int n, const int *__restrict__ root_lo,
+                                                                  const int *__restrict__ root_hi,
+                                                                  const cs_val *__restrict__ pool, int capacity, int slot,
+                                                                  int lane) {
+  if (slot < 0) return 0;
+  if (slot >= capacity) return -1;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (fstride * fstride);
+  const cs_val head = base[0];
+  const int depth = __builtin_amdgcn_readfirstlane(head.lo);
+  if (__builtin_amdgcn_readfirstlane(head.hi) != CS_DIVE_CK_MAGIC || depth < 0 || depth >= n) return -1;
+  long long mine = 0;
+  bool bad = false;
+  for (int d = lane; d <= depth && !bad; d += CS_WAVE) {
+    const cs_val *f = base + fstride * (1 + (size_t)d);
+    const cs_val meta = f[n];
+    if (meta.lo < 0 || meta.lo >= n) {
+      bad = true;
+    } else {
+      const cs_val node = f[meta.lo];
+      if (node.lo < 0 || node.hi > root_hi[meta.lo] - root_lo[meta.lo] || meta.hi < node.lo || meta.hi > node.hi)
+        bad = true;
+      else
+        mine += (long long)node.hi - (long long)meta.hi + 1;
+    }
+  }
+  if (__ballot(bad) != 0ull) return -1;
+  for (int o = CS_WAVE / 2; o > 0; o >>= 1) mine += __shfl_xor(mine, o, CS_WAVE);
+  return cs_dive_uniform(mine);
+}
+
+/* children[i] = the untried children of the checkpoint in slot slots[i]: 0 for slots[i] < 0, -1 for a slot that is refused */
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_dive_children(int n, const int *__restrict__ root_lo,
+                                                                                const int *__restrict__ root_hi,
+                                                                                const cs_val *__restrict__ pool, int capacity,
+                                                                                const int *__restrict__ slots, long long count,
+                                                                                long long *__restrict__ children) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
+  const long long c = cs_dive_slot_children(n, root_lo, root_hi, pool, capacity, slot, lane);
+  if (lane == 0) children[i] = c;
+}
+
+/* rows[offsets[i] ..] = the children of instance i in walk order, owner[row] = i.  The instance is counted again first: it
+ * writes nothing unless offsets[i + 1] - offsets[i] is its count and its rows lie inside [0, total) */
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_dive_fanout(int n, const int *__restrict__ root_lo,
+                                                                              const int *__restrict__ root_hi,
+                                                                              const cs_val *__restrict__ pool, int capacity,
+                                                                              const int *__restrict__ slots, long long count,
+                                                                              const long long *__restrict__ offsets,
+                                                                              long long total, cs_val *__restrict__ rows,
+                                                                              int *__restrict__ owner) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
+  if (slot < 0) return;
+  const long long mine = cs_dive_slot_children(n, root_lo, root_hi, pool, capacity, slot, lane);
+  const long long off = cs_dive_uniform(offsets[i]), end = cs_dive_uniform(offsets[i + 1]);
+  if (mine <= 0 || off < 0 || end > total || end - off != mine) return;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (fstride * fstride);
+  const int depth = __builtin_amdgcn_readfirstlane(base[0].lo);
+  long long row = off;
+  for (int d = depth; d >= 0; d--) {
+    const cs_val *f = base + fstride * (1 + (size_t)d);
+    const cs_val meta = f[n];
+    const int bv = __builtin_amdgcn_readfirstlane(meta.lo);
+    const int next = __builtin_amdgcn_readfirstlane(meta.hi);
+    const int hi = __builtin_amdgcn_readfirstlane(f[bv].hi);
+    for (long long v = next; v <= (long long)hi && row < end; v++, row++) {
+      cs_val *dst = rows + (size_t)row * (size_t)n;
+      for (int x = lane; x < n; x += CS_WAVE) {
+        const cs_val e = f[x];
+        const int b = root_lo[x];
+        dst[x] = x == bv ? cs_interval((int)v + b, (int)v + b) : cs_interval(e.lo + b, e.hi + b);
+      }
+      if (owner != nullptr && lane == 0) owner[row] = (int)i;
+    }
+  }
+}
+
+/* results[owner[t]] += the contribution of sub-instance record t (above); status and root_props of the owner stay */
+__global__ __launch_bounds__(256) void cs_dive_fold(const cs_dive_result *__restrict__ sub, const int *__restrict__ owner,
+                                                    long long total, cs_dive_result *results) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int o = owner[t];
+  if (o < 0) return;
+  const cs_dive_result r = sub[t];
+  cs_dive_result *dst = results + o;
+  const long long cuts = r.cuts + (r.status == 0 /* CSGPU_MANY_DONE */ && r.nodes == 0 && r.solutions == 0 ? 1 : 0);
+  const long long props = (long long)r.root_props + r.props;
+  __hip_atomic_fetch_add(&dst->nodes, 1 + r.nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (cuts != 0) __hip_atomic_fetch_add(&dst->cuts, cuts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (props != 0) __hip_atomic_fetch_add(&dst->props, props, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (r.solutions != 0) __hip_atomic_fetch_add(&dst->solutions, r.solutions, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 #endif

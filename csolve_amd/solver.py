@@ -924,6 +924,170 @@ class Model:
         out["status"][i] = 0
         out["slot"][i] = -1
 
+    def checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None) -> torch.Tensor:
+        """the untried children of the checkpoints in `slots` (int32 [S] on the device) -> int64 [S]: 0 for a slot < 0,
+        -1 for a slot that is refused (csgpu_many_checkpoint_children)"""
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+        S = slots.shape[0]
+        children = torch.empty((max(S, 1),), dtype=torch.int64, device=slots.device)
+        check(load_library().csgpu_many_checkpoint_children(checkpoints._h, slots.data_ptr(), S, children.data_ptr(),
+                                                            _stream_ptr(stream)))
+        return children[:S]
+
+    def checkpoint_fanout(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, offsets: torch.Tensor, total: int,
+                          rows: torch.Tensor = None, owner: torch.Tensor = None, stream=None):
+        """the children of the checkpoints in `slots` as root rows, in walk order (csgpu_many_checkpoint_fanout): offsets
+        int64 [S + 1], the exclusive prefix sum of checkpoint_children() on the device.  -> (rows int32 [total, n_vars, 2],
+        owner int32 [total]: the index into `slots` a row came from); given buffers are written in place, and an instance
+        whose count disagrees with its offsets writes nothing"""
+        n, S, total = self.n_vars, slots.shape[0], int(total)
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and tuple(offsets.shape) == (S + 1,)
+        if rows is None:
+            rows = torch.empty((max(total, 1), n, 2), dtype=torch.int32, device=slots.device)
+        if owner is None:
+            owner = torch.empty((max(total, 1),), dtype=torch.int32, device=slots.device)
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= total * n * 2
+        assert owner.dtype == torch.int32 and owner.is_contiguous() and owner.numel() >= total
+        check(load_library().csgpu_many_checkpoint_fanout(checkpoints._h, slots.data_ptr(), S, offsets.data_ptr(),
+                                                          rows.data_ptr(), owner.data_ptr(), total, _stream_ptr(stream)))
+        return rows[:total], owner[:total]
+
+    def fold_many(self, sub: dict, owner: torch.Tensor, result: dict, stream=None) -> dict:
+        """add the records of the sub-instances `sub` (a checkpointed solve_many answer over fanned rows) to their owners
+        in `result` (csgpu_many_fold): owner int32 [T] indexes result's instances.  Exactly once per batch: a second
+        call counts it twice."""
+        T = sub["status"].shape[0]
+        assert owner.is_cuda and owner.dtype == torch.int32 and owner.is_contiguous() and owner.shape[0] == T
+        check(load_library().csgpu_many_fold(sub["_records"].data_ptr(), owner.data_ptr(), T, result["_records"].data_ptr(),
+                                             _stream_ptr(stream)))
+        return result
+
+    def solve_many_spread(self, roots, *, budgets=(256, 4096), max_rounds=64, max_rows=1 << 18, solutions=True, stream=None,
+                          pool_bytes=1 << 30, pools=None) -> dict:
+        """solve_many under ALL whose stopped instances are spread over the idle waves: round 0 is a checkpointed
+        solve_many with budgets[0]; every later round counts the untried children of the stopped instances
+        (checkpoint_children), fans them out as root rows of their own (checkpoint_fanout) and walks those as a fresh
+        checkpointed ALL batch with that round's budget (the last budget repeats).  A batch is folded into its owners
+        exactly once, when it is left (fold_many); a sub-instance's owner is mapped through the owner vector of the level
+        before.  The split is exact: an owner whose sub-instances all ended DONE is DONE with the record of the one ALL
+        call, field for field, and `first` is the walk's first solution.
+        max_rows: a round with more children is not fanned out, its stopped walks go on in place (resume_many) with that
+        round's budget.  max_rounds (round 0 included): owners with work left after it end LIMIT with the counters
+        folded so far, as does the owner of a stopped instance that got no slot.  Two alternating pools hold the
+        checkpoints, each of at most pool_bytes; pools=(a, b): two pools of many_checkpoints() to use instead (a caller
+        that times or repeats the call keeps them).  Synchronises once or twice per round (the counts of stopped
+        instances and of their children).
+        -> the dict of solve_many (device tensors [K]) plus `rounds`, `sub_instances` and `round_rows` (the rows fanned
+        out for every round after round 0; 0 for a round that went on in place)"""
+        budgets = tuple(int(b) for b in budgets)
+        assert len(budgets) >= 1 and max_rounds >= 1 and max_rows >= 0
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            own_pools = pools is None
+            pools = [None, None] if own_pools else list(pools)
+            try:
+                return self._solve_many_spread(roots, budgets, int(max_rounds), int(max_rows), bool(solutions), stream,
+                                               int(pool_bytes), pools, own_pools)
+            finally:
+                if own_pools:
+                    for p in pools:
+                        if p is not None:
+                            p.close()
+
+    def _solve_many_spread(self, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools, own_pools) -> dict:
+        BIG = 1 << 62  # "no solution yet": above every row number
+        slot_bytes = max(self.checkpoint_bytes(), 1)
+
+        def pool_for(rnd, batch):
+            """the pool of round `rnd`, empty: the one of round rnd - 1 is still read by the fan-out"""
+            k = rnd % 2
+            need = max(1, min(batch, pool_bytes // slot_bytes))
+            if own_pools and (pools[k] is None or pools[k].capacity < need):
+                if pools[k] is not None:
+                    pools[k].close()
+                pools[k] = self.many_checkpoints(need)
+            else:
+                pools[k].reset(stream)
+            return pools[k]
+
+        def budget(rnd):
+            return budgets[min(rnd, len(budgets) - 1)]
+
+        pool = pool_for(0, int(roots.shape[0]))
+        main = self.solve_many(roots, "ALL", max_nodes=budget(0), solutions=solutions, stream=stream, checkpoints=pool)
+        K = main["status"].shape[0]
+        dev = main["status"].device
+        limited = torch.zeros((max(K, 1),), dtype=torch.int32, device=dev)  # owners that end LIMIT
+        pos = None  # per owner, in the row numbers of the batch: a solution of a row below it comes before the owner's `first`
+        batch, owner = main, None  # owner: int32 [T], None for round 0 (every instance is its own)
+        rounds, round_rows = 1, []
+
+        def owners_of(index):
+            return index if owner is None else owner.long()[index]
+
+        def leave(last):
+            """fold the batch and take its first solutions; its stopped instances without a slot (`last`: all its
+            stopped instances) make their owners LIMIT"""
+            nonlocal pos
+            T = batch["status"].shape[0]
+            rows = torch.arange(T, dtype=torch.int64, device=dev)
+            stopped = batch["status"] == 1
+            if not last:
+                stopped = stopped & (batch["slot"] < 0)
+            stopped = stopped | (batch["status"] == 3)  # (a resume in place refused its slot: BAD_SLOT)
+            limited.index_add_(0, owners_of(rows), stopped.to(torch.int32))
+            if owner is not None:
+                self.fold_many(batch, owner, main, stream)
+            if not solutions:
+                return
+            has = batch["solutions"] > 0
+            if owner is None:
+                pos = torch.where(has, torch.zeros_like(rows), torch.full_like(rows, BIG))
+                return
+            lowest = torch.full((max(K, 1),), BIG, dtype=torch.int64, device=dev)
+            lowest.scatter_reduce_(0, owner.long(), torch.where(has, rows, torch.full_like(rows, BIG)), "amin")
+            lowest = lowest[:K]
+            take = lowest < pos
+            src = batch["first"][lowest.clamp(max=max(T - 1, 0))]
+            main["first"].copy_(torch.where(take[:, None], src, main["first"]))
+            pos = torch.where(take, lowest, pos)
+
+        while rounds < max_rounds and K > 0:
+            index = torch.nonzero((batch["status"] == 1) & (batch["slot"] >= 0)).flatten()  # ascending; waits for the batch
+            S = int(index.shape[0])
+            if S == 0:
+                break
+            slots = batch["slot"][index].contiguous()
+            children = self.checkpoint_children(pool, slots, stream)
+            offsets = torch.zeros((S + 1,), dtype=torch.int64, device=dev)
+            torch.cumsum(children.clamp(min=0), 0, out=offsets[1:])
+            total = int(offsets[-1].item())
+            if total > max_rows:  # too wide to fan out: the stopped walks go on where they are
+                self.resume_many(batch, max_nodes=budget(rounds), objective="ALL", stream=stream)
+                round_rows.append(0)
+                rounds += 1
+                continue
+            limited.index_add_(0, owners_of(index), (children < 0).to(torch.int32))  # refused slots: their work is lost
+            if total == 0:
+                break
+            rows, came_from = self.checkpoint_fanout(pool, slots, offsets, total, stream=stream)
+            leave(False)
+            if solutions:
+                pos = offsets[torch.searchsorted(index, pos)]
+            owner = owners_of(index[came_from.long()]).to(torch.int32).contiguous()
+            pool = pool_for(rounds, total)
+            batch = self.solve_many(rows, "ALL", max_nodes=budget(rounds), solutions=solutions, stream=stream, checkpoints=pool)
+            round_rows.append(total)
+            rounds += 1
+        leave(True)
+        status = main["status"]
+        status.copy_(torch.where(status == 2, status, (limited[:K] > 0).to(status.dtype)))
+        if own_pools:
+            torch.cuda.current_stream().synchronize()  # the pools go with the call
+        out = {k: v for k, v in main.items() if not k.startswith("_") and k != "slot"}
+        out["rounds"], out["sub_instances"], out["round_rows"] = rounds, sum(round_rows), round_rows
+        return out
+
     def _many_symbol(self, export: str):
         """the instantiation a family of solve_many launches for this model (template-id), by the library's `export`;
         None if the model does not qualify"""

@@ -310,6 +310,45 @@ int csgpu_solve_many_resume(const csgpu_model *m, int64_t count, const csgpu_man
 int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap, int64_t *count,
                                  void *stream);
 
+/* ---- stopped ALL walks spread over the waves of the next call ----
+ * A launch lasts as long as its deepest instance while the other waves idle.  A checkpoint holds what splits such a
+ * walk: every frame is "node, branching variable bv, next value", and the walk's untried children are, in WALK ORDER,
+ * the values next .. hi(bv) of the current node (ascending), then those of the frame below it, down to the oldest frame.
+ * Each child -- the frame's node in absolute bounds with bv = [v, v] -- is a root row that csgpu_solve_many[_checkpointed]
+ * walks like any other, and its record gives its owner, exactly (ALL only):
+ *   nodes += 1 + sub.nodes;  cuts += sub.cuts + (the row was inconsistent as a root: DONE, 0 nodes, 0 solutions);
+ *   props += sub.root_props + sub.props;  solutions += sub.solutions
+ * (the fixpoint of a != network is unique, props counts units shaved, and the assignment itself is counted on neither
+ * side).  Summed over all children, over any number of levels, that is the record of the one ALL call, field for field;
+ * the first solution in row order is the walk's first.
+ *   csgpu_many_checkpoint_children   d_children[i] = the children of the checkpoint in slot d_slots[i] (int64 [count]):
+ *                                    0 for d_slots[i] < 0; -1 for a slot that is refused: a number >= capacity, a header
+ *                                    without a checkpoint or with a depth outside [0, n_vars), a frame whose variable is
+ *                                    outside [0, n_vars), whose node's bounds of it lie outside the root domain or whose
+ *                                    next value lies outside those bounds.  Everything is compared before what depends
+ *                                    on it is read; a refused slot is never a count
+ *   csgpu_many_checkpoint_fanout     d_offsets: int64 [count + 1], the exclusive prefix sum of the counts (refused ones as
+ *                                    0), on the device: no host round trip in between.  Instance i writes its children
+ *                                    to rows d_offsets[i] .. of d_rows ([total][n_vars]) in walk order and, if d_owner is
+ *                                    not NULL, d_owner[row] = i (int32 [total]).  It counts its slot again first and
+ *                                    writes NOTHING unless d_offsets[i + 1] - d_offsets[i] is that count and the rows lie
+ *                                    inside [0, total).  The rows are copies: the pool may be reset once this has run
+ *   csgpu_many_fold                  d_results[d_owner[t]] += the contribution above of d_sub_results[t], t < total, with
+ *                                    relaxed device-scope 64-bit adds; status and root_props of the owner are not touched,
+ *                                    d_owner[t] < 0 is skipped.  Folding a record twice counts it twice: a batch is
+ *                                    folded exactly once, when the caller leaves it.  Owners across levels: map a row's
+ *                                    owner through the owner vector of the level before
+ * All three are asynchronous on `stream` and read the pool only; they take a pool of csgpu_many_checkpoints_create.
+ * Errors before any HIP call, in this order: a null pointer (d_owner of the fan-out may be null) -> CSGPU_E_ARG; count < 0
+ * or total < 0 -> CSGPU_E_ARG; a pool of csgpu_many_clause_checkpoints_create -> CSGPU_E_ARG; count > 2^31 - 1 ->
+ * CSGPU_E_LIMIT.  Then count == 0 or total == 0 -> CSGPU_OK, nothing is launched. */
+int csgpu_many_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count, int64_t *d_children,
+                                   void *stream);
+int csgpu_many_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count, const int64_t *d_offsets,
+                                 csgpu_val *d_rows, int32_t *d_owner, int64_t total, void *stream);
+int csgpu_many_fold(const csgpu_many_result *d_sub_results, const int32_t *d_owner, int64_t total, csgpu_many_result *d_results,
+                    void *stream);
+
 /* ---- up to k solutions per instance: csgpu_solve_many, left at an instance's k-th solution ----
  * "Is the solution unique?", "give me the first k": the instance walks exactly the ALL walk (same branching rule, same
  * value order, same counters) and stops right after accepting its k-th solution, as ANY stops after its first.

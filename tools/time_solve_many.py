@@ -10,6 +10,7 @@ oracle walk (tests/many_walk.py).
   python tools/time_solve_many.py --set sudoku9 [--count 65536] [--reps 5] [--loop-sample 256] [--check 32]
                                   [--sliced B0,B1,... [--finish resume|search]] [--upto K]
                                   [--restarts BASE [--seed S]] [--revealed R] [--stream ROWS]
+                                  [--spread B0,B1,... [--spread-rows ROWS]] [--max-nodes N]
   --sliced: the same instances through Model.solve_many_sliced as well (a checkpointed call with budget B0, a resume
   with every following budget; --finish search: what is left after the last budget through one Search per instance):
   the time of the whole, the time until the answers of the first slice are there, and whether it found what the one
@@ -29,7 +30,12 @@ oracle walk (tests/many_walk.py).
   one stream call with room for every solution, (c) the loop call / take / zero with a stream of ROWS rows, which fills
   (the output says how many calls it took); medians and ranges of --reps, whether every record of (b) and (c) equals (a)'s
   and every solution arrived, and --check sampled instances' rows re-checked against the host walk of tests/many_walk.py.
-  sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY),
+  --spread B0,B1,...: Model.solve_many_spread (ALL; the stopped instances of a round fanned out over the waves of the next,
+  budget B0 for round 0, B1 for round 1, the last one repeated; --spread-rows: its max_rows) beside the counting ALL call of
+  solve_many on the same instances, in this process after a warm-up, interleaved, two pools kept over the calls: medians and
+  ranges of --reps, rounds and rows per round, the launch of round 0 alone, and whether every field of every instance and
+  every first solution equals the one call's.
+  sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 / queens13 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY),
   sparse40 (a sparse != network of 40 variables, 16-bit table, three of them open: nearly every node is a solution, ALL)
 """
 import argparse
@@ -69,6 +75,9 @@ def instances(which, count, revealed=None):
     if which == "queens12":
         import many_sets
         return problems.queens(12, "ALL"), many_sets.queens_two(12, count, 7), "ALL", 1 << 20
+    if which == "queens13":
+        import many_sets
+        return problems.queens(13, "ALL"), many_sets.queens_two(13, count, 7), "ALL", 1 << 22
     if which == "sparse40":
         import many_sets
         text = many_sets._sparse16(40, 3)
@@ -97,9 +106,13 @@ def main():
     ap.add_argument("--restarts", type=int, default=None, help="BASE: time solve_many_restarts beside the ANY call")
     ap.add_argument("--revealed", type=float, default=None, help="share of givens of every sudoku (default: the set's own)")
     ap.add_argument("--stream", type=int, default=None, help="ROWS: time solve_many_stream beside the counting ALL call")
+    ap.add_argument("--spread", default=None, help="budgets of the rounds of solve_many_spread, e.g. 256,4096")
+    ap.add_argument("--spread-rows", type=int, default=1 << 18, help="max_rows of solve_many_spread")
+    ap.add_argument("--max-nodes", type=int, default=None, help="the budget of the one call (default: the set's own)")
     args = ap.parse_args()
-    count = args.count or {"sudoku9": 65536, "queens12": 16384, "sudoku16": 4096, "sparse40": 256}[args.set]
+    count = args.count or {"sudoku9": 65536, "queens12": 16384, "queens13": 48, "sudoku16": 4096, "sparse40": 256}[args.set]
     text, roots, objective, budget = instances(args.set, count, args.revealed)
+    budget = args.max_nodes or budget
     model = solve_root(text)
     dev = torch.from_numpy(roots).cuda()
 
@@ -328,8 +341,55 @@ def main():
                     "all": summary_s("all"), "stream_roomy": summary_s("stream_roomy"), "stream_loop": summary_s("stream_loop"),
                     "oracle_checked": len(picks_s), "oracle_ok": bool(rows_ok)}
 
+    spread = None
+    if args.spread:
+        fields_p = ("status", "root_props", "nodes", "cuts", "props", "solutions", "first")
+        budgets_p = tuple(int(b) for b in args.spread.split(","))
+        slot_bytes = model.checkpoint_bytes()
+        per_pool = max(1, min(max(count, args.spread_rows), (1 << 30) // slot_bytes))  # a slot per row, 1 GiB at the most
+        pools_p = (model.many_checkpoints(per_pool), model.many_checkpoints(per_pool))  # kept: a caller that repeats the call
+
+        def timed_p(call):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = call()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, res
+
+        calls_p = {"all": lambda: model.solve_many(dev, "ALL", max_nodes=budget),
+                   "spread": lambda: model.solve_many_spread(dev, budgets=budgets_p, max_rows=args.spread_rows, pools=pools_p)}
+        for call in calls_p.values():  # warm-up: code load, workspace, the allocator's blocks
+            timed_p(call)
+            timed_p(call)
+        series_p = {name: [] for name in calls_p}
+        answers_p = {}
+        for _ in range(args.reps):  # interleaved: a drift of the machine falls on both alike
+            for name, call in calls_p.items():
+                dt, answers_p[name] = timed_p(call)
+                series_p[name].append(dt)
+        one, res_p = answers_p["all"], answers_p["spread"]
+
+        def ms_p(name):
+            ts = series_p[name]
+            return {"median": round(statistics.median(ts) * 1e3, 3), "min": round(min(ts) * 1e3, 3), "max": round(max(ts) * 1e3, 3),
+                    "reps": args.reps}
+
+        # where the time of the spread goes: the launch of round 0 alone, and the largest tree below a row of the last round
+        first_ms = statistics.median(timed_p(lambda: model.solve_many(dev, "ALL", max_nodes=budgets_p[0],
+                                                                      checkpoints=pools_p[0].reset()))[0] for _ in range(3)) * 1e3
+        spread = {"budgets": list(budgets_p), "max_rows": args.spread_rows, "max_nodes_of_the_one_call": budget,
+                  "all_ms": ms_p("all"), "spread_ms": ms_p("spread"),
+                  "all_status_counts": torch.bincount(one["status"].long(), minlength=3).tolist(),
+                  "spread_status_counts": torch.bincount(res_p["status"].long(), minlength=3).tolist(),
+                  "nodes": int(one["nodes"].sum()), "largest_tree": int(one["nodes"].max()), "solutions": int(one["solutions"].sum()),
+                  "rounds": res_p["rounds"], "sub_instances": res_p["sub_instances"], "rows_per_round": res_p["round_rows"],
+                  "round_0_ms": round(first_ms, 3), "slot_bytes": slot_bytes,
+                  # (an instance the one call leaves at LIMIT has no whole record to compare with)
+                  "every_field_equals_the_one_call_where_it_is_done":
+                      all(bool((res_p[f] == one[f])[one["status"] == 0].all()) for f in fields_p)}
+
     # the per-instance loop: one Search, reset and seeded per instance
-    sample = np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
+    sample =np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
     search = Search(model, 1 << 18, 1 << 14)
     node = torch.tensor([[-1, 0, 0, 0]], dtype=torch.int32, device="cuda")
 
@@ -383,6 +443,7 @@ def main():
         **({"upto": upto} if upto else {}),
         **({"restarts": restarts} if restarts else {}),
         **({"stream": streamed} if streamed else {}),
+        **({"spread": spread} if spread else {}),
     }))
     return 0 if checked_ok and (upto is None or upto["oracle_ok"]) and (restarts is None or restarts["oracle_ok"]) and \
         (streamed is None or streamed["oracle_ok"]) else 1
