@@ -268,6 +268,8 @@ def load_library():
     L.csgpu_solve_many_clauses_resume.argtypes = [vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp, vp]
     L.csgpu_many_clause_checkpoint_states.argtypes = [vp, C.c_int32, vp, i64, C.POINTER(i64), C.POINTER(C.c_int32),
                                                       C.POINTER(C.c_int32), vp]
+    L.csgpu_many_clause_checkpoint_children.argtypes = [vp, vp, i64, vp, vp]
+    L.csgpu_many_clause_checkpoint_fanout.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
     L.csgpu_solve_many_clauses_upto.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp]
     L.csgpu_solve_many_clauses_upto_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
     L.csgpu_solve_many_clauses_upto_resume.argtypes = [vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]

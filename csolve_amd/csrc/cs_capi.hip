@@ -2230,6 +2230,43 @@ extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints 
   return rc;
 }
 
+/* ---- stopped ALL walks of a clause model spread over the next launch (cs_walk_children, cs_walk_fanout); the fold is
+ * csgpu_many_fold, which works on records alone ---- */
+
+extern "C" int csgpu_many_clause_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                     int64_t *d_children, void *stream) {
+  if (ck == NULL || d_slots == NULL || d_children == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  if (count > 0x7fffffff) return set_err(CSGPU_E_LIMIT, MANY_FAN_LIMIT);
+  if (count == 0) return CSGPU_OK;
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  hipLaunchKernelGGL(cs_walk_children, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, m->host->n_vars,
+                     (const cs_val *)m->d_walk_root, (const cs_val *)ck->d_pool, (int)ck->capacity, (const int *)d_slots,
+                     (long long)count, (long long *)d_children);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                   const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total,
+                                                   void *stream) {
+  if (ck == NULL || d_slots == NULL || d_offsets == NULL || d_rows == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (total < 0) return set_err(CSGPU_E_ARG, "negative row count");
+  if (ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  if (count > 0x7fffffff) return set_err(CSGPU_E_LIMIT, MANY_FAN_LIMIT);
+  if (count == 0 || total == 0) return CSGPU_OK;
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  hipLaunchKernelGGL(cs_walk_fanout, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, m->host->n_vars,
+                     (const cs_val *)m->d_walk_root, (const cs_val *)ck->d_pool, (int)ck->capacity, (const int *)d_slots,
+                     (long long)count, (const long long *)d_offsets, (long long)total, (cs_val *)d_rows, (int *)d_owner);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
 /* ---- up to k solutions per instance of a clause model (cs_walk_upto) ---- */
 
 extern "C" int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,

@@ -191,4 +191,103 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_stream(cs_tables T, cs_walk_
 #undef CS_WALK_CK
 }
 
+/* ---- a stopped ALL walk spread over the waves of the next launch (csgpu_many_clause_checkpoint_children / _fanout; the
+ * fold is cs_dive_fold, which knows records only)
+ *
+ * What cs_dive_children / cs_dive_fanout (cs_dive.hip.h) are to a kernel-7 pool, for a clause pool: the same frames "node,
+ * branching variable bv, next value" and the same walk order -- the values next .. node[bv].hi of the current node (frame
+ * 1 + depth of the slot), then those of the frame below it, down to frame 1 -- but the bounds are absolute, the header is
+ * a frame of its own (frame 0) and a domain may be 2^32 values wide, so a frame's count is taken in 64 bits.  A parent is
+ * pushed only while it has values left, so every frame has a child.  Child (d, v) as a root row of its own is what the walk
+ * makes of it: cs_walk_body.hip.h runs the root row and every child through the same text -- the node in the LDS slice,
+ * then cs_rounds_body.hip.h -- and under ALL no incumbent touches the slice.  So the contribution of cs_dive_fold holds
+ * here as well, props included.
+ *
+ * ALL only: under MIN / MAX the private incumbent is sequential, a split would change the tree.  A header whose code is
+ * not ALL's (ANY 0, MIN 2, MAX 3, CS_WALK_CK_UPTO, CS_WALK_CK_STREAM) is refused like a slot without a checkpoint.
+ * Not templated, one wave per instance, CS_DIVE_FAN_WAVES instances per workgroup, 64-bit row indices, no atomics.  A
+ * slot is checked before anything that depends on it is read: a slot number outside the pool, a header without the magic,
+ * a depth outside [0, n), another code, a frame whose bv is outside [0, n), whose node's bounds of bv lie outside the root
+ * domain or whose next value is outside those bounds give -1, never a count. */
+#define CS_WALK_CK_ALL 1 /* the header's code of a checkpoint written under ALL (CS_OBJ_ALL) */
+
+static __device__ __forceinline__ long long cs_walk_slot_children(int n, const cs_val *__restrict__ root_dom,
+                                                                  const cs_val *__restrict__ pool, int capacity, int slot,
+                                                                  int lane) {
+  if (slot < 0) return 0;
+  if (slot >= capacity) return -1;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (fstride * fstride);
+  const cs_val head = base[0];
+  const int depth = __builtin_amdgcn_readfirstlane(head.lo);
+  if (__builtin_amdgcn_readfirstlane(head.hi) != CS_WALK_CK_MAGIC || depth < 0 || depth >= n) return -1;
+  if ((__builtin_amdgcn_readfirstlane(base[1].hi) >> 1) != CS_WALK_CK_ALL) return -1; /* have_best | code << 1 */
+  long long mine = 0;
+  bool bad = false;
+  for (int d = lane; d <= depth && !bad; d += CS_WAVE) {
+    const cs_val *f = base + fstride * (1 + (size_t)d);
+    const cs_val meta = f[n];
+    if (meta.lo < 0 || meta.lo >= n) {
+      bad = true;
+    } else {
+      const cs_val node = f[meta.lo], r = root_dom[meta.lo];
+      if (node.lo < r.lo || node.hi > r.hi || node.lo > node.hi || meta.hi < node.lo || meta.hi > node.hi)
+        bad = true;
+      else
+        mine += (long long)node.hi - (long long)meta.hi + 1;
+    }
+  }
+  if (__ballot(bad) != 0ull) return -1;
+  for (int o = CS_WAVE / 2; o > 0; o >>= 1) mine += __shfl_xor(mine, o, CS_WAVE);
+  return cs_dive_uniform(mine);
+}
+
+/* children[i] = the untried children of the clause checkpoint in slot slots[i]: 0 for slots[i] < 0, -1 for a refused slot */
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_children(int n, const cs_val *__restrict__ root_dom,
+                                                                                const cs_val *__restrict__ pool, int capacity,
+                                                                                const int *__restrict__ slots, long long count,
+                                                                                long long *__restrict__ children) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
+  const long long c = cs_walk_slot_children(n, root_dom, pool, capacity, slot, lane);
+  if (lane == 0) children[i] = c;
+}
+
+/* rows[offsets[i] ..] = the children of instance i in walk order, in absolute bounds as the frames hold them, owner[row] =
+ * i.  The instance is counted again first: it writes nothing unless offsets[i + 1] - offsets[i] is its count and its rows
+ * lie inside [0, total) */
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_fanout(int n, const cs_val *__restrict__ root_dom,
+                                                                              const cs_val *__restrict__ pool, int capacity,
+                                                                              const int *__restrict__ slots, long long count,
+                                                                              const long long *__restrict__ offsets,
+                                                                              long long total, cs_val *__restrict__ rows,
+                                                                              int *__restrict__ owner) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
+  if (slot < 0) return;
+  const long long mine = cs_walk_slot_children(n, root_dom, pool, capacity, slot, lane);
+  const long long off = cs_dive_uniform(offsets[i]), end = cs_dive_uniform(offsets[i + 1]);
+  if (mine <= 0 || off < 0 || end > total || end - off != mine) return;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (fstride * fstride);
+  const int depth = __builtin_amdgcn_readfirstlane(base[0].lo);
+  long long row = off;
+  for (int d = depth; d >= 0; d--) {
+    const cs_val *f = base + fstride * (1 + (size_t)d);
+    const cs_val meta = f[n];
+    const int bv = __builtin_amdgcn_readfirstlane(meta.lo);
+    const int next = __builtin_amdgcn_readfirstlane(meta.hi);
+    const int hi = __builtin_amdgcn_readfirstlane(f[bv].hi);
+    for (long long v = next; v <= (long long)hi && row < end; v++, row++) {
+      cs_val *dst = rows + (size_t)row * (size_t)n;
+      for (int x = lane; x < n; x += CS_WAVE) dst[x] = x == bv ? cs_interval((int)v, (int)v) : f[x];
+      if (owner != nullptr && lane == 0) owner[row] = (int)i;
+    }
+  }
+}
+
 #endif

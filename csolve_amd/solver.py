@@ -980,13 +980,20 @@ class Model:
         instances and of their children).
         -> the dict of solve_many (device tensors [K]) plus `rounds`, `sub_instances` and `round_rows` (the rows fanned
         out for every round after round 0; 0 for a round that went on in place)"""
+        family = dict(solve=self.solve_many, resume=lambda batch, **kw: self.resume_many(batch, objective="ALL", **kw),
+                      children=self.checkpoint_children, fanout=self.checkpoint_fanout, make_pool=self.many_checkpoints,
+                      slot_bytes=self.checkpoint_bytes(), qualifies=True)
+        return self._spread_call(family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
+
+    def _spread_call(self, family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools) -> dict:
+        """solve_many_spread and solve_many_clauses_spread around their one driver: the stream and the two pools"""
         budgets = tuple(int(b) for b in budgets)
         assert len(budgets) >= 1 and max_rounds >= 1 and max_rows >= 0
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             own_pools = pools is None
             pools = [None, None] if own_pools else list(pools)
             try:
-                return self._solve_many_spread(roots, budgets, int(max_rounds), int(max_rows), bool(solutions), stream,
+                return self._solve_many_spread(family, roots, budgets, int(max_rounds), int(max_rows), bool(solutions), stream,
                                                int(pool_bytes), pools, own_pools)
             finally:
                 if own_pools:
@@ -994,9 +1001,15 @@ class Model:
                         if p is not None:
                             p.close()
 
-    def _solve_many_spread(self, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools, own_pools) -> dict:
+    def _solve_many_spread(self, family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools,
+                           own_pools) -> dict:
+        """the driver of solve_many_spread and solve_many_clauses_spread.  `family`: what the two differ in -- `solve` (the
+        family's solve_many, walked under "ALL"), `resume` (its resume in place), `children` and `fanout` (its count and
+        fan-out of a pool), `make_pool`, `slot_bytes` and `qualifies` (False: the solve call itself refuses the model,
+        before a pool is made for it)"""
         BIG = 1 << 62  # "no solution yet": above every row number
-        slot_bytes = max(self.checkpoint_bytes(), 1)
+        slot_bytes = max(family["slot_bytes"], 1)
+        solve, resume = family["solve"], family["resume"]
 
         def pool_for(rnd, batch):
             """the pool of round `rnd`, empty: the one of round rnd - 1 is still read by the fan-out"""
@@ -1005,7 +1018,7 @@ class Model:
             if own_pools and (pools[k] is None or pools[k].capacity < need):
                 if pools[k] is not None:
                     pools[k].close()
-                pools[k] = self.many_checkpoints(need)
+                pools[k] = family["make_pool"](need)
             else:
                 pools[k].reset(stream)
             return pools[k]
@@ -1013,8 +1026,10 @@ class Model:
         def budget(rnd):
             return budgets[min(rnd, len(budgets) - 1)]
 
+        if not family["qualifies"]:  # the call says why, as it does without the spread
+            solve(roots, "ALL", max_nodes=budget(0), solutions=solutions, stream=stream)
         pool = pool_for(0, int(roots.shape[0]))
-        main = self.solve_many(roots, "ALL", max_nodes=budget(0), solutions=solutions, stream=stream, checkpoints=pool)
+        main = solve(roots, "ALL", max_nodes=budget(0), solutions=solutions, stream=stream, checkpoints=pool)
         K = main["status"].shape[0]
         dev = main["status"].device
         limited = torch.zeros((max(K, 1),), dtype=torch.int32, device=dev)  # owners that end LIMIT
@@ -1058,25 +1073,25 @@ class Model:
             if S == 0:
                 break
             slots = batch["slot"][index].contiguous()
-            children = self.checkpoint_children(pool, slots, stream)
+            children = family["children"](pool, slots, stream)
             offsets = torch.zeros((S + 1,), dtype=torch.int64, device=dev)
             torch.cumsum(children.clamp(min=0), 0, out=offsets[1:])
             total = int(offsets[-1].item())
             if total > max_rows:  # too wide to fan out: the stopped walks go on where they are
-                self.resume_many(batch, max_nodes=budget(rounds), objective="ALL", stream=stream)
+                resume(batch, max_nodes=budget(rounds), stream=stream)
                 round_rows.append(0)
                 rounds += 1
                 continue
             limited.index_add_(0, owners_of(index), (children < 0).to(torch.int32))  # refused slots: their work is lost
             if total == 0:
                 break
-            rows, came_from = self.checkpoint_fanout(pool, slots, offsets, total, stream=stream)
+            rows, came_from = family["fanout"](pool, slots, offsets, total, stream=stream)
             leave(False)
             if solutions:
                 pos = offsets[torch.searchsorted(index, pos)]
             owner = owners_of(index[came_from.long()]).to(torch.int32).contiguous()
             pool = pool_for(rounds, total)
-            batch = self.solve_many(rows, "ALL", max_nodes=budget(rounds), solutions=solutions, stream=stream, checkpoints=pool)
+            batch = solve(rows, "ALL", max_nodes=budget(rounds), solutions=solutions, stream=stream, checkpoints=pool)
             round_rows.append(total)
             rounds += 1
         leave(True)
@@ -1087,6 +1102,50 @@ class Model:
         out = {k: v for k, v in main.items() if not k.startswith("_") and k != "slot"}
         out["rounds"], out["sub_instances"], out["round_rows"] = rounds, sum(round_rows), round_rows
         return out
+
+    def clause_checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None) -> torch.Tensor:
+        """checkpoint_children for a pool of many_clause_checkpoints() (csgpu_many_clause_checkpoint_children): the untried
+        children of the clause checkpoints in `slots` (int32 [S] on the device) -> int64 [S]: 0 for a slot < 0, -1 for a
+        slot that is refused, one written under another objective than ALL among them"""
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+        S = slots.shape[0]
+        children = torch.empty((max(S, 1),), dtype=torch.int64, device=slots.device)
+        check(load_library().csgpu_many_clause_checkpoint_children(checkpoints._h, slots.data_ptr(), S, children.data_ptr(),
+                                                                   _stream_ptr(stream)))
+        return children[:S]
+
+    def clause_checkpoint_fanout(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, offsets: torch.Tensor, total: int,
+                                 rows: torch.Tensor = None, owner: torch.Tensor = None, stream=None):
+        """checkpoint_fanout for a pool of many_clause_checkpoints() (csgpu_many_clause_checkpoint_fanout): the children of
+        the clause checkpoints in `slots` as root rows of solve_many_clauses, in walk order.  offsets, total, rows, owner
+        and the answer: as checkpoint_fanout"""
+        n, S, total = self.n_vars, slots.shape[0], int(total)
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and tuple(offsets.shape) == (S + 1,)
+        if rows is None:
+            rows = torch.empty((max(total, 1), n, 2), dtype=torch.int32, device=slots.device)
+        if owner is None:
+            owner = torch.empty((max(total, 1),), dtype=torch.int32, device=slots.device)
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= total * n * 2
+        assert owner.dtype == torch.int32 and owner.is_contiguous() and owner.numel() >= total
+        check(load_library().csgpu_many_clause_checkpoint_fanout(checkpoints._h, slots.data_ptr(), S, offsets.data_ptr(),
+                                                                 rows.data_ptr(), owner.data_ptr(), total, _stream_ptr(stream)))
+        return rows[:total], owner[:total]
+
+    def solve_many_clauses_spread(self, roots, *, budgets=(256, 4096), max_rounds=64, max_rows=1 << 18, solutions=True,
+                                  stream=None, pool_bytes=1 << 30, pools=None) -> dict:
+        """solve_many_spread for the clause models: solve_many_clauses under ALL whose stopped instances are spread over the
+        idle waves, by the same driver over solve_many_clauses, resume_many_clauses, clause_checkpoint_children,
+        clause_checkpoint_fanout and fold_many.  The split is exact here too: the kernel runs a root row and a child
+        through the same rounds, and under ALL no incumbent narrows a node, so an owner whose sub-instances all ended DONE
+        has the record of solve_many_clauses(roots, "ALL"), field for field, and its first solution.  ALL only: a MIN /
+        MAX walk's incumbent is sequential.  budgets, max_rounds, max_rows, solutions, stream, pool_bytes and the answer:
+        as solve_many_spread (no `best`); pools=(a, b): two pools of many_clause_checkpoints().  The model must satisfy
+        qualifies_many_clauses(); one that does not is refused as solve_many_clauses refuses it."""
+        family = dict(solve=self.solve_many_clauses, resume=self.resume_many_clauses, children=self.clause_checkpoint_children,
+                      fanout=self.clause_checkpoint_fanout, make_pool=self.many_clause_checkpoints,
+                      slot_bytes=self.clause_checkpoint_bytes(), qualifies=self.qualifies_many_clauses())
+        return self._spread_call(family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
 
     def _many_symbol(self, export: str):
         """the instantiation a family of solve_many launches for this model (template-id), by the library's `export`;

@@ -337,7 +337,9 @@ int csgpu_many_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot,
  *                                    relaxed device-scope 64-bit adds; status and root_props of the owner are not touched,
  *                                    d_owner[t] < 0 is skipped.  Folding a record twice counts it twice: a batch is
  *                                    folded exactly once, when the caller leaves it.  Owners across levels: map a row's
- *                                    owner through the owner vector of the level before
+ *                                    owner through the owner vector of the level before.  It takes no pool and knows no
+ *                                    model: the clause family's spread (csgpu_many_clause_checkpoint_children /
+ *                                    _fanout below) folds with this same call
  * All three are asynchronous on `stream` and read the pool only; they take a pool of csgpu_many_checkpoints_create.
  * Errors before any HIP call, in this order: a null pointer (d_owner of the fan-out may be null) -> CSGPU_E_ARG; count < 0
  * or total < 0 -> CSGPU_E_ARG; a pool of csgpu_many_clause_checkpoints_create -> CSGPU_E_ARG; count > 2^31 - 1 ->
@@ -592,6 +594,40 @@ int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const c
                                     csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
 int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
                                         int64_t *count, int32_t *best, int32_t *have_best, void *stream);
+
+/* ---- stopped ALL walks of a clause model spread over the waves of the next call ----
+ * What "stopped ALL walks spread over the waves of the next call" above is to csgpu_solve_many, for the clause models, whose
+ * batches are the most uneven and the smallest: a call launches at most the resident waves.  A clause checkpoint is the
+ * same list of frames "node, branching variable bv, next value" (frame 0 of the slot is the header, frames 1 .. 1 + depth
+ * the pushed frames and then the current node), and the walk's untried children are, in WALK ORDER, the values next ..
+ * hi(bv) of the current node (ascending), then those of the frame below it, down to the oldest frame.  Each child -- the
+ * frame's node, in the absolute bounds it is stored in, with bv = [v, v] -- is a root row that
+ * csgpu_solve_many_clauses[_checkpointed] walks like any other: the kernel runs a root row and a child through the same
+ * rounds, and under ALL no incumbent narrows the node.  Its record gives its owner exactly the contribution stated above
+ * (nodes 1 + sub.nodes; cuts sub.cuts, plus 1 for a row inconsistent as a root; props sub.root_props + sub.props;
+ * solutions), and csgpu_many_fold, which reads records and owners only, is SHARED by the two families.
+ * ALL only.  Under MIN / MAX an instance's incumbent is sequential: a subtree walked without the bound of the one before
+ * it is another tree.  So a checkpoint whose header code is not ALL's 1 -- ANY 0, MIN 2, MAX 3, up-to-k 4, the stream 5 --
+ * is refused like a slot without a checkpoint.
+ *   csgpu_many_clause_checkpoint_children   d_children[i] = the children of the checkpoint in slot d_slots[i] (int64
+ *                                    [count], a frame's count is taken in 64 bits: a domain may be 2^32 wide): 0 for
+ *                                    d_slots[i] < 0; -1 for a slot that is refused: a number >= capacity, a header
+ *                                    without a clause checkpoint, with a depth outside [0, n_vars) or with another code
+ *                                    than ALL's, a frame whose variable is outside [0, n_vars), whose node's bounds of it
+ *                                    lie outside the model's root domain or are empty, or whose next value lies outside
+ *                                    those bounds.  Everything is compared before what depends on it is read
+ *   csgpu_many_clause_checkpoint_fanout     as csgpu_many_checkpoint_fanout: d_offsets int64 [count + 1] on the device,
+ *                                    rows in walk order to d_rows ([total][n_vars]), d_owner[row] = i if d_owner is not
+ *                                    NULL; the slot is counted again first and NOTHING is written unless d_offsets[i + 1]
+ *                                    - d_offsets[i] is that count and the rows lie inside [0, total).  The rows are copies
+ * Both are asynchronous on `stream`, read the pool only, use no atomics, and take a pool of
+ * csgpu_many_clause_checkpoints_create.  Errors before any HIP call, in this order: a null pointer (d_owner may be null) ->
+ * CSGPU_E_ARG; count < 0 or total < 0 -> CSGPU_E_ARG; a pool of csgpu_many_checkpoints_create -> CSGPU_E_ARG; count >
+ * 2^31 - 1 -> CSGPU_E_LIMIT.  Then count == 0 or total == 0 -> CSGPU_OK, nothing is launched. */
+int csgpu_many_clause_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                          int64_t *d_children, void *stream);
+int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                        const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total, void *stream);
 
 /* ---- up to k solutions per instance of a clause model: csgpu_solve_many_clauses, left at the k-th solution ----
  * "Which of these 10,000 schedule rows have a unique timetable?", "three alternatives per row": what "up to k solutions

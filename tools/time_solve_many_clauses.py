@@ -37,7 +37,14 @@ room for everything (pool and stream made once, reset per repetition), and the l
 of ROWS rows (its pool and stream made per repetition, as a caller's would be).  The rows are those of
 tests/many_clause_stream_sets.py (--set one of its names, default wcet_max), repeated up to --count; every walk ends within
 the default budget of 16,000 nodes.  The records of both stream routes must equal the counting call's in every field, and
-the rows of the seeded sample the host walk's, in walk order."""
+the rows of the seeded sample the host walk's, in walk order.
+
+--spread B1,B2,... [--spread-rows ROWS] [--budget N] times Model.solve_many_clauses_spread (ALL; the stopped instances of a
+round fanned out over the waves of the next, budget B1 for round 0, B2 for round 1, the last one repeated; --spread-rows:
+its max_rows) beside the counting ALL call of solve_many_clauses on the same rows (--set, walked under ALL whatever the
+set's objective, repeated up to --count) and the same budget, interleaved in this process after a warm-up, two pools kept
+over the calls: medians and ranges of --reps, rounds and rows per round, the launch of round 0 alone, and whether every
+field of every instance -- props and root_props included -- and every first solution equals the one call's."""
 import argparse
 import json
 import os
@@ -87,7 +94,13 @@ def main():
     ap.add_argument("--rotate-first", action="store_true", help="with --restarts: run 0 rotates as well")
     ap.add_argument("--stream", type=int, default=None, help="ROWS: time the counting ALL call, one stream call with room for "
                                                              "everything and the loop with a stream of ROWS rows")
+    ap.add_argument("--spread", default=None, help="B1,B2,...: time solve_many_clauses_spread beside the counting ALL call")
+    ap.add_argument("--spread-rows", type=int, default=1 << 18, help="max_rows of solve_many_clauses_spread")
     args = ap.parse_args()
+    if args.spread is not None:
+        if args.stream is not None or args.sliced or args.upto is not None or args.restarts is not None:
+            ap.error("--spread B1,B2,...: without --stream, --sliced, --upto and --restarts")
+        return spread_route(args)
     if args.stream is not None:
         if args.stream < 1 or args.sliced or args.upto is not None or args.restarts is not None:
             ap.error("--stream ROWS: ROWS >= 1, without --sliced, --upto and --restarts")
@@ -331,6 +344,67 @@ def stream_route(args):
         "records_equal_the_counting_call": bool(same), "oracle_checked": len(picks), "oracle_ok": bool(ok),
     }))
     return 0 if ok and same else 1
+
+
+def spread_route(args):
+    """the spread beside the counting ALL call of the same rows, same budget, same build"""
+    import many_clause_sets as sets
+    name = args.set or "linear20_all"
+    if name not in sets.SETS:
+        raise SystemExit(f"--spread: --set is one of {sorted(sets.SETS)}")
+    text, base, _, budget = sets.build(name)
+    budget = args.budget or budget
+    budgets = tuple(int(b) for b in args.spread.split(","))
+    roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
+    count = len(roots)
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+    fields = ("status", "root_props", "nodes", "cuts", "props", "solutions", "first")
+    slot_bytes = model.clause_checkpoint_bytes()
+    per_pool = max(1, min(max(count, args.spread_rows), (1 << 30) // slot_bytes))  # a slot per row, 1 GiB at the most
+    pools = (model.many_clause_checkpoints(per_pool), model.many_clause_checkpoints(per_pool))  # kept: a caller that repeats the call
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    calls = {"all": lambda: model.solve_many_clauses(dev, "ALL", max_nodes=budget),
+             "spread": lambda: model.solve_many_clauses_spread(dev, budgets=budgets, max_rows=args.spread_rows, pools=pools)}
+    for call in calls.values():  # warm-up: code load, workspace, the allocator's blocks
+        timed(call)
+        timed(call)
+    times, outs = {k: [] for k in calls}, {}
+    for _ in range(args.reps):  # interleaved: a drift of the machine falls on both alike
+        for k, call in calls.items():
+            dt, outs[k] = timed(call)
+            times[k].append(dt)
+    one, got = outs["all"], outs["spread"]
+    # where the time of the spread goes: the launch of round 0 alone
+    first_ms = statistics.median(timed(lambda: model.solve_many_clauses(dev, "ALL", max_nodes=budgets[0],
+                                                                        checkpoints=pools[0].reset()))[0] for _ in range(3)) * 1e3
+    done = one["status"] == 0  # (an instance the one call leaves at LIMIT has no whole record to compare with)
+    differing = {f: int((got[f] != one[f])[done].reshape(int(done.sum()), -1).any(dim=1).sum()) for f in fields}
+    same = not any(differing.values())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(json.dumps({
+        "tool": "time_solve_many_clauses", "route": "spread", "commit": commit(), "command": " ".join(sys.argv), "set": name,
+        "instances": count, "max_nodes_of_the_one_call": budget, "n_vars": model.n_vars, "clauses": model.n_clauses,
+        "kernel": model.many_clauses_kernel(), "resume_kernel": model.many_clauses_resume_kernel(),
+        "waves": model.many_clauses_waves(count), "slot_bytes": slot_bytes, "budgets": list(budgets), "max_rows": args.spread_rows,
+        "all_ms": spread(times["all"]), "spread_ms": spread(times["spread"]),
+        "all_over_spread": round(med["all"] / med["spread"], 3),
+        "all_status_counts": torch.bincount(one["status"].long(), minlength=3).tolist(),
+        "spread_status_counts": torch.bincount(got["status"].long(), minlength=3).tolist(),
+        "nodes": int(one["nodes"].sum()), "largest_tree": int(one["nodes"].max()), "solutions": int(one["solutions"].sum()),
+        "rounds": got["rounds"], "sub_instances": got["sub_instances"], "rows_per_round": got["round_rows"],
+        "round_0_ms": round(first_ms, 3),
+        "instances_that_differ_where_the_one_call_is_done": differing,
+        "every_field_equals_the_one_call_where_it_is_done": same,
+    }))
+    return 0 if same else 1
 
 
 def upto_route(args, model, text, roots, dev, budget, upto, rng):
