@@ -278,6 +278,15 @@ def load_library():
     L.csgpu_internal_many_clauses_restart_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_clauses_stream.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, C.POINTER(ManyStream), vp]
     L.csgpu_internal_many_clauses_stream_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many_clauses_from.argtypes = [vp, vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_clauses_from_resume.argtypes = [vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp, vp]
+    L.csgpu_many_clause_checkpoint_children_obj.argtypes = [vp, vp, i64, C.c_int, vp, vp]
+    L.csgpu_many_clause_checkpoint_fanout_obj.argtypes = [vp, vp, i64, C.c_int, vp, vp, vp, vp, vp, i64, vp]
+    L.csgpu_many_fold_best.argtypes = [vp, vp, vp, i64, C.c_int, vp, vp]
+    L.csgpu_many_best_key.argtypes = [C.c_int, C.c_int32, C.c_uint32]
+    L.csgpu_many_best_key.restype = C.c_uint64
+    L.csgpu_many_key_decode.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    L.csgpu_internal_many_clauses_from_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_many_value.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, Val, C.c_uint32, C.c_int32]
     L.csgpu_many_value.restype = C.c_int32
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -196,6 +196,21 @@ CS_HD static inline int32_t cs_many_value(uint32_t seed, uint32_t run, int32_t v
   return cs_many_rotated(bounds.lo, width, cs_many_start(seed, run, var, width, flags), j % width);
 }
 
+/* The key of csgpu_many_fold_best (csolve_gpu.h): (rank(best) << 32) | row, rank the order-preserving map of int32 to
+ * uint32 under MIN (sense 1) and its complement under MAX (sense 2), so that the smallest key of an owner names its best
+ * value and the lowest row that holds it.  All ones is "nothing found": no row is 2^32 - 1. */
+CS_HD static inline uint64_t cs_many_best_key(int sense, int32_t best, uint32_t row) {
+  const uint32_t rank = (uint32_t)best ^ 0x80000000u;
+  return ((uint64_t)(sense == 2 ? ~rank : rank) << 32) | row;
+}
+CS_HD static inline int cs_many_key_decode(int sense, uint64_t key, int32_t *best, uint32_t *row) {
+  if (key == ~(uint64_t)0) return 0;
+  const uint32_t rank = (uint32_t)(key >> 32);
+  *best = (int32_t)((sense == 2 ? ~rank : rank) ^ 0x80000000u);
+  *row = (uint32_t)key;
+  return 1;
+}
+
 /* The branching rule's key (strategy_var_cmp, reference src/strategy.c:79-121): the variable with the SMALLEST key is
  * branched on first -- what the reference keeps at the top of its heap.  order: 0 none, 1 smallest domain, 2 largest
  * domain, 3 smallest value, 4 largest value; then, with prefer_failing, the higher failure count; the caller breaks

@@ -80,6 +80,7 @@ struct cs_kernel_plan {
   cs_planned walk_upto;            /* cs_walk_upto (csgpu_solve_many_clauses_upto and its two checkpoint calls): the same */
   cs_planned walk_restart;         /* cs_walk_restart (csgpu_solve_many_clauses_restarts): the same */
   cs_planned walk_stream;          /* cs_walk_stream (csgpu_solve_many_clauses_stream): the same */
+  cs_planned walk_from;            /* cs_walk_from (csgpu_solve_many_clauses_from / _from_resume): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -1042,6 +1043,17 @@ static int plan_general(csgpu_model *m) {
             occ < m->plan.walk_stream.per_cu)
           m->plan.walk_stream.per_cu = occ;
         if (m->plan.walk_stream.per_cu < 1) m->plan.walk_stream.per_cu = 1;
+      }
+      { /* cs_walk_from: the same slices, its own registers */
+#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_from<CPL, true> : (const void *)cs_walk_from<CPL, false>)
+        const void *fn_from = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
+#undef CS_PICKW
+        if ((rc = plan_kernel(&m->plan.walk_from, fn_from, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_from, CS_BLOCK, m->plan.walk_from.lds) == hipSuccess && occ >= 1 &&
+            occ < m->plan.walk_from.per_cu)
+          m->plan.walk_from.per_cu = occ;
+        if (m->plan.walk_from.per_cu < 1) m->plan.walk_from.per_cu = 1;
       }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
@@ -2044,6 +2056,9 @@ extern "C" int csgpu_internal_many_clauses_restart_symbol(const csgpu_model *m, 
 extern "C" int csgpu_internal_many_clauses_stream_symbol(const csgpu_model *m, char *buf, size_t len) {
   return many_clauses_symbol(m, m != NULL ? &m->plan.walk_stream : NULL, "cs_walk_stream", buf, len);
 }
+extern "C" int csgpu_internal_many_clauses_from_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_from : NULL, "cs_walk_from", buf, len);
+}
 
 /* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
  * whose `frames` frames each fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices
@@ -2071,17 +2086,20 @@ struct many_clauses_rs {
   int32_t *d_restarts;
 };
 
-/* The one path of the eight entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
+/* The one path of the ten entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
  * has a pool and slot numbers and launches cs_walk_resume; `resume` (pooled, and no roots): the instances go on in their
  * slots, so the call needs no workspace.  An up-to-k entry brings `upto_options` in place of `options` (the other one is
  * NULL): the ALL walk by cs_walk_upto, pooled or not, its rows [count][max_solutions][n_vars] in d_solutions.  The
  * restart entry brings `rs` (else NULL) and neither of the two: the ANY walk by cs_walk_restart, one frame more per wave.
  * The stream entry brings `out` (else NULL), is pooled and not `resume` -- d_slots says per instance whether it starts or
- * goes on, so the workspace is a fresh call's: the ALL walk by cs_walk_stream, its rows in *out. */
+ * goes on, so the workspace is a fresh call's: the ALL walk by cs_walk_stream, its rows in *out.  The two start entries
+ * bring `from` (else 0): the MIN / MAX walk by cs_walk_from, pooled or not like an up-to-k entry, with d_start unless it
+ * is the resume. */
 static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
                              const csgpu_many_upto_options *upto_options, const many_clauses_rs *rs, csgpu_many_result *d_results,
                              int32_t *d_solutions, int32_t *d_best, int pooled, csgpu_many_checkpoints *ck, int32_t *d_slots,
-                             int resume, int streamed, const csgpu_many_stream *out, void *stream) {
+                             int resume, int streamed, const csgpu_many_stream *out, int from, const csgpu_many_start *d_start,
+                             void *stream) {
   const csgpu_many_restart_options *rs_options = rs != NULL ? rs->options : NULL;
   const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL ||
                        (options == NULL && upto_options == NULL && rs_options == NULL) ||
@@ -2121,6 +2139,15 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
                                   "workgroup, more than the 160 KiB of a CU", (int)m->host->n_vars, m->plan.rounds.lds, CS_WAVES_PER_BLOCK);
   }
   if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  if (from) { /* after csgpu_solve_many_clauses's own errors: the start, the objective, then the pool and the slots together */
+    if (!resume && d_start == NULL) return set_err(CSGPU_E_ARG, "null argument: d_start, the incumbents the instances start with");
+    if (objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
+      return set_err(CSGPU_E_ARG, "a start incumbent bounds a MIN / MAX walk (objective 2 or 3), not objective %d", objective);
+    if ((ck == NULL) != (d_slots == NULL))
+      return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers, a plain one neither");
+    pooled = ck != NULL;
+    if (resume && !pooled) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
+  }
   if (pooled) {
     if (ck == NULL || d_slots == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
     if (ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
@@ -2130,7 +2157,8 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   csgpu_model *mm = const_cast<csgpu_model *>(m);
   const cs_planned *k = rs_options != NULL ? &m->plan.walk_restart
                         : (upto_options != NULL ? &m->plan.walk_upto
-                           : (streamed ? &m->plan.walk_stream : (pooled ? &m->plan.walk_ck : &m->plan.walk)));
+                           : (streamed ? &m->plan.walk_stream
+                              : (from ? &m->plan.walk_from : (pooled ? &m->plan.walk_ck : &m->plan.walk))));
   const int n = m->host->n_vars;
   const int frames = rs_options != NULL ? n + 1 : n; /* at most n - 1 pushed frames and the current node's; cs_walk_restart: and the root node's */
   const int64_t waves = many_clauses_waves(m, k, count, frames);
@@ -2152,7 +2180,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   cs_walk_ck wk;
   wk.pool = pooled ? ck->d_pool : NULL;
   wk.next = pooled ? ck->d_next : NULL;
-  wk.capacity = pooled ? (int)ck->capacity : 0; /* 0: the pool that cs_walk_upto does not touch */
+  wk.capacity = pooled ? (int)ck->capacity : 0; /* 0: the pool that cs_walk_upto and cs_walk_from do not touch */
   wk.resume = resume;
   wk.code = upto_options != NULL ? CS_WALK_CK_UPTO : (streamed ? CS_WALK_CK_STREAM : objective);
   wk.slots = pooled ? d_slots : NULL;
@@ -2170,8 +2198,10 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   ok.capacity = streamed ? (long long)out->capacity : 0;
   cs_tables tab = m->tab;
   /* cs_walk_clauses takes the first two, cs_walk_resume the first three; cs_walk_restart: the tables, io and `dr`;
-   * cs_walk_stream: the first three and `ok` */
-  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (void *)&wk, streamed ? (void *)&ok : (void *)&upto };
+   * cs_walk_stream: the first three and `ok`; cs_walk_from: the first three and the starts */
+  const cs_walk_start *starts = (const cs_walk_start *)d_start;
+  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (void *)&wk,
+                   streamed ? (void *)&ok : (from ? (void *)&starts : (void *)&upto) };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
 }
@@ -2179,7 +2209,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
 extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                         const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
                                         int32_t *d_best, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, 0, NULL, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, 0, NULL, 0, NULL, stream);
 }
 
 /* ---- clause checkpoints: csgpu_solve_many_clauses in slices (cs_walk_resume) ---- */
@@ -2209,13 +2239,13 @@ extern "C" int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const
                                                      const csgpu_many_options *options, csgpu_many_result *d_results,
                                                      int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
                                                      int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, 0, NULL, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, 0, NULL, 0, NULL, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
                                                csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
                                                csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, 0, NULL, stream);
+  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, 0, NULL, 0, NULL, stream);
 }
 
 extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
@@ -2233,8 +2263,10 @@ extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints 
 /* ---- stopped ALL walks of a clause model spread over the next launch (cs_walk_children, cs_walk_fanout); the fold is
  * csgpu_many_fold, which works on records alone ---- */
 
-extern "C" int csgpu_many_clause_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
-                                                     int64_t *d_children, void *stream) {
+/* the two calls and their _obj forms: `code`, the header code the checkpoints must carry; d_start (the _obj fan-out):
+ * where every row's start incumbent goes, d_owner_start: NULL or what the owners hold */
+static int many_clause_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count, int code,
+                                int64_t *d_children, void *stream) {
   if (ck == NULL || d_slots == NULL || d_children == NULL) return set_err(CSGPU_E_ARG, "null argument");
   if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
   if (ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
@@ -2244,15 +2276,16 @@ extern "C" int csgpu_many_clause_checkpoint_children(const csgpu_many_checkpoint
   const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
   hipLaunchKernelGGL(cs_walk_children, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, m->host->n_vars,
                      (const cs_val *)m->d_walk_root, (const cs_val *)ck->d_pool, (int)ck->capacity, (const int *)d_slots,
-                     (long long)count, (long long *)d_children);
+                     (long long)count, (long long *)d_children, code);
   HIP_TRY(hipGetLastError());
   return CSGPU_OK;
 }
 
-extern "C" int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
-                                                   const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total,
-                                                   void *stream) {
-  if (ck == NULL || d_slots == NULL || d_offsets == NULL || d_rows == NULL) return set_err(CSGPU_E_ARG, "null argument");
+static int many_clause_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count, int code,
+                              const csgpu_many_start *d_owner_start, const int64_t *d_offsets, csgpu_val *d_rows,
+                              int32_t *d_owner, csgpu_many_start *d_start, int64_t total, void *stream) {
+  if (ck == NULL || d_slots == NULL || d_offsets == NULL || d_rows == NULL || (code != CS_WALK_CK_ALL && d_start == NULL))
+    return set_err(CSGPU_E_ARG, "null argument");
   if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
   if (total < 0) return set_err(CSGPU_E_ARG, "negative row count");
   if (ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
@@ -2262,7 +2295,80 @@ extern "C" int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints 
   const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
   hipLaunchKernelGGL(cs_walk_fanout, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, m->host->n_vars,
                      (const cs_val *)m->d_walk_root, (const cs_val *)ck->d_pool, (int)ck->capacity, (const int *)d_slots,
-                     (long long)count, (const long long *)d_offsets, (long long)total, (cs_val *)d_rows, (int *)d_owner);
+                     (long long)count, (const long long *)d_offsets, (long long)total, (cs_val *)d_rows, (int *)d_owner, code,
+                     (const cs_walk_start *)d_owner_start, (cs_walk_start *)d_start);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_clause_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                     int64_t *d_children, void *stream) {
+  return many_clause_children(ck, d_slots, count, CS_WALK_CK_ALL, d_children, stream);
+}
+
+extern "C" int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                   const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total,
+                                                   void *stream) {
+  return many_clause_fanout(ck, d_slots, count, CS_WALK_CK_ALL, NULL, d_offsets, d_rows, d_owner, NULL, total, stream);
+}
+
+/* ---- an instance that starts with an incumbent it did not find itself, and stopped MIN / MAX walks spread with it
+ * (cs_walk_from; cs_walk_children / cs_walk_fanout with MIN's or MAX's code; cs_walk_fold_best) ---- */
+
+extern "C" int csgpu_solve_many_clauses_from(const csgpu_model *m, const csgpu_val *d_roots, const csgpu_many_start *d_start,
+                                             int64_t count, const csgpu_many_options *options, csgpu_many_result *d_results,
+                                             int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                             void *stream) {
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, ck, d_slots, 0, 0, NULL, 1,
+                           d_start, stream);
+}
+
+extern "C" int csgpu_solve_many_clauses_from_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                                    csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                                    csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
+  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, 0, NULL, 1,
+                           NULL, stream);
+}
+
+#define MANY_OBJ_CODE "the checkpoints of a MIN or a MAX walk are asked for (objective 2 or 3), not objective %d"
+
+extern "C" int csgpu_many_clause_checkpoint_children_obj(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                         int objective, int64_t *d_children, void *stream) {
+  if (objective != CS_OBJ_MIN && objective != CS_OBJ_MAX) return set_err(CSGPU_E_ARG, MANY_OBJ_CODE, objective);
+  return many_clause_children(ck, d_slots, count, objective, d_children, stream);
+}
+
+extern "C" int csgpu_many_clause_checkpoint_fanout_obj(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                       int objective, const csgpu_many_start *d_owner_start,
+                                                       const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner,
+                                                       csgpu_many_start *d_start, int64_t total, void *stream) {
+  if (objective != CS_OBJ_MIN && objective != CS_OBJ_MAX) return set_err(CSGPU_E_ARG, MANY_OBJ_CODE, objective);
+  return many_clause_fanout(ck, d_slots, count, objective, d_owner_start, d_offsets, d_rows, d_owner, d_start, total, stream);
+}
+
+extern "C" uint64_t csgpu_many_best_key(int objective, int32_t best, uint32_t row) {
+  return cs_many_best_key(objective_sense(objective), best, row);
+}
+extern "C" int csgpu_many_key_decode(int objective, uint64_t key, int32_t *best, uint32_t *row) {
+  int32_t b = 0;
+  uint32_t r = 0;
+  const int found = cs_many_key_decode(objective_sense(objective), key, &b, &r);
+  if (found && best != NULL) *best = b;
+  if (found && row != NULL) *row = r;
+  return found;
+}
+
+extern "C" int csgpu_many_fold_best(const csgpu_many_result *d_sub_results, const int32_t *d_sub_best, const int32_t *d_owner,
+                                    int64_t total, int objective, uint64_t *d_key, void *stream) {
+  if (d_sub_results == NULL || d_sub_best == NULL || d_owner == NULL || d_key == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (total < 0) return set_err(CSGPU_E_ARG, "negative record count");
+  if (objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
+    return set_err(CSGPU_E_ARG, "the best value is that of a MIN or a MAX walk (objective 2 or 3), not objective %d", objective);
+  if (total >= 0x100000000ll) return set_err(CSGPU_E_LIMIT, "2^32 records or more in one call: a key names its row in 32 bits");
+  if (total == 0) return CSGPU_OK;
+  hipLaunchKernelGGL(cs_walk_fold_best, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const cs_dive_result *)d_sub_results, (const int *)d_sub_best, (const int *)d_owner, (long long)total,
+                     objective_sense(objective), (unsigned long long *)d_key);
   HIP_TRY(hipGetLastError());
   return CSGPU_OK;
 }
@@ -2272,20 +2378,20 @@ extern "C" int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints 
 extern "C" int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                              const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                              int32_t *d_solutions, void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, stream);
+  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, 0, NULL, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                                           const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                                           int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                                           void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 0, 0, NULL, stream);
+  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 0, 0, NULL, 0, NULL, stream);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
                                                     csgpu_many_result *d_results, int32_t *d_solutions,
                                                     csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 1, 0, NULL, stream);
+  return many_clauses_call(m, NULL, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 1, 0, NULL, 0, NULL, stream);
 }
 
 /* ---- Luby restarts with a seeded value order for ANY instances of a clause model (cs_walk_restart) ---- */
@@ -2298,7 +2404,7 @@ extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csg
   rs.options = options;
   rs.d_seeds = d_seeds;
   rs.d_restarts = d_restarts;
-  return many_clauses_call(m, d_roots, count, NULL, NULL, &rs, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, stream);
+  return many_clauses_call(m, d_roots, count, NULL, NULL, &rs, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, 0, NULL, stream);
 }
 
 /* ---- every solution of every instance of a clause model under ALL, through one bounded stream (cs_walk_stream) ---- */
@@ -2307,7 +2413,7 @@ extern "C" int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu
                                                const csgpu_many_options *options, csgpu_many_result *d_results,
                                                csgpu_many_checkpoints *ck, int32_t *d_slots, const csgpu_many_stream *out,
                                                void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, NULL, NULL, 1, ck, d_slots, 0, 1, out, stream);
+  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, NULL, NULL, 1, ck, d_slots, 0, 1, out, 0, NULL, stream);
 }
 
 #ifdef CS_SHAVE_TIMELINE

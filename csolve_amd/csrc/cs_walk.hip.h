@@ -78,7 +78,15 @@
  * counted (the draw stands before nodes and props move) and the instance stops with CSGPU_MANY_FULL through the budget's
  * checkpoint code, {bv, nv} with nv that very value, so the next call tries it again; the node is intact in its frame.
  * Fresh or resumed is a fact per instance (slots[i] == -2 or >= 0).  The header's code is CS_WALK_CK_STREAM.  A wave that
- * finds the stream full when it has drawn a ticket does not walk.  Three atomics: ticket, pool, stream. */
+ * finds the stream full when it has drawn a ticket does not walk.  Three atomics: ticket, pool, stream.
+ *
+ * Start incumbents (cs_walk_from, csgpu_solve_many_clauses_from / _from_resume): the same loop a sixth time, CS_WALK_CK 1
+ * and CS_WALK_FROM 1, the MIN / MAX walk of cs_walk_resume.  A fresh instance with start[inst].have != 0 begins with
+ * have_best, best = start[inst].best -- dom[obj] of its root row takes the objective bound before the root node's rounds
+ * -- and only a solution of the instance's own is reported (io.best iff solutions > 0; the row is written at solutions
+ * only anyway).  The header's code is the objective's, so a checkpoint of this kernel and one of cs_walk_resume continue
+ * under either.  ck.capacity == 0: no pool, as cs_walk_upto.  It is what lets a stopped MIN / MAX walk be spread: see the
+ * fan-out below. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
 
@@ -110,7 +118,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
@@ -139,7 +149,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_resume(cs_tables T, cs_walk_
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
@@ -153,7 +165,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_upto(cs_tables T, cs_walk_io
 #define CS_WALK_UPTO 1
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
@@ -168,7 +182,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_restart(cs_tables T, cs_walk
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 1
 #define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
@@ -184,7 +200,32 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_stream(cs_tables T, cs_walk_
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 1
+#define CS_WALK_FROM 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_FROM
+#undef CS_WALK_STREAM
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+/* the incumbent an instance of cs_walk_from starts with (csgpu_many_start): `best` counts only where `have` is not 0 */
+struct cs_walk_start {
+  int best;
+  int have;
+};
+
+/* the MIN / MAX walk of cs_walk_resume whose fresh instances may start with an incumbent they did not find themselves, and
+ * which reports only solutions of their own (csgpu_solve_many_clauses_from / _from_resume); ck.capacity == 0: no pool */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_from(cs_tables T, cs_walk_io io, cs_walk_ck ck, const cs_walk_start *start) {
+#define CS_WALK_CK 1
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
+#define CS_WALK_FROM 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
 #undef CS_WALK_UPTO
@@ -203,17 +244,24 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_stream(cs_tables T, cs_walk_
  * then cs_rounds_body.hip.h -- and under ALL no incumbent touches the slice.  So the contribution of cs_dive_fold holds
  * here as well, props included.
  *
- * ALL only: under MIN / MAX the private incumbent is sequential, a split would change the tree.  A header whose code is
- * not ALL's (ANY 0, MIN 2, MAX 3, CS_WALK_CK_UPTO, CS_WALK_CK_STREAM) is refused like a slot without a checkpoint.
+ * The ALL entries are ALL only: under MIN / MAX the private incumbent is sequential, a split would change the tree.  A
+ * header whose code is not the one asked for (ALL's: ANY 0, MIN 2, MAX 3, CS_WALK_CK_UPTO, CS_WALK_CK_STREAM) is refused
+ * like a slot without a checkpoint.
  * Not templated, one wave per instance, CS_DIVE_FAN_WAVES instances per workgroup, 64-bit row indices, no atomics.  A
  * slot is checked before anything that depends on it is read: a slot number outside the pool, a header without the magic,
  * a depth outside [0, n), another code, a frame whose bv is outside [0, n), whose node's bounds of bv lie outside the root
- * domain or whose next value is outside those bounds give -1, never a count. */
+ * domain or whose next value is outside those bounds give -1, never a count.
+ *
+ * The same two kernels serve csgpu_many_clause_checkpoint_children_obj / _fanout_obj with `code` MIN's 2 or MAX's 3 in
+ * place of ALL's 1 (a scalar; the ALL entries pass CS_WALK_CK_ALL and NULL for the starts): a stopped MIN / MAX walk's
+ * untried children are independent sub-problems, and any known solution value is a valid bound for all of them.  The
+ * fan-out then writes, beside each row, the incumbent it starts with: the strictly better of the header's and the
+ * owner's (owner_start, NULL or [count]), lane 0's 8-byte store; the children are walked by cs_walk_from. */
 #define CS_WALK_CK_ALL 1 /* the header's code of a checkpoint written under ALL (CS_OBJ_ALL) */
 
 static __device__ __forceinline__ long long cs_walk_slot_children(int n, const cs_val *__restrict__ root_dom,
                                                                   const cs_val *__restrict__ pool, int capacity, int slot,
-                                                                  int lane) {
+                                                                  int lane, int code) {
   if (slot < 0) return 0;
   if (slot >= capacity) return -1;
   const size_t fstride = (size_t)n + 1;
@@ -221,7 +269,7 @@ static __device__ __forceinline__ long long cs_walk_slot_children(int n, const c
   const cs_val head = base[0];
   const int depth = __builtin_amdgcn_readfirstlane(head.lo);
   if (__builtin_amdgcn_readfirstlane(head.hi) != CS_WALK_CK_MAGIC || depth < 0 || depth >= n) return -1;
-  if ((__builtin_amdgcn_readfirstlane(base[1].hi) >> 1) != CS_WALK_CK_ALL) return -1; /* have_best | code << 1 */
+  if ((__builtin_amdgcn_readfirstlane(base[1].hi) >> 1) != code) return -1; /* have_best | code << 1 */
   long long mine = 0;
   bool bad = false;
   for (int d = lane; d <= depth && !bad; d += CS_WAVE) {
@@ -246,12 +294,12 @@ static __device__ __forceinline__ long long cs_walk_slot_children(int n, const c
 __global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_children(int n, const cs_val *__restrict__ root_dom,
                                                                                 const cs_val *__restrict__ pool, int capacity,
                                                                                 const int *__restrict__ slots, long long count,
-                                                                                long long *__restrict__ children) {
+                                                                                long long *__restrict__ children, int code) {
   const int lane = (int)(threadIdx.x % CS_WAVE);
   const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
   if (i >= count) return;
   const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
-  const long long c = cs_walk_slot_children(n, root_dom, pool, capacity, slot, lane);
+  const long long c = cs_walk_slot_children(n, root_dom, pool, capacity, slot, lane, code);
   if (lane == 0) children[i] = c;
 }
 
@@ -263,18 +311,36 @@ __global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_fanout(in
                                                                               const int *__restrict__ slots, long long count,
                                                                               const long long *__restrict__ offsets,
                                                                               long long total, cs_val *__restrict__ rows,
-                                                                              int *__restrict__ owner) {
+                                                                              int *__restrict__ owner, int code,
+                                                                              const cs_walk_start *__restrict__ owner_start,
+                                                                              cs_walk_start *__restrict__ start_out) {
   const int lane = (int)(threadIdx.x % CS_WAVE);
   const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
   if (i >= count) return;
   const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
   if (slot < 0) return;
-  const long long mine = cs_walk_slot_children(n, root_dom, pool, capacity, slot, lane);
+  const long long mine = cs_walk_slot_children(n, root_dom, pool, capacity, slot, lane, code);
   const long long off = cs_dive_uniform(offsets[i]), end = cs_dive_uniform(offsets[i + 1]);
   if (mine <= 0 || off < 0 || end > total || end - off != mine) return;
   const size_t fstride = (size_t)n + 1;
   const cs_val *base = pool + (size_t)slot * (fstride * fstride);
   const int depth = __builtin_amdgcn_readfirstlane(base[0].lo);
+  cs_walk_start st; /* what every child of this slot starts with: the header's incumbent, or the owner's better one */
+  st.best = 0;
+  st.have = 0;
+  if (start_out != nullptr) {
+    const int sense = code == 2 ? 1 : 2;
+    st.have = __builtin_amdgcn_readfirstlane(base[1].hi) & 1;
+    if (st.have != 0) st.best = __builtin_amdgcn_readfirstlane(base[1].lo);
+    if (owner_start != nullptr) {
+      const int ohave = __builtin_amdgcn_readfirstlane(owner_start[i].have);
+      if (ohave != 0) {
+        const int obest = __builtin_amdgcn_readfirstlane(owner_start[i].best);
+        if (st.have == 0 || cs_objective_better(sense, cs_interval(obest, obest), st.best)) st.best = obest;
+        st.have = 1;
+      }
+    }
+  }
   long long row = off;
   for (int d = depth; d >= 0; d--) {
     const cs_val *f = base + fstride * (1 + (size_t)d);
@@ -286,8 +352,22 @@ __global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_fanout(in
       cs_val *dst = rows + (size_t)row * (size_t)n;
       for (int x = lane; x < n; x += CS_WAVE) dst[x] = x == bv ? cs_interval((int)v, (int)v) : f[x];
       if (owner != nullptr && lane == 0) owner[row] = (int)i;
+      if (start_out != nullptr && lane == 0) start_out[row] = st;
     }
   }
+}
+
+/* csgpu_many_fold_best: every sub-record with a solution offers (rank(best) << 32) | row to its owner's key, one relaxed
+ * agent-scope 64-bit unsigned min; the caller set the keys to all ones.  total < 2^32 (the host checks it) */
+__global__ __launch_bounds__(256) void cs_walk_fold_best(const cs_dive_result *__restrict__ sub, const int *__restrict__ best,
+                                                         const int *__restrict__ owner, long long total, int sense,
+                                                         unsigned long long *__restrict__ key) {
+  const long long t = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
+  if (t >= total) return;
+  const int o = owner[t];
+  if (o < 0 || sub[t].solutions <= 0) return;
+  __hip_atomic_fetch_min(key + o, (unsigned long long)cs_many_best_key(sense, best[t], (uint32_t)t), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
 }
 
 #endif

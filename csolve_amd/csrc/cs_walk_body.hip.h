@@ -1,5 +1,6 @@
-/* cs_walk_body.hip.h -- the body of the five kernels of cs_walk.hip.h, which includes it inside each of them under four
- * switches:            CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART  CS_WALK_STREAM
+/* cs_walk_body.hip.h -- the body of the six kernels of cs_walk.hip.h, which includes it inside each of them under five
+ * switches (the fifth, CS_WALK_FROM, is 1 for cs_walk_from alone: cs_walk_resume's row, and `start`):
+ *                      CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART  CS_WALK_STREAM
  *   cs_walk_clauses        0           0              0              0       csgpu_solve_many_clauses
  *   cs_walk_resume         1           0              0              0       one more argument, `ck`: the pool and the slots of the call
  *   cs_walk_upto           1           1              0              0       and `upto` (k >= 1, a scalar)
@@ -22,7 +23,13 @@
  * or resumed is a fact per instance, its ck.slots entry (-2 / >= 0).  A node without open variables asks for its row
  * BEFORE it is counted: without room a child goes round once more with `refused` set and leaves through the checkpoint
  * code of the budget, status 4, nv still that value; a root node leaves with zero fields and its slot entry -2.  New
- * per-instance state is scalars only: refused, room, the row index. */
+ * per-instance state is scalars only: refused, room, the row index.
+ * CS_WALK_FROM: the MIN / MAX walk of cs_walk_resume, one more argument `start` ([count] of cs_walk_start).  A fresh instance
+ * with start[inst].have != 0 begins with that incumbent: have_best, best = start[inst].best, and dom[obj] of the root row
+ * takes the objective bound before the root node's rounds, as a child's does (a bound that empties it fails in the first
+ * round: DONE, no node).  io.best[inst] is written only when the instance has a solution of its own (sols > 0, the record's
+ * count included when it is resumed): one that proves that nothing beats its start leaves best and its row alone.
+ * ck.capacity == 0 means "no pool" as under CS_WALK_UPTO.  New per-instance state is scalars only: start_have, start_best. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -114,6 +121,14 @@
       stack = ck.pool + (size_t)slot * (fstride * fstride) + fstride;
     }
 #endif
+#if CS_WALK_FROM
+    /* the incumbent a fresh instance starts with: `have` as a scalar, and `best` only behind it */
+    int start_have = 0, start_best = 0;
+    if (!resumed) {
+      start_have = __builtin_amdgcn_readfirstlane(start[inst].have);
+      if (start_have != 0) start_best = __builtin_amdgcn_readfirstlane(start[inst].best);
+    }
+#endif
     /* the root row, into the LDS slice */
     bool bad_l = false;
 #if CS_WALK_CK
@@ -129,6 +144,9 @@
     int acc_props = 0;                                  /* per lane, added to props every 64 nodes */
     int best = 0;
     bool have_best = false;
+#if CS_WALK_FROM
+    if (start_have != 0) { best = start_best; have_best = true; }
+#endif
 #if CS_WALK_CK
     long long nodes0 = 0; /* the nodes of earlier launches: the budget counts those of this one */
     if (resumed) {        /* the counters go on from the instance's record, the incumbent from the header */
@@ -190,6 +208,13 @@
         fresh = false;
       }
 #endif
+#if CS_WALK_FROM
+      /* the root row under the start incumbent: what a child gets, once every lane's part of the row stands in the slice */
+      if (!resumed && have_best) {
+        cs_wave_sync();
+        if (lane == 0) dom[io.obj_var] = cs_objective_bound(io.sense, dom[io.obj_var], best);
+      }
+#endif
       for (;;) {
         depth = __builtin_amdgcn_readfirstlane(depth);
         bv = __builtin_amdgcn_readfirstlane(bv);
@@ -207,6 +232,9 @@
             /* leave a checkpoint, if the pool has a slot */
 #if CS_WALK_UPTO
             if (ck.capacity > 0) /* no pool: no slot is drawn, the instance ends as without checkpoints */
+#endif
+#if CS_WALK_FROM
+            if (ck.capacity > 0) /* the same */
 #endif
             if (!resumed) {
               unsigned long long drawn = 0ull;
@@ -421,11 +449,18 @@
       res.status = status; res.root_props = root_props;
       res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
       io.results[inst] = res;
+#if CS_WALK_FROM
+      if (sols > 0 && io.best != nullptr) io.best[inst] = best; /* a solution of its own: never the start's value */
+#else
       if (have_best && io.best != nullptr) io.best[inst] = best;
+#endif
 #if CS_WALK_RESTART
       if (rs.restarts != nullptr) rs.restarts[inst] = restarts;
 #endif
 #if CS_WALK_UPTO
+      if (ck.capacity > 0)
+#endif
+#if CS_WALK_FROM
       if (ck.capacity > 0)
 #endif
 #if CS_WALK_CK

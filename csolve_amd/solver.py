@@ -475,7 +475,8 @@ class Model:
             out["restarts"] = count[:K]
         return out
 
-    def solve_many_clauses(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
+    def solve_many_clauses(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None, checkpoints=None,
+                           start=None) -> dict:
         """solve_many for clause models (csgpu_solve_many_clauses: `=`, `<`, disjunctions, expression trees; the model
         must satisfy qualifies_many_clauses()), a depth-first search per wavefront on kernel 6's fixpoint, also under
         "MIN" / "MAX": the model's own sense, each instance with a private incumbent, walked to the end of its tree.
@@ -485,12 +486,20 @@ class Model:
         best found so far: an anytime answer.
         checkpoints: a pool of many_clause_checkpoints(): an instance that stops at max_nodes keeps its walk and its
         incumbent in a slot of it (csgpu_solve_many_clauses_checkpointed); the answer then has `slot` [K] int32 (-1: no
-        checkpoint) and is what resume_many_clauses() continues.  Without it nothing changes."""
+        checkpoint) and is what resume_many_clauses() continues.  Without it nothing changes.
+        start: int32 [K, 2] on the device, {best, have} per instance (csgpu_solve_many_clauses_from, MIN / MAX only): an
+        instance with have != 0 starts its walk with the incumbent `best`, which it did not find itself -- a warm start,
+        or "prove that nothing beats 45".  `first` / `best` are then written only for solutions of the instance's own,
+        each strictly better than its start; one that proves that nothing beats its start ends with status 0 and
+        solutions == 0, its `best` and row untouched (zero).  have == 0 is the walk without a start.  None: today's
+        calls, untouched."""
         L = load_library()
         n = self.n_vars
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         opt = ManyOptions(obj, 0, int(max_nodes))
         bad = obj not in (0, 1) and (obj not in (2, 3) or self.objective != obj or self.objective_var < 0)
+        if start is not None:
+            return self._solve_many_clauses_from(roots, obj, opt, bad, solutions, stream, checkpoints, start)
         roots, K = self._many_roots(roots, bad, lambda ptr, count: check(
             L.csgpu_solve_many_clauses(self._h, ptr, count, C.byref(opt), ptr, None, None, None)),
             qualifies=self.qualifies_many_clauses())
@@ -514,7 +523,31 @@ class Model:
             out["best"] = best[:K]
         return out
 
-    def resume_many_clauses(self, result: dict, *, max_nodes, stream=None, max_solutions=None) -> dict:
+    def _solve_many_clauses_from(self, roots, obj, opt, bad, solutions, stream, checkpoints, start) -> dict:
+        """solve_many_clauses with start incumbents: the one entry, with or without a pool"""
+        L = load_library()
+        n = self.n_vars
+        roots, K = self._many_roots(roots, bad, lambda ptr, count: check(
+            L.csgpu_solve_many_clauses_from(self._h, ptr, ptr, count, C.byref(opt), ptr, None, None, None, None, None)),
+            qualifies=self.qualifies_many_clauses())
+        assert torch.is_tensor(start) and start.is_cuda and start.dtype == torch.int32 and start.is_contiguous() and \
+            tuple(start.shape) == (K, 2), "start is int32 [K, 2] on the device: {best, have}"
+        buf = self._many_records(K, roots.device)
+        first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
+        best = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device)
+        slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device) if checkpoints is not None else None
+        check(L.csgpu_solve_many_clauses_from(self._h, roots.data_ptr() if K else buf.data_ptr(),
+                                              start.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                                              first.data_ptr() if solutions and K else None, best.data_ptr(),
+                                              checkpoints._h if checkpoints is not None else None,
+                                              slots.data_ptr() if slots is not None else None, _stream_ptr(stream)))
+        out = self._many_answer(buf, K, first, slots, checkpoints)
+        if checkpoints is not None:
+            out["_objective"], out["_best"] = obj, best
+        out["best"] = best[:K]
+        return out
+
+    def resume_many_clauses(self, result: dict, *, max_nodes, stream=None, max_solutions=None, own_solutions=False) -> dict:
         """continue, in place, the instances of a checkpointed solve_many_clauses answer that stopped with a checkpoint
         (csgpu_solve_many_clauses_resume): `max_nodes` more nodes each, under the answer's objective.  Counters
         accumulate; under MIN / MAX `first` / `best` are overwritten at every improvement, the incumbent travelling in
@@ -522,7 +555,10 @@ class Model:
         slot are not touched.  -> result
         An answer of solve_many_clauses_upto(..., checkpoints=pool) goes on through csgpu_solve_many_clauses_upto_resume:
         its rows continue at index `solutions`.  max_solutions: the k of THIS slice, by default the answer's, exactly as
-        in resume_many()."""
+        in resume_many().
+        own_solutions: continue through csgpu_solve_many_clauses_from_resume (MIN / MAX answers): `best` is written only
+        for an instance with a solution of its own, never with the start incumbent its checkpoint carries.  A checkpoint
+        of either MIN / MAX call may be continued either way."""
         if "_checkpoints" in result and "_upto" in result:
             return self._resume_many_upto(result, int(max_nodes), max_solutions, stream,
                                           entry="csgpu_solve_many_clauses_upto_resume")
@@ -531,11 +567,11 @@ class Model:
         opt = ManyOptions(result["_objective"], 0, int(max_nodes))
         first, best = result.get("first"), result["_best"]
         K = result["status"].shape[0]
-        check(load_library().csgpu_solve_many_clauses_resume(self._h, K, C.byref(opt), result["_records"].data_ptr(),
-                                                             first.data_ptr() if first is not None and K else None,
-                                                             best.data_ptr() if best is not None else None,
-                                                             result["_checkpoints"]._h, result["_slots"].data_ptr(),
-                                                             _stream_ptr(stream)))
+        L = load_library()
+        entry = L.csgpu_solve_many_clauses_from_resume if own_solutions else L.csgpu_solve_many_clauses_resume
+        check(entry(self._h, K, C.byref(opt), result["_records"].data_ptr(),
+                    first.data_ptr() if first is not None and K else None, best.data_ptr() if best is not None else None,
+                    result["_checkpoints"]._h, result["_slots"].data_ptr(), _stream_ptr(stream)))
         return result
 
     def solve_many_clauses_upto(self, roots, k, *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
@@ -587,6 +623,10 @@ class Model:
     def many_clauses_stream_kernel(self):
         """the cs_walk_stream instantiation solve_many_clauses_stream launches, or None"""
         return self._many_symbol("csgpu_internal_many_clauses_stream_symbol")
+
+    def many_clauses_from_kernel(self):
+        """the cs_walk_from instantiation solve_many_clauses(..., start=) and the own-solutions resume launch"""
+        return self._many_symbol("csgpu_internal_many_clauses_from_symbol")
 
     def many_clauses_restart_kernel(self):
         """the cs_walk_restart instantiation solve_many_clauses_restarts launches, or None"""
@@ -1103,22 +1143,33 @@ class Model:
         out["rounds"], out["sub_instances"], out["round_rows"] = rounds, sum(round_rows), round_rows
         return out
 
-    def clause_checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None) -> torch.Tensor:
+    def clause_checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None,
+                                   objective=None) -> torch.Tensor:
         """checkpoint_children for a pool of many_clause_checkpoints() (csgpu_many_clause_checkpoint_children): the untried
         children of the clause checkpoints in `slots` (int32 [S] on the device) -> int64 [S]: 0 for a slot < 0, -1 for a
-        slot that is refused, one written under another objective than ALL among them"""
+        slot that is refused, one written under another objective than ALL among them.  objective "MIN" / "MAX": the
+        checkpoints of such a walk instead (csgpu_many_clause_checkpoint_children_obj), every other one refused"""
         assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
         S = slots.shape[0]
         children = torch.empty((max(S, 1),), dtype=torch.int64, device=slots.device)
+        if objective is not None:
+            obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+            check(load_library().csgpu_many_clause_checkpoint_children_obj(checkpoints._h, slots.data_ptr(), S, obj,
+                                                                           children.data_ptr(), _stream_ptr(stream)))
+            return children[:S]
         check(load_library().csgpu_many_clause_checkpoint_children(checkpoints._h, slots.data_ptr(), S, children.data_ptr(),
                                                                    _stream_ptr(stream)))
         return children[:S]
 
     def clause_checkpoint_fanout(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, offsets: torch.Tensor, total: int,
-                                 rows: torch.Tensor = None, owner: torch.Tensor = None, stream=None):
+                                 rows: torch.Tensor = None, owner: torch.Tensor = None, stream=None, objective=None,
+                                 owner_start: torch.Tensor = None, start: torch.Tensor = None):
         """checkpoint_fanout for a pool of many_clause_checkpoints() (csgpu_many_clause_checkpoint_fanout): the children of
         the clause checkpoints in `slots` as root rows of solve_many_clauses, in walk order.  offsets, total, rows, owner
-        and the answer: as checkpoint_fanout"""
+        and the answer: as checkpoint_fanout.  objective "MIN" / "MAX": the checkpoints of such a walk
+        (csgpu_many_clause_checkpoint_fanout_obj); the answer is then (rows, owner, start), start int32 [total, 2] the
+        {best, have} every row begins with in solve_many_clauses(..., start=): the strictly better of its checkpoint's
+        incumbent and owner_start[i] (int32 [S, 2] on the device, or None)"""
         n, S, total = self.n_vars, slots.shape[0], int(total)
         assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
         assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and tuple(offsets.shape) == (S + 1,)
@@ -1128,24 +1179,177 @@ class Model:
             owner = torch.empty((max(total, 1),), dtype=torch.int32, device=slots.device)
         assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= total * n * 2
         assert owner.dtype == torch.int32 and owner.is_contiguous() and owner.numel() >= total
+        if objective is not None:
+            obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+            if start is None:
+                start = torch.empty((max(total, 1), 2), dtype=torch.int32, device=slots.device)
+            assert start.dtype == torch.int32 and start.is_contiguous() and start.numel() >= total * 2
+            assert owner_start is None or (owner_start.is_cuda and owner_start.dtype == torch.int32 and
+                                           owner_start.is_contiguous() and tuple(owner_start.shape) == (S, 2))
+            check(load_library().csgpu_many_clause_checkpoint_fanout_obj(
+                checkpoints._h, slots.data_ptr(), S, obj, owner_start.data_ptr() if owner_start is not None and S else None,
+                offsets.data_ptr(), rows.data_ptr(), owner.data_ptr(), start.data_ptr(), total, _stream_ptr(stream)))
+            return rows[:total], owner[:total], start[:total]
+        assert owner_start is None and start is None, "start incumbents travel with objective MIN / MAX"
         check(load_library().csgpu_many_clause_checkpoint_fanout(checkpoints._h, slots.data_ptr(), S, offsets.data_ptr(),
                                                                  rows.data_ptr(), owner.data_ptr(), total, _stream_ptr(stream)))
         return rows[:total], owner[:total]
 
-    def solve_many_clauses_spread(self, roots, *, budgets=(256, 4096), max_rounds=64, max_rows=1 << 18, solutions=True,
-                                  stream=None, pool_bytes=1 << 30, pools=None) -> dict:
+    def fold_many_best(self, sub: dict, owner: torch.Tensor, K: int, objective, stream=None):
+        """the best value every owner has in the batch `sub` (a MIN / MAX solve_many_clauses answer over fanned rows) and
+        the LOWEST row that holds it (csgpu_many_fold_best): owner int32 [T], rows with owner < 0 or without a solution
+        are skipped.  -> (has [K] bool, best [K] int32, row [K] int64; best and row are 0 where has is False)"""
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        T = sub["status"].shape[0]
+        assert owner.is_cuda and owner.dtype == torch.int32 and owner.is_contiguous() and owner.shape[0] == T
+        key = torch.full((max(int(K), 1),), -1, dtype=torch.int64, device=owner.device)  # all ones
+        check(load_library().csgpu_many_fold_best(sub["_records"].data_ptr() if "_records" in sub else sub["status"].data_ptr(),
+                                                  sub["best"].data_ptr() if T else key.data_ptr(), owner.data_ptr(), T, obj,
+                                                  key.data_ptr(), _stream_ptr(stream)))
+        key = key[:K]
+        has = key != -1
+        rank = (key >> 32) & 0xFFFFFFFF  # csgpu_many_key_decode, on the device
+        best = torch.where(has, rank - (1 << 31) if obj == 2 else (1 << 31) - 1 - rank, torch.zeros_like(rank))
+        return has, best.to(torch.int32), torch.where(has, key & 0xFFFFFFFF, torch.zeros_like(key))
+
+    def solve_many_clauses_spread(self, roots, objective="ALL", *, budgets=(256, 4096), max_rounds=64, max_rows=1 << 18,
+                                  solutions=True, stream=None, pool_bytes=1 << 30, pools=None) -> dict:
         """solve_many_spread for the clause models: solve_many_clauses under ALL whose stopped instances are spread over the
         idle waves, by the same driver over solve_many_clauses, resume_many_clauses, clause_checkpoint_children,
         clause_checkpoint_fanout and fold_many.  The split is exact here too: the kernel runs a root row and a child
         through the same rounds, and under ALL no incumbent narrows a node, so an owner whose sub-instances all ended DONE
-        has the record of solve_many_clauses(roots, "ALL"), field for field, and its first solution.  ALL only: a MIN /
-        MAX walk's incumbent is sequential.  budgets, max_rounds, max_rows, solutions, stream, pool_bytes and the answer:
-        as solve_many_spread (no `best`); pools=(a, b): two pools of many_clause_checkpoints().  The model must satisfy
-        qualifies_many_clauses(); one that does not is refused as solve_many_clauses refuses it."""
+        has the record of solve_many_clauses(roots, "ALL"), field for field, and its first solution.  budgets, max_rounds,
+        max_rows, solutions, stream, pool_bytes and the answer: as solve_many_spread (no `best`); pools=(a, b): two pools
+        of many_clause_checkpoints().  The model must satisfy qualifies_many_clauses(); one that does not is refused as
+        solve_many_clauses refuses it.
+        objective "MIN" / "MAX" (the model's own sense): the same rounds, pools, max_rows fallback (resume in place),
+        max_rounds and answer keys, plus `best` [K].  A MIN / MAX walk's incumbent is sequential, so the split cannot
+        reproduce the one call's TREE -- but a stopped walk's untried children are independent sub-problems and any known
+        solution value bounds all of them: round 0 is a checkpointed solve_many_clauses under the objective, and every
+        child of a later round starts (solve_many_clauses(..., start=)) from the strictly better of its checkpoint's
+        incumbent and its owner's best after the fold of the batch it came from.  After every batch the counters are
+        folded (fold_many) and an owner's `best` / `first` are replaced only by a strictly better value, from the lowest
+        row of the batch that holds it (fold_many_best).  An owner ends with status 0 when all its sub-instances did, else
+        1 with the best folded so far (`best` untouched and solutions == 0 if nothing was found).
+        Promised: status 0 and `best` are those of solve_many_clauses(roots, objective) with a budget that finishes the
+        instance, and the whole answer is deterministic in (roots, budgets, max_rounds, max_rows).
+        Not promised: nodes / cuts / props / solutions are those of the walk that was made, which is larger than the one
+        call's; `first` is a solution of value `best`, not necessarily the one call's row."""
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        if obj in (2, 3):
+            budgets = tuple(int(b) for b in budgets)
+            assert len(budgets) >= 1 and max_rounds >= 1 and max_rows >= 0
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                own_pools = pools is None
+                pools = [None, None] if own_pools else list(pools)
+                try:
+                    return self._solve_many_clauses_spread_best(roots, obj, budgets, int(max_rounds), int(max_rows),
+                                                                bool(solutions), stream, int(pool_bytes), pools, own_pools)
+                finally:
+                    if own_pools:
+                        for p in pools:
+                            if p is not None:
+                                p.close()
+        assert obj == 1, "solve_many_clauses_spread walks under ALL, or under the model's MIN / MAX"
         family = dict(solve=self.solve_many_clauses, resume=self.resume_many_clauses, children=self.clause_checkpoint_children,
                       fanout=self.clause_checkpoint_fanout, make_pool=self.many_clause_checkpoints,
                       slot_bytes=self.clause_checkpoint_bytes(), qualifies=self.qualifies_many_clauses())
         return self._spread_call(family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
+
+    def _solve_many_clauses_spread_best(self, roots, obj, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools,
+                                        own_pools) -> dict:
+        """the driver of solve_many_clauses_spread under MIN / MAX: the rounds of _solve_many_spread, with the incumbents"""
+        slot_bytes = max(self.clause_checkpoint_bytes(), 1)
+        minimise = obj == 2
+
+        def pool_for(rnd, batch):
+            k = rnd % 2
+            need = max(1, min(batch, pool_bytes // slot_bytes))
+            if own_pools and (pools[k] is None or pools[k].capacity < need):
+                if pools[k] is not None:
+                    pools[k].close()
+                pools[k] = self.many_clause_checkpoints(need)
+            else:
+                pools[k].reset(stream)
+            return pools[k]
+
+        def budget(rnd):
+            return budgets[min(rnd, len(budgets) - 1)]
+
+        if not self.qualifies_many_clauses() or self.objective != obj:  # the call says why, as it does without the spread
+            self.solve_many_clauses(roots, obj, max_nodes=budget(0), solutions=solutions, stream=stream)
+        pool = pool_for(0, int(roots.shape[0]))
+        main = self.solve_many_clauses(roots, obj, max_nodes=budget(0), solutions=solutions, stream=stream, checkpoints=pool)
+        K = main["status"].shape[0]
+        dev = main["status"].device
+        limited = torch.zeros((max(K, 1),), dtype=torch.int32, device=dev)  # owners that end LIMIT
+        has = None  # per owner: it holds a solution; its value is main["best"], its row main["first"]
+        batch, owner = main, None  # owner: int32 [T], None for round 0 (every instance is its own)
+        rounds, round_rows = 1, []
+
+        def owners_of(index):
+            return index if owner is None else owner.long()[index]
+
+        def leave(last):
+            """fold the batch: the counters, then the best values, which replace an owner's only when strictly better; its
+            stopped instances without a slot (`last`: all its stopped instances) make their owners LIMIT"""
+            nonlocal has
+            T = batch["status"].shape[0]
+            rows = torch.arange(T, dtype=torch.int64, device=dev)
+            stopped = batch["status"] == 1
+            if not last:
+                stopped = stopped & (batch["slot"] < 0)
+            stopped = stopped | (batch["status"] == 3)  # (a resume in place refused its slot: BAD_SLOT)
+            limited.index_add_(0, owners_of(rows), stopped.to(torch.int32))
+            if owner is None:
+                has = batch["solutions"] > 0
+                return
+            self.fold_many(batch, owner, main, stream)
+            found, value, row = self.fold_many_best(batch, owner, K, obj, stream)
+            mine = main["best"]
+            take = found & (~has | (value < mine if minimise else value > mine))
+            if solutions:
+                main["first"].copy_(torch.where(take[:, None], batch["first"][row.clamp(max=max(T - 1, 0))], main["first"]))
+            mine.copy_(torch.where(take, value, mine))
+            has = has | found
+
+        while rounds < max_rounds and K > 0:
+            index = torch.nonzero((batch["status"] == 1) & (batch["slot"] >= 0)).flatten()  # ascending; waits for the batch
+            S = int(index.shape[0])
+            if S == 0:
+                break
+            slots = batch["slot"][index].contiguous()
+            children = self.clause_checkpoint_children(pool, slots, stream, objective=obj)
+            offsets = torch.zeros((S + 1,), dtype=torch.int64, device=dev)
+            torch.cumsum(children.clamp(min=0), 0, out=offsets[1:])
+            total = int(offsets[-1].item())
+            if total > max_rows:  # too wide to fan out: the stopped walks go on where they are
+                self.resume_many_clauses(batch, max_nodes=budget(rounds), stream=stream, own_solutions=owner is not None)
+                round_rows.append(0)
+                rounds += 1
+                continue
+            limited.index_add_(0, owners_of(index), (children < 0).to(torch.int32))  # refused slots: their work is lost
+            if total == 0:
+                break
+            leave(False)  # before the fan-out: the children start from their owners' best after this fold
+            whose = owners_of(index)
+            owner_start = torch.stack([main["best"][whose], has[whose].to(torch.int32)], 1).contiguous()
+            rows, came_from, start = self.clause_checkpoint_fanout(pool, slots, offsets, total, stream=stream, objective=obj,
+                                                                   owner_start=owner_start)
+            owner = whose[came_from.long()].to(torch.int32).contiguous()
+            pool = pool_for(rounds, total)
+            batch = self.solve_many_clauses(rows, obj, max_nodes=budget(rounds), solutions=solutions, stream=stream,
+                                            checkpoints=pool, start=start)
+            round_rows.append(total)
+            rounds += 1
+        leave(True)
+        status = main["status"]
+        status.copy_(torch.where(status == 2, status, (limited[:K] > 0).to(status.dtype)))
+        if own_pools:
+            torch.cuda.current_stream().synchronize()  # the pools go with the call
+        out = {k: v for k, v in main.items() if not k.startswith("_") and k != "slot"}
+        out["rounds"], out["sub_instances"], out["round_rows"] = rounds, sum(round_rows), round_rows
+        return out
 
     def _many_symbol(self, export: str):
         """the instantiation a family of solve_many launches for this model (template-id), by the library's `export`;

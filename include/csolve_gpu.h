@@ -606,8 +606,9 @@ int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_
  * rounds, and under ALL no incumbent narrows the node.  Its record gives its owner exactly the contribution stated above
  * (nodes 1 + sub.nodes; cuts sub.cuts, plus 1 for a row inconsistent as a root; props sub.root_props + sub.props;
  * solutions), and csgpu_many_fold, which reads records and owners only, is SHARED by the two families.
- * ALL only.  Under MIN / MAX an instance's incumbent is sequential: a subtree walked without the bound of the one before
- * it is another tree.  So a checkpoint whose header code is not ALL's 1 -- ANY 0, MIN 2, MAX 3, up-to-k 4, the stream 5 --
+ * These two calls are ALL only.  Under MIN / MAX an instance's incumbent is sequential: a subtree walked without the bound
+ * of the one before it is another tree (the same optimum all the same: "start incumbents" below spreads such walks by calls
+ * of their own).  So a checkpoint whose header code is not ALL's 1 -- ANY 0, MIN 2, MAX 3, up-to-k 4, the stream 5 --
  * is refused like a slot without a checkpoint.
  *   csgpu_many_clause_checkpoint_children   d_children[i] = the children of the checkpoint in slot d_slots[i] (int64
  *                                    [count], a frame's count is taken in 64 bits: a domain may be 2^32 wide): 0 for
@@ -628,6 +629,72 @@ int csgpu_many_clause_checkpoint_children(const csgpu_many_checkpoints *ck, cons
                                           int64_t *d_children, void *stream);
 int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
                                         const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total, void *stream);
+
+/* ---- start incumbents, and stopped MIN / MAX walks of a clause model spread over the waves of the next call ----
+ * The sequential incumbent above only matters if a split has to reproduce the one call's TREE.  It does not matter for the
+ * OPTIMUM: a stopped MIN / MAX walk's untried children are independent sub-problems, and any known solution value is a
+ * valid bound for all of them.  The primitive is an instance that starts its walk with an incumbent it did not find
+ * itself; it also serves as a warm start (a row with a known upper bound) and for "prove that nothing beats 45".
+ * The walk (kernel cs_walk_from) is csgpu_solve_many_clauses's under MIN / MAX -- same root check, branching rule, value
+ * order, counters and budget -- with three differences:
+ *   starting      a fresh instance i with d_start[i].have != 0 begins with have_best = true, best = d_start[i].best: dom[obj]
+ *                 of its root row becomes csgpu_objective_bound(objective, dom[obj], best) before the root node's rounds, as
+ *                 a child's does once the instance has a solution.  A bound that empties dom[obj] makes the root node
+ *                 inconsistent: DONE, 0 nodes, 0 solutions.  have == 0 gives the walk of csgpu_solve_many_clauses
+ *                 [_checkpointed], field for field and row for row (`best` is then not read)
+ *   own solutions d_best[i] and row i of d_solutions are written only for solutions the instance found itself: d_best iff
+ *                 solutions > 0 (the record's count included for a resumed instance).  Every such solution is strictly
+ *                 better than the start.  An instance that proves that nothing beats its start ends DONE with solutions ==
+ *                 0, its d_best and its row untouched
+ *   resuming      a checkpoint's header carries {best, have_best | objective << 1} as every MIN / MAX checkpoint does, the
+ *                 start's value included.  csgpu_solve_many_clauses_resume continues such an instance without change (it
+ *                 writes d_best whenever the header has an incumbent); csgpu_solve_many_clauses_from_resume continues it
+ *                 under the own-solutions rule.  A checkpoint of either MIN / MAX call may be resumed by either resume
+ *   csgpu_solve_many_clauses_from         d_start [count] is required; ck == NULL and d_slots == NULL: no checkpoints (the
+ *                                         plain call), both given: the checkpointed call
+ *   csgpu_solve_many_clauses_from_resume  as csgpu_solve_many_clauses_resume
+ * Errors before any HIP call: those of csgpu_solve_many_clauses, in its order and with its codes; then a null d_start, an
+ * objective ANY / ALL, exactly one of ck / d_slots null (the resume: either) -> CSGPU_E_ARG; then the pool's errors of
+ * csgpu_solve_many_clauses_checkpointed; then count == 0 -> CSGPU_OK.
+ *
+ * The spread.  csgpu_many_clause_checkpoint_children_obj / _fanout_obj are the two calls above for checkpoints whose
+ * header code is `objective` (MIN 2 or MAX 3; anything else -> CSGPU_E_ARG, before the other errors, which are the same):
+ * every comparison-before-read rule holds, a slot with another code (an ALL one among them) is -1.  The fan-out writes,
+ * beside each row, d_start[row]: the better -- strictly, by csgpu_objective_better's order -- of the slot's header
+ * incumbent and d_owner_start[i] (NULL, or [count]; have == 0: none); have == 0 when neither exists.  d_start is required.
+ * Nothing is written unless the counted children match the offsets.  The rows are walked by
+ * csgpu_solve_many_clauses_from; each sub-instance is deterministic; its counters fold with the unchanged csgpu_many_fold
+ * (a sub-row whose start bound emptied dom[obj] is "inconsistent as a root": the +1 cut), and the owner is DONE with the
+ * proven optimum when all its sub-instances are DONE.  The walk that was made is larger than the one call's: the optimum
+ * is the one call's, the counters are not.
+ *   csgpu_many_fold_best   d_key is uint64 [owners], set to all ones by the caller.  For every row t < total with
+ *                          d_owner[t] >= 0 and d_sub_results[t].solutions > 0: one relaxed agent-scope 64-bit unsigned min
+ *                          of csgpu_many_best_key(objective, d_sub_best[t], t) into d_key[d_owner[t]].  Afterwards a key is
+ *                          all ones (nothing found) or names the owner's best value in the batch and the LOWEST row that
+ *                          holds it.  Errors: a null pointer, total < 0, an objective other than MIN / MAX -> CSGPU_E_ARG;
+ *                          total >= 2^32 -> CSGPU_E_LIMIT; then total == 0 -> CSGPU_OK
+ *   csgpu_many_best_key    (rank(best) << 32) | row on the host: rank is the order-preserving map of int32 to uint32 (the
+ *                          sign bit flipped) for MIN and its complement for MAX
+ *   csgpu_many_key_decode  0 for all ones; else 1, with *best and *row (either may be NULL) */
+typedef struct csgpu_many_start {
+  int32_t best; /* counts only where have != 0 */
+  int32_t have;
+} csgpu_many_start;
+int csgpu_solve_many_clauses_from(const csgpu_model *m, const csgpu_val *d_roots, const csgpu_many_start *d_start, int64_t count,
+                                  const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                  int32_t *d_best, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_solve_many_clauses_from_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                         csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                         csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_many_clause_checkpoint_children_obj(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                              int objective, int64_t *d_children, void *stream);
+int csgpu_many_clause_checkpoint_fanout_obj(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count, int objective,
+                                            const csgpu_many_start *d_owner_start, const int64_t *d_offsets, csgpu_val *d_rows,
+                                            int32_t *d_owner, csgpu_many_start *d_start, int64_t total, void *stream);
+int csgpu_many_fold_best(const csgpu_many_result *d_sub_results, const int32_t *d_sub_best, const int32_t *d_owner, int64_t total,
+                         int objective, uint64_t *d_key, void *stream);
+uint64_t csgpu_many_best_key(int objective, int32_t best, uint32_t row);
+int csgpu_many_key_decode(int objective, uint64_t key, int32_t *best, uint32_t *row);
 
 /* ---- up to k solutions per instance of a clause model: csgpu_solve_many_clauses, left at the k-th solution ----
  * "Which of these 10,000 schedule rows have a unique timetable?", "three alternatives per row": what "up to k solutions

@@ -44,7 +44,10 @@ round fanned out over the waves of the next, budget B1 for round 0, B2 for round
 its max_rows) beside the counting ALL call of solve_many_clauses on the same rows (--set, walked under ALL whatever the
 set's objective, repeated up to --count) and the same budget, interleaved in this process after a warm-up, two pools kept
 over the calls: medians and ranges of --reps, rounds and rows per round, the launch of round 0 alone, and whether every
-field of every instance -- props and root_props included -- and every first solution equals the one call's."""
+field of every instance -- props and root_props included -- and every first solution equals the one call's.
+--spread-objective own (default all): on a MIN / MAX set, the one call and the spread walk under the set's objective instead
+(solve_many_clauses_spread(roots, "MIN" / "MAX"): start incumbents); the check is then that every instance the one call
+ends is ended by the spread with the same optimum, and the spread's own nodes are printed beside the one call's."""
 import argparse
 import json
 import os
@@ -96,6 +99,8 @@ def main():
                                                              "everything and the loop with a stream of ROWS rows")
     ap.add_argument("--spread", default=None, help="B1,B2,...: time solve_many_clauses_spread beside the counting ALL call")
     ap.add_argument("--spread-rows", type=int, default=1 << 18, help="max_rows of solve_many_clauses_spread")
+    ap.add_argument("--spread-objective", default="all", choices=("all", "own"),
+                    help="own: walk a MIN / MAX set under its objective (the spread with start incumbents)")
     args = ap.parse_args()
     if args.spread is not None:
         if args.stream is not None or args.sliced or args.upto is not None or args.restarts is not None:
@@ -352,7 +357,11 @@ def spread_route(args):
     name = args.set or "linear20_all"
     if name not in sets.SETS:
         raise SystemExit(f"--spread: --set is one of {sorted(sets.SETS)}")
-    text, base, _, budget = sets.build(name)
+    text, base, objective, budget = sets.build(name)
+    own = args.spread_objective == "own"
+    if own and objective not in ("MIN", "MAX"):
+        raise SystemExit(f"--spread-objective own: {name} is walked under {objective}, not MIN / MAX")
+    objective = objective if own else "ALL"
     budget = args.budget or budget
     budgets = tuple(int(b) for b in args.spread.split(","))
     roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
@@ -371,8 +380,9 @@ def spread_route(args):
         torch.cuda.synchronize()
         return time.perf_counter() - t, out
 
-    calls = {"all": lambda: model.solve_many_clauses(dev, "ALL", max_nodes=budget),
-             "spread": lambda: model.solve_many_clauses_spread(dev, budgets=budgets, max_rows=args.spread_rows, pools=pools)}
+    calls = {"all": lambda: model.solve_many_clauses(dev, objective, max_nodes=budget),
+             "spread": lambda: model.solve_many_clauses_spread(dev, objective, budgets=budgets, max_rows=args.spread_rows,
+                                                               pools=pools)}
     for call in calls.values():  # warm-up: code load, workspace, the allocator's blocks
         timed(call)
         timed(call)
@@ -383,14 +393,17 @@ def spread_route(args):
             times[k].append(dt)
     one, got = outs["all"], outs["spread"]
     # where the time of the spread goes: the launch of round 0 alone
-    first_ms = statistics.median(timed(lambda: model.solve_many_clauses(dev, "ALL", max_nodes=budgets[0],
+    first_ms = statistics.median(timed(lambda: model.solve_many_clauses(dev, objective, max_nodes=budgets[0],
                                                                         checkpoints=pools[0].reset()))[0] for _ in range(3)) * 1e3
     done = one["status"] == 0  # (an instance the one call leaves at LIMIT has no whole record to compare with)
+    if own:  # the optimum and DONE are promised, the walk that was made is another
+        fields = ("status", "best")
     differing = {f: int((got[f] != one[f])[done].reshape(int(done.sum()), -1).any(dim=1).sum()) for f in fields}
     same = not any(differing.values())
     med = {k: statistics.median(v) for k, v in times.items()}
     print(json.dumps({
         "tool": "time_solve_many_clauses", "route": "spread", "commit": commit(), "command": " ".join(sys.argv), "set": name,
+        "objective": objective, "spread_nodes": int(got["nodes"].sum()),
         "instances": count, "max_nodes_of_the_one_call": budget, "n_vars": model.n_vars, "clauses": model.n_clauses,
         "kernel": model.many_clauses_kernel(), "resume_kernel": model.many_clauses_resume_kernel(),
         "waves": model.many_clauses_waves(count), "slot_bytes": slot_bytes, "budgets": list(budgets), "max_rows": args.spread_rows,
