@@ -251,6 +251,11 @@ def load_library():
     L.csgpu_solve_many_upto_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
     L.csgpu_solve_many_upto_resume.argtypes = [vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
     L.csgpu_internal_many_upto_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_model_qualifies_many_allowed.argtypes = [vp]
+    L.csgpu_solve_many_allowed.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp]
+    L.csgpu_solve_many_allowed_upto.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp]
+    L.csgpu_internal_many_allowed_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_internal_many_allowed_upto_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_restarts.argtypes = [vp, vp, vp, i64, C.POINTER(ManyRestartOptions), vp, vp, vp, vp]
     L.csgpu_internal_many_restart_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_stream.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, C.POINTER(ManyStream), vp]

@@ -56,10 +56,12 @@ struct cs_planned {
   int per_cu;     /* resident workgroups per CU */
 };
 
-/* the kernels of the csgpu_solve_many family (cs_dive.hip.h): one loop, compiled five times */
-enum { MANY_PLAIN, MANY_CK, MANY_UPTO, MANY_RESTART, MANY_STREAM, MANY_FAMILIES };
+/* the kernels of the csgpu_solve_many family (cs_dive.hip.h): one loop, compiled five times, and the two that branch on
+ * the allowed values (planned only for root domains of at most CS_DIVE_ALLOWED_WIDTH values) */
+enum { MANY_PLAIN, MANY_CK, MANY_UPTO, MANY_RESTART, MANY_STREAM, MANY_ALLOWED, MANY_ALLOWED_UPTO, MANY_FAMILIES };
 static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "cs_dive_resume", "cs_dive_upto", "cs_dive_restart",
-                                                             "cs_dive_stream" };
+                                                             "cs_dive_stream", "cs_dive_allowed", "cs_dive_allowed_upto" };
+#define CS_DIVE_ALLOWED_WIDTH 128 /* the widest root domain the allowed sets of cs_dive_allowed hold (four 32-bit words) */
 
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
 struct cs_kernel_plan {
@@ -74,7 +76,8 @@ struct cs_kernel_plan {
   cs_planned shave, shave_trace;   /* kernel 7 (the instantiation whose FULL matches the model); its tracing variant */
   cs_planned server;               /* the resident single-node server */
   cs_planned step_shave, step_packed, step_import;
-  cs_planned dive[MANY_FAMILIES];  /* by MANY_*: all five or none; not among csgpu_internal_plan_symbol's families */
+  cs_planned dive[MANY_FAMILIES];  /* by MANY_*: the first five all or none, the two MANY_ALLOWED* with them unless the
+                                      domains are too wide; not among csgpu_internal_plan_symbol's families */
   cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
   cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
   cs_planned walk_upto;            /* cs_walk_upto (csgpu_solve_many_clauses_upto and its two checkpoint calls): the same */
@@ -809,8 +812,18 @@ static const void *step_shave_kernel(int width, int n_vars, int slots, int full)
 }
 
 /* ---- cs_dive.hip.h: a depth-first search per wave (csgpu_solve_many); the slot count is always a run-time value ---- */
-static const void *dive_kernel(int family, int width, int n_vars) {
+static const void *dive_kernel(int family, int width, int n_vars, int set_words) {
   const int r = cs_dense_strides(n_vars);
+  if (family == MANY_ALLOWED || family == MANY_ALLOWED_UPTO) { /* set_words: 1 or 4 words of 32 allowed values per variable */
+#define CS_PICK_R(K, E, NW) (r == 1 ? (const void *)K<E, 1, NW> : r == 2 ? (const void *)K<E, 2, NW> : (const void *)K<E, 4, NW>)
+#define CS_PICK_E(K, NW) (width == 1 ? CS_PICK_R(K, unsigned char, NW) : CS_PICK_R(K, unsigned short, NW))
+#define CS_PICK(K) return set_words == 1 ? CS_PICK_E(K, 1) : CS_PICK_E(K, 4);
+    if (family == MANY_ALLOWED) { CS_PICK(cs_dive_allowed) }
+    CS_PICK(cs_dive_allowed_upto)
+#undef CS_PICK
+#undef CS_PICK_E
+#undef CS_PICK_R
+  }
 #define CS_PICK_R(K, E) (r == 1 ? (const void *)K<E, 1> : r == 2 ? (const void *)K<E, 2> : (const void *)K<E, 4>)
 #define CS_PICK(K) return width == 1 ? CS_PICK_R(K, unsigned char) : CS_PICK_R(K, unsigned short);
   switch (family) {
@@ -1112,14 +1125,20 @@ static int plan_lds_resident(csgpu_model *m) {
  * host domains really are the root state (the bit windows are anchored at the root bounds) */
 /* its shape from the host image alone: waves per workgroup (0: the model does not qualify), set words per variable and
  * LDS bytes per workgroup */
-static int forbidden_sets_shape(const csgpu_model *m, int *fw_out, size_t *lds_out) {
+static int64_t widest_root_domain(const csgpu_model *m) {
   const cs_model *h = m->host;
-  if (m->img->sym_width == 0 || m->not_root) return 0;
   int64_t width = 1;
   for (int32_t v = 0; v < h->n_vars; v++) {
     const int64_t w = (int64_t)h->dom[v].hi - (int64_t)h->dom[v].lo + 1;
     if (w > width) width = w;
   }
+  return width;
+}
+
+static int forbidden_sets_shape(const csgpu_model *m, int *fw_out, size_t *lds_out) {
+  const cs_model *h = m->host;
+  if (m->img->sym_width == 0 || m->not_root) return 0;
+  const int64_t width = widest_root_domain(m);
   const int fw = width <= 64 ? 1 : (width <= 128 ? 2 : (width <= 256 ? 4 : 0));
   if (!fw) return 0;
   const size_t n_words = ((size_t)h->n_vars + 31) / 32; /* cs_tables.n_words */
@@ -1201,8 +1220,12 @@ static int plan_dense_table(csgpu_model *m) {
     m->plan.server.fn = shave_server_kernel(width, n, slots);
   }
   /* the cs_dive_* kernels: the table alone; the upper bounds of the root domains for its check of the root rows */
-  for (int family = 0; family < MANY_FAMILIES; family++)
-    if ((rc = plan_kernel(&m->plan.dive[family], dive_kernel(family, width, n), table, waves))) return rc;
+  const int64_t widest = widest_root_domain(m);
+  for (int family = 0; family < MANY_FAMILIES; family++) {
+    const int by_allowed = family == MANY_ALLOWED || family == MANY_ALLOWED_UPTO;
+    if (by_allowed && widest > CS_DIVE_ALLOWED_WIDTH) continue; /* not planned: the calls say why */
+    if ((rc = plan_kernel(&m->plan.dive[family], dive_kernel(family, width, n, widest <= 32 ? 1 : 4), table, waves))) return rc;
+  }
   {
     int *hi = (int *)malloc((size_t)n * sizeof(int));
     if (hi == NULL) return set_err(CSGPU_E_ARG, "out of memory");
@@ -1367,6 +1390,8 @@ extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf
 extern "C" int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_UPTO, buf, len); }
 extern "C" int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_RESTART, buf, len); }
 extern "C" int csgpu_internal_many_stream_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_STREAM, buf, len); }
+extern "C" int csgpu_internal_many_allowed_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED, buf, len); }
+extern "C" int csgpu_internal_many_allowed_upto_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED_UPTO, buf, len); }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
   if (m != NULL) const_cast<csgpu_model *>(m)->engines += delta;
@@ -1936,6 +1961,49 @@ extern "C" int csgpu_many_fold(const csgpu_many_result *d_sub_results, const int
                      (const cs_dive_result *)d_sub_results, (const int *)d_owner, (long long)total, (cs_dive_result *)d_results);
   HIP_TRY(hipGetLastError());
   return CSGPU_OK;
+}
+
+/* ---- branching on the allowed values (cs_dive_allowed, cs_dive_allowed_upto): the plain walk and up to k, no checkpoints ---- */
+
+extern "C" int csgpu_model_qualifies_many_allowed(const csgpu_model *m) {
+  if (m == NULL || !many_qualifies(m)) return 0;
+  if (m->finalized) return m->plan.dive[MANY_ALLOWED].fn != NULL;
+  return widest_root_domain(m) <= CS_DIVE_ALLOWED_WIDTH;
+}
+
+/* a model of csgpu_solve_many whose domains the allowed sets do not hold: said before many_check_tail's general refusal */
+static int many_check_allowed_width(const csgpu_model *m) {
+  if (m->finalized && m->plan.dive[MANY_PLAIN].fn != NULL && m->plan.dive[MANY_ALLOWED].fn == NULL)
+    return set_err(CSGPU_E_LIMIT, "csgpu_solve_many_allowed: a root domain of this model has more than %d values, which is as wide "
+                                  "as the allowed-value sets of the kernels are; csgpu_solve_many runs it",
+                   CS_DIVE_ALLOWED_WIDTH);
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_solve_many_allowed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                        const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                        void *stream) {
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance")) ||
+      (rc = many_check_objective(options->objective)) || (rc = many_check_allowed_width(m)) ||
+      (rc = many_check_tail(m, MANY_ALLOWED, NULL, count)))
+    return rc;
+  return many_launch(m, MANY_ALLOWED, d_roots, count, options->max_nodes, options->objective == CS_OBJ_ALL, d_results,
+                     d_solutions, 0, stream, NULL, NULL);
+}
+
+extern "C" int csgpu_solve_many_allowed_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                             const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                             int32_t *d_solutions, void *stream) {
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance"))) return rc;
+  if (options->max_solutions < 1) return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
+  if ((rc = many_check_allowed_width(m)) || (rc = many_check_tail(m, MANY_ALLOWED_UPTO, NULL, count))) return rc;
+  int upto = options->max_solutions;
+  return many_launch(m, MANY_ALLOWED_UPTO, d_roots, count, options->max_nodes, 1 /* not read */, d_results, d_solutions, 0, stream,
+                     &upto, NULL);
 }
 
 /* ---- up to k solutions per instance (cs_dive_upto): csgpu_solve_many, stopped at the k-th solution, all k rows kept ---- */

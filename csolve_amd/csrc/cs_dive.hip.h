@@ -228,6 +228,124 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_stream(int n, 
 #undef CS_DIVE_CK
 }
 
+/* ---- branching on the allowed values (cs_dive_allowed, cs_dive_allowed_upto: csgpu_solve_many_allowed / _allowed_upto)
+ *
+ * The walk of cs_dive_shave with another branching rule (specified in csolve_gpu.h): at a node, a value of an open variable
+ * that some VALUED variable forbids through a clause of the model is neither tried nor counted; the walk branches on the
+ * open variable with the fewest other ("allowed") values and tries those in ascending order.  On a != network an interval
+ * hides holes, and the width says little about how constrained a variable is.
+ *
+ * Allowed sets: NW 32-bit words per variable, bit k = the value root_lo + k, the coordinates of the node's bounds.  They
+ * are REBUILT from the node's row whenever a node is entered or a frame is popped, and are dead before the child's
+ * fixpoint starts: frames, slots and the workspace hold nothing new.  For every valued variable u, lane w reads its own
+ * entries of u's table row -- the conflict-free LDS read of cs_shave_core::push_var, f = cd - row[k * W + r2 * CS_WAVE],
+ * the sentinel giving f < 0 -- and sets bit f of its forbidden words: (valued variables x slots x R) LDS reads per ENTERED
+ * node, no atomics, no lane reads what another wrote.  32-bit words: the library contains no 64-bit vector shift by a
+ * register amount.  NW is 1 (root widths up to 32) or 4 (up to 128); wider models are refused. */
+
+/* al[r][j] = the allowed values of the variable (lane, r) in the node plo / phi, valued variables pval: the values of
+ * [plo, phi] that no valued variable forbids (meaningful for open variables only) */
+template <typename E, int R, int NW>
+__device__ __forceinline__ void cs_dive_allowed_sets(const cs_shave_core<E, R, 0, false> &C, const int (&plo)[R],
+                                                     const int (&phi)[R], const unsigned long long (&pval)[R],
+                                                     unsigned (&al)[R][NW]) {
+  constexpr int W = CS_WAVE * R;
+  unsigned fb[R][NW];
+#pragma unroll
+  for (int r2 = 0; r2 < R; r2++)
+#pragma unroll
+    for (int j = 0; j < NW; j++) fb[r2][j] = 0u;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int cdv = plo[r] + C.kb[r]; /* value - dmin of a valued variable */
+    unsigned long long bits = pval[r];
+    while (bits != 0ull) {
+      const int ul = __builtin_ctzll(bits);
+      bits = cs_bitset0(bits, ul);
+      const int cd = __builtin_amdgcn_readlane(cdv, ul);
+      const E *row = C.s_tab + (size_t)(ul + r * CS_WAVE) * C.slots * W + C.lane;
+      for (int k = 0; k < C.slots; k++) {
+#pragma unroll
+        for (int r2 = 0; r2 < R; r2++) {
+          const int f = cd - (int)row[k * W + r2 * CS_WAVE]; /* the value of w that u forbids (sentinel: < 0) */
+          const unsigned bit = 1u << (f & 31);
+          if (NW == 1) {
+            fb[r2][0] |= (unsigned)f < 32u ? bit : 0u;
+          } else {
+            const int word = f >> 5; /* negative for the sentinel */
+#pragma unroll
+            for (int j = 0; j < NW; j++) fb[r2][j] |= word == j ? bit : 0u;
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r2 = 0; r2 < R; r2++) {
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+      const int lo = plo[r2] - 32 * j, hi = phi[r2] - 32 * j; /* the bounds in word j's coordinates */
+      const unsigned range = (0xffffffffu >> (31 - (hi > 31 ? 31 : hi & 31))) & (0xffffffffu << (lo < 0 ? 0 : lo & 31));
+      al[r2][j] = hi < 0 || lo > 31 ? 0u : ~fb[r2][j] & range;
+    }
+  }
+}
+
+/* NW wave-uniform words of values still to be tried: is one left; the lowest, which is taken out; those below `next` out */
+template <int NW>
+__device__ __forceinline__ bool cs_dive_any_bits(const unsigned (&aw)[NW]) {
+  unsigned any = 0u;
+#pragma unroll
+  for (int j = 0; j < NW; j++) any |= aw[j];
+  return any != 0u;
+}
+template <int NW>
+__device__ __forceinline__ int cs_dive_take_lowest(unsigned (&aw)[NW]) {
+  int value = 0;
+  bool taken = false;
+#pragma unroll
+  for (int j = 0; j < NW; j++) {
+    const bool here = !taken && aw[j] != 0u;
+    if (here) {
+      value = 32 * j + __builtin_ctz(aw[j]);
+      aw[j] &= aw[j] - 1u;
+    }
+    taken = taken || here;
+  }
+  return value;
+}
+template <int NW>
+__device__ __forceinline__ void cs_dive_bits_from(unsigned (&aw)[NW], int next) {
+#pragma unroll
+  for (int j = 0; j < NW; j++) {
+    const int t = next - 32 * j;
+    aw[j] &= t <= 0 ? 0xffffffffu : (t > 31 ? 0u : 0xffffffffu << t);
+  }
+}
+
+template <typename E, int R, int NW>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_allowed(int n, const E *__restrict__ tab_g, int slots, int dmin,
+                                                                          const int *__restrict__ root_lo,
+                                                                          const int *__restrict__ root_hi,
+                                                                          const int *__restrict__ sym_off, size_t tab_bytes,
+                                                                          cs_dive_io io) {
+#define CS_DIVE_UPTO 0
+#include "cs_dive_allowed_body.hip.h"
+#undef CS_DIVE_UPTO
+}
+
+/* the same, leaving an instance right after its `upto`-th solution and keeping all of them (upto >= 1; io.all is not read) */
+template <typename E, int R, int NW>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_allowed_upto(int n, const E *__restrict__ tab_g, int slots,
+                                                                               int dmin, const int *__restrict__ root_lo,
+                                                                               const int *__restrict__ root_hi,
+                                                                               const int *__restrict__ sym_off, size_t tab_bytes,
+                                                                               cs_dive_io io, int upto) {
+#define CS_DIVE_UPTO 1
+#include "cs_dive_allowed_body.hip.h"
+#undef CS_DIVE_UPTO
+}
+
 /* csgpu_many_checkpoint_states: frame d of slot `slot` (d <= depth, the oldest first) as a state in absolute bounds, its
  * branching variable narrowed to the values not tried yet, [next, hi].  One workgroup per frame. */
 __global__ void cs_dive_export(int n, const int *__restrict__ root_lo, const cs_val *__restrict__ slot_base,

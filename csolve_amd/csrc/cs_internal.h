@@ -64,6 +64,8 @@ int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t le
 int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len);   /* cs_dive_upto */
 int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len); /* cs_dive_restart */
 int csgpu_internal_many_stream_symbol(const csgpu_model *m, char *buf, size_t len);  /* cs_dive_stream */
+int csgpu_internal_many_allowed_symbol(const csgpu_model *m, char *buf, size_t len);      /* cs_dive_allowed */
+int csgpu_internal_many_allowed_upto_symbol(const csgpu_model *m, char *buf, size_t len); /* cs_dive_allowed_upto */
 int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count);
 /* the same for cs_walk_clauses (csgpu_solve_many_clauses) */
 int csgpu_internal_many_clauses_symbol(const csgpu_model *m, char *buf, size_t len);

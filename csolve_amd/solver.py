@@ -262,7 +262,24 @@ class Model:
             return solutions
         return torch.zeros(tuple(max(d, 0) for d in shape), dtype=torch.int32, device=device) if solutions else None
 
-    def solve_many(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
+    MANY_BRANCHINGS = ("width", "allowed")
+
+    @classmethod
+    def _many_branching(cls, branching, checkpoints) -> bool:
+        """is `branching` the allowed-values rule?  (that walk has no checkpoints)"""
+        if branching not in cls.MANY_BRANCHINGS:
+            raise ValueError(f"branching is one of {cls.MANY_BRANCHINGS}, not {branching!r}")
+        if branching == "allowed" and checkpoints is not None:
+            raise ValueError('branching="allowed" has no checkpoints: checkpoints= goes with branching="width"')
+        return branching == "allowed"
+
+    def qualifies_many_allowed(self) -> bool:
+        """may solve_many(..., branching="allowed") run this model (kernel 7's rule, and no root domain of more than 128
+        values)?  Host only: after build_tables or finalize"""
+        return bool(load_library().csgpu_model_qualifies_many_allowed(self._h))
+
+    def solve_many(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None, checkpoints=None,
+                   branching="width") -> dict:
         """K instances of this model, a depth-first search per wavefront (csgpu_solve_many; the model must qualify for
         kernel 7).  roots: int32 [K, n_vars, 2] root rows inside the model's root domains, a torch tensor on the device
         (a numpy array is uploaded).  max_nodes: the budget per instance (children tried); there is no "unlimited".
@@ -271,19 +288,25 @@ class Model:
         has one (zeros elsewhere).  Asynchronous on the stream; one call in flight per model.
         checkpoints: a pool of many_checkpoints(): an instance that stops at max_nodes keeps its walk in a slot of it
         (csgpu_solve_many_checkpointed); the answer then has `slot` [K] int32 (-1: no checkpoint) and is what
-        resume_many() continues.  Without it the call is csgpu_solve_many."""
+        resume_many() continues.  Without it the call is csgpu_solve_many.
+        branching: "width" (the engine's rule: the smallest interval, every value of it) or "allowed" (the open variable
+        with the fewest values that no valued neighbour forbids, and only those values: csgpu_solve_many_allowed, another
+        tree with the same solutions; no checkpoints; the model must pass qualifies_many_allowed())."""
         L = load_library()
         n = self.n_vars
+        allowed = self._many_branching(branching, checkpoints)
+        plain = L.csgpu_solve_many_allowed if allowed else L.csgpu_solve_many
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         opt = ManyOptions(obj, 0, int(max_nodes))
         roots, K = self._many_roots(roots, False, lambda ptr, count: check(
-            L.csgpu_solve_many(self._h, ptr, count, C.byref(opt), ptr, None, None)))
+            plain(self._h, ptr, count, C.byref(opt), ptr, None, None)),
+            qualifies=self.qualifies_many_allowed() if allowed else None)
         buf = self._many_records(K, roots.device)
         first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
         # (an empty batch still goes through the library's checks: any non-null pointer stands for its rows)
         if checkpoints is None:
-            check(L.csgpu_solve_many(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
-                                     first.data_ptr() if solutions and K else None, _stream_ptr(stream)))
+            check(plain(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                        first.data_ptr() if solutions and K else None, _stream_ptr(stream)))
             return self._many_answer(buf, K, first)
         slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
         check(L.csgpu_solve_many_checkpointed(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
@@ -305,21 +328,26 @@ class Model:
             out["_records"], out["_slots"], out["_checkpoints"] = buf, slots, checkpoints
         return out
 
-    def solve_many_upto(self, roots, k, *, max_nodes, solutions=True, stream=None, checkpoints=None) -> dict:
+    def solve_many_upto(self, roots, k, *, max_nodes, solutions=True, stream=None, checkpoints=None,
+                        branching="width") -> dict:
         """solve_many that leaves an instance right after its k-th solution and keeps all k (csgpu_solve_many_upto): the
         ALL walk, stopped as ANY stops after the first.  k = 1 is ANY, an instance with fewer than k solutions ends as
         under ALL; status DONE means solutions == min(k, solutions of the tree).  roots, max_nodes, stream, checkpoints:
         as solve_many.  -> the dict of solve_many with `rows` [K, k, n_vars] int32 in place of `first`: row j of instance
         i is its j-th solution in walk order, rows >= solutions[i] are not written.  solutions: True (a zeroed buffer),
         False (no rows), or an int32 device tensor [K, k, n_vars] to write into.  With a pool the answer has `slot` and
-        is what resume_many() continues (csgpu_solve_many_upto_checkpointed)."""
+        is what resume_many() continues (csgpu_solve_many_upto_checkpointed).  branching: as solve_many ("allowed" is
+        csgpu_solve_many_allowed_upto, without checkpoints)."""
+        if self._many_branching(branching, checkpoints):
+            return self._solve_many_upto("csgpu_solve_many_allowed_upto", self.qualifies_many_allowed(), roots, k, max_nodes,
+                                         solutions, stream, None)
         return self._solve_many_upto("csgpu_solve_many_upto", None, roots, k, max_nodes, solutions, stream, checkpoints)
 
     def _solve_many_upto(self, entry, qualifies, roots, k, max_nodes, solutions, stream, checkpoints) -> dict:
         """solve_many_upto / solve_many_clauses_upto: `entry` and `entry`_checkpointed of the library, which take the same
         arguments in both families; `qualifies` as _many_roots takes it"""
         L = load_library()
-        plain, pooled = getattr(L, entry), getattr(L, entry + "_checkpointed")
+        plain, pooled = getattr(L, entry), getattr(L, entry + "_checkpointed", None)  # (no pooled call: no checkpoints)
         n, k = self.n_vars, int(k)
         opt = ManyUptoOptions(k, 0, int(max_nodes))
         roots, K = self._many_roots(roots, k < 1, lambda ptr, count: check(
@@ -789,10 +817,11 @@ class Model:
         """waves a solve_many_clauses of `count` instances launches"""
         return int(load_library().csgpu_internal_many_clauses_waves(self._h, int(count)))
 
-    def classify_many(self, roots, *, max_nodes, stream=None) -> torch.Tensor:
+    def classify_many(self, roots, *, max_nodes, stream=None, branching="width") -> torch.Tensor:
         """is the solution unique?  -> int8 [K] on the device: 0 no solution, 1 exactly one, 2 several, -1 undecided
-        within max_nodes (LIMIT), -2 bad root row.  A solve_many_upto with k = 2 and no rows."""
-        return self._many_classes(self.solve_many_upto(roots, 2, max_nodes=max_nodes, solutions=False, stream=stream), stream)
+        within max_nodes (LIMIT), -2 bad root row.  A solve_many_upto with k = 2 and no rows; branching as there."""
+        return self._many_classes(self.solve_many_upto(roots, 2, max_nodes=max_nodes, solutions=False, stream=stream,
+                                                       branching=branching), stream)
 
     @staticmethod
     def _many_classes(out: dict, stream) -> torch.Tensor:
@@ -1369,6 +1398,14 @@ class Model:
     def many_upto_kernel(self):
         """the cs_dive_upto instantiation solve_many_upto and its checkpoint calls launch"""
         return self._many_symbol("csgpu_internal_many_upto_symbol")
+
+    def many_allowed_kernel(self):
+        """the cs_dive_allowed instantiation solve_many(..., branching="allowed") launches"""
+        return self._many_symbol("csgpu_internal_many_allowed_symbol")
+
+    def many_allowed_upto_kernel(self):
+        """the cs_dive_allowed_upto instantiation solve_many_upto(..., branching="allowed") launches"""
+        return self._many_symbol("csgpu_internal_many_allowed_upto_symbol")
 
     def many_restart_kernel(self):
         """the cs_dive_restart instantiation solve_many_restarts launches"""

@@ -387,6 +387,47 @@ int csgpu_solve_many_upto_resume(const csgpu_model *m, int64_t count, const csgp
                                  csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                  void *stream);
 
+/* ---- branching on the allowed values: csgpu_solve_many that skips what a valued neighbour forbids ----
+ * csgpu_solve_many branches on the smallest INTERVAL and tries every value of it; a value that a valued neighbour forbids
+ * is a node and a cut.  That makes its counters the engine's, but on a != network an interval hides holes: a variable
+ * with bounds [1, 9] of which only 1 and 9 are still possible looks like the widest of the board.  These two calls walk
+ * with the classic forward-checking rule instead.  Opt-in: another tree, the same set of solutions.
+ * The walk is exactly csgpu_solve_many's except for the branching.  Unchanged: the root check and BAD_ROOT; the root node
+ * (every valued variable pushes) and root_props; a child is the assignment followed by the same interval fixpoint;
+ * max_nodes is compared before a child is tried; ANY / ALL / DONE / LIMIT; the first solution is stored.  At a node (a
+ * fixpoint with open variables), for an open variable w with bounds [lo, hi]:
+ *   forbidden value   c in [lo, hi] is forbidden if some VALUED variable u and some clause w + a != u + b of the model, in
+ *                     any slot of the pair, has c + a == value(u) + b
+ *   allowed(w)        the other values of [lo, hi].  At a fixpoint lo and hi are always allowed (the fixpoint has found
+ *                     them supported), so |allowed(w)| >= 2, its first value is lo and its last is hi
+ *   branching         the open variable with the smallest |allowed(w)|, ties to the lowest index; its allowed values in
+ *                     ascending order.  A forbidden value is NOT a node: it is neither tried nor counted
+ *   counters          keep their definitions: nodes = children tried, cuts = inconsistent children, props = narrowings of
+ *                     the consistent children, solutions
+ *   frames            a frame is pushed when the node has an allowed value left after the one being entered; none for
+ *                     the last value, which is hi.  A frame stays {row, variable, next = value + 1}: coming back to it
+ *                     the walk recomputes allowed(variable) on the frame's row and goes on at the first allowed value
+ *                     >= next.  The workspace is csgpu_solve_many's, formula and all
+ * Domains stay intervals and the fixpoint is untouched: no interior value is ever removed from a domain.
+ * csgpu_solve_many_allowed is csgpu_solve_many with this walk; csgpu_solve_many_allowed_upto is csgpu_solve_many_upto
+ * with it (rows [count][max_solutions][n_vars] in walk order, rows >= solutions untouched, max_solutions = 1 is the ANY
+ * call field for field, an instance with fewer than k solutions ends as under ALL).  Which models qualify
+ * (csgpu_model_qualifies_many_allowed, usable after csgpu_model_build_tables alone): kernel 7's rule, and no root domain
+ * of more than 128 values, which is what the kernels' allowed sets hold.
+ * Not on this walk (use the width rule): checkpoints, resume and slices, restarts, the solution stream, the spread of
+ * stopped instances, and the clause family; the csgpu_search strategies are not touched either.
+ * "One call in flight per model" covers these calls (same workspace, same ticket counters, left at zero); calls of the
+ * whole family may be queued behind each other on one stream.
+ * Errors before any HIP call are those of csgpu_solve_many (csgpu_solve_many_upto for the second call), in their order;
+ * in addition a finalized model that qualifies for kernel 7 but has a root domain of more than 128 values ->
+ * CSGPU_E_LIMIT with a message that says so.  count == 0 -> CSGPU_OK, nothing is launched. */
+int csgpu_model_qualifies_many_allowed(const csgpu_model *m);
+int csgpu_solve_many_allowed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                             csgpu_many_result *d_results, int32_t *d_solutions, void *stream);
+int csgpu_solve_many_allowed_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                  const csgpu_many_upto_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                  void *stream);
+
 /* ---- Luby restarts with a seeded value order, for ANY: csgpu_solve_many whose deep walks are cut short ----
  * The deep instances of a batch are the heavy tail of a depth-first search with a fixed value order.  This call walks
  * the ANY walk of csgpu_solve_many with two changes, both per instance; everything not mentioned (the root check and

@@ -11,6 +11,7 @@ oracle walk (tests/many_walk.py).
                                   [--sliced B0,B1,... [--finish resume|search]] [--upto K]
                                   [--restarts BASE [--seed S]] [--revealed R] [--stream ROWS]
                                   [--spread B0,B1,... [--spread-rows ROWS]] [--max-nodes N]
+                                  [--branching allowed [--upto K] [--objective ANY|ALL]]
   --sliced: the same instances through Model.solve_many_sliced as well (a checkpointed call with budget B0, a resume
   with every following budget; --finish search: what is left after the last budget through one Search per instance):
   the time of the whole, the time until the answers of the first slice are there, and whether it found what the one
@@ -35,6 +36,12 @@ oracle walk (tests/many_walk.py).
   solve_many on the same instances, in this process after a warm-up, interleaved, two pools kept over the calls: medians and
   ranges of --reps, rounds and rows per round, the launch of round 0 alone, and whether every field of every instance and
   every first solution equals the one call's.
+  --branching allowed: ONLY this comparison -- Model.solve_many(..., branching="allowed") (the open variable with the fewest
+  values no valued neighbour forbids, only those values) beside the width call of the same build on the same rows, in this
+  process after a warm-up, interleaved, same budget; with --upto K both through solve_many_upto.  For both rules: nodes
+  total, the deepest instance, ms per call (median and range of --reps) and ns per node; the ratios allowed / width; whether
+  both found the same `solutions` where neither stopped at the budget; --check sampled answers of the allowed call re-checked
+  against the host walk of tests/many_walk_allowed.py.  --objective: instead of the set's own.
   sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 / queens13 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY),
   sparse40 (a sparse != network of 40 variables, 16-bit table, three of them open: nearly every node is a solution, ALL)
 """
@@ -85,6 +92,63 @@ def instances(which, count, revealed=None):
     raise SystemExit(f"no set {which}")
 
 
+def both_rules(args, model, text, roots, dev, objective, budget, count):
+    """--branching allowed: the width call and the allowed call on the same rows, interleaved -> the JSON record"""
+    import many_walk_allowed
+
+    def call(rule):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        if args.upto is None:
+            out = model.solve_many(dev, objective, max_nodes=budget, branching=rule)
+        else:
+            out = model.solve_many_upto(dev, args.upto, max_nodes=budget, branching=rule)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    rules = ("width", "allowed")
+    for rule in rules:  # warm-up: code load, workspace, the allocator's blocks
+        call(rule)
+        call(rule)
+    series, outs = {rule: [] for rule in rules}, {}
+    for _ in range(args.reps):
+        for rule in rules:
+            dt, outs[rule] = call(rule)
+            series[rule].append(dt)
+    rec = {"what": "solve_many, branching width against allowed", "set": args.set, "revealed": args.revealed, "instances": count,
+           "objective": objective if args.upto is None else f"up to {args.upto}", "max_nodes": budget, "reps": args.reps,
+           "device": torch.cuda.get_device_name(0), "commit": commit(), "waves": model.many_waves(count),
+           "kernels": {"width": model.many_kernel() if args.upto is None else model.many_upto_kernel(),
+                       "allowed": model.many_allowed_kernel() if args.upto is None else model.many_allowed_upto_kernel()}}
+    for rule in rules:
+        out, ts = outs[rule], series[rule]
+        nodes = int(out["nodes"].sum())
+        rec[rule] = {"nodes": nodes, "deepest": int(out["nodes"].max()), "solutions": int(out["solutions"].sum()),
+                     "status": torch.bincount(out["status"].long(), minlength=3).tolist(),
+                     "ms": {"median": round(statistics.median(ts) * 1e3, 3), "min": round(min(ts) * 1e3, 3),
+                            "max": round(max(ts) * 1e3, 3)},
+                     "ns_per_node": round(statistics.median(ts) * 1e9 / max(nodes, 1), 2)}
+    w, a = rec["width"], rec["allowed"]
+    rec["allowed_over_width"] = {"nodes": round(a["nodes"] / max(w["nodes"], 1), 4), "deepest": round(a["deepest"] / max(w["deepest"], 1), 4),
+                                 "ms": round(a["ms"]["median"] / w["ms"]["median"], 4),
+                                 "ns_per_node": round(a["ns_per_node"] / w["ns_per_node"], 4)}
+    done = (outs["width"]["status"] == 0) & (outs["allowed"]["status"] == 0)
+    rec["same_solutions_where_both_finished"] = bool((outs["width"]["solutions"] == outs["allowed"]["solutions"])[done].all())
+    rec["both_finished"] = int(done.sum())
+    rng = np.random.default_rng(args.seed)
+    sample = sorted(rng.choice(count, size=min(args.check, count), replace=False).tolist())
+    got = {f: outs["allowed"][f].cpu().numpy() for f in many_walk_allowed.FIELDS}
+    good = 0
+    for i in sample:
+        if args.upto is None:
+            want = many_walk_allowed.dive(text, roots[i], objective, budget)
+        else:
+            want = many_walk_allowed.upto(text, roots[i], args.upto, budget)
+        good += all(int(got[f][i]) == want[f] for f in many_walk_allowed.FIELDS)
+    rec["checked_against_the_host_walk"] = {"instances": len(sample), "equal": good}
+    return rec
+
+
 def commit():
     try:
         return open(os.path.join(ROOT, "csolve_amd", "csrc", "build", "COMMIT")).read().strip()
@@ -109,12 +173,18 @@ def main():
     ap.add_argument("--spread", default=None, help="budgets of the rounds of solve_many_spread, e.g. 256,4096")
     ap.add_argument("--spread-rows", type=int, default=1 << 18, help="max_rows of solve_many_spread")
     ap.add_argument("--max-nodes", type=int, default=None, help="the budget of the one call (default: the set's own)")
+    ap.add_argument("--branching", default="width", choices=("width", "allowed"),
+                    help="allowed: time the allowed-values walk beside the width walk (with or without --upto K), nothing else")
+    ap.add_argument("--objective", default=None, choices=("ANY", "ALL"), help="instead of the set's own (--branching allowed)")
     args = ap.parse_args()
     count = args.count or {"sudoku9": 65536, "queens12": 16384, "queens13": 48, "sudoku16": 4096, "sparse40": 256}[args.set]
     text, roots, objective, budget = instances(args.set, count, args.revealed)
     budget = args.max_nodes or budget
     model = solve_root(text)
     dev = torch.from_numpy(roots).cuda()
+    if args.branching == "allowed":
+        print(json.dumps(both_rules(args, model, text, roots, dev, args.objective or objective, budget, count)))
+        return
 
     def many(max_nodes, rows=dev):
         torch.cuda.synchronize()
