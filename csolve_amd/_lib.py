@@ -256,6 +256,14 @@ def load_library():
     L.csgpu_solve_many_allowed_upto.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp]
     L.csgpu_internal_many_allowed_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_internal_many_allowed_upto_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many_allowed_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_allowed_resume.argtypes = [vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_allowed_upto_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_allowed_upto_resume.argtypes = [vp, i64, C.POINTER(ManyUptoOptions), vp, vp, vp, vp, vp]
+    L.csgpu_many_allowed_checkpoint_children.argtypes = [vp, vp, i64, vp, vp]
+    L.csgpu_many_allowed_checkpoint_fanout.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
+    L.csgpu_internal_many_allowed_resume_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_internal_many_allowed_upto_resume_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_restarts.argtypes = [vp, vp, vp, i64, C.POINTER(ManyRestartOptions), vp, vp, vp, vp]
     L.csgpu_internal_many_restart_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_solve_many_stream.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, C.POINTER(ManyStream), vp]

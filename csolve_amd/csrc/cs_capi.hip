@@ -56,11 +56,14 @@ struct cs_planned {
   int per_cu;     /* resident workgroups per CU */
 };
 
-/* the kernels of the csgpu_solve_many family (cs_dive.hip.h): one loop, compiled five times, and the two that branch on
+/* the kernels of the csgpu_solve_many family (cs_dive.hip.h): one loop, compiled five times, and the four that branch on
  * the allowed values (planned only for root domains of at most CS_DIVE_ALLOWED_WIDTH values) */
-enum { MANY_PLAIN, MANY_CK, MANY_UPTO, MANY_RESTART, MANY_STREAM, MANY_ALLOWED, MANY_ALLOWED_UPTO, MANY_FAMILIES };
+enum { MANY_PLAIN, MANY_CK, MANY_UPTO, MANY_RESTART, MANY_STREAM, MANY_ALLOWED, MANY_ALLOWED_UPTO, MANY_ALLOWED_CK,
+       MANY_ALLOWED_UPTO_CK, MANY_FAMILIES };
 static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "cs_dive_resume", "cs_dive_upto", "cs_dive_restart",
-                                                             "cs_dive_stream", "cs_dive_allowed", "cs_dive_allowed_upto" };
+                                                             "cs_dive_stream", "cs_dive_allowed", "cs_dive_allowed_upto",
+                                                             "cs_dive_allowed_resume", "cs_dive_allowed_upto_resume" };
+#define MANY_BY_ALLOWED(family) ((family) >= MANY_ALLOWED && (family) <= MANY_ALLOWED_UPTO_CK)
 #define CS_DIVE_ALLOWED_WIDTH 128 /* the widest root domain the allowed sets of cs_dive_allowed hold (four 32-bit words) */
 
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
@@ -76,7 +79,7 @@ struct cs_kernel_plan {
   cs_planned shave, shave_trace;   /* kernel 7 (the instantiation whose FULL matches the model); its tracing variant */
   cs_planned server;               /* the resident single-node server */
   cs_planned step_shave, step_packed, step_import;
-  cs_planned dive[MANY_FAMILIES];  /* by MANY_*: the first five all or none, the two MANY_ALLOWED* with them unless the
+  cs_planned dive[MANY_FAMILIES];  /* by MANY_*: the first five all or none, the four MANY_ALLOWED* with them unless the
                                       domains are too wide; not among csgpu_internal_plan_symbol's families */
   cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
   cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
@@ -814,11 +817,13 @@ static const void *step_shave_kernel(int width, int n_vars, int slots, int full)
 /* ---- cs_dive.hip.h: a depth-first search per wave (csgpu_solve_many); the slot count is always a run-time value ---- */
 static const void *dive_kernel(int family, int width, int n_vars, int set_words) {
   const int r = cs_dense_strides(n_vars);
-  if (family == MANY_ALLOWED || family == MANY_ALLOWED_UPTO) { /* set_words: 1 or 4 words of 32 allowed values per variable */
+  if (MANY_BY_ALLOWED(family)) { /* set_words: 1 or 4 words of 32 allowed values per variable */
 #define CS_PICK_R(K, E, NW) (r == 1 ? (const void *)K<E, 1, NW> : r == 2 ? (const void *)K<E, 2, NW> : (const void *)K<E, 4, NW>)
 #define CS_PICK_E(K, NW) (width == 1 ? CS_PICK_R(K, unsigned char, NW) : CS_PICK_R(K, unsigned short, NW))
 #define CS_PICK(K) return set_words == 1 ? CS_PICK_E(K, 1) : CS_PICK_E(K, 4);
     if (family == MANY_ALLOWED) { CS_PICK(cs_dive_allowed) }
+    if (family == MANY_ALLOWED_CK) { CS_PICK(cs_dive_allowed_resume) }           /* csgpu_solve_many_allowed_checkpointed / _resume */
+    if (family == MANY_ALLOWED_UPTO_CK) { CS_PICK(cs_dive_allowed_upto_resume) } /* and up to k */
     CS_PICK(cs_dive_allowed_upto)
 #undef CS_PICK
 #undef CS_PICK_E
@@ -1222,7 +1227,7 @@ static int plan_dense_table(csgpu_model *m) {
   /* the cs_dive_* kernels: the table alone; the upper bounds of the root domains for its check of the root rows */
   const int64_t widest = widest_root_domain(m);
   for (int family = 0; family < MANY_FAMILIES; family++) {
-    const int by_allowed = family == MANY_ALLOWED || family == MANY_ALLOWED_UPTO;
+    const int by_allowed = MANY_BY_ALLOWED(family);
     if (by_allowed && widest > CS_DIVE_ALLOWED_WIDTH) continue; /* not planned: the calls say why */
     if ((rc = plan_kernel(&m->plan.dive[family], dive_kernel(family, width, n, widest <= 32 ? 1 : 4), table, waves))) return rc;
   }
@@ -1392,6 +1397,8 @@ extern "C" int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *bu
 extern "C" int csgpu_internal_many_stream_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_STREAM, buf, len); }
 extern "C" int csgpu_internal_many_allowed_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED, buf, len); }
 extern "C" int csgpu_internal_many_allowed_upto_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED_UPTO, buf, len); }
+extern "C" int csgpu_internal_many_allowed_resume_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED_CK, buf, len); }
+extern "C" int csgpu_internal_many_allowed_upto_resume_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED_UPTO_CK, buf, len); }
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
   if (m != NULL) const_cast<csgpu_model *>(m)->engines += delta;
@@ -1894,7 +1901,9 @@ static int many_pool_states(const csgpu_many_checkpoints *ck, int kind, int32_t 
   HIP_TRY(hipMemcpyAsync(header, base, sizeof header, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   const cs_val head = header[0];
-  if (head.hi != (kind == MANY_POOL_WALK ? CS_WALK_CK_MAGIC : CS_DIVE_CK_MAGIC) || head.lo < 0 || head.lo >= n)
+  const int magic_ok = kind == MANY_POOL_WALK ? head.hi == CS_WALK_CK_MAGIC /* a dive pool: a slot of either walk */
+                                              : head.hi == CS_DIVE_CK_MAGIC || head.hi == CS_DIVE_CK_MAGIC_ALLOWED;
+  if (!magic_ok || head.lo < 0 || head.lo >= n)
     return set_err(CSGPU_E_STATE, "slot %d holds no checkpoint", slot);
   if (head2 != NULL) { head2[0] = header[0]; head2[1] = header[1]; }
   *count = (int64_t)head.lo + 1;
@@ -1963,7 +1972,7 @@ extern "C" int csgpu_many_fold(const csgpu_many_result *d_sub_results, const int
   return CSGPU_OK;
 }
 
-/* ---- branching on the allowed values (cs_dive_allowed, cs_dive_allowed_upto): the plain walk and up to k, no checkpoints ---- */
+/* ---- branching on the allowed values (cs_dive_allowed, cs_dive_allowed_upto): the plain walk and up to k ---- */
 
 extern "C" int csgpu_model_qualifies_many_allowed(const csgpu_model *m) {
   if (m == NULL || !many_qualifies(m)) return 0;
@@ -2004,6 +2013,121 @@ extern "C" int csgpu_solve_many_allowed_upto(const csgpu_model *m, const csgpu_v
   int upto = options->max_solutions;
   return many_launch(m, MANY_ALLOWED_UPTO, d_roots, count, options->max_nodes, 1 /* not read */, d_results, d_solutions, 0, stream,
                      &upto, NULL);
+}
+
+/* ---- the allowed walk with checkpoints (cs_dive_allowed_resume, cs_dive_allowed_upto_resume), and its spread ---- */
+
+/* csgpu_solve_many_allowed_checkpointed, and with `resume` (and no roots) csgpu_solve_many_allowed_resume: the checks of
+ * many_ck_call in its order, the width of the domains before the general refusal */
+static int many_allowed_ck_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                                csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                int resume, void *stream) {
+  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || options == NULL || ck == NULL || d_slots == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "slice")) ||
+      (rc = many_check_objective(options->objective)) || (rc = many_check_allowed_width(m)) ||
+      (rc = many_check_tail(m, MANY_ALLOWED_CK, ck, count)))
+    return rc;
+  cs_dive_ck dk = many_ck_arg(ck, d_slots, resume);
+  return many_launch(m, MANY_ALLOWED_CK, d_roots, count, options->max_nodes, options->objective == CS_OBJ_ALL, d_results,
+                     d_solutions, resume, stream, &dk, NULL);
+}
+
+extern "C" int csgpu_solve_many_allowed_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                     const csgpu_many_options *options, csgpu_many_result *d_results,
+                                                     int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                                     void *stream) {
+  return many_allowed_ck_call(m, d_roots, count, options, d_results, d_solutions, ck, d_slots, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_allowed_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                               csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                               int32_t *d_slots, void *stream) {
+  return many_allowed_ck_call(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
+}
+
+/* the two up-to-k calls: the checks of many_upto_call (pooled) in its order */
+static int many_allowed_upto_ck_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                     const csgpu_many_upto_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                     csgpu_many_checkpoints *ck, int32_t *d_slots, int resume, void *stream) {
+  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL || options == NULL || ck == NULL || d_slots == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance"))) return rc;
+  if (options->max_solutions < 1) return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
+  if ((rc = many_check_allowed_width(m)) || (rc = many_check_tail(m, MANY_ALLOWED_UPTO_CK, ck, count))) return rc;
+  cs_dive_ck dk = many_ck_arg(ck, d_slots, resume);
+  int upto = options->max_solutions;
+  return many_launch(m, MANY_ALLOWED_UPTO_CK, d_roots, count, options->max_nodes, 1 /* not read */, d_results, d_solutions, resume,
+                     stream, &dk, &upto);
+}
+
+extern "C" int csgpu_solve_many_allowed_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                          const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                                          int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                                          void *stream) {
+  return many_allowed_upto_ck_call(m, d_roots, count, options, d_results, d_solutions, ck, d_slots, 0, stream);
+}
+
+extern "C" int csgpu_solve_many_allowed_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
+                                                    csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                                    int32_t *d_slots, void *stream) {
+  return many_allowed_upto_ck_call(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
+}
+
+/* the pool's model runs csgpu_solve_many (the pool exists) but not the allowed walk: its domains are too wide */
+static int many_fan_allowed_width(const csgpu_many_checkpoints *ck) {
+  if (ck->m->plan.dive[MANY_ALLOWED_CK].fn == NULL)
+    return set_err(CSGPU_E_LIMIT, "csgpu_solve_many_allowed: a root domain of this model has more than %d values, which is as wide "
+                                  "as the allowed-value sets of the kernels are; csgpu_solve_many runs it",
+                   CS_DIVE_ALLOWED_WIDTH);
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_allowed_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                      int64_t *d_children, void *stream) {
+  if (ck == NULL || d_slots == NULL || d_children == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (ck->kind != MANY_POOL_DIVE) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  if (count > 0x7fffffff) return set_err(CSGPU_E_LIMIT, MANY_FAN_LIMIT);
+  if (count == 0) return CSGPU_OK;
+  int rc;
+  if ((rc = many_fan_allowed_width(ck))) return rc; /* (after the empty call, which looks into no pool) */
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  const int n = m->host->n_vars, slots = m->img->dense_slots, dmin = m->img->dense_dmin, cols = m->img->dense_cols;
+#define CS_FAN(E)                                                                                                             \
+  hipLaunchKernelGGL(cs_dive_allowed_children<E>, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, n,    \
+                     (const int *)m->d_root_lo, (const int *)m->d_root_hi, (const E *)m->d_dense_tab, slots, dmin, cols,       \
+                     (const cs_val *)ck->d_pool, (int)ck->capacity, (const int *)d_slots, (long long)count, (long long *)d_children)
+  if (m->img->dense_width == 1) CS_FAN(unsigned char); else CS_FAN(unsigned short);
+#undef CS_FAN
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_allowed_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                    const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total,
+                                                    void *stream) {
+  if (ck == NULL || d_slots == NULL || d_offsets == NULL || d_rows == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (total < 0) return set_err(CSGPU_E_ARG, "negative row count");
+  if (ck->kind != MANY_POOL_DIVE) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  if (count > 0x7fffffff) return set_err(CSGPU_E_LIMIT, MANY_FAN_LIMIT);
+  if (count == 0 || total == 0) return CSGPU_OK;
+  int rc;
+  if ((rc = many_fan_allowed_width(ck))) return rc;
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  const int n = m->host->n_vars, slots = m->img->dense_slots, dmin = m->img->dense_dmin, cols = m->img->dense_cols;
+#define CS_FAN(E)                                                                                                             \
+  hipLaunchKernelGGL(cs_dive_allowed_fanout<E>, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, n,      \
+                     (const int *)m->d_root_lo, (const int *)m->d_root_hi, (const E *)m->d_dense_tab, slots, dmin, cols,       \
+                     (const cs_val *)ck->d_pool, (int)ck->capacity, (const int *)d_slots, (long long)count,                    \
+                     (const long long *)d_offsets, (long long)total, (cs_val *)d_rows, (int *)d_owner)
+  if (m->img->dense_width == 1) CS_FAN(unsigned char); else CS_FAN(unsigned short);
+#undef CS_FAN
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
 }
 
 /* ---- up to k solutions per instance (cs_dive_upto): csgpu_solve_many, stopped at the k-th solution, all k rows kept ---- */

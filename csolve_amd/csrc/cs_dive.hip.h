@@ -73,7 +73,27 @@
  * stands before that very value, so the next call tries it again.  The fixpoint runs on copies, the parent node is intact.
  * Whether an instance is fresh or goes on from a slot is a fact per instance here (slots[i] == -2 or >= 0): a fresh one
  * walks in the wave's workspace slice and copies its frames out when it stops, a resumed one walks in its slot.  A wave
- * that finds the stream full when it has drawn a ticket does not walk.  New per-wave state is scalars. */
+ * that finds the stream full when it has drawn a ticket does not walk.  New per-wave state is scalars.
+ *
+ * The allowed walk in slices and spread (cs_dive_allowed_resume / cs_dive_allowed_upto_resume, cs_dive_allowed_children /
+ * cs_dive_allowed_fanout; csgpu_solve_many_allowed_checkpointed / _resume and the up-to-k pair, csgpu_many_allowed_
+ * checkpoint_children / _fanout): cs_dive_allowed_body.hip.h with CS_DIVE_CK 1.  The slot layout is cs_dive_resume's: a
+ * frame of the allowed walk is {row, bv, next = value + 1} already, and coming back to a frame the kernel rebuilds
+ * allowed(bv) on the frame's row and drops the bits below next -- exactly what a resume does on the current node, whose
+ * entry is {bv, nv} with nv the lowest bit still in aw (the budget is compared after the pop loop: aw is not empty).  The
+ * header's magic is CS_DIVE_CK_MAGIC_ALLOWED: the trees and counters of the two walks differ, so each walk's kernels refuse
+ * the other's slots before they read them; cs_dive_export takes both ([next, hi] covers the open subtrees of either walk).
+ * The spread lists, per frame, only the untried values that no valued variable of the frame's row forbids, from the dense
+ * table in global memory, and folds with cs_dive_fold.  Exact because the allowed sets are a function of the node's row and
+ * the table only and the fixpoint of a != network is unique: the root node of a child row is the child's fixpoint, the
+ * sub-walk the subtree (the argument stands with the kernels below and in csolve_gpu.h).
+ * Resources (-Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / SGPRs / scratch bytes / waves per SIMD; 8- and 16-bit
+ * table entries give the same figures):
+ *                                 R=1 NW=1      R=1 NW=4      R=2 NW=1      R=2 NW=4      R=4 NW=1       R=4 NW=4
+ *   cs_dive_allowed_resume        46/78/0/8     47/78/0/8     54/78/0/8     64/78/0/8     79/106/0/6     99/106/0/4
+ *   cs_dive_allowed_upto_resume   42/78/0/8     43/78/0/8     53/78/0/8     64/78/0/8     78/106/0/6     98/106/0/4
+ *   cs_dive_allowed_children<E> 29/49/0/8, cs_dive_allowed_fanout<E> 29/68/0/8.  New per-wave state across the child's
+ *   fixpoint is scalars (slot, kept, depth0, nodes0, resumed). */
 #ifndef CS_DIVE_HIP_H
 #define CS_DIVE_HIP_H
 
@@ -110,6 +130,7 @@ struct cs_dive_io {
 };
 
 #define CS_DIVE_CK_MAGIC 0x636b7074 /* header entry 0 .hi of a slot that holds a checkpoint */
+#define CS_DIVE_CK_MAGIC_ALLOWED 0x636b616c /* the same of a slot written by the allowed walk: another tree, other counters */
 
 /* the checkpoint pool and the slot numbers of a call (cs_dive_resume) */
 struct cs_dive_ck {
@@ -329,9 +350,11 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_allowed(int n,
                                                                           const int *__restrict__ root_hi,
                                                                           const int *__restrict__ sym_off, size_t tab_bytes,
                                                                           cs_dive_io io) {
+#define CS_DIVE_CK 0
 #define CS_DIVE_UPTO 0
 #include "cs_dive_allowed_body.hip.h"
 #undef CS_DIVE_UPTO
+#undef CS_DIVE_CK
 }
 
 /* the same, leaving an instance right after its `upto`-th solution and keeping all of them (upto >= 1; io.all is not read) */
@@ -341,9 +364,43 @@ __global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_allowed_upto(i
                                                                                const int *__restrict__ root_hi,
                                                                                const int *__restrict__ sym_off, size_t tab_bytes,
                                                                                cs_dive_io io, int upto) {
+#define CS_DIVE_CK 0
 #define CS_DIVE_UPTO 1
 #include "cs_dive_allowed_body.hip.h"
 #undef CS_DIVE_UPTO
+#undef CS_DIVE_CK
+}
+
+/* the allowed walk with checkpoints (csgpu_solve_many_allowed_checkpointed / _resume): fresh instances (ck.resume == 0) or
+ * the instances of ck.slots going on.  A slot is laid out as cs_dive_resume's and carries CS_DIVE_CK_MAGIC_ALLOWED: the
+ * trees differ, so a slot of one walk is no checkpoint of the other. */
+template <typename E, int R, int NW>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_allowed_resume(int n, const E *__restrict__ tab_g, int slots,
+                                                                                 int dmin, const int *__restrict__ root_lo,
+                                                                                 const int *__restrict__ root_hi,
+                                                                                 const int *__restrict__ sym_off, size_t tab_bytes,
+                                                                                 cs_dive_io io, cs_dive_ck ck) {
+#define CS_DIVE_CK 1
+#define CS_DIVE_UPTO 0
+#include "cs_dive_allowed_body.hip.h"
+#undef CS_DIVE_UPTO
+#undef CS_DIVE_CK
+}
+
+/* the same up to k (csgpu_solve_many_allowed_upto_checkpointed / _resume); the pool always has slots here: the plain
+ * up-to-k call launches cs_dive_allowed_upto */
+template <typename E, int R, int NW>
+__global__ __launch_bounds__(1024, (R <= 2 ? 8 : 4)) void cs_dive_allowed_upto_resume(int n, const E *__restrict__ tab_g, int slots,
+                                                                                      int dmin, const int *__restrict__ root_lo,
+                                                                                      const int *__restrict__ root_hi,
+                                                                                      const int *__restrict__ sym_off,
+                                                                                      size_t tab_bytes, cs_dive_io io, cs_dive_ck ck,
+                                                                                      int upto) {
+#define CS_DIVE_CK 1
+#define CS_DIVE_UPTO 1
+#include "cs_dive_allowed_body.hip.h"
+#undef CS_DIVE_UPTO
+#undef CS_DIVE_CK
 }
 
 /* csgpu_many_checkpoint_states: frame d of slot `slot` (d <= depth, the oldest first) as a state in absolute bounds, its
@@ -479,6 +536,142 @@ __global__ __launch_bounds__(256) void cs_dive_fold(const cs_dive_result *__rest
   if (cuts != 0) __hip_atomic_fetch_add(&dst->cuts, cuts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (props != 0) __hip_atomic_fetch_add(&dst->props, props, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (r.solutions != 0) __hip_atomic_fetch_add(&dst->solutions, r.solutions, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* ---- the same for a stopped ALLOWED walk (csgpu_many_allowed_checkpoint_children / _fanout; the fold is cs_dive_fold)
+ *
+ * The untried children of frame d of an allowed slot are the values c of [next, node[bv].hi] that no valued variable of the
+ * frame's row forbids, ascending; frames from `depth` down to 0, as above.  The forbidden values of the ONE variable bv come
+ * from the model's dense pair table in global memory, with the arithmetic of cs_dive_allowed_sets: for a valued u and slot k,
+ * f = value(u) + kb(u) - tab[(u * slots + k) * W + bv], the sentinel giving f < 0.  Lanes stride over u, an OR across the wave
+ * gives the four words.  A cold path: no LDS, table reads from global memory.
+ *
+ * The split is exact for the reason it is exact on the width walk.  The allowed sets are a function of the node's row and
+ * the table only, so a child row -- the frame's row with bv = [c, c] -- names its subtree whoever walks it; the fixpoint of a
+ * != network is unique, so the root node of the child row IS the child's fixpoint and the sub-walk branches as the one walk
+ * does below it.  Hence, per child: nodes 1 + sub.nodes; cuts sub.cuts + (inconsistent as a root); props sub.root_props +
+ * sub.props; solutions sub.solutions -- cs_dive_fold's sums.  A value that a valued variable forbids is no child: the walk
+ * neither tries nor counts it, and as a root row it would be one more cut.
+ *
+ * The slot checks are cs_dive_slot_children's, each compared before what depends on it is read, with the other magic; a
+ * node whose bounds of bv pass the 128 values the sets hold is refused too.  One wave per instance, CS_DIVE_FAN_WAVES
+ * instances per workgroup, 64-bit row indices, no atomics.  Templated on the table's entry type alone. */
+#define CS_DIVE_ALLOWED_WORDS 4 /* 32-bit words of allowed values: 128, the widest root domain of the allowed walk */
+
+/* aw = the untried allowed values of the frame f (wave-uniform), bv its branching variable; false: the frame is refused */
+template <typename E>
+static __device__ __forceinline__ bool cs_dive_allowed_frame(int n, const int *__restrict__ root_lo,
+                                                             const int *__restrict__ root_hi, const E *__restrict__ tab_g,
+                                                             int slots, int dmin, int cols, const cs_val *__restrict__ f, int lane,
+                                                             unsigned (&aw)[CS_DIVE_ALLOWED_WORDS], int &bv) {
+  const cs_val meta = f[n];
+  bv = __builtin_amdgcn_readfirstlane(meta.lo);
+  const int next = __builtin_amdgcn_readfirstlane(meta.hi);
+  if (bv < 0 || bv >= n) return false;
+  const cs_val node = f[bv];
+  const int lo = __builtin_amdgcn_readfirstlane(node.lo), hi = __builtin_amdgcn_readfirstlane(node.hi);
+  if (lo < 0 || hi > root_hi[bv] - root_lo[bv] || hi >= 32 * CS_DIVE_ALLOWED_WORDS || next < lo || next > hi) return false;
+  unsigned fb[CS_DIVE_ALLOWED_WORDS];
+#pragma unroll
+  for (int j = 0; j < CS_DIVE_ALLOWED_WORDS; j++) fb[j] = 0u;
+  for (int u = lane; u < n; u += CS_WAVE) {
+    const cs_val e = f[u];
+    if (e.lo != e.hi) continue; /* an open variable forbids nothing */
+    const int cd = e.lo + root_lo[u] - dmin;
+    const E *row = tab_g + (size_t)u * (size_t)slots * (size_t)cols + (size_t)bv;
+    for (int k = 0; k < slots; k++) {
+      const int fv = cd - (int)row[(size_t)k * (size_t)cols]; /* the value of bv that u forbids (sentinel: < 0) */
+      const unsigned bit = 1u << (fv & 31);
+      const int word = fv >> 5;
+#pragma unroll
+      for (int j = 0; j < CS_DIVE_ALLOWED_WORDS; j++) fb[j] |= word == j ? bit : 0u;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < CS_DIVE_ALLOWED_WORDS; j++) {
+    for (int o = CS_WAVE / 2; o > 0; o >>= 1) fb[j] |= (unsigned)__shfl_xor((int)fb[j], o, CS_WAVE);
+    const int l = next - 32 * j, h = hi - 32 * j; /* [next, hi] in word j's coordinates */
+    const unsigned range = (0xffffffffu >> (31 - (h > 31 ? 31 : h & 31))) & (0xffffffffu << (l < 0 ? 0 : l & 31));
+    aw[j] = (unsigned)__builtin_amdgcn_readfirstlane((int)(h < 0 || l > 31 ? 0u : ~fb[j] & range));
+  }
+  return true;
+}
+
+/* the untried children of the allowed checkpoint in `slot`: 0 for slot < 0, -1 for a slot that is refused */
+template <typename E>
+static __device__ __forceinline__ long long cs_dive_allowed_slot_children(int n, const int *__restrict__ root_lo,
+                                                                          const int *__restrict__ root_hi,
+                                                                          const E *__restrict__ tab_g, int slots, int dmin, int cols,
+                                                                          const cs_val *__restrict__ pool, int capacity, int slot,
+                                                                          int lane) {
+  if (slot < 0) return 0;
+  if (slot >= capacity) return -1;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (fstride * fstride);
+  const cs_val head = base[0];
+  const int depth = __builtin_amdgcn_readfirstlane(head.lo);
+  if (__builtin_amdgcn_readfirstlane(head.hi) != CS_DIVE_CK_MAGIC_ALLOWED || depth < 0 || depth >= n) return -1;
+  long long count = 0;
+  for (int d = depth; d >= 0; d--) {
+    unsigned aw[CS_DIVE_ALLOWED_WORDS];
+    int bv;
+    if (!cs_dive_allowed_frame<E>(n, root_lo, root_hi, tab_g, slots, dmin, cols, base + fstride * (1 + (size_t)d), lane, aw, bv))
+      return -1;
+#pragma unroll
+    for (int j = 0; j < CS_DIVE_ALLOWED_WORDS; j++) count += __popc(aw[j]);
+  }
+  return count;
+}
+
+template <typename E>
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_dive_allowed_children(
+    int n, const int *__restrict__ root_lo, const int *__restrict__ root_hi, const E *__restrict__ tab_g, int slots, int dmin,
+    int cols, const cs_val *__restrict__ pool, int capacity, const int *__restrict__ slot_of, long long count,
+    long long *__restrict__ children) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slot_of[i]);
+  const long long c = cs_dive_allowed_slot_children<E>(n, root_lo, root_hi, tab_g, slots, dmin, cols, pool, capacity, slot, lane);
+  if (lane == 0) children[i] = c;
+}
+
+/* rows[offsets[i] ..] = the children of instance i in walk order, owner[row] = i.  The instance is counted again first: it
+ * writes nothing unless offsets[i + 1] - offsets[i] is its count and its rows lie inside [0, total) */
+template <typename E>
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_dive_allowed_fanout(
+    int n, const int *__restrict__ root_lo, const int *__restrict__ root_hi, const E *__restrict__ tab_g, int slots, int dmin,
+    int cols, const cs_val *__restrict__ pool, int capacity, const int *__restrict__ slot_of, long long count,
+    const long long *__restrict__ offsets, long long total, cs_val *__restrict__ rows, int *__restrict__ owner) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slot_of[i]);
+  if (slot < 0) return;
+  const long long mine = cs_dive_allowed_slot_children<E>(n, root_lo, root_hi, tab_g, slots, dmin, cols, pool, capacity, slot, lane);
+  const long long off = cs_dive_uniform(offsets[i]), end = cs_dive_uniform(offsets[i + 1]);
+  if (mine <= 0 || off < 0 || end > total || end - off != mine) return;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (fstride * fstride);
+  const int depth = __builtin_amdgcn_readfirstlane(base[0].lo);
+  long long row = off;
+  for (int d = depth; d >= 0; d--) {
+    const cs_val *f = base + fstride * (1 + (size_t)d);
+    unsigned aw[CS_DIVE_ALLOWED_WORDS];
+    int bv;
+    if (!cs_dive_allowed_frame<E>(n, root_lo, root_hi, tab_g, slots, dmin, cols, f, lane, aw, bv)) return; /* (counted: it passes) */
+    while (cs_dive_any_bits<CS_DIVE_ALLOWED_WORDS>(aw) && row < end) {
+      const int v = cs_dive_take_lowest<CS_DIVE_ALLOWED_WORDS>(aw);
+      cs_val *dst = rows + (size_t)row * (size_t)n;
+      for (int x = lane; x < n; x += CS_WAVE) {
+        const cs_val e = f[x];
+        const int b = root_lo[x];
+        dst[x] = x == bv ? cs_interval(v + b, v + b) : cs_interval(e.lo + b, e.hi + b);
+      }
+      if (owner != nullptr && lane == 0) owner[row] = (int)i;
+      row++;
+    }
+  }
 }
 
 #endif

@@ -1,8 +1,16 @@
-/* cs_dive_allowed_body.hip.h -- the body of the two kernels of cs_dive.hip.h that branch on the allowed values, which
- * includes it inside each of them under one switch:
- *                          CS_DIVE_UPTO
- *   cs_dive_allowed             0          csgpu_solve_many_allowed
- *   cs_dive_allowed_upto        1          csgpu_solve_many_allowed_upto: one more argument, `upto` (k >= 1, a scalar)
+/* cs_dive_allowed_body.hip.h -- the body of the four kernels of cs_dive.hip.h that branch on the allowed values, which
+ * includes it inside each of them under two switches:
+ *                               CS_DIVE_CK  CS_DIVE_UPTO
+ *   cs_dive_allowed                 0            0        csgpu_solve_many_allowed
+ *   cs_dive_allowed_upto            0            1        csgpu_solve_many_allowed_upto: one more argument, `upto` (k >= 1, a scalar)
+ *   cs_dive_allowed_resume          1            0        csgpu_solve_many_allowed_checkpointed / _resume: `ck`, the pool and the slots
+ *   cs_dive_allowed_upto_resume     1            1        csgpu_solve_many_allowed_upto_checkpointed / _resume: `ck` and `upto`
+ * Every line of CS_DIVE_CK stands under its `#if`: the two kernels that define it 0 see the text they saw before it.
+ * CS_DIVE_CK: cs_dive_body.hip.h's checkpoints on this walk.  An instance that stops at max_nodes with work left draws a
+ * slot and leaves there the header {depth, CS_DIVE_CK_MAGIC_ALLOWED}, its frames and the current node with {bv, nv}, nv the
+ * lowest value still in aw (the budget is compared after the pop loop: aw is not empty there).  A resumed instance checks
+ * slot number, magic and depth before anything else of the slot is read, walks in its slot, rebuilds the sets of the
+ * current node and drops the bits below nv -- the pop path's own steps -- and goes on with the counters of its record.
  * A body of its own, not a fifth switch of cs_dive_body.hip.h: the five older kernels see the text they saw.  The ticket
  * loop, the root node, the child (assignment + cs_shave_core::fixpoint), the counters and the frames {row, bv, value + 1}
  * are those of cs_dive_body.hip.h with CS_DIVE_CK 0; text, not a function, for the reason given there.  What differs is
@@ -49,7 +57,11 @@
   const unsigned waves_x = (unsigned)((((int)gridDim.x - 1 - shard) / nsh + 1) * waves_per_block);
   unsigned *my_ticket = io.tickets + (size_t)shard * CS_DIVE_TICKET_STRIDE;
   const size_t fstride = (size_t)n + 1;
+#if CS_DIVE_CK
+  cs_val *const wave_stack = io.stack + (size_t)wave_global * (size_t)io.frames * fstride;
+#else
   cs_val *const stack = io.stack + (size_t)wave_global * (size_t)io.frames * fstride;
+#endif
 
   /* the valued variables of the node in plo / phi and the allowed values of every open one (al) */
 #define CS_DIVE_ASETS()                                                                                              \
@@ -99,24 +111,84 @@
 
     int plo[R], phi[R]; /* the current node, relative to the root lower bounds; a lane without a variable is the value 0 */
     bool bad_l = false;
+#if CS_DIVE_CK
+    /* the instance's slot (-1: none yet), the slot a checkpoint was written to in this launch, the stack the instance
+     * walks on and, resuming, the checkpoint's depth */
+    int slot = -1, kept = -1, depth0 = 0;
+    cs_val *stack = wave_stack;
+    bool resumed = false;
+    if (ck.resume) {
+      slot = __builtin_amdgcn_readfirstlane(ck.slots[inst]);
+      if (slot < 0) continue; /* not stopped, or stopped without a checkpoint: nothing of it is written */
+      cs_val head = cs_interval(-1, 0);
+      if (slot < ck.capacity) head = ck.pool[(size_t)slot * (fstride * fstride)]; /* compared before it is read */
+      depth0 = __builtin_amdgcn_readfirstlane(head.lo);
+      if (depth0 < 0 || depth0 >= n || __builtin_amdgcn_readfirstlane(head.hi) != CS_DIVE_CK_MAGIC_ALLOWED) {
+        if (lane == 0) io.results[inst].status = 3; /* CSGPU_MANY_BAD_SLOT */
+        continue;
+      }
+      resumed = true;
+      stack = ck.pool + (size_t)slot * (fstride * fstride) + fstride;
+      const cs_val *f = stack + (size_t)depth0 * fstride; /* the current node */
 #pragma unroll
-    for (int r = 0; r < R; r++) {
-      plo[r] = 0; phi[r] = 0;
-      if (live[r]) {
-        const cs_val d = io.roots[rrow + lane + r * CS_WAVE];
-        bad_l = bad_l || d.lo > d.hi || d.lo < b0[r] || d.hi > h0[r];
-        plo[r] = d.lo - b0[r];
-        phi[r] = d.hi - b0[r];
+      for (int r = 0; r < R; r++) {
+        plo[r] = 0; phi[r] = 0;
+        if (live[r]) {
+          const cs_val d = f[lane + r * CS_WAVE];
+          plo[r] = d.lo; phi[r] = d.hi;
+        }
+      }
+    }
+    if (!resumed)
+#endif
+    { /* a fresh instance: its root row */
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        plo[r] = 0; phi[r] = 0;
+        if (live[r]) {
+          const cs_val d = io.roots[rrow + lane + r * CS_WAVE];
+          bad_l = bad_l || d.lo > d.hi || d.lo < b0[r] || d.hi > h0[r];
+          plo[r] = d.lo - b0[r];
+          phi[r] = d.hi - b0[r];
+        }
       }
     }
     int status = 0 /* CSGPU_MANY_DONE */, root_props = 0;
     long long nodes = 0, cuts = 0, sols = 0, props = 0; /* scalars */
     int acc_props = 0;                                  /* per lane, added to props every 64 nodes */
+#if CS_DIVE_CK
+    long long nodes0 = 0; /* the nodes of earlier launches: the budget counts those of this one */
+    if (resumed) {        /* the counters go on from the instance's record */
+      const cs_dive_result *was = io.results + inst;
+      root_props = __builtin_amdgcn_readfirstlane(was->root_props);
+      nodes0 = cs_dive_uniform(was->nodes);
+      cuts = cs_dive_uniform(was->cuts);
+      props = cs_dive_uniform(was->props);
+      sols = cs_dive_uniform(was->solutions);
+      nodes = nodes0;
+    }
+#if CS_DIVE_UPTO
+    /* a resumed instance that holds its k solutions already (a smaller k than the slice before): DONE before it tries a
+     * node, nothing of it is written but this; unsigned, so that a negative count in the caller's record ends here too */
+    if (resumed && (unsigned long long)sols >= (unsigned long long)upto) {
+      if (lane == 0) {
+        io.results[inst].status = 0; /* CSGPU_MANY_DONE */
+        ck.slots[inst] = -1;
+      }
+      continue;
+    }
+#endif
+#endif
 
     if (__ballot(bad_l) != 0ull) {
       status = 2; /* CSGPU_MANY_BAD_ROOT */
     } else {
+#if CS_DIVE_CK
+      int fail_var = -1;
+      if (!resumed)
+#else
       int fail_var;
+#endif
       { /* the root node: nothing is taken for granted, every valued variable pushes */
         u64 pushed[R], push[R], dl[R], dh[R], val[R];
         int shaved = 0;
@@ -159,9 +231,23 @@
         u64 pval[R];
 #pragma unroll
         for (int j = 0; j < NW; j++) aw[j] = 0u;
-        CS_DIVE_ASETS();
-        CS_DIVE_ASELECT();
-        CS_DIVE_AENTER();
+#if CS_DIVE_CK
+        if (resumed) { /* "go on at value nv of variable bv on the node plo / phi": the pop path's steps */
+          depth = depth0;
+          cs_val meta = cs_interval(0, 0);
+          if (lane == 0) meta = stack[(size_t)depth0 * fstride + n];
+          bv = __builtin_amdgcn_readfirstlane(meta.lo);
+          const int nv = __builtin_amdgcn_readfirstlane(meta.hi);
+          CS_DIVE_ASETS();
+          CS_DIVE_AENTER();
+          cs_dive_bits_from<NW>(aw, nv);
+        } else
+#endif
+        {
+          CS_DIVE_ASETS();
+          CS_DIVE_ASELECT();
+          CS_DIVE_AENTER();
+        }
         for (;;) {
           depth = __builtin_amdgcn_readfirstlane(depth);
           bv = __builtin_amdgcn_readfirstlane(bv);
@@ -190,10 +276,54 @@
             cs_dive_bits_from<NW>(aw, next);
           }
           if (finished) break;
+#if CS_DIVE_CK
+          if (nodes - nodes0 >= io.max_nodes) {
+            status = 1; /* CSGPU_MANY_LIMIT */
+            { /* leave a checkpoint, if the pool has a slot */
+              if (!resumed) {
+                unsigned long long drawn = 0ull;
+                if (lane == 0) drawn = __hip_atomic_fetch_add(ck.next, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned dlo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)drawn);
+                const unsigned dhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(drawn >> 32));
+                slot = dhi == 0u && dlo < (unsigned)ck.capacity ? (int)dlo : -1;
+              }
+              if (depth >= n) slot = -1; /* cannot happen (at most n - 1 frames in use): never write past the slot */
+              if (slot >= 0) {
+                cs_val *base = ck.pool + (size_t)slot * (fstride * fstride);
+                cs_val *frames = base + fstride;
+                if (!resumed) { /* the frames in use, every lane the entries it wrote */
+                  for (int d = 0; d < depth; d++) {
+                    const cs_val *src = stack + (size_t)d * fstride;
+                    cs_val *dst = frames + (size_t)d * fstride;
+#pragma unroll
+                    for (int r = 0; r < R; r++)
+                      if (live[r]) dst[lane + r * CS_WAVE] = src[lane + r * CS_WAVE];
+                    if (lane == 0) dst[n] = src[n];
+                  }
+                }
+                unsigned rest[NW]; /* aw is not empty here: its lowest bit is the value the walk would try next */
+#pragma unroll
+                for (int j = 0; j < NW; j++) rest[j] = aw[j];
+                const int nv = cs_dive_take_lowest<NW>(rest);
+                cs_val *f = frames + (size_t)depth * fstride;
+#pragma unroll
+                for (int r = 0; r < R; r++)
+                  if (live[r]) f[lane + r * CS_WAVE] = cs_interval(plo[r], phi[r]);
+                if (lane == 0) {
+                  f[n] = cs_interval(bv, nv);
+                  base[0] = cs_interval(depth, CS_DIVE_CK_MAGIC_ALLOWED);
+                }
+              }
+              kept = slot;
+            }
+            break;
+          }
+#else
           if (nodes >= io.max_nodes) {
             status = 1; /* CSGPU_MANY_LIMIT */
             break;
           }
+#endif
           const int value = cs_dive_take_lowest<NW>(aw); /* relative to the root lower bound, as plo / phi are */
           const bool last = !cs_dive_any_bits<NW>(aw);
           int rlo[R], rhi[R];
@@ -273,6 +403,9 @@
       res.status = status; res.root_props = root_props;
       res.nodes = nodes; res.cuts = cuts; res.props = props; res.solutions = sols;
       io.results[inst] = res;
+#if CS_DIVE_CK
+      ck.slots[inst] = kept;
+#endif
     }
   }
 #undef CS_DIVE_ASETS

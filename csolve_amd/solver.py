@@ -291,11 +291,17 @@ class Model:
         resume_many() continues.  Without it the call is csgpu_solve_many.
         branching: "width" (the engine's rule: the smallest interval, every value of it) or "allowed" (the open variable
         with the fewest values that no valued neighbour forbids, and only those values: csgpu_solve_many_allowed, another
-        tree with the same solutions; no checkpoints; the model must pass qualifies_many_allowed())."""
+        tree with the same solutions; the model must pass qualifies_many_allowed(); its checkpoints go through
+        solve_many_allowed())."""
+        return self._solve_many(self._many_branching(branching, checkpoints), roots, objective, max_nodes, solutions, stream,
+                                checkpoints)
+
+    def _solve_many(self, allowed, roots, objective, max_nodes, solutions, stream, checkpoints) -> dict:
+        """solve_many / solve_many_allowed: the plain or the checkpointed call of either walk"""
         L = load_library()
         n = self.n_vars
-        allowed = self._many_branching(branching, checkpoints)
         plain = L.csgpu_solve_many_allowed if allowed else L.csgpu_solve_many
+        pooled = L.csgpu_solve_many_allowed_checkpointed if allowed else L.csgpu_solve_many_checkpointed
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         opt = ManyOptions(obj, 0, int(max_nodes))
         roots, K = self._many_roots(roots, False, lambda ptr, count: check(
@@ -309,10 +315,29 @@ class Model:
                         first.data_ptr() if solutions and K else None, _stream_ptr(stream)))
             return self._many_answer(buf, K, first)
         slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
-        check(L.csgpu_solve_many_checkpointed(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
-                                              buf.data_ptr(), first.data_ptr() if solutions and K else None,
-                                              checkpoints._h, slots.data_ptr(), _stream_ptr(stream)))
-        return self._many_answer(buf, K, first, slots, checkpoints)
+        check(pooled(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                     first.data_ptr() if solutions and K else None, checkpoints._h, slots.data_ptr(), _stream_ptr(stream)))
+        out = self._many_answer(buf, K, first, slots, checkpoints)
+        if allowed:
+            out["_allowed"] = True  # resume_many goes on through the allowed walk's resume calls
+        return out
+
+    def solve_many_allowed(self, roots, objective="ANY", *, max_nodes, max_solutions=None, checkpoints=None, solutions=True,
+                           stream=None) -> dict:
+        """the allowed-values walk with everything it has: without a pool solve_many(..., branching="allowed"), or with
+        max_solutions=k solve_many_upto(..., branching="allowed") (`objective` does not apply); with
+        checkpoints=many_checkpoints(cap) the checkpointed call of either (csgpu_solve_many_allowed_checkpointed /
+        _allowed_upto_checkpointed): an instance that stops at max_nodes keeps its walk in a slot, the answer has `slot`
+        [K] and is what resume_many() continues -- through the allowed walk's own resume calls.  A slot of this walk is
+        no checkpoint of the width walk, and the other way round (BAD_SLOT)."""
+        if max_solutions is not None:
+            out = self._solve_many_upto("csgpu_solve_many_allowed_upto", self.qualifies_many_allowed(), roots, max_solutions,
+                                        max_nodes, solutions, stream, checkpoints)
+        else:
+            out = self._solve_many(True, roots, objective, max_nodes, solutions, stream, checkpoints)
+        if checkpoints is not None:
+            out["_allowed"] = True
+        return out
 
     @staticmethod
     def _many_answer(buf, K, first, slots=None, checkpoints=None) -> dict:
@@ -850,17 +875,19 @@ class Model:
         answer's; an instance that already holds that many ends DONE untouched; with another k the rows are laid out
         anew for the call ([K, max(k), n_vars] stays or grows)."""
         assert "_checkpoints" in result, "an answer of solve_many(..., checkpoints=pool)"
+        allowed = bool(result.get("_allowed"))  # an answer of solve_many_allowed: the allowed walk's resume calls
         if "_upto" in result:
-            return self._resume_many_upto(result, int(max_nodes), max_solutions, stream)
+            return self._resume_many_upto(result, int(max_nodes), max_solutions, stream,
+                                          "csgpu_solve_many_allowed_upto_resume" if allowed else "csgpu_solve_many_upto_resume")
         assert max_solutions is None, "max_solutions continues an answer of solve_many_upto"
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         opt = ManyOptions(obj, 0, int(max_nodes))
         first = result.get("first")
         K = result["status"].shape[0]
-        check(load_library().csgpu_solve_many_resume(self._h, K, C.byref(opt), result["_records"].data_ptr(),
-                                                     first.data_ptr() if first is not None and K else None,
-                                                     result["_checkpoints"]._h, result["_slots"].data_ptr(),
-                                                     _stream_ptr(stream)))
+        L = load_library()
+        entry = L.csgpu_solve_many_allowed_resume if allowed else L.csgpu_solve_many_resume
+        check(entry(self._h, K, C.byref(opt), result["_records"].data_ptr(), first.data_ptr() if first is not None and K else None,
+                    result["_checkpoints"]._h, result["_slots"].data_ptr(), _stream_ptr(stream)))
         return result
 
     def _resume_many_upto(self, result: dict, max_nodes: int, max_solutions, stream,
@@ -918,7 +945,7 @@ class Model:
         return out[alive & ~complete].contiguous(), out[alive & complete].contiguous()
 
     def solve_many_sliced(self, roots, objective="ANY", *, budgets, finish="resume", solutions=True, pool_capacity=1 << 18,
-                          max_children=1 << 14, max_solutions=None) -> dict:
+                          max_children=1 << 14, max_solutions=None, branching="width") -> dict:
         """solve_many in slices: a checkpointed call with budgets[0], then a resume with each following budget while
         an instance is at LIMIT.  finish="resume": that is all (instances still at LIMIT stay so, with their slots).
         finish="search": after the last budget every instance still at LIMIT hands its open subtrees to a Search of
@@ -930,8 +957,12 @@ class Model:
         -> the dict of solve_many plus `slot` and `sliced`: {"slices": calls made, "searched": instances finished by
         a Search}
         max_solutions=k: the slices are solve_many_upto calls (`objective` does not apply, the answer has `rows`), with
-        finish="resume" only."""
+        finish="resume" only.
+        branching="allowed": the slices are solve_many_allowed calls.  finish="search" hands the engine [next, hi] of every
+        frame, a cover of the allowed walk's open subtrees (the engine cuts the forbidden values itself): `solutions` is
+        the walk's, the added counters are the engine's."""
         assert finish in ("resume", "search") and len(budgets) >= 1
+        allowed = self._many_branching(branching, None)
         if max_solutions is not None:
             if finish == "search":
                 raise ValueError("finish=\"search\" with max_solutions: an engine search cannot stop at a k-th solution "
@@ -939,6 +970,9 @@ class Model:
             obj, more = None, {}  # resume_many takes the k from the answer
 
             def first_slice(pool):
+                if allowed:
+                    return self.solve_many_allowed(roots, max_nodes=budgets[0], max_solutions=max_solutions, solutions=solutions,
+                                                   checkpoints=pool)
                 return self.solve_many_upto(roots, max_solutions, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
         else:
             obj, more = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective), {"objective": objective}
@@ -946,6 +980,8 @@ class Model:
                 raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
 
             def first_slice(pool):
+                if allowed:
+                    return self.solve_many_allowed(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
                 return self.solve_many(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
         pool = self.many_checkpoints(max(roots.shape[0], 1))
         out = first_slice(pool)
@@ -993,22 +1029,29 @@ class Model:
         out["status"][i] = 0
         out["slot"][i] = -1
 
-    def checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None) -> torch.Tensor:
+    def checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None,
+                            branching="width") -> torch.Tensor:
         """the untried children of the checkpoints in `slots` (int32 [S] on the device) -> int64 [S]: 0 for a slot < 0,
-        -1 for a slot that is refused (csgpu_many_checkpoint_children)"""
+        -1 for a slot that is refused (csgpu_many_checkpoint_children).  branching="allowed": the slots of the allowed
+        walk, whose children are the untried values no valued variable forbids (csgpu_many_allowed_checkpoint_children);
+        each call refuses the other walk's slots."""
         assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+        L = load_library()
+        entry = L.csgpu_many_allowed_checkpoint_children if self._many_branching(branching, None) else L.csgpu_many_checkpoint_children
         S = slots.shape[0]
         children = torch.empty((max(S, 1),), dtype=torch.int64, device=slots.device)
-        check(load_library().csgpu_many_checkpoint_children(checkpoints._h, slots.data_ptr(), S, children.data_ptr(),
-                                                            _stream_ptr(stream)))
+        check(entry(checkpoints._h, slots.data_ptr(), S, children.data_ptr(), _stream_ptr(stream)))
         return children[:S]
 
     def checkpoint_fanout(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, offsets: torch.Tensor, total: int,
-                          rows: torch.Tensor = None, owner: torch.Tensor = None, stream=None):
+                          rows: torch.Tensor = None, owner: torch.Tensor = None, stream=None, branching="width"):
         """the children of the checkpoints in `slots` as root rows, in walk order (csgpu_many_checkpoint_fanout): offsets
         int64 [S + 1], the exclusive prefix sum of checkpoint_children() on the device.  -> (rows int32 [total, n_vars, 2],
         owner int32 [total]: the index into `slots` a row came from); given buffers are written in place, and an instance
-        whose count disagrees with its offsets writes nothing"""
+        whose count disagrees with its offsets writes nothing.  branching="allowed": as checkpoint_children
+        (csgpu_many_allowed_checkpoint_fanout)"""
+        L = load_library()
+        entry = L.csgpu_many_allowed_checkpoint_fanout if self._many_branching(branching, None) else L.csgpu_many_checkpoint_fanout
         n, S, total = self.n_vars, slots.shape[0], int(total)
         assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
         assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and tuple(offsets.shape) == (S + 1,)
@@ -1018,8 +1061,8 @@ class Model:
             owner = torch.empty((max(total, 1),), dtype=torch.int32, device=slots.device)
         assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= total * n * 2
         assert owner.dtype == torch.int32 and owner.is_contiguous() and owner.numel() >= total
-        check(load_library().csgpu_many_checkpoint_fanout(checkpoints._h, slots.data_ptr(), S, offsets.data_ptr(),
-                                                          rows.data_ptr(), owner.data_ptr(), total, _stream_ptr(stream)))
+        check(entry(checkpoints._h, slots.data_ptr(), S, offsets.data_ptr(), rows.data_ptr(), owner.data_ptr(), total,
+                    _stream_ptr(stream)))
         return rows[:total], owner[:total]
 
     def fold_many(self, sub: dict, owner: torch.Tensor, result: dict, stream=None) -> dict:
@@ -1033,7 +1076,7 @@ class Model:
         return result
 
     def solve_many_spread(self, roots, *, budgets=(256, 4096), max_rounds=64, max_rows=1 << 18, solutions=True, stream=None,
-                          pool_bytes=1 << 30, pools=None) -> dict:
+                          pool_bytes=1 << 30, pools=None, branching="width") -> dict:
         """solve_many under ALL whose stopped instances are spread over the idle waves: round 0 is a checkpointed
         solve_many with budgets[0]; every later round counts the untried children of the stopped instances
         (checkpoint_children), fans them out as root rows of their own (checkpoint_fanout) and walks those as a fresh
@@ -1048,10 +1091,19 @@ class Model:
         that times or repeats the call keeps them).  Synchronises once or twice per round (the counts of stopped
         instances and of their children).
         -> the dict of solve_many (device tensors [K]) plus `rounds`, `sub_instances` and `round_rows` (the rows fanned
-        out for every round after round 0; 0 for a round that went on in place)"""
+        out for every round after round 0; 0 for a round that went on in place)
+        branching="allowed": the same driver on the allowed-values walk -- every batch a solve_many_allowed, the children
+        the untried ALLOWED values (csgpu_many_allowed_checkpoint_children / _fanout), the same fold; the answer is the
+        record of solve_many(..., "ALL", branching="allowed")."""
         family = dict(solve=self.solve_many, resume=lambda batch, **kw: self.resume_many(batch, objective="ALL", **kw),
                       children=self.checkpoint_children, fanout=self.checkpoint_fanout, make_pool=self.many_checkpoints,
                       slot_bytes=self.checkpoint_bytes(), qualifies=True)
+        if self._many_branching(branching, None):
+            family.update(
+                solve=self.solve_many_allowed, qualifies=self.qualifies_many_allowed(),
+                children=lambda pool, slots, stream=None: self.checkpoint_children(pool, slots, stream, branching="allowed"),
+                fanout=lambda pool, slots, offsets, total, stream=None: self.checkpoint_fanout(
+                    pool, slots, offsets, total, stream=stream, branching="allowed"))
         return self._spread_call(family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
 
     def _spread_call(self, family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools) -> dict:
@@ -1402,6 +1454,14 @@ class Model:
     def many_allowed_kernel(self):
         """the cs_dive_allowed instantiation solve_many(..., branching="allowed") launches"""
         return self._many_symbol("csgpu_internal_many_allowed_symbol")
+
+    def many_allowed_resume_kernel(self):
+        """the cs_dive_allowed_resume instantiation solve_many_allowed(..., checkpoints=pool) and its resume launch"""
+        return self._many_symbol("csgpu_internal_many_allowed_resume_symbol")
+
+    def many_allowed_upto_resume_kernel(self):
+        """the cs_dive_allowed_upto_resume instantiation of the up-to-k calls with a pool"""
+        return self._many_symbol("csgpu_internal_many_allowed_upto_resume_symbol")
 
     def many_allowed_upto_kernel(self):
         """the cs_dive_allowed_upto instantiation solve_many_upto(..., branching="allowed") launches"""

@@ -414,8 +414,8 @@ int csgpu_solve_many_upto_resume(const csgpu_model *m, int64_t count, const csgp
  * call field for field, an instance with fewer than k solutions ends as under ALL).  Which models qualify
  * (csgpu_model_qualifies_many_allowed, usable after csgpu_model_build_tables alone): kernel 7's rule, and no root domain
  * of more than 128 values, which is what the kernels' allowed sets hold.
- * Not on this walk (use the width rule): checkpoints, resume and slices, restarts, the solution stream, the spread of
- * stopped instances, and the clause family; the csgpu_search strategies are not touched either.
+ * Not on this walk (use the width rule): restarts, the solution stream, and the clause family; the csgpu_search
+ * strategies are not touched either.  Checkpoints, resume and the spread of stopped instances: the calls further down.
  * "One call in flight per model" covers these calls (same workspace, same ticket counters, left at zero); calls of the
  * whole family may be queued behind each other on one stream.
  * Errors before any HIP call are those of csgpu_solve_many (csgpu_solve_many_upto for the second call), in their order;
@@ -427,6 +427,57 @@ int csgpu_solve_many_allowed(const csgpu_model *m, const csgpu_val *d_roots, int
 int csgpu_solve_many_allowed_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                   const csgpu_many_upto_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
                                   void *stream);
+
+/* ---- the allowed walk in slices, and its stopped ALL walks spread over the next launch ----
+ * csgpu_solve_many_allowed_checkpointed / _resume and csgpu_solve_many_allowed_upto_checkpointed / _upto_resume are to the
+ * two calls above what csgpu_solve_many_checkpointed / _resume and csgpu_solve_many_upto_checkpointed / _upto_resume are to
+ * csgpu_solve_many / _upto.  The pool is csgpu_many_checkpoints_create's; slot bytes, reset and free are unchanged, and a
+ * frame is the walk's own {row, variable, next}: the current node is kept with next = the allowed value the walk would try
+ * next, and a resume rebuilds allowed(variable) on it and drops the values below next, as coming back to a frame does.
+ * d_slots: as in the width calls, word for word -- [count], written by the checkpointed call and read by the resume;
+ * -1 = no checkpoint (DONE, BAD_ROOT, or LIMIT while the pool was empty, which then ends exactly as the plain allowed
+ * call); a resumed instance goes back into the same slot.  max_nodes is the budget of THIS call; counters accumulate; the
+ * first solution, or under up-to-k row index `solutions`, goes on where it was, so a walk in slices is, field for field and
+ * row for row, the plain allowed call with the summed budget.  A resumed up-to-k instance whose record already holds
+ * max_solutions solutions ends DONE before it tries a node.
+ * A slot written by these calls carries a magic of its own: the two walks are different trees with different counters.
+ * csgpu_solve_many_resume / _upto_resume on an allowed slot, and the allowed resumes on a width slot, a free slot or a
+ * slot >= capacity, give CSGPU_MANY_BAD_SLOT with nothing else of the instance touched; csgpu_many_checkpoint_children
+ * counts -1 for an allowed slot and csgpu_many_checkpoint_fanout writes nothing for it.
+ * csgpu_many_checkpoint_states accepts the slots of both walks: [next, hi] of every frame is a correct cover of an allowed
+ * walk's open subtrees for a csgpu_search, which cuts the forbidden values itself.  The solutions are the walk's; the
+ * counters of such a finish are the engine's, not this walk's.
+ * csgpu_many_allowed_checkpoint_children / _fanout are csgpu_many_checkpoint_children / _fanout for allowed slots: the
+ * untried children of frame d are the values c in [next, hi(variable)] of the frame's row that no valued variable of that
+ * row forbids, ascending, frames from `depth` down to 0; a child row is the frame's row in absolute bounds with variable =
+ * [c, c], d_owner[row] = i.  -1 for a refused slot (the checks of the width count, with the allowed magic), nothing
+ * written unless d_offsets[i + 1] - d_offsets[i] is the count and the rows lie inside [0, total).  The sub-instances are
+ * walked by csgpu_solve_many_allowed_checkpointed under ALL and folded by csgpu_many_fold, unchanged.  The split is exact
+ * for the reason it is exact on the width walk: the allowed sets are a function of the node's row and the model's table
+ * only; the fixpoint of a != network is unique, so the root node of a child row is the child's fixpoint and the sub-walk
+ * is the subtree; hence nodes += 1 + sub.nodes, cuts += sub.cuts + (inconsistent as a root), props += sub.root_props +
+ * sub.props, solutions += sub.solutions.  A forbidden value is no child row: the walk does not count it either.
+ * Errors before any HIP call, in order, are those of the corresponding width entry; in addition the root domain of more
+ * than 128 values -> CSGPU_E_LIMIT of the allowed family (for the two fan-out calls after those of
+ * csgpu_many_checkpoint_children / _fanout, a clause-kind pool -> CSGPU_E_ARG included).  "One call in flight per model"
+ * covers these calls; calls of all families may be queued behind each other on one stream. */
+int csgpu_solve_many_allowed_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                          const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
+                                          csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_solve_many_allowed_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                    csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                    int32_t *d_slots, void *stream);
+int csgpu_solve_many_allowed_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                               const csgpu_many_upto_options *options, csgpu_many_result *d_results,
+                                               int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_solve_many_allowed_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
+                                         csgpu_many_result *d_results, int32_t *d_solutions, csgpu_many_checkpoints *ck,
+                                         int32_t *d_slots, void *stream);
+int csgpu_many_allowed_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                           int64_t *d_children, void *stream);
+int csgpu_many_allowed_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                         const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner, int64_t total,
+                                         void *stream);
 
 /* ---- Luby restarts with a seeded value order, for ANY: csgpu_solve_many whose deep walks are cut short ----
  * The deep instances of a batch are the heavy tail of a depth-first search with a fixed value order.  This call walks

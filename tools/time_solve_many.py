@@ -42,6 +42,11 @@ oracle walk (tests/many_walk.py).
   total, the deepest instance, ms per call (median and range of --reps) and ns per node; the ratios allowed / width; whether
   both found the same `solutions` where neither stopped at the budget; --check sampled answers of the allowed call re-checked
   against the host walk of tests/many_walk_allowed.py.  --objective: instead of the set's own.
+  --branching allowed with --sliced B1,B2,... and / or --spread B0,B1: instead of that comparison, the allowed walk in slices
+  (Model.solve_many_sliced(branching="allowed"), with --upto K its up-to-k slices) beside the one allowed call with the budget
+  --max-nodes, and the allowed spread (Model.solve_many_spread(branching="allowed")) beside the one allowed ALL call and the
+  width spread with the same budgets on the same rows: interleaved after a warm-up, medians and ranges of --reps, nodes in
+  total, rounds and rows, and whether every field equals the one allowed call's.
   sets: sudoku9 (9x9, revealed 0.35-0.45, ANY), queens12 / queens13 (two queens placed at random, ALL), sudoku16 (16x16, 0.6, ANY),
   sparse40 (a sparse != network of 40 variables, 16-bit table, three of them open: nearly every node is a solution, ALL)
 """
@@ -149,6 +154,77 @@ def both_rules(args, model, text, roots, dev, objective, budget, count):
     return rec
 
 
+def allowed_slices_and_spread(args, model, dev, objective, budget, count):
+    """--branching allowed with --sliced / --spread -> the JSON record"""
+    def timed(call):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    def measure(variants):
+        for call in variants.values():  # warm-up: code load, workspace, pools, the allocator's blocks
+            timed(call)
+            timed(call)
+        series, outs = {name: [] for name in variants}, {}
+        for _ in range(args.reps):
+            for name, call in variants.items():
+                dt, outs[name] = timed(call)
+                series[name].append(dt)
+        ms = {name: {"median": round(statistics.median(ts) * 1e3, 3), "min": round(min(ts) * 1e3, 3), "max": round(max(ts) * 1e3, 3)}
+              for name, ts in series.items()}
+        return ms, outs
+
+    def equal(a, b, fields):
+        return all(bool((a[f] == b[f]).all()) for f in fields)
+
+    fields = ("status", "root_props", "nodes", "cuts", "props", "solutions")
+    rec = {"what": "solve_many, the allowed walk in slices and spread", "set": args.set, "revealed": args.revealed, "instances": count,
+           "max_nodes": budget, "reps": args.reps, "device": torch.cuda.get_device_name(0), "commit": commit(),
+           "waves": model.many_waves(count), "kernels": {"resume": model.many_allowed_resume_kernel(),
+                                                         "upto_resume": model.many_allowed_upto_resume_kernel()}}
+    if args.spread:
+        budgets = tuple(int(b) for b in args.spread.split(","))
+        slot = max(model.checkpoint_bytes(), 1)
+        pools = {rule: tuple(model.many_checkpoints(max(1, min(max(count, args.spread_rows), (1 << 30) // slot))) for _ in range(2))
+                 for rule in ("allowed", "width")}
+        ms, outs = measure({
+            "one_allowed_call": lambda: model.solve_many(dev, "ALL", max_nodes=budget, branching="allowed"),
+            "allowed_spread": lambda: model.solve_many_spread(dev, budgets=budgets, max_rows=args.spread_rows, pools=pools["allowed"],
+                                                              branching="allowed"),
+            "one_width_call": lambda: model.solve_many(dev, "ALL", max_nodes=budget),
+            "width_spread": lambda: model.solve_many_spread(dev, budgets=budgets, max_rows=args.spread_rows, pools=pools["width"])})
+        rec["spread"] = {"budgets": list(budgets), "ms": ms,
+                         "nodes": {name: int(out["nodes"].sum()) for name, out in outs.items()},
+                         "deepest": {name: int(outs[name]["nodes"].max()) for name in ("one_allowed_call", "one_width_call")},
+                         "at_limit": {name: int((out["status"] == 1).sum()) for name, out in outs.items()},
+                         "rounds": {name: outs[name]["rounds"] for name in ("allowed_spread", "width_spread")},
+                         "round_rows": {name: outs[name]["round_rows"] for name in ("allowed_spread", "width_spread")},
+                         "allowed_spread_equals_one_allowed_call": equal(outs["allowed_spread"], outs["one_allowed_call"], fields + ("first",)),
+                         "width_spread_equals_one_width_call": equal(outs["width_spread"], outs["one_width_call"], fields + ("first",))}
+    if args.sliced:
+        budgets = tuple(int(b) for b in args.sliced.split(","))
+        if args.upto is None:
+            one = lambda: model.solve_many(dev, objective, max_nodes=budget, branching="allowed")  # noqa: E731
+            cut = lambda: model.solve_many_sliced(dev, objective, budgets=budgets, branching="allowed")  # noqa: E731
+            rows = "first"
+        else:
+            one = lambda: model.solve_many_upto(dev, args.upto, max_nodes=budget, branching="allowed")  # noqa: E731
+            cut = lambda: model.solve_many_sliced(dev, budgets=budgets, max_solutions=args.upto, branching="allowed")  # noqa: E731
+            rows = "rows"
+        ms, outs = measure({"one_allowed_call": one, "allowed_sliced": cut})
+        done = (outs["one_allowed_call"]["status"] != 1) & (outs["allowed_sliced"]["status"] != 1)
+        rec["sliced"] = {"budgets": list(budgets), "objective": objective if args.upto is None else f"up to {args.upto}", "ms": ms,
+                         "calls": outs["allowed_sliced"]["sliced"]["slices"],
+                         "nodes": {name: int(out["nodes"].sum()) for name, out in outs.items()},
+                         "deepest": int(outs["one_allowed_call"]["nodes"].max()),
+                         "at_limit": {name: int((out["status"] == 1).sum()) for name, out in outs.items()},
+                         "equal_where_both_finished": all(bool((outs["allowed_sliced"][f] == outs["one_allowed_call"][f])[done].all())
+                                                          for f in fields + (rows,))}
+    return rec
+
+
 def commit():
     try:
         return open(os.path.join(ROOT, "csolve_amd", "csrc", "build", "COMMIT")).read().strip()
@@ -182,6 +258,9 @@ def main():
     budget = args.max_nodes or budget
     model = solve_root(text)
     dev = torch.from_numpy(roots).cuda()
+    if args.branching == "allowed" and (args.sliced or args.spread):
+        print(json.dumps(allowed_slices_and_spread(args, model, dev, args.objective or objective, budget, count)))
+        return
     if args.branching == "allowed":
         print(json.dumps(both_rules(args, model, text, roots, dev, args.objective or objective, budget, count)))
         return
