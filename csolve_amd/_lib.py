@@ -63,6 +63,12 @@ class ManyUptoOptions(C.Structure):
     _fields_ = [("max_solutions", C.c_int32), ("reserved", C.c_int32), ("max_nodes", C.c_int64)]
 
 
+class ManyOrderOptions(C.Structure):
+    """csgpu_many_order_options: a variable order of the engine's five, and the width above which an interval is halved"""
+    _fields_ = [("objective", C.c_int32), ("order", C.c_int32), ("split_width", C.c_int32), ("reserved", C.c_int32),
+                ("max_nodes", C.c_int64)]
+
+
 MANY_ROTATE_FIRST = 1  # CSGPU_MANY_ROTATE_FIRST
 
 
@@ -300,6 +306,10 @@ def load_library():
     L.csgpu_many_best_key.restype = C.c_uint64
     L.csgpu_many_key_decode.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     L.csgpu_internal_many_clauses_from_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many_clauses_ordered.argtypes = [vp, vp, i64, C.POINTER(ManyOrderOptions), vp, vp, vp, vp, vp]
+    L.csgpu_many_clauses_ordered_frames.argtypes = [vp, C.c_int32]
+    L.csgpu_many_clauses_ordered_frames.restype = i64
+    L.csgpu_internal_many_clauses_order_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_many_value.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, Val, C.c_uint32, C.c_int32]
     L.csgpu_many_value.restype = C.c_int32
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -87,6 +87,7 @@ struct cs_kernel_plan {
   cs_planned walk_restart;         /* cs_walk_restart (csgpu_solve_many_clauses_restarts): the same */
   cs_planned walk_stream;          /* cs_walk_stream (csgpu_solve_many_clauses_stream): the same */
   cs_planned walk_from;            /* cs_walk_from (csgpu_solve_many_clauses_from / _from_resume): the same */
+  cs_planned walk_order;           /* cs_walk_order (csgpu_solve_many_clauses_ordered): the same */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -1072,6 +1073,17 @@ static int plan_general(csgpu_model *m) {
             occ < m->plan.walk_from.per_cu)
           m->plan.walk_from.per_cu = occ;
         if (m->plan.walk_from.per_cu < 1) m->plan.walk_from.per_cu = 1;
+      }
+      { /* cs_walk_order: the same slices, its own registers */
+#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_order<CPL, true> : (const void *)cs_walk_order<CPL, false>)
+        const void *fn_ord = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
+#undef CS_PICKW
+        if ((rc = plan_kernel(&m->plan.walk_order, fn_ord, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_ord, CS_BLOCK, m->plan.walk_order.lds) == hipSuccess && occ >= 1 &&
+            occ < m->plan.walk_order.per_cu)
+          m->plan.walk_order.per_cu = occ;
+        if (m->plan.walk_order.per_cu < 1) m->plan.walk_order.per_cu = 1;
       }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
@@ -2251,6 +2263,9 @@ extern "C" int csgpu_internal_many_clauses_stream_symbol(const csgpu_model *m, c
 extern "C" int csgpu_internal_many_clauses_from_symbol(const csgpu_model *m, char *buf, size_t len) {
   return many_clauses_symbol(m, m != NULL ? &m->plan.walk_from : NULL, "cs_walk_from", buf, len);
 }
+extern "C" int csgpu_internal_many_clauses_order_symbol(const csgpu_model *m, char *buf, size_t len) {
+  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_order : NULL, "cs_walk_order", buf, len);
+}
 
 /* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
  * whose `frames` frames each fit MANY_CLAUSES_STACK_MAX (one workgroup's always do: n is at most 5118 where four slices
@@ -2271,6 +2286,32 @@ extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64
   return many_clauses_waves(m, &m->plan.walk, count, m->host->n_vars);
 }
 
+/* The frames a wave of cs_walk_order needs, from the root domains alone: n + sum of h(v), h(v) the smallest h for which
+ * the root width of v, halved h times with ceiling, is at most split_width.  A pushed frame is a parent with children
+ * left: one that enumerates has valued a variable in the child it waits for (at most n - 1 of those along a path, and the
+ * current node's frame), one that halves waits for its second half while its first, of at most ceil(width / 2) values,
+ * is walked -- at most h(v) of those per variable, since rows lie inside the root domains and intervals only shrink. */
+static int64_t many_clauses_ordered_frames(const csgpu_model *m, int32_t split_width) {
+  const int64_t split = split_width == 0 ? 256 : (int64_t)split_width;
+  int64_t frames = m->host->n_vars;
+  for (int32_t v = 0; v < m->host->n_vars; v++) {
+    int64_t w = (int64_t)m->host->dom[v].hi - (int64_t)m->host->dom[v].lo + 1;
+    for (; w > split; w = (w + 1) >> 1) frames++;
+  }
+  return frames;
+}
+
+extern "C" int64_t csgpu_many_clauses_ordered_frames(const csgpu_model *m, int32_t split_width) {
+  if (!csgpu_model_qualifies_many_clauses(m) || split_width < 0) return 0;
+  return many_clauses_ordered_frames(m, split_width);
+}
+
+/* the ordered entry's own arguments: its options in place of the other three, and the halving counts */
+struct many_clauses_ord {
+  const csgpu_many_order_options *options;
+  int64_t *d_halvings;
+};
+
 /* the restart entry's own arguments: its options in place of the other two, the seeds and the restart counts */
 struct many_clauses_rs {
   const csgpu_many_restart_options *options;
@@ -2286,18 +2327,21 @@ struct many_clauses_rs {
  * The stream entry brings `out` (else NULL), is pooled and not `resume` -- d_slots says per instance whether it starts or
  * goes on, so the workspace is a fresh call's: the ALL walk by cs_walk_stream, its rows in *out.  The two start entries
  * bring `from` (else 0): the MIN / MAX walk by cs_walk_from, pooled or not like an up-to-k entry, with d_start unless it
- * is the resume. */
+ * is the resume.  The ordered entry brings `ord` (else NULL) and none of the three options: any objective by cs_walk_order,
+ * plain, with the frames of many_clauses_ordered_frames per wave. */
 static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
                              const csgpu_many_upto_options *upto_options, const many_clauses_rs *rs, csgpu_many_result *d_results,
                              int32_t *d_solutions, int32_t *d_best, int pooled, csgpu_many_checkpoints *ck, int32_t *d_slots,
                              int resume, int streamed, const csgpu_many_stream *out, int from, const csgpu_many_start *d_start,
-                             void *stream) {
+                             void *stream, const many_clauses_ord *ord = NULL) {
   const csgpu_many_restart_options *rs_options = rs != NULL ? rs->options : NULL;
+  const csgpu_many_order_options *ord_options = ord != NULL ? ord->options : NULL;
   const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL ||
-                       (options == NULL && upto_options == NULL && rs_options == NULL) ||
+                       (options == NULL && upto_options == NULL && rs_options == NULL && ord_options == NULL) ||
                        (streamed && (ck == NULL || d_slots == NULL || out == NULL));
   const int64_t max_nodes = null_arg ? 0 : (rs_options != NULL ? rs_options->max_nodes
-                                            : (upto_options != NULL ? upto_options->max_nodes : options->max_nodes));
+                                            : (upto_options != NULL ? upto_options->max_nodes
+                                               : (ord_options != NULL ? ord_options->max_nodes : options->max_nodes)));
   int rc;
   if ((rc = many_check_head(null_arg, count, max_nodes, pooled ? "slice" : "instance"))) return rc;
   if (upto_options != NULL && upto_options->max_solutions < 1)
@@ -2305,7 +2349,8 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   if (rs_options != NULL && rs_options->restart_base < 0) return set_err(CSGPU_E_ARG, "restart_base must not be negative (0: no restarts)");
   if (rs_options != NULL && (rs_options->flags & ~CSGPU_MANY_ROTATE_FIRST) != 0)
     return set_err(CSGPU_E_ARG, "unknown flags 0x%x", (unsigned)rs_options->flags);
-  const int objective = rs_options != NULL ? CS_OBJ_ANY : (upto_options != NULL ? CS_OBJ_ALL : options->objective);
+  const int objective = rs_options != NULL ? CS_OBJ_ANY : (upto_options != NULL ? CS_OBJ_ALL
+                                                           : (ord_options != NULL ? ord_options->objective : options->objective));
   if (streamed) { /* before the model is looked at: ALL only, and a stream that can take a row */
     if (objective != CS_OBJ_ALL)
       return set_err(CSGPU_E_ARG, "csgpu_solve_many_clauses_stream walks under ALL (objective 1), not objective %d", objective);
@@ -2340,6 +2385,13 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
     pooled = ck != NULL;
     if (resume && !pooled) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
   }
+  if (ord_options != NULL) { /* after csgpu_solve_many_clauses's own errors, before any device call */
+    if (ord_options->order < 0 || ord_options->order > 4)
+      return set_err(CSGPU_E_ARG, "no variable order %d (0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value)",
+                     (int)ord_options->order);
+    if (ord_options->split_width < 0) return set_err(CSGPU_E_ARG, "split_width must not be negative (0: the engine's 256)");
+    if (ord_options->reserved != 0) return set_err(CSGPU_E_ARG, "reserved must be 0");
+  }
   if (pooled) {
     if (ck == NULL || d_slots == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
     if (ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
@@ -2350,9 +2402,12 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   const cs_planned *k = rs_options != NULL ? &m->plan.walk_restart
                         : (upto_options != NULL ? &m->plan.walk_upto
                            : (streamed ? &m->plan.walk_stream
-                              : (from ? &m->plan.walk_from : (pooled ? &m->plan.walk_ck : &m->plan.walk))));
+                              : (from ? &m->plan.walk_from
+                                 : (ord_options != NULL ? &m->plan.walk_order : (pooled ? &m->plan.walk_ck : &m->plan.walk)))));
   const int n = m->host->n_vars;
-  const int frames = rs_options != NULL ? n + 1 : n; /* at most n - 1 pushed frames and the current node's; cs_walk_restart: and the root node's */
+  /* at most n - 1 pushed frames and the current node's; cs_walk_restart: and the root node's; cs_walk_order: and the
+   * halving parents' (at most 33 n, n <= 5118: an int) */
+  const int frames = rs_options != NULL ? n + 1 : (ord_options != NULL ? (int)many_clauses_ordered_frames(m, ord_options->split_width) : n);
   const int64_t waves = many_clauses_waves(m, k, count, frames);
   if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
   cs_walk_io io;
@@ -2388,11 +2443,16 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
   ok.owner = streamed ? out->d_owner : NULL;
   ok.count = streamed ? (unsigned long long *)out->d_count : NULL;
   ok.capacity = streamed ? (long long)out->capacity : 0;
+  cs_walk_ord wo;
+  wo.order = ord_options != NULL ? ord_options->order : 1;
+  wo.split_width = ord_options != NULL && ord_options->split_width != 0 ? ord_options->split_width : 256;
+  wo.halvings = ord != NULL ? (long long *)ord->d_halvings : NULL;
   cs_tables tab = m->tab;
   /* cs_walk_clauses takes the first two, cs_walk_resume the first three; cs_walk_restart: the tables, io and `dr`;
-   * cs_walk_stream: the first three and `ok`; cs_walk_from: the first three and the starts */
+   * cs_walk_stream: the first three and `ok`; cs_walk_from: the first three and the starts; cs_walk_order: the tables, io
+   * and `wo` */
   const cs_walk_start *starts = (const cs_walk_start *)d_start;
-  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (void *)&wk,
+  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (ord_options != NULL ? (void *)&wo : (void *)&wk),
                    streamed ? (void *)&ok : (from ? (void *)&starts : (void *)&upto) };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
   return CSGPU_OK;
@@ -2597,6 +2657,18 @@ extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csg
   rs.d_seeds = d_seeds;
   rs.d_restarts = d_restarts;
   return many_clauses_call(m, d_roots, count, NULL, NULL, &rs, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, 0, NULL, stream);
+}
+
+/* ---- the engine's five variable orders and interval halving for the instances of a clause model (cs_walk_order) ---- */
+
+extern "C" int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                const csgpu_many_order_options *options, csgpu_many_result *d_results,
+                                                int32_t *d_solutions, int32_t *d_best, int64_t *d_halvings, void *stream) {
+  many_clauses_ord ord;
+  ord.options = options;
+  ord.d_halvings = d_halvings;
+  return many_clauses_call(m, d_roots, count, NULL, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, 0, NULL, 0, NULL,
+                           stream, &ord);
 }
 
 /* ---- every solution of every instance of a clause model under ALL, through one bounded stream (cs_walk_stream) ---- */

@@ -86,7 +86,15 @@
  * -- and only a solution of the instance's own is reported (io.best iff solutions > 0; the row is written at solutions
  * only anyway).  The header's code is the objective's, so a checkpoint of this kernel and one of cs_walk_resume continue
  * under either.  ck.capacity == 0: no pool, as cs_walk_upto.  It is what lets a stopped MIN / MAX walk be spread: see the
- * fan-out below. */
+ * fan-out below.
+ *
+ * Variable orders and halving (cs_walk_order, csgpu_solve_many_clauses_ordered): the same loop a seventh time,
+ * CS_WALK_ORDER 1, without checkpoints, pools, the stream or restarts.  The two wave minima run over cs_order_key(order, d)
+ * (cs_arith.h, the engine's key) in place of the width, and a node whose branching variable has more than split_width
+ * values makes two children, [lo, mid] and [mid + 1, hi], in place of one per value.  Kind and mid are scalars read from
+ * the node as it was entered; a frame's {variable, next} keeps its 8 bytes, next = mid + 1 for a halving node, whose kind
+ * is read back from the frame's row.  A pushed halving parent values no variable, so the frames per wave are the host's
+ * bound n + sum of h(v), not n. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
 
@@ -119,7 +127,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
+#define CS_WALK_ORDER 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
@@ -150,7 +160,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_resume(cs_tables T, cs_walk_
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
+#define CS_WALK_ORDER 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
@@ -166,7 +178,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_upto(cs_tables T, cs_walk_io
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
+#define CS_WALK_ORDER 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
@@ -183,7 +197,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_restart(cs_tables T, cs_walk
 #define CS_WALK_RESTART 1
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
+#define CS_WALK_ORDER 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
@@ -201,7 +217,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_stream(cs_tables T, cs_walk_
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 1
 #define CS_WALK_FROM 0
+#define CS_WALK_ORDER 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART
@@ -224,7 +242,37 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_from(cs_tables T, cs_walk_io
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 1
+#define CS_WALK_ORDER 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
+#undef CS_WALK_FROM
+#undef CS_WALK_STREAM
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+/* what cs_walk_order takes beside cs_walk_clauses's arguments (csgpu_many_order_options) */
+struct cs_walk_ord {
+  int order;           /* cs_order_key's: 0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value */
+  int split_width;     /* >= 1: a branching variable of more values is halved, not enumerated */
+  long long *halvings; /* [count] or NULL: parents split in two */
+};
+
+/* cs_walk_clauses's walk under one of the engine's five variable orders, with intervals of more than split_width values
+ * halved (csgpu_solve_many_clauses_ordered; the walk is defined in csolve_gpu.h): the same loop a seventh time,
+ * CS_WALK_ORDER 1 and every other switch 0.  A halving parent that is pushed values no variable, so io.frames is
+ * n + sum of h(v) (csgpu_many_clauses_ordered_frames), computed on the host from the root domains */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_order(cs_tables T, cs_walk_io io, cs_walk_ord ord) {
+#define CS_WALK_CK 0
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
+#define CS_WALK_ORDER 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
 #undef CS_WALK_RESTART

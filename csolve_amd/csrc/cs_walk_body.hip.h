@@ -1,11 +1,13 @@
-/* cs_walk_body.hip.h -- the body of the six kernels of cs_walk.hip.h, which includes it inside each of them under five
- * switches (the fifth, CS_WALK_FROM, is 1 for cs_walk_from alone: cs_walk_resume's row, and `start`):
+/* cs_walk_body.hip.h -- the body of the seven kernels of cs_walk.hip.h, which includes it inside each of them under six
+ * switches (the fifth, CS_WALK_FROM, is 1 for cs_walk_from alone: cs_walk_resume's row, and `start`; the sixth,
+ * CS_WALK_ORDER, for cs_walk_order alone: cs_walk_clauses's row, and `ord`):
  *                      CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART  CS_WALK_STREAM
  *   cs_walk_clauses        0           0              0              0       csgpu_solve_many_clauses
  *   cs_walk_resume         1           0              0              0       one more argument, `ck`: the pool and the slots of the call
  *   cs_walk_upto           1           1              0              0       and `upto` (k >= 1, a scalar)
  *   cs_walk_restart        0           0              1              0       one more argument, `rs` (the walk is defined in csolve_gpu.h)
  *   cs_walk_stream         1           0              0              1       `ck` and `out`, the solution stream of the call
+ *   cs_walk_order          0           0              0              0       one more argument, `ord`: the order, split_width, the halving counts
  * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of a switch stands under its `#if`, so a kernel
  * that defines it 0 sees the text it saw before the switch was there and compiles to the same instructions.
  * CS_WALK_CK: an instance that stops at its budget leaves its frames, its current node, {bv, nv} and its incumbent in a
@@ -29,7 +31,15 @@
  * takes the objective bound before the root node's rounds, as a child's does (a bound that empties it fails in the first
  * round: DONE, no node).  io.best[inst] is written only when the instance has a solution of its own (sols > 0, the record's
  * count included when it is resumed): one that proves that nothing beats its start leaves best and its row alone.
- * ck.capacity == 0 means "no pool" as under CS_WALK_UPTO.  New per-instance state is scalars only: start_have, start_best. */
+ * ck.capacity == 0 means "no pool" as under CS_WALK_UPTO.  New per-instance state is scalars only: start_have, start_best.
+ * CS_WALK_ORDER (a sixth switch, 1 for cs_walk_order alone, every other switch 0): cs_walk_clauses's walk with one more
+ * argument `ord` -- the branching variable is the open one with the smallest cs_order_key(ord.order, d) (cs_arith.h) in
+ * place of the width in the two wave minima, and a node whose branching variable has more than ord.split_width values has
+ * two children, [lo, mid] and [mid + 1, hi], mid = (lo + hi) >> 1 in 64 bits.  Kind and mid are read from the node as it
+ * was entered (the slice when `fresh`, else its frame's row), before lane 0 writes the child and the incumbent's bound, so
+ * a popped frame makes the same children; nv is the child's lower bound in both kinds, and a frame's entry {variable,
+ * next}: the next value, or mid + 1.  io.frames is the host's bound (csgpu_many_clauses_ordered_frames).  New per-instance
+ * state is scalars only: halvings, then. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -141,6 +151,9 @@
     }
     int status = 0 /* CSGPU_MANY_DONE */, root_props = 0;
     long long nodes = 0, cuts = 0, sols = 0, props = 0; /* scalars */
+#if CS_WALK_ORDER
+    long long halvings = 0; /* parents split in two */
+#endif
     int acc_props = 0;                                  /* per lane, added to props every 64 nodes */
     int best = 0;
     bool have_best = false;
@@ -188,6 +201,9 @@
       int depth = 0, bv = 0, nv = 0;
       bool root = true, fresh = true; /* fresh: the slice holds the current node as it was entered */
       cs_val *f = wave_stack;
+#if CS_WALK_ORDER
+      int then = 0; /* what the current node tries after this child: the next value, or the second half's lower bound */
+#endif
 #if CS_WALK_STREAM
       bool refused = false; /* the child that was tried last is a solution the stream had no room for */
 #endif
@@ -278,6 +294,16 @@
           start = (unsigned)cs_many_value(rs_seed, run, bv, cs_interval(xlo, xhi), 0u, rs.flags) - (unsigned)xlo;
           last = (unsigned)nv == width - 1u;
           const int value = cs_many_rotated(xlo, width, start, (unsigned)nv);
+#elif CS_WALK_ORDER
+          /* the node as it was entered says whether it halves, and where: scalars, 64-bit width and middle */
+          const int xlo = __builtin_amdgcn_readfirstlane(dom[bv].lo), xhi = __builtin_amdgcn_readfirstlane(dom[bv].hi);
+          const bool halves = (long long)xhi - (long long)xlo + 1 > (long long)ord.split_width;
+          const int xmid = (int)(((long long)xlo + (long long)xhi) >> 1);
+          const bool first_half = halves && nv == xlo;
+          last = halves ? !first_half : nv == xhi;
+          then = halves ? xmid + 1 : (int)((unsigned)nv + 1u); /* (not used after a last child: INT32_MAX wraps, unread) */
+          const int child_hi = halves ? (first_half ? xmid : xhi) : nv;
+          if (first_half) halvings++;
 #else
           last = nv == __builtin_amdgcn_readfirstlane(dom[bv].hi);
 #endif
@@ -285,6 +311,8 @@
           if (lane == 0) {
 #if CS_WALK_RESTART
             dom[bv] = cs_interval(value, value);
+#elif CS_WALK_ORDER
+            dom[bv] = cs_interval(nv, child_hi); /* the assignment, or the half: not counted in PROPS */
 #else
             dom[bv] = cs_interval(nv, nv); /* the assignment: not counted in PROPS */
 #endif
@@ -304,7 +332,11 @@
             const int v = v0 + lane;
             const cs_val d = v < n ? dom[v] : cs_value(0);
             const bool open = d.lo != d.hi;
+#if CS_WALK_ORDER
+            const unsigned w = cs_order_key(ord.order, d); /* below 0xffffffff for every open interval */
+#else
             const unsigned w = (unsigned)d.hi - (unsigned)d.lo;
+#endif
             if (open && w < kw) { kw = w; kv = (unsigned)v; }
             open_vars += __popcll(__ballot(open));
           }
@@ -408,14 +440,18 @@
 #endif
         if (descend) {
           if (!at_root && !last) { /* the parent comes back for its next value */
+#if CS_WALK_ORDER
+            if (lane == 0) f[n] = cs_interval(bv, then);
+#else
             if (lane == 0) f[n] = cs_interval(bv, nv + 1);
+#endif
             depth++;
             f += fstride;
           }
 #if CS_WALK_RESTART
           if (depth >= io.frames - 1) { status = 1; break; } /* cannot happen (frames = n + 1); the last frame is the root node's */
 #else
-          if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames = n): never write past the slice */
+          if (depth >= io.frames) { status = 1; break; } /* cannot happen (frames = n; cs_walk_order: the host's bound): never write past the slice */
 #endif
           for (int v = lane; v < n; v += CS_WAVE) f[v] = dom[v];
           const unsigned wmin = cs_wave_min_u32(kw);
@@ -438,7 +474,11 @@
           nv = __builtin_amdgcn_readfirstlane(meta.hi);
           fresh = false;
         } else {
+#if CS_WALK_ORDER
+          nv = then;
+#else
           nv = nv + 1;
+#endif
           fresh = false;
         }
       }
@@ -456,6 +496,9 @@
 #endif
 #if CS_WALK_RESTART
       if (rs.restarts != nullptr) rs.restarts[inst] = restarts;
+#endif
+#if CS_WALK_ORDER
+      if (ord.halvings != nullptr) ord.halvings[inst] = halvings;
 #endif
 #if CS_WALK_UPTO
       if (ck.capacity > 0)

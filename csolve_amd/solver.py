@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import (MANY_ROTATE_FIRST, MANY_SLOT_FRESH, PLAN_FAMILIES, CsolveError, ManyOptions, ManyRestartOptions, ManyResult,
+from ._lib import (MANY_ROTATE_FIRST, MANY_SLOT_FRESH, PLAN_FAMILIES, CsolveError, ManyOptions, ManyOrderOptions, ManyRestartOptions, ManyResult,
                    ManyStream, ManyUptoOptions, Node, Result, SearchStats, Val, check, demangle, load_library)
 
 STATUS_FAIL = -1
@@ -599,6 +599,51 @@ class Model:
             out["_objective"], out["_best"] = obj, best
         out["best"] = best[:K]
         return out
+
+    MANY_ORDERS = {"none": 0, "smallest-domain": 1, "largest-domain": 2, "smallest-value": 3, "largest-value": 4}
+
+    def solve_many_clauses_ordered(self, roots, objective="ANY", *, max_nodes, order="smallest-domain", split_width=256,
+                                   solutions=True, stream=None) -> dict:
+        """solve_many_clauses under one of the engine's five variable orders, with wide intervals halved
+        (csgpu_solve_many_clauses_ordered): the same walk, but the branching variable is the open one the order puts
+        first -- "none", "smallest-domain", "largest-domain", "smallest-value", "largest-value", the names of
+        `csolve_gpu -o`, ties to the lowest index -- and a node whose branching variable has more than `split_width`
+        values (>= 1) has two children, [lo, mid] and [mid + 1, hi] with mid = (lo + hi) >> 1, instead of one per value.
+        A row that leaves a variable at its root width (an open `end` of a schedule) is then bisected, not enumerated.
+        roots, objective, max_nodes, solutions, stream: as solve_many_clauses.  -> the dict of solve_many_clauses and
+        `halvings` [K] int64: the parents split in two.  No checkpoints, no start incumbents."""
+        L = load_library()
+        n = self.n_vars
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        opt = ManyOrderOptions(obj, self.MANY_ORDERS[order] if isinstance(order, str) else int(order), int(split_width), 0,
+                               int(max_nodes))
+        bad = obj not in (0, 1) and (obj not in (2, 3) or self.objective != obj or self.objective_var < 0)
+        bad = bad or not 0 <= opt.order <= 4 or opt.split_width < 0
+        roots, K = self._many_roots(roots, bad, lambda ptr, count: check(
+            L.csgpu_solve_many_clauses_ordered(self._h, ptr, count, C.byref(opt), ptr, None, None, None, None)),
+            qualifies=self.qualifies_many_clauses())
+        buf = self._many_records(K, roots.device)
+        first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
+        best = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if obj in (2, 3) else None
+        halvings = torch.zeros((max(K, 1),), dtype=torch.int64, device=roots.device)
+        check(L.csgpu_solve_many_clauses_ordered(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
+                                                 buf.data_ptr(), first.data_ptr() if solutions and K else None,
+                                                 best.data_ptr() if best is not None else None, halvings.data_ptr(),
+                                                 _stream_ptr(stream)))
+        out = self._many_answer(buf, K, first)
+        if best is not None:
+            out["best"] = best[:K]
+        out["halvings"] = halvings[:K]
+        return out
+
+    def many_clauses_ordered_frames(self, split_width=256) -> int:
+        """frames per wave of a solve_many_clauses_ordered call (csgpu_many_clauses_ordered_frames): n_vars + for every
+        variable the halvings that bring its root width down to split_width; 0 if the model does not qualify.  Host only"""
+        return int(load_library().csgpu_many_clauses_ordered_frames(self._h, int(split_width)))
+
+    def many_clauses_order_kernel(self):
+        """the cs_walk_order instantiation solve_many_clauses_ordered launches, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_order_symbol")
 
     def resume_many_clauses(self, result: dict, *, max_nodes, stream=None, max_solutions=None, own_solutions=False) -> dict:
         """continue, in place, the instances of a checkpointed solve_many_clauses answer that stopped with a checkpoint

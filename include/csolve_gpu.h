@@ -924,6 +924,57 @@ int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu_val *d_roo
                                     const csgpu_many_options *options, csgpu_many_result *d_results,
                                     csgpu_many_checkpoints *ck, int32_t *d_slots, const csgpu_many_stream *out, void *stream);
 
+/* ---- the engine's five variable orders and interval halving for the instances of a clause model ----
+ * csgpu_solve_many_clauses branches on the smallest interval and tries every value of it: a variable that a row leaves
+ * at its root width of 2^31 values is enumerated until the budget runs out.  This entry walks the same walk with the two
+ * things the search engine has for that (csgpu_search_set_strategy's orders, and halving of an interval of more than 256
+ * values).  csgpu_many_result is csgpu_solve_many's.
+ *
+ * The walk is csgpu_solve_many_clauses's -- root row checks and the root node, the counters, max_nodes compared before a
+ * child is tried, a child entered at once and its parent pushed only if it has children left, ANY / ALL / MIN / MAX, the
+ * private incumbent and its bound on dom[obj] before every child's fixpoint, d_best and d_solutions -- with two changes.
+ *   Branching.  The branching variable is the open variable with the smallest csgpu_branch_key(order, 0, value, 0,
+ *               index): order 0 none, 1 smallest domain, 2 largest domain, 3 smallest value (the lowest lo), 4 largest
+ *               value (the highest hi), ties to the lowest index, over all variables including "<obj>".  The key's
+ *               domain size saturates as csgpu_branch_key's does: an interval with a bound at INT32_MIN or INT32_MAX
+ *               (the reference's infinities), or of 2^31 values or more, has the largest size there is, 2^31 - 1, so
+ *               among such intervals orders 1 and 2 choose by index alone.  (csgpu_solve_many_clauses compares hi - lo
+ *               in full; the two walks are the same tree for order 1 wherever no open interval saturates and nothing
+ *               halves.)
+ *   Children.   A node whose branching variable has more than split_width values -- hi - lo + 1, in 64 bits -- has two
+ *               children: [lo, mid] first, then [mid + 1, hi], mid = (lo + hi) >> 1, a floor taken in 64 bits.  Any
+ *               other node has its values in ascending order.  Whether a node halves, and its mid, are fixed by the
+ *               node's row as it was entered, before any incumbent bound: a frame popped later makes the same children.
+ *               A half is "narrow the variable to that half, then the fixpoint": a node in `nodes`, and a cut if the
+ *               fixpoint fails or the incumbent's bound empties dom[obj].  The second half is its node's last child.
+ *   d_halvings  NULL, or [count] int64: the parents of the instance that were split in two, each counted once, when its
+ *               first half is tried.  0 for a row that is not searched.
+ * Prefer-failing is not part of this walk: which variable a failed fixpoint blames depends on kernel 6's revision order.
+ * Frames.  A pushed halving parent values no variable, so a wave's stack can be deeper than n_vars.
+ * csgpu_many_clauses_ordered_frames(m, split_width) is the frames per wave of a call, from the model's root domains alone
+ * and without a HIP call: n_vars + the sum over the variables of h(v), h(v) the smallest h for which the root width,
+ * halved h times with ceiling, is at most split_width (0 means 256) -- rows lie inside the root domains and intervals only
+ * shrink along a path.  0 for a model that does not qualify, or a negative split_width.  The call launches
+ * min(count, resident waves) waves, fewer where their frames would pass 1 GiB, as csgpu_solve_many_clauses does; the
+ * kernel compares the depth with that count before it writes all the same (CSGPU_MANY_LIMIT).
+ * Errors before any HIP call: csgpu_solve_many_clauses's in its order (options is this entry's struct), then an order
+ * outside 0 .. 4, a negative split_width or a non-zero `reserved` -> CSGPU_E_ARG.  count == 0 -> CSGPU_OK, nothing is
+ * launched.
+ * Not on this walk: checkpoints and resume, up to k solutions, the solution stream, the spread over idle waves, restarts,
+ * prefer-failing, and the kernel-7 walks of csgpu_solve_many, which keep their one rule. */
+typedef struct csgpu_many_order_options {
+  int32_t objective;   /* 0 ANY, 1 ALL, 2 MIN, 3 MAX */
+  int32_t order;       /* 0..4, csgpu_search_set_strategy's numbers */
+  int32_t split_width; /* >= 1; 0 means 256, the engine's */
+  int32_t reserved;    /* 0 */
+  int64_t max_nodes;
+} csgpu_many_order_options;
+int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                     const csgpu_many_order_options *options, csgpu_many_result *d_results,
+                                     int32_t *d_solutions /* NULL or [count][n_vars] */, int32_t *d_best /* NULL or [count] */,
+                                     int64_t *d_halvings /* NULL or [count] */, void *stream);
+int64_t csgpu_many_clauses_ordered_frames(const csgpu_model *m, int32_t split_width);
+
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */
 int csgpu_eval_batch(const csgpu_model *m, const csgpu_val *d_states, int32_t *d_truth, int64_t batch,

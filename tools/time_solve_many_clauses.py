@@ -47,7 +47,14 @@ over the calls: medians and ranges of --reps, rounds and rows per round, the lau
 field of every instance -- props and root_props included -- and every first solution equals the one call's.
 --spread-objective own (default all): on a MIN / MAX set, the one call and the spread walk under the set's objective instead
 (solve_many_clauses_spread(roots, "MIN" / "MAX"): start incumbents); the check is then that every instance the one call
-ends is ended by the spread with the same optimum, and the spread's own nodes are printed beside the one call's."""
+ends is ended by the spread with the same optimum, and the spread's own nodes are printed beside the one call's.
+
+--order NAME --split W [--budget N] times Model.solve_many_clauses_ordered(order=NAME, split_width=W) beside the plain call
+of solve_many_clauses on the same rows and the same budget, alternating in this process after a warm-up (--set: a set of
+tests/many_clause_sets.py or of tests/many_walk_ordered.py, e.g. schedule5_open_min, whose rows leave `end` at its root
+width; repeated up to --count): medians and ranges of both, both node totals, how many rows each leaves at LIMIT, the
+time per node of both, whether every field equals the plain call's (what smallest-domain gives where nothing halves),
+and the seeded sample of the ordered answers re-checked against the host walk (tests/many_walk_ordered.py)."""
 import argparse
 import json
 import os
@@ -101,7 +108,13 @@ def main():
     ap.add_argument("--spread-rows", type=int, default=1 << 18, help="max_rows of solve_many_clauses_spread")
     ap.add_argument("--spread-objective", default="all", choices=("all", "own"),
                     help="own: walk a MIN / MAX set under its objective (the spread with start incumbents)")
+    ap.add_argument("--order", default=None, help="NAME: time solve_many_clauses_ordered beside the plain call (with --split)")
+    ap.add_argument("--split", type=int, default=256, help="with --order: split_width")
     args = ap.parse_args()
+    if args.order is not None:
+        if args.spread is not None or args.stream is not None or args.sliced or args.upto is not None or args.restarts is not None:
+            ap.error("--order NAME: without --spread, --stream, --sliced, --upto and --restarts")
+        return order_route(args)
     if args.spread is not None:
         if args.stream is not None or args.sliced or args.upto is not None or args.restarts is not None:
             ap.error("--spread B1,B2,...: without --stream, --sliced, --upto and --restarts")
@@ -202,6 +215,73 @@ def main():
         "oracle_checked": len(picks), "oracle_ok": bool(ok),
     }))
     return 0 if ok and same_optimum is not False else 1
+
+
+def order_route(args):
+    """the ordered call beside the plain call of the same rows, same budget, same build"""
+    import many_clause_sets as sets
+    import many_walk_ordered as O
+    name = args.set or "schedule5_min"
+    if name not in sets.SETS and name not in O.SETS:
+        raise SystemExit(f"--order: --set is one of {sorted(set(sets.SETS) | set(O.SETS))}")
+    if args.order not in O.ORDERS or args.split < 1:
+        raise SystemExit(f"--order is one of {O.ORDERS}, --split at least 1")
+    text, base, objective, budget = (sets if name in sets.SETS else O).build(name)
+    budget = args.budget or budget
+    roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
+    count = len(roots)
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+    rng = np.random.default_rng(args.seed)
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    calls = {"plain": lambda: model.solve_many_clauses(dev, objective, max_nodes=budget),
+             "ordered": lambda: model.solve_many_clauses_ordered(dev, objective, max_nodes=budget, order=args.order,
+                                                                 split_width=args.split)}
+    for _ in range(2):  # warm-up: code load, workspace
+        for call in calls.values():
+            timed(call)
+    times, outs = {k: [] for k in calls}, {}
+    for _ in range(args.reps):  # alternating: a drift of the machine falls on both alike
+        for k, call in calls.items():
+            dt, outs[k] = timed(call)
+            times[k].append(dt)
+    host = {k: {f: v.cpu().numpy() for f, v in o.items() if torch.is_tensor(v)} for k, o in outs.items()}
+    plain, got = host["plain"], host["ordered"]
+    same = all(bool((got[f] == plain[f]).all()) for f in plain)
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    want = O.walk_many(text, roots[picks], objective, budget, args.order, args.split)
+    has = want["solutions"] > 0
+    ok = all((got[f][picks] == want[f]).all() for f in ("status", "nodes", "cuts", "solutions", "halvings")) and \
+        bool((got["first"][picks][has] == want["first"][has]).all())
+    if objective in ("MIN", "MAX"):
+        ok = ok and bool((got["best"][picks][has] == want["best"][has]).all())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    nodes = {k: int(host[k]["nodes"].sum()) for k in calls}
+    print(json.dumps({
+        "tool": "time_solve_many_clauses", "route": "order", "commit": commit(), "command": " ".join(sys.argv), "set": name,
+        "objective": objective, "order": args.order, "split_width": args.split, "instances": count, "max_nodes": budget,
+        "n_vars": model.n_vars, "clauses": model.n_clauses, "kernel": model.many_clauses_kernel(),
+        "order_kernel": model.many_clauses_order_kernel(), "waves": model.many_clauses_waves(count),
+        "frames_per_wave": {"plain": model.n_vars, "ordered": model.many_clauses_ordered_frames(args.split)},
+        "plain_ms": spread(times["plain"]), "ordered_ms": spread(times["ordered"]),
+        "ordered_over_plain": round(med["ordered"] / med["plain"], 4),
+        "plain_nodes": nodes["plain"], "ordered_nodes": nodes["ordered"],
+        "plain_ns_per_node": round(med["plain"] * 1e9 / max(nodes["plain"], 1), 2),
+        "ordered_ns_per_node": round(med["ordered"] * 1e9 / max(nodes["ordered"], 1), 2),
+        "plain_status_counts": np.bincount(plain["status"], minlength=3).tolist(),
+        "ordered_status_counts": np.bincount(got["status"], minlength=3).tolist(),
+        "plain_largest_tree": int(plain["nodes"].max()), "ordered_largest_tree": int(got["nodes"].max()),
+        "halvings": int(got["halvings"].sum()), "every_field_equals_the_plain_call": same,
+        "oracle_checked": len(picks), "oracle_ok": bool(ok),
+    }))
+    return 0 if ok else 1
 
 
 def restart_route(args):
