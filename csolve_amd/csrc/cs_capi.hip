@@ -66,6 +66,11 @@ static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "c
 #define MANY_BY_ALLOWED(family) ((family) >= MANY_ALLOWED && (family) <= MANY_ALLOWED_UPTO_CK)
 #define CS_DIVE_ALLOWED_WIDTH 128 /* the widest root domain the allowed sets of cs_dive_allowed hold (four 32-bit words) */
 
+/* the kernels of the csgpu_solve_many_clauses family (cs_walk.hip.h): one loop on kernel 6's fixpoint, compiled seven times */
+enum { WALK_PLAIN, WALK_CK, WALK_UPTO, WALK_RESTART, WALK_STREAM, WALK_FROM, WALK_ORDER, WALK_FAMILIES };
+static const char *const walk_kernel_name[WALK_FAMILIES] = { "cs_walk_clauses", "cs_walk_resume", "cs_walk_upto", "cs_walk_restart",
+                                                             "cs_walk_stream", "cs_walk_from", "cs_walk_order" };
+
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
 struct cs_kernel_plan {
   cs_planned events, traced;       /* kernel 1; its tracing variant (one node) */
@@ -81,13 +86,7 @@ struct cs_kernel_plan {
   cs_planned step_shave, step_packed, step_import;
   cs_planned dive[MANY_FAMILIES];  /* by MANY_*: the first five all or none, the four MANY_ALLOWED* with them unless the
                                       domains are too wide; not among csgpu_internal_plan_symbol's families */
-  cs_planned walk;                 /* cs_walk_clauses (csgpu_solve_many_clauses): kernel 6's instantiation; no plan family either */
-  cs_planned walk_ck;              /* cs_walk_resume (csgpu_solve_many_clauses_checkpointed / _resume): planned with `walk` or not at all */
-  cs_planned walk_upto;            /* cs_walk_upto (csgpu_solve_many_clauses_upto and its two checkpoint calls): the same */
-  cs_planned walk_restart;         /* cs_walk_restart (csgpu_solve_many_clauses_restarts): the same */
-  cs_planned walk_stream;          /* cs_walk_stream (csgpu_solve_many_clauses_stream): the same */
-  cs_planned walk_from;            /* cs_walk_from (csgpu_solve_many_clauses_from / _from_resume): the same */
-  cs_planned walk_order;           /* cs_walk_order (csgpu_solve_many_clauses_ordered): the same */
+  cs_planned walk[WALK_FAMILIES];  /* by WALK_*: kernel 6's instantiation of each, all or none; no plan families either */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -843,6 +842,24 @@ static const void *dive_kernel(int family, int width, int n_vars, int set_words)
 #undef CS_PICK_R
 }
 
+/* ---- cs_walk.hip.h: a depth-first search per wave on kernel 6's fixpoint (csgpu_solve_many_clauses); `cpl`: kernel 6's
+ * clauses per lane, `tree`: some adjacency entry is a tree clause ---- */
+static const void *walk_kernel(int family, int cpl, int tree) {
+#define CS_PICK_T(K, CPL) (tree ? (const void *)K<CPL, true> : (const void *)K<CPL, false>)
+#define CS_PICK(K) return cpl == 1 ? CS_PICK_T(K, 1) : (cpl == 2 ? CS_PICK_T(K, 2) : (cpl == 4 ? CS_PICK_T(K, 4) : CS_PICK_T(K, 8)));
+  switch (family) {
+  case WALK_CK: CS_PICK(cs_walk_resume)       /* with checkpoints (csgpu_solve_many_clauses_checkpointed / _resume) */
+  case WALK_UPTO: CS_PICK(cs_walk_upto)       /* leaving at the k-th solution (csgpu_solve_many_clauses_upto and its two checkpoint calls) */
+  case WALK_RESTART: CS_PICK(cs_walk_restart) /* ANY with a seeded value order and Luby restarts (csgpu_solve_many_clauses_restarts) */
+  case WALK_STREAM: CS_PICK(cs_walk_stream)   /* ALL, every solution appended to a shared stream (csgpu_solve_many_clauses_stream) */
+  case WALK_FROM: CS_PICK(cs_walk_from)       /* MIN / MAX from a start incumbent (csgpu_solve_many_clauses_from / _from_resume) */
+  case WALK_ORDER: CS_PICK(cs_walk_order)     /* the five variable orders, interval halving (csgpu_solve_many_clauses_ordered) */
+  default: CS_PICK(cs_walk_clauses)
+  }
+#undef CS_PICK
+#undef CS_PICK_T
+}
+
 /* ---- the resident single-node server (cs_shave.hip.h) ---- */
 static const void *shave_server_kernel(int width, int n_vars, int slots) {
   const int r = cs_dense_strides(n_vars);
@@ -1005,85 +1022,18 @@ static int plan_general(csgpu_model *m) {
     m->plan.rounds.lds = ((((size_t)h->n_vars * sizeof(cs_val) + 16 + 15) & ~(size_t)15)) * CS_WAVES_PER_BLOCK;
     m->plan.rounds.waves = CS_WAVES_PER_BLOCK;
     m->plan.rounds.per_cu = 8;
-    /* cs_walk_clauses: kernel 6's slices; planned when a workgroup's fit a CU (csgpu_solve_many_clauses says so otherwise) */
+    /* the cs_walk_* kernels: kernel 6's slices, each its own registers; planned when a workgroup's fit a CU
+     * (csgpu_solve_many_clauses says so otherwise) */
     if (m->plan.rounds.lds <= CS_CU_LDS) {
-#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_clauses<CPL, true> : (const void *)cs_walk_clauses<CPL, false>)
-      const int cpl = m->plan.rounds_cpl;
-      const void *fn = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
-#undef CS_PICKW
-      if ((rc = plan_kernel(&m->plan.walk, fn, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
-      { /* persistent waves: no more workgroups than stay resident with the instantiation's registers and scratch */
+      for (int family = 0; family < WALK_FAMILIES; family++) {
+        cs_planned *k = &m->plan.walk[family];
+        if ((rc = plan_kernel(k, walk_kernel(family, m->plan.rounds_cpl, m->has_tree_adj), m->plan.rounds.lds, CS_WAVES_PER_BLOCK)))
+          return rc;
+        /* persistent waves: no more workgroups than stay resident with the instantiation's registers and scratch */
         int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, CS_BLOCK, m->plan.walk.lds) == hipSuccess && occ >= 1 &&
-            occ < m->plan.walk.per_cu)
-          m->plan.walk.per_cu = occ;
-        if (m->plan.walk.per_cu < 1) m->plan.walk.per_cu = 1;
-      }
-      { /* cs_walk_resume: the same slices, its own registers */
-#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_resume<CPL, true> : (const void *)cs_walk_resume<CPL, false>)
-        const void *fn_ck = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
-#undef CS_PICKW
-        if ((rc = plan_kernel(&m->plan.walk_ck, fn_ck, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_ck, CS_BLOCK, m->plan.walk_ck.lds) == hipSuccess && occ >= 1 &&
-            occ < m->plan.walk_ck.per_cu)
-          m->plan.walk_ck.per_cu = occ;
-        if (m->plan.walk_ck.per_cu < 1) m->plan.walk_ck.per_cu = 1;
-      }
-      { /* cs_walk_upto: the same slices, its own registers */
-#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_upto<CPL, true> : (const void *)cs_walk_upto<CPL, false>)
-        const void *fn_upto = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
-#undef CS_PICKW
-        if ((rc = plan_kernel(&m->plan.walk_upto, fn_upto, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_upto, CS_BLOCK, m->plan.walk_upto.lds) == hipSuccess && occ >= 1 &&
-            occ < m->plan.walk_upto.per_cu)
-          m->plan.walk_upto.per_cu = occ;
-        if (m->plan.walk_upto.per_cu < 1) m->plan.walk_upto.per_cu = 1;
-      }
-      { /* cs_walk_restart: the same slices, its own registers */
-#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_restart<CPL, true> : (const void *)cs_walk_restart<CPL, false>)
-        const void *fn_rs = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
-#undef CS_PICKW
-        if ((rc = plan_kernel(&m->plan.walk_restart, fn_rs, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_rs, CS_BLOCK, m->plan.walk_restart.lds) == hipSuccess && occ >= 1 &&
-            occ < m->plan.walk_restart.per_cu)
-          m->plan.walk_restart.per_cu = occ;
-        if (m->plan.walk_restart.per_cu < 1) m->plan.walk_restart.per_cu = 1;
-      }
-      { /* cs_walk_stream: the same slices, its own registers */
-#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_stream<CPL, true> : (const void *)cs_walk_stream<CPL, false>)
-        const void *fn_st = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
-#undef CS_PICKW
-        if ((rc = plan_kernel(&m->plan.walk_stream, fn_st, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_st, CS_BLOCK, m->plan.walk_stream.lds) == hipSuccess && occ >= 1 &&
-            occ < m->plan.walk_stream.per_cu)
-          m->plan.walk_stream.per_cu = occ;
-        if (m->plan.walk_stream.per_cu < 1) m->plan.walk_stream.per_cu = 1;
-      }
-      { /* cs_walk_from: the same slices, its own registers */
-#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_from<CPL, true> : (const void *)cs_walk_from<CPL, false>)
-        const void *fn_from = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
-#undef CS_PICKW
-        if ((rc = plan_kernel(&m->plan.walk_from, fn_from, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_from, CS_BLOCK, m->plan.walk_from.lds) == hipSuccess && occ >= 1 &&
-            occ < m->plan.walk_from.per_cu)
-          m->plan.walk_from.per_cu = occ;
-        if (m->plan.walk_from.per_cu < 1) m->plan.walk_from.per_cu = 1;
-      }
-      { /* cs_walk_order: the same slices, its own registers */
-#define CS_PICKW(CPL) (m->has_tree_adj ? (const void *)cs_walk_order<CPL, true> : (const void *)cs_walk_order<CPL, false>)
-        const void *fn_ord = cpl == 1 ? CS_PICKW(1) : (cpl == 2 ? CS_PICKW(2) : (cpl == 4 ? CS_PICKW(4) : CS_PICKW(8)));
-#undef CS_PICKW
-        if ((rc = plan_kernel(&m->plan.walk_order, fn_ord, m->plan.rounds.lds, CS_WAVES_PER_BLOCK))) return rc;
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn_ord, CS_BLOCK, m->plan.walk_order.lds) == hipSuccess && occ >= 1 &&
-            occ < m->plan.walk_order.per_cu)
-          m->plan.walk_order.per_cu = occ;
-        if (m->plan.walk_order.per_cu < 1) m->plan.walk_order.per_cu = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k->fn, CS_BLOCK, k->lds) == hipSuccess && occ >= 1 && occ < k->per_cu)
+          k->per_cu = occ;
+        if (k->per_cu < 1) k->per_cu = 1;
       }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
@@ -1386,13 +1336,14 @@ extern "C" int csgpu_internal_plan_symbol(const csgpu_model *m, int family, char
   return CSGPU_OK;
 }
 
-/* the same for the cs_dive_* kernels, which are no families of the list above (the plan dictionary stays what it was) */
-static int many_symbol(const csgpu_model *m, int family, char *buf, size_t len) {
+/* the same for the cs_dive_* and the cs_walk_* kernels, which are no families of the list above (the plan dictionary
+ * stays what it was): the instantiation of `k`, a kernel called `name`, by its dynamic symbol ("" where the model plans
+ * none; k is NULL with m) */
+static int many_symbol(const csgpu_model *m, const cs_planned *k, const char *name, char *buf, size_t len) {
   if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
   buf[0] = '\0';
-  const void *fn = m->plan.dive[family].fn;
-  const char *name = many_kernel_name[family];
+  const void *fn = k->fn;
   if (fn == NULL) return CSGPU_OK;
   Dl_info info;
   if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
@@ -1402,15 +1353,27 @@ static int many_symbol(const csgpu_model *m, int family, char *buf, size_t len) 
   return CSGPU_OK;
 }
 
-extern "C" int csgpu_internal_many_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_PLAIN, buf, len); }
-extern "C" int csgpu_internal_many_resume_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_CK, buf, len); }
-extern "C" int csgpu_internal_many_upto_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_UPTO, buf, len); }
-extern "C" int csgpu_internal_many_restart_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_RESTART, buf, len); }
-extern "C" int csgpu_internal_many_stream_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_STREAM, buf, len); }
-extern "C" int csgpu_internal_many_allowed_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED, buf, len); }
-extern "C" int csgpu_internal_many_allowed_upto_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED_UPTO, buf, len); }
-extern "C" int csgpu_internal_many_allowed_resume_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED_CK, buf, len); }
-extern "C" int csgpu_internal_many_allowed_upto_resume_symbol(const csgpu_model *m, char *buf, size_t len) { return many_symbol(m, MANY_ALLOWED_UPTO_CK, buf, len); }
+#define MANY_SYMBOL(EXPORT, PLANNED, NAMES, FAMILY)                                       \
+  extern "C" int EXPORT(const csgpu_model *m, char *buf, size_t len) {                    \
+    return many_symbol(m, m != NULL ? &m->plan.PLANNED[FAMILY] : NULL, NAMES[FAMILY], buf, len); \
+  }
+MANY_SYMBOL(csgpu_internal_many_symbol, dive, many_kernel_name, MANY_PLAIN)
+MANY_SYMBOL(csgpu_internal_many_resume_symbol, dive, many_kernel_name, MANY_CK)
+MANY_SYMBOL(csgpu_internal_many_upto_symbol, dive, many_kernel_name, MANY_UPTO)
+MANY_SYMBOL(csgpu_internal_many_restart_symbol, dive, many_kernel_name, MANY_RESTART)
+MANY_SYMBOL(csgpu_internal_many_stream_symbol, dive, many_kernel_name, MANY_STREAM)
+MANY_SYMBOL(csgpu_internal_many_allowed_symbol, dive, many_kernel_name, MANY_ALLOWED)
+MANY_SYMBOL(csgpu_internal_many_allowed_upto_symbol, dive, many_kernel_name, MANY_ALLOWED_UPTO)
+MANY_SYMBOL(csgpu_internal_many_allowed_resume_symbol, dive, many_kernel_name, MANY_ALLOWED_CK)
+MANY_SYMBOL(csgpu_internal_many_allowed_upto_resume_symbol, dive, many_kernel_name, MANY_ALLOWED_UPTO_CK)
+MANY_SYMBOL(csgpu_internal_many_clauses_symbol, walk, walk_kernel_name, WALK_PLAIN)
+MANY_SYMBOL(csgpu_internal_many_clauses_resume_symbol, walk, walk_kernel_name, WALK_CK)
+MANY_SYMBOL(csgpu_internal_many_clauses_upto_symbol, walk, walk_kernel_name, WALK_UPTO)
+MANY_SYMBOL(csgpu_internal_many_clauses_restart_symbol, walk, walk_kernel_name, WALK_RESTART)
+MANY_SYMBOL(csgpu_internal_many_clauses_stream_symbol, walk, walk_kernel_name, WALK_STREAM)
+MANY_SYMBOL(csgpu_internal_many_clauses_from_symbol, walk, walk_kernel_name, WALK_FROM)
+MANY_SYMBOL(csgpu_internal_many_clauses_order_symbol, walk, walk_kernel_name, WALK_ORDER)
+#undef MANY_SYMBOL
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
   if (m != NULL) const_cast<csgpu_model *>(m)->engines += delta;
@@ -2227,44 +2190,7 @@ extern "C" int csgpu_solve_many_stream(const csgpu_model *m, const csgpu_val *d_
 #define MANY_CLAUSES_STACK_MAX ((size_t)1 << 30) /* bytes of frames a call keeps: fewer waves rather than more memory */
 
 extern "C" int csgpu_model_qualifies_many_clauses(const csgpu_model *m) {
-  return m != NULL && m->finalized && m->plan.walk.fn != NULL;
-}
-
-/* the instantiation of `k` by its dynamic symbol, for the tests ("" where the model plans none) */
-static int many_clauses_symbol(const csgpu_model *m, const cs_planned *k, const char *name, char *buf, size_t len) {
-  if (m == NULL || buf == NULL || len == 0) return set_err(CSGPU_E_ARG, "null argument");
-  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  buf[0] = '\0';
-  const void *fn = k->fn;
-  if (fn == NULL) return CSGPU_OK;
-  Dl_info info;
-  if (dladdr(fn, &info) == 0 || info.dli_sname == NULL || info.dli_saddr != fn)
-    return set_err(CSGPU_E_STATE, "%s: the kernel handle has no dynamic symbol", name);
-  if (strlen(info.dli_sname) >= len) return set_err(CSGPU_E_LIMIT, "%s: symbol longer than the buffer", name);
-  strcpy(buf, info.dli_sname);
-  return CSGPU_OK;
-}
-
-extern "C" int csgpu_internal_many_clauses_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_clauses_symbol(m, m != NULL ? &m->plan.walk : NULL, "cs_walk_clauses", buf, len);
-}
-extern "C" int csgpu_internal_many_clauses_resume_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_ck : NULL, "cs_walk_resume", buf, len);
-}
-extern "C" int csgpu_internal_many_clauses_upto_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_upto : NULL, "cs_walk_upto", buf, len);
-}
-extern "C" int csgpu_internal_many_clauses_restart_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_restart : NULL, "cs_walk_restart", buf, len);
-}
-extern "C" int csgpu_internal_many_clauses_stream_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_stream : NULL, "cs_walk_stream", buf, len);
-}
-extern "C" int csgpu_internal_many_clauses_from_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_from : NULL, "cs_walk_from", buf, len);
-}
-extern "C" int csgpu_internal_many_clauses_order_symbol(const csgpu_model *m, char *buf, size_t len) {
-  return many_clauses_symbol(m, m != NULL ? &m->plan.walk_order : NULL, "cs_walk_order", buf, len);
+  return m != NULL && m->finalized && m->plan.walk[WALK_PLAIN].fn != NULL;
 }
 
 /* waves a call with `count` instances launches: the resident ones, no more than the instances need, and no more than
@@ -2283,7 +2209,7 @@ static int64_t many_clauses_waves(const csgpu_model *m, const cs_planned *k, int
 
 extern "C" int64_t csgpu_internal_many_clauses_waves(const csgpu_model *m, int64_t count) {
   if (!csgpu_model_qualifies_many_clauses(m) || count < 1) return 0;
-  return many_clauses_waves(m, &m->plan.walk, count, m->host->n_vars);
+  return many_clauses_waves(m, &m->plan.walk[WALK_PLAIN], count, m->host->n_vars);
 }
 
 /* The frames a wave of cs_walk_order needs, from the root domains alone: n + sum of h(v), h(v) the smallest h for which
@@ -2306,58 +2232,11 @@ extern "C" int64_t csgpu_many_clauses_ordered_frames(const csgpu_model *m, int32
   return many_clauses_ordered_frames(m, split_width);
 }
 
-/* the ordered entry's own arguments: its options in place of the other three, and the halving counts */
-struct many_clauses_ord {
-  const csgpu_many_order_options *options;
-  int64_t *d_halvings;
-};
-
-/* the restart entry's own arguments: its options in place of the other two, the seeds and the restart counts */
-struct many_clauses_rs {
-  const csgpu_many_restart_options *options;
-  const uint32_t *d_seeds;
-  int32_t *d_restarts;
-};
-
-/* The one path of the ten entries: the checks, none of which touches the device, then the launch.  `pooled`: the call
- * has a pool and slot numbers and launches cs_walk_resume; `resume` (pooled, and no roots): the instances go on in their
- * slots, so the call needs no workspace.  An up-to-k entry brings `upto_options` in place of `options` (the other one is
- * NULL): the ALL walk by cs_walk_upto, pooled or not, its rows [count][max_solutions][n_vars] in d_solutions.  The
- * restart entry brings `rs` (else NULL) and neither of the two: the ANY walk by cs_walk_restart, one frame more per wave.
- * The stream entry brings `out` (else NULL), is pooled and not `resume` -- d_slots says per instance whether it starts or
- * goes on, so the workspace is a fresh call's: the ALL walk by cs_walk_stream, its rows in *out.  The two start entries
- * bring `from` (else 0): the MIN / MAX walk by cs_walk_from, pooled or not like an up-to-k entry, with d_start unless it
- * is the resume.  The ordered entry brings `ord` (else NULL) and none of the three options: any objective by cs_walk_order,
- * plain, with the frames of many_clauses_ordered_frames per wave. */
-static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
-                             const csgpu_many_upto_options *upto_options, const many_clauses_rs *rs, csgpu_many_result *d_results,
-                             int32_t *d_solutions, int32_t *d_best, int pooled, csgpu_many_checkpoints *ck, int32_t *d_slots,
-                             int resume, int streamed, const csgpu_many_stream *out, int from, const csgpu_many_start *d_start,
-                             void *stream, const many_clauses_ord *ord = NULL) {
-  const csgpu_many_restart_options *rs_options = rs != NULL ? rs->options : NULL;
-  const csgpu_many_order_options *ord_options = ord != NULL ? ord->options : NULL;
-  const int null_arg = m == NULL || (!resume && d_roots == NULL) || d_results == NULL ||
-                       (options == NULL && upto_options == NULL && rs_options == NULL && ord_options == NULL) ||
-                       (streamed && (ck == NULL || d_slots == NULL || out == NULL));
-  const int64_t max_nodes = null_arg ? 0 : (rs_options != NULL ? rs_options->max_nodes
-                                            : (upto_options != NULL ? upto_options->max_nodes
-                                               : (ord_options != NULL ? ord_options->max_nodes : options->max_nodes)));
-  int rc;
-  if ((rc = many_check_head(null_arg, count, max_nodes, pooled ? "slice" : "instance"))) return rc;
-  if (upto_options != NULL && upto_options->max_solutions < 1)
-    return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
-  if (rs_options != NULL && rs_options->restart_base < 0) return set_err(CSGPU_E_ARG, "restart_base must not be negative (0: no restarts)");
-  if (rs_options != NULL && (rs_options->flags & ~CSGPU_MANY_ROTATE_FIRST) != 0)
-    return set_err(CSGPU_E_ARG, "unknown flags 0x%x", (unsigned)rs_options->flags);
-  const int objective = rs_options != NULL ? CS_OBJ_ANY : (upto_options != NULL ? CS_OBJ_ALL
-                                                           : (ord_options != NULL ? ord_options->objective : options->objective));
-  if (streamed) { /* before the model is looked at: ALL only, and a stream that can take a row */
-    if (objective != CS_OBJ_ALL)
-      return set_err(CSGPU_E_ARG, "csgpu_solve_many_clauses_stream walks under ALL (objective 1), not objective %d", objective);
-    if (out->capacity < 1)
-      return set_err(CSGPU_E_ARG, "the solution stream has room for at least one row (capacity %lld)", (long long)out->capacity);
-    if (out->d_rows == NULL || out->d_owner == NULL || out->d_count == NULL) return set_err(CSGPU_E_ARG, "null pointer in the solution stream");
-  }
+/* The checks of every clause entry, none of which touches the device: many_check_head, the entry's own checks of its
+ * options (and the stream's of its stream), many_clauses_check_model, what the start and the ordered entries add, and
+ * many_clauses_check_pool for a call that has a pool.  This one: the objective the call walks under, against the model;
+ * then the model and the count. */
+static int many_clauses_check_model(const csgpu_model *m, int objective, int64_t count) {
   if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
     return set_err(CSGPU_E_ARG, "no objective %d", objective);
   if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX) {
@@ -2368,7 +2247,7 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
                      m->host->objective == CS_OBJ_MIN ? "MIN" : "MAX", objective == CS_OBJ_MIN ? "MIN" : "MAX");
   }
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
-  if (m->plan.walk.fn == NULL) {
+  if (m->plan.walk[WALK_PLAIN].fn == NULL) {
     if (m->plan.rounds_cpl == 0)
       return set_err(CSGPU_E_LIMIT, "model does not qualify for the clause-resident kernel (at most 512 clauses; this one has %d), "
                                     "which csgpu_solve_many_clauses is built on", (int)m->img->n_clauses);
@@ -2376,100 +2255,94 @@ static int many_clauses_call(const csgpu_model *m, const csgpu_val *d_roots, int
                                   "workgroup, more than the 160 KiB of a CU", (int)m->host->n_vars, m->plan.rounds.lds, CS_WAVES_PER_BLOCK);
   }
   if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
-  if (from) { /* after csgpu_solve_many_clauses's own errors: the start, the objective, then the pool and the slots together */
-    if (!resume && d_start == NULL) return set_err(CSGPU_E_ARG, "null argument: d_start, the incumbents the instances start with");
-    if (objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
-      return set_err(CSGPU_E_ARG, "a start incumbent bounds a MIN / MAX walk (objective 2 or 3), not objective %d", objective);
-    if ((ck == NULL) != (d_slots == NULL))
-      return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers, a plain one neither");
-    pooled = ck != NULL;
-    if (resume && !pooled) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
-  }
-  if (ord_options != NULL) { /* after csgpu_solve_many_clauses's own errors, before any device call */
-    if (ord_options->order < 0 || ord_options->order > 4)
-      return set_err(CSGPU_E_ARG, "no variable order %d (0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value)",
-                     (int)ord_options->order);
-    if (ord_options->split_width < 0) return set_err(CSGPU_E_ARG, "split_width must not be negative (0: the engine's 256)");
-    if (ord_options->reserved != 0) return set_err(CSGPU_E_ARG, "reserved must be 0");
-  }
-  if (pooled) {
-    if (ck == NULL || d_slots == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
-    if (ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
-    if (ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
-  }
-  if (count == 0) return CSGPU_OK;
+  return CSGPU_OK;
+}
+
+/* what the caller of an entry brought (the trailing ones NULL where the entry has none) */
+struct many_clauses_bufs {
+  const csgpu_val *d_roots; /* NULL: a resume */
+  int64_t count;
+  csgpu_many_result *d_results;
+  void *stream;
+  int32_t *d_solutions;
+  int32_t *d_best; /* read under MIN / MAX alone */
+  csgpu_many_checkpoints *ck;
+  int32_t *d_slots;
+};
+
+static int many_clauses_check_pool(const csgpu_model *m, const many_clauses_bufs *b) {
+  if (b->ck == NULL || b->d_slots == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
+  if (b->ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
+  if (b->ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  return CSGPU_OK;
+}
+
+/* the pool and slot numbers as the kernels take them, `code` in the header of every checkpoint the call writes or goes on
+ * from; without a pool: one of capacity 0 that cs_walk_upto and cs_walk_from do not touch */
+static cs_walk_ck many_clauses_ck_arg(const many_clauses_bufs *b, int resume, int code) {
+  cs_walk_ck wk;
+  wk.pool = b->ck != NULL ? b->ck->d_pool : NULL;
+  wk.next = b->ck != NULL ? b->ck->d_next : NULL;
+  wk.capacity = b->ck != NULL ? (int)b->ck->capacity : 0;
+  wk.resume = resume;
+  wk.code = code;
+  wk.slots = b->ck != NULL ? b->d_slots : NULL;
+  return wk;
+}
+
+
+/* The one launch of a cs_walk_* kernel, after the checks.  `frames` per wave: at most n - 1 pushed frames and the current
+ * node's; cs_walk_restart: and the root node's; cs_walk_order: and the halving parents' (at most 33 n, n <= 5118: an int).
+ * `tail0`, `tail1`: the family's own kernel arguments after the tables and the cs_walk_io (NULL where it has fewer).
+ * `resume`: the instances go on in the frames of their checkpoint slots, so the call brings no roots and needs no stacks. */
+static int many_clauses_launch(const csgpu_model *m, int family, int frames, int objective, int64_t max_nodes,
+                               const many_clauses_bufs *b, int resume, void *tail0, void *tail1) {
+  if (b->count == 0) return CSGPU_OK;
   csgpu_model *mm = const_cast<csgpu_model *>(m);
-  const cs_planned *k = rs_options != NULL ? &m->plan.walk_restart
-                        : (upto_options != NULL ? &m->plan.walk_upto
-                           : (streamed ? &m->plan.walk_stream
-                              : (from ? &m->plan.walk_from
-                                 : (ord_options != NULL ? &m->plan.walk_order : (pooled ? &m->plan.walk_ck : &m->plan.walk)))));
-  const int n = m->host->n_vars;
-  /* at most n - 1 pushed frames and the current node's; cs_walk_restart: and the root node's; cs_walk_order: and the
-   * halving parents' (at most 33 n, n <= 5118: an int) */
-  const int frames = rs_options != NULL ? n + 1 : (ord_options != NULL ? (int)many_clauses_ordered_frames(m, ord_options->split_width) : n);
-  const int64_t waves = many_clauses_waves(m, k, count, frames);
+  const cs_planned *k = &m->plan.walk[family];
+  const int64_t waves = many_clauses_waves(m, k, b->count, frames);
+  int rc;
   if ((rc = many_workspace(mm, resume ? 0 : waves, frames))) return rc;
   cs_walk_io io;
-  io.roots = (const cs_val *)d_roots;
+  io.roots = (const cs_val *)b->d_roots;
   io.root_dom = m->d_walk_root;
-  io.count = (int)count;
+  io.count = (int)b->count;
   io.all = objective != CS_OBJ_ANY;
   io.sense = objective_sense(objective);
   io.obj_var = io.sense != 0 ? m->host->obj_var : -1;
   io.max_nodes = (long long)max_nodes;
-  io.results = (cs_dive_result *)d_results;
-  io.solutions = d_solutions;
-  io.best = io.sense != 0 ? d_best : NULL;
+  io.results = (cs_dive_result *)b->d_results;
+  io.solutions = b->d_solutions;
+  io.best = io.sense != 0 ? b->d_best : NULL;
   io.stack = resume ? NULL : (cs_val *)mm->d_many_stack;
   io.frames = frames;
   io.tickets = mm->d_many_tickets;
-  cs_walk_ck wk;
-  wk.pool = pooled ? ck->d_pool : NULL;
-  wk.next = pooled ? ck->d_next : NULL;
-  wk.capacity = pooled ? (int)ck->capacity : 0; /* 0: the pool that cs_walk_upto and cs_walk_from do not touch */
-  wk.resume = resume;
-  wk.code = upto_options != NULL ? CS_WALK_CK_UPTO : (streamed ? CS_WALK_CK_STREAM : objective);
-  wk.slots = pooled ? d_slots : NULL;
-  int upto = upto_options != NULL ? upto_options->max_solutions : 0;
-  cs_dive_rs dr;
-  dr.seeds = rs != NULL ? rs->d_seeds : NULL;
-  dr.restarts = rs != NULL ? rs->d_restarts : NULL;
-  dr.restart_base = rs_options != NULL ? (long long)rs_options->restart_base : 0;
-  dr.seed = rs_options != NULL ? rs_options->seed : 0u;
-  dr.flags = rs_options != NULL ? rs_options->flags : 0;
-  cs_dive_out ok;
-  ok.rows = streamed ? out->d_rows : NULL;
-  ok.owner = streamed ? out->d_owner : NULL;
-  ok.count = streamed ? (unsigned long long *)out->d_count : NULL;
-  ok.capacity = streamed ? (long long)out->capacity : 0;
-  cs_walk_ord wo;
-  wo.order = ord_options != NULL ? ord_options->order : 1;
-  wo.split_width = ord_options != NULL && ord_options->split_width != 0 ? ord_options->split_width : 256;
-  wo.halvings = ord != NULL ? (long long *)ord->d_halvings : NULL;
   cs_tables tab = m->tab;
-  /* cs_walk_clauses takes the first two, cs_walk_resume the first three; cs_walk_restart: the tables, io and `dr`;
-   * cs_walk_stream: the first three and `ok`; cs_walk_from: the first three and the starts; cs_walk_order: the tables, io
-   * and `wo` */
-  const cs_walk_start *starts = (const cs_walk_start *)d_start;
-  void *args[] = { &tab, &io, rs_options != NULL ? (void *)&dr : (ord_options != NULL ? (void *)&wo : (void *)&wk),
-                   streamed ? (void *)&ok : (from ? (void *)&starts : (void *)&upto) };
-  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds, (hipStream_t)stream));
+  void *args[] = { &tab, &io, tail0, tail1 };
+  HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds,
+                          (hipStream_t)b->stream));
   return CSGPU_OK;
 }
 
 extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                         const csgpu_many_options *options, csgpu_many_result *d_results, int32_t *d_solutions,
                                         int32_t *d_best, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, 0, NULL, 0, NULL, stream);
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance")) ||
+      (rc = many_clauses_check_model(m, options->objective, count)))
+    return rc;
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best };
+  return many_clauses_launch(m, WALK_PLAIN, m->host->n_vars, options->objective, options->max_nodes, &b, 0, NULL, NULL);
 }
+
 
 /* ---- clause checkpoints: csgpu_solve_many_clauses in slices (cs_walk_resume) ---- */
 
 /* does the model run the cs_walk_* kernels?  What finalize planned; before finalize, the same rules on the host tables
  * (csgpu_model_build_tables) as they stand */
 static int many_clauses_qualifies(const csgpu_model *m) {
-  if (m->finalized) return m->plan.walk.fn != NULL;
+  if (m->finalized) return m->plan.walk[WALK_PLAIN].fn != NULL;
   if (m->img == NULL) return 0;
   const size_t slice = ((size_t)m->host->n_vars * sizeof(cs_val) + 16 + 15) & ~(size_t)15;
   return m->img->n_clauses > 0 && m->img->n_clauses <= 8 * CS_WAVE && slice * CS_WAVES_PER_BLOCK <= CS_CU_LDS;
@@ -2487,17 +2360,30 @@ extern "C" int csgpu_many_clause_checkpoints_create(const csgpu_model *m, int64_
                           csgpu_many_clause_checkpoint_bytes(m), out);
 }
 
+/* the checkpointed call and its resume (no roots): cs_walk_resume under the options' objective, which is the checkpoints' code */
+static int many_clauses_pooled(const csgpu_model *m, const many_clauses_bufs *b, const csgpu_many_options *options, int resume) {
+  const int null_arg = m == NULL || (!resume && b->d_roots == NULL) || b->d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, "slice")) ||
+      (rc = many_clauses_check_model(m, options->objective, b->count)) || (rc = many_clauses_check_pool(m, b)))
+    return rc;
+  cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective);
+  return many_clauses_launch(m, WALK_CK, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, NULL);
+}
+
 extern "C" int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                                      const csgpu_many_options *options, csgpu_many_result *d_results,
                                                      int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
                                                      int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 0, 0, NULL, 0, NULL, stream);
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_pooled(m, &b, options, 0);
 }
 
 extern "C" int csgpu_solve_many_clauses_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
                                                csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
                                                csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, 0, NULL, 0, NULL, stream);
+  const many_clauses_bufs b = { NULL, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_pooled(m, &b, options, 1);
 }
 
 extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints *ck, int32_t slot, csgpu_val *d_states, int64_t cap,
@@ -2567,19 +2453,41 @@ extern "C" int csgpu_many_clause_checkpoint_fanout(const csgpu_many_checkpoints 
 /* ---- an instance that starts with an incumbent it did not find itself, and stopped MIN / MAX walks spread with it
  * (cs_walk_from; cs_walk_children / cs_walk_fanout with MIN's or MAX's code; cs_walk_fold_best) ---- */
 
+/* the start call, checkpointed with a pool and slot numbers and plain with neither, and its resume (no roots, no starts:
+ * the slots hold the incumbents), which is checkpointed: cs_walk_from under MIN / MAX.  What the two refuse comes after
+ * csgpu_solve_many_clauses's own errors: the start, the objective, then the pool and the slots together */
+static int many_clauses_from(const csgpu_model *m, const many_clauses_bufs *b, const csgpu_many_start *d_start,
+                             const csgpu_many_options *options, int resume) {
+  const int null_arg = m == NULL || (!resume && b->d_roots == NULL) || b->d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, resume ? "slice" : "instance")) ||
+      (rc = many_clauses_check_model(m, options->objective, b->count)))
+    return rc;
+  if (!resume && d_start == NULL) return set_err(CSGPU_E_ARG, "null argument: d_start, the incumbents the instances start with");
+  if (options->objective != CS_OBJ_MIN && options->objective != CS_OBJ_MAX)
+    return set_err(CSGPU_E_ARG, "a start incumbent bounds a MIN / MAX walk (objective 2 or 3), not objective %d", options->objective);
+  if ((b->ck == NULL) != (b->d_slots == NULL))
+    return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers, a plain one neither");
+  if (resume && b->ck == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
+  if (b->ck != NULL && (rc = many_clauses_check_pool(m, b))) return rc;
+  cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective);
+  const cs_walk_start *starts = (const cs_walk_start *)d_start;
+  return many_clauses_launch(m, WALK_FROM, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, &starts);
+}
+
 extern "C" int csgpu_solve_many_clauses_from(const csgpu_model *m, const csgpu_val *d_roots, const csgpu_many_start *d_start,
                                              int64_t count, const csgpu_many_options *options, csgpu_many_result *d_results,
                                              int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                              void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, d_solutions, d_best, 0, ck, d_slots, 0, 0, NULL, 1,
-                           d_start, stream);
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_from(m, &b, d_start, options, 0);
 }
 
 extern "C" int csgpu_solve_many_clauses_from_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
                                                     csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
                                                     csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, options, NULL, NULL, d_results, d_solutions, d_best, 1, ck, d_slots, 1, 0, NULL, 1,
-                           NULL, stream);
+  const many_clauses_bufs b = { NULL, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_from(m, &b, NULL, options, 1);
 }
 
 #define MANY_OBJ_CODE "the checkpoints of a MIN or a MAX walk are asked for (objective 2 or 3), not objective %d"
@@ -2625,25 +2533,44 @@ extern "C" int csgpu_many_fold_best(const csgpu_many_result *d_sub_results, cons
   return CSGPU_OK;
 }
 
-/* ---- up to k solutions per instance of a clause model (cs_walk_upto) ---- */
+/* ---- up to k solutions per instance of a clause model (cs_walk_upto): the ALL walk, left at the k-th solution, the rows
+ * [count][max_solutions][n_vars] in d_solutions ---- */
+
+/* the three entries: `pooled`, a call with a pool and slot numbers (else it has neither: the pool of capacity 0), and
+ * `resume` (pooled, no roots) */
+static int many_clauses_upto(const csgpu_model *m, const many_clauses_bufs *b, const csgpu_many_upto_options *options,
+                             int pooled, int resume) {
+  const int null_arg = m == NULL || (!resume && b->d_roots == NULL) || b->d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, pooled ? "slice" : "instance"))) return rc;
+  if (options->max_solutions < 1)
+    return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
+  if ((rc = many_clauses_check_model(m, CS_OBJ_ALL, b->count)) || (pooled && (rc = many_clauses_check_pool(m, b)))) return rc;
+  cs_walk_ck wk = many_clauses_ck_arg(b, resume, CS_WALK_CK_UPTO);
+  int upto = options->max_solutions;
+  return many_clauses_launch(m, WALK_UPTO, m->host->n_vars, CS_OBJ_ALL, options->max_nodes, b, resume, &wk, &upto);
+}
 
 extern "C" int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                              const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                              int32_t *d_solutions, void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, 0, NULL, stream);
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions };
+  return many_clauses_upto(m, &b, options, 0, 0);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                                           const csgpu_many_upto_options *options, csgpu_many_result *d_results,
                                                           int32_t *d_solutions, csgpu_many_checkpoints *ck, int32_t *d_slots,
                                                           void *stream) {
-  return many_clauses_call(m, d_roots, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 0, 0, NULL, 0, NULL, stream);
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, NULL /* no best */, ck, d_slots };
+  return many_clauses_upto(m, &b, options, 1, 0);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto_resume(const csgpu_model *m, int64_t count, const csgpu_many_upto_options *options,
                                                     csgpu_many_result *d_results, int32_t *d_solutions,
                                                     csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
-  return many_clauses_call(m, NULL, count, NULL, options, NULL, d_results, d_solutions, NULL, 1, ck, d_slots, 1, 0, NULL, 0, NULL, stream);
+  const many_clauses_bufs b = { NULL, count, d_results, stream, d_solutions, NULL /* no best */, ck, d_slots };
+  return many_clauses_upto(m, &b, options, 1, 1);
 }
 
 /* ---- Luby restarts with a seeded value order for ANY instances of a clause model (cs_walk_restart) ---- */
@@ -2652,11 +2579,21 @@ extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csg
                                                  int64_t count, const csgpu_many_restart_options *options,
                                                  csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_restarts,
                                                  void *stream) {
-  many_clauses_rs rs;
-  rs.options = options;
-  rs.d_seeds = d_seeds;
-  rs.d_restarts = d_restarts;
-  return many_clauses_call(m, d_roots, count, NULL, NULL, &rs, d_results, d_solutions, NULL, 0, NULL, NULL, 0, 0, NULL, 0, NULL, stream);
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance"))) return rc;
+  if (options->restart_base < 0) return set_err(CSGPU_E_ARG, "restart_base must not be negative (0: no restarts)");
+  if ((options->flags & ~CSGPU_MANY_ROTATE_FIRST) != 0) return set_err(CSGPU_E_ARG, "unknown flags 0x%x", (unsigned)options->flags);
+  if ((rc = many_clauses_check_model(m, CS_OBJ_ANY, count))) return rc;
+  cs_dive_rs dr;
+  dr.seeds = d_seeds;
+  dr.restarts = d_restarts;
+  dr.restart_base = (long long)options->restart_base;
+  dr.seed = options->seed;
+  dr.flags = options->flags;
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions };
+  return many_clauses_launch(m, WALK_RESTART, m->host->n_vars + 1 /* and the root node's */, CS_OBJ_ANY, options->max_nodes, &b, 0,
+                             &dr, NULL);
 }
 
 /* ---- the engine's five variable orders and interval halving for the instances of a clause model (cs_walk_order) ---- */
@@ -2664,11 +2601,24 @@ extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csg
 extern "C" int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
                                                 const csgpu_many_order_options *options, csgpu_many_result *d_results,
                                                 int32_t *d_solutions, int32_t *d_best, int64_t *d_halvings, void *stream) {
-  many_clauses_ord ord;
-  ord.options = options;
-  ord.d_halvings = d_halvings;
-  return many_clauses_call(m, d_roots, count, NULL, NULL, NULL, d_results, d_solutions, d_best, 0, NULL, NULL, 0, 0, NULL, 0, NULL,
-                           stream, &ord);
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance")) ||
+      (rc = many_clauses_check_model(m, options->objective, count)))
+    return rc;
+  /* after csgpu_solve_many_clauses's own errors, before any device call */
+  if (options->order < 0 || options->order > 4)
+    return set_err(CSGPU_E_ARG, "no variable order %d (0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value)",
+                   (int)options->order);
+  if (options->split_width < 0) return set_err(CSGPU_E_ARG, "split_width must not be negative (0: the engine's 256)");
+  if (options->reserved != 0) return set_err(CSGPU_E_ARG, "reserved must be 0");
+  cs_walk_ord wo;
+  wo.order = options->order;
+  wo.split_width = options->split_width != 0 ? options->split_width : 256;
+  wo.halvings = (long long *)d_halvings;
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best };
+  return many_clauses_launch(m, WALK_ORDER, (int)many_clauses_ordered_frames(m, options->split_width), options->objective,
+                             options->max_nodes, &b, 0, &wo, NULL);
 }
 
 /* ---- every solution of every instance of a clause model under ALL, through one bounded stream (cs_walk_stream) ---- */
@@ -2677,7 +2627,27 @@ extern "C" int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu
                                                const csgpu_many_options *options, csgpu_many_result *d_results,
                                                csgpu_many_checkpoints *ck, int32_t *d_slots, const csgpu_many_stream *out,
                                                void *stream) {
-  return many_clauses_call(m, d_roots, count, options, NULL, NULL, d_results, NULL, NULL, 1, ck, d_slots, 0, 1, out, 0, NULL, stream);
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL || ck == NULL || d_slots == NULL || out == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "slice"))) return rc;
+  /* before the model is looked at: ALL only, and a stream that can take a row */
+  if (options->objective != CS_OBJ_ALL)
+    return set_err(CSGPU_E_ARG, "csgpu_solve_many_clauses_stream walks under ALL (objective 1), not objective %d", options->objective);
+  if (out->capacity < 1)
+    return set_err(CSGPU_E_ARG, "the solution stream has room for at least one row (capacity %lld)", (long long)out->capacity);
+  if (out->d_rows == NULL || out->d_owner == NULL || out->d_count == NULL) return set_err(CSGPU_E_ARG, "null pointer in the solution stream");
+  many_clauses_bufs b = { d_roots, count, d_results, stream }; /* no rows of its own: they go to *out */
+  b.ck = ck;
+  b.d_slots = d_slots;
+  if ((rc = many_clauses_check_model(m, CS_OBJ_ALL, count)) || (rc = many_clauses_check_pool(m, &b))) return rc;
+  /* not a resume: d_slots says per instance whether it starts or goes on, so the workspace is a fresh call's */
+  cs_walk_ck wk = many_clauses_ck_arg(&b, 0, CS_WALK_CK_STREAM);
+  cs_dive_out ok;
+  ok.rows = out->d_rows;
+  ok.owner = out->d_owner;
+  ok.count = (unsigned long long *)out->d_count;
+  ok.capacity = (long long)out->capacity;
+  return many_clauses_launch(m, WALK_STREAM, m->host->n_vars, CS_OBJ_ALL, options->max_nodes, &b, 0, &wk, &ok);
 }
 
 #ifdef CS_SHAVE_TIMELINE

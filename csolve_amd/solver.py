@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -816,27 +817,34 @@ class Model:
             out = self.solve_many_clauses_upto(roots, max_solutions, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
         else:
             out = self.solve_many_clauses(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
+        return self._many_slices(out, pool, budgets, self.resume_many_clauses, obj,
+                                 self.open_clause_subtrees if finish == "search" else None, pool_capacity, max_children)
+
+    def _many_slices(self, out: dict, pool, budgets, resume, obj, open_subtrees, pool_capacity, max_children) -> dict:
+        """solve_many_sliced and solve_many_clauses_sliced after their first slice `out`: `resume` with each following
+        budget while an instance is at LIMIT; then, where the finish is a Search, every instance still at LIMIT with a slot
+        hands the (states, complete, best) of `open_subtrees` (else None) to one reused Search"""
         slices = 1
         for budget in budgets[1:]:
             if not bool((out["status"] == 1).any()):
                 break
-            self.resume_many_clauses(out, max_nodes=budget)
+            resume(out, max_nodes=budget)
             slices += 1
         searched = 0
-        if finish == "search":
+        if open_subtrees is not None:
             left = torch.nonzero((out["status"] == 1) & (out["slot"] >= 0)).flatten().tolist()
             if left:
                 search = Search(self, pool_capacity, max_children)
                 for i in left:
-                    self._finish_clauses_by_search(search, pool, out, i, obj)
+                    self._finish_by_search(search, out, i, obj, *open_subtrees(pool, int(out["slot"][i])))
                     searched += 1
                 search.close()
         out["sliced"] = {"slices": slices, "searched": searched}
         return out
 
-    def _finish_clauses_by_search(self, search: "Search", pool, out: dict, i: int, obj: int):
-        """instance i of `out`, stopped with a clause checkpoint: its open subtrees through `search`, the totals added"""
-        states, complete, best = self.open_clause_subtrees(pool, int(out["slot"][i]))
+    def _finish_by_search(self, search: "Search", out: dict, i: int, obj: int, states, complete, best):
+        """instance i of `out`, stopped with a checkpoint: its open subtrees `states` through `search` and its `complete`
+        states, each a solution, the totals added.  best: the incumbent of a clause checkpoint, or None"""
         found = int(complete.shape[0])
         bounded, ov = obj in (2, 3), self.objective_var
         first = None
@@ -1029,50 +1037,9 @@ class Model:
                     return self.solve_many_allowed(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
                 return self.solve_many(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
         pool = self.many_checkpoints(max(roots.shape[0], 1))
-        out = first_slice(pool)
-        slices = 1
-        for budget in budgets[1:]:
-            if not bool((out["status"] == 1).any()):
-                break
-            self.resume_many(out, max_nodes=budget, **more)
-            slices += 1
-        searched = 0
-        if finish == "search":
-            left = torch.nonzero((out["status"] == 1) & (out["slot"] >= 0)).flatten().tolist()
-            if left:
-                search = Search(self, pool_capacity, max_children)
-                for i in left:
-                    self._finish_by_search(search, pool, out, i, obj)
-                    searched += 1
-                search.close()
-        out["sliced"] = {"slices": slices, "searched": searched}
-        return out
-
-    def _finish_by_search(self, search: "Search", pool, out: dict, i: int, obj: int):
-        """instance i of `out`, stopped with a checkpoint: its open subtrees through `search`, the totals added"""
-        states, complete = self.open_subtrees(pool, int(out["slot"][i]))
-        found = int(complete.shape[0])
-        first = complete[0, :, 0] if found else None
-        nodes = cuts = props = 0
-        if states.shape[0] and not (obj == 0 and found):
-            search.reset()
-            search.put(states)
-            st = search.run()
-            assert st["done"] == 1
-            nodes, cuts, props = st["nodes"], st["cuts"], st["props"]
-            if st["solutions"] and first is None:
-                first = torch.from_numpy(search.solutions(1)[0].astype(np.int32)).to(states.device)
-            found += st["solutions"]
-        if obj == 0:
-            found = min(found, 1)
-        if found and int(out["solutions"][i]) == 0 and "first" in out:
-            out["first"][i] = first
-        out["solutions"][i] += found
-        out["nodes"][i] += nodes
-        out["cuts"][i] += cuts
-        out["props"][i] += props
-        out["status"][i] = 0
-        out["slot"][i] = -1
+        return self._many_slices(first_slice(pool), pool, budgets, functools.partial(self.resume_many, **more), obj,
+                                 (lambda pool, slot: (*self.open_subtrees(pool, slot), None)) if finish == "search" else None,
+                                 pool_capacity, max_children)
 
     def checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None,
                             branching="width") -> torch.Tensor:
@@ -1149,84 +1116,57 @@ class Model:
                 children=lambda pool, slots, stream=None: self.checkpoint_children(pool, slots, stream, branching="allowed"),
                 fanout=lambda pool, slots, offsets, total, stream=None: self.checkpoint_fanout(
                     pool, slots, offsets, total, stream=stream, branching="allowed"))
-        return self._spread_call(family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
+        return self._spread_call(functools.partial(self._solve_many_spread, family), family["make_pool"], family["slot_bytes"],
+                                 roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
 
-    def _spread_call(self, family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools) -> dict:
-        """solve_many_spread and solve_many_clauses_spread around their one driver: the stream and the two pools"""
+    def _spread_call(self, driver, make_pool, slot_bytes, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes,
+                     pools) -> dict:
+        """solve_many_spread and solve_many_clauses_spread around `driver`, one of the two below: the stream, the two pools
+        and what the rounds of both share (_SpreadRounds)"""
         budgets = tuple(int(b) for b in budgets)
         assert len(budgets) >= 1 and max_rounds >= 1 and max_rows >= 0
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            own_pools = pools is None
-            pools = [None, None] if own_pools else list(pools)
+            sp = _SpreadRounds(make_pool, slot_bytes, budgets, stream, int(pool_bytes), pools)
             try:
-                return self._solve_many_spread(family, roots, budgets, int(max_rounds), int(max_rows), bool(solutions), stream,
-                                               int(pool_bytes), pools, own_pools)
+                return driver(sp, roots, int(max_rounds), int(max_rows), bool(solutions), stream)
             finally:
-                if own_pools:
-                    for p in pools:
+                if sp.own_pools:
+                    for p in sp.pools:
                         if p is not None:
                             p.close()
 
-    def _solve_many_spread(self, family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools,
-                           own_pools) -> dict:
-        """the driver of solve_many_spread and solve_many_clauses_spread.  `family`: what the two differ in -- `solve` (the
-        family's solve_many, walked under "ALL"), `resume` (its resume in place), `children` and `fanout` (its count and
-        fan-out of a pool), `make_pool`, `slot_bytes` and `qualifies` (False: the solve call itself refuses the model,
-        before a pool is made for it)"""
+    def _solve_many_spread(self, family, sp, roots, max_rounds, max_rows, solutions, stream) -> dict:
+        """the driver of solve_many_spread and solve_many_clauses_spread under ALL.  `family`: what the two differ in --
+        `solve` (the family's solve_many, walked under "ALL"), `resume` (its resume in place), `children` and `fanout` (its
+        count and fan-out of a pool), `make_pool`, `slot_bytes` and `qualifies` (False: the solve call itself refuses the
+        model, before a pool is made for it)"""
         BIG = 1 << 62  # "no solution yet": above every row number
-        slot_bytes = max(family["slot_bytes"], 1)
         solve, resume = family["solve"], family["resume"]
-
-        def pool_for(rnd, batch):
-            """the pool of round `rnd`, empty: the one of round rnd - 1 is still read by the fan-out"""
-            k = rnd % 2
-            need = max(1, min(batch, pool_bytes // slot_bytes))
-            if own_pools and (pools[k] is None or pools[k].capacity < need):
-                if pools[k] is not None:
-                    pools[k].close()
-                pools[k] = family["make_pool"](need)
-            else:
-                pools[k].reset(stream)
-            return pools[k]
-
-        def budget(rnd):
-            return budgets[min(rnd, len(budgets) - 1)]
-
         if not family["qualifies"]:  # the call says why, as it does without the spread
-            solve(roots, "ALL", max_nodes=budget(0), solutions=solutions, stream=stream)
-        pool = pool_for(0, int(roots.shape[0]))
-        main = solve(roots, "ALL", max_nodes=budget(0), solutions=solutions, stream=stream, checkpoints=pool)
-        K = main["status"].shape[0]
-        dev = main["status"].device
-        limited = torch.zeros((max(K, 1),), dtype=torch.int32, device=dev)  # owners that end LIMIT
+            solve(roots, "ALL", max_nodes=sp.budget(0), solutions=solutions, stream=stream)
+        pool = sp.pool_for(0, int(roots.shape[0]))
+        main = solve(roots, "ALL", max_nodes=sp.budget(0), solutions=solutions, stream=stream, checkpoints=pool)
+        K, dev = sp.begin(main)
         pos = None  # per owner, in the row numbers of the batch: a solution of a row below it comes before the owner's `first`
-        batch, owner = main, None  # owner: int32 [T], None for round 0 (every instance is its own)
+        batch = main
         rounds, round_rows = 1, []
-
-        def owners_of(index):
-            return index if owner is None else owner.long()[index]
 
         def leave(last):
             """fold the batch and take its first solutions; its stopped instances without a slot (`last`: all its
             stopped instances) make their owners LIMIT"""
             nonlocal pos
             T = batch["status"].shape[0]
-            rows = torch.arange(T, dtype=torch.int64, device=dev)
-            stopped = batch["status"] == 1
-            if not last:
-                stopped = stopped & (batch["slot"] < 0)
-            stopped = stopped | (batch["status"] == 3)  # (a resume in place refused its slot: BAD_SLOT)
-            limited.index_add_(0, owners_of(rows), stopped.to(torch.int32))
-            if owner is not None:
-                self.fold_many(batch, owner, main, stream)
+            rows = sp.count_stopped(batch, last)
+            if sp.owner is not None:
+                self.fold_many(batch, sp.owner, main, stream)
             if not solutions:
                 return
             has = batch["solutions"] > 0
-            if owner is None:
+            if sp.owner is None:
                 pos = torch.where(has, torch.zeros_like(rows), torch.full_like(rows, BIG))
                 return
             lowest = torch.full((max(K, 1),), BIG, dtype=torch.int64, device=dev)
-            lowest.scatter_reduce_(0, owner.long(), torch.where(has, rows, torch.full_like(rows, BIG)), "amin")
+            lowest.scatter_reduce_(0, sp.owner.long(), torch.where(has, rows, torch.full_like(rows, BIG)), "amin")
             lowest = lowest[:K]
             take = lowest < pos
             src = batch["first"][lowest.clamp(max=max(T - 1, 0))]
@@ -1244,30 +1184,24 @@ class Model:
             torch.cumsum(children.clamp(min=0), 0, out=offsets[1:])
             total = int(offsets[-1].item())
             if total > max_rows:  # too wide to fan out: the stopped walks go on where they are
-                resume(batch, max_nodes=budget(rounds), stream=stream)
+                resume(batch, max_nodes=sp.budget(rounds), stream=stream)
                 round_rows.append(0)
                 rounds += 1
                 continue
-            limited.index_add_(0, owners_of(index), (children < 0).to(torch.int32))  # refused slots: their work is lost
+            sp.count_refused(index, children)
             if total == 0:
                 break
             rows, came_from = family["fanout"](pool, slots, offsets, total, stream=stream)
             leave(False)
             if solutions:
                 pos = offsets[torch.searchsorted(index, pos)]
-            owner = owners_of(index[came_from.long()]).to(torch.int32).contiguous()
-            pool = pool_for(rounds, total)
-            batch = solve(rows, "ALL", max_nodes=budget(rounds), solutions=solutions, stream=stream, checkpoints=pool)
+            sp.owner = sp.owners_of(index[came_from.long()]).to(torch.int32).contiguous()
+            pool = sp.pool_for(rounds, total)
+            batch = solve(rows, "ALL", max_nodes=sp.budget(rounds), solutions=solutions, stream=stream, checkpoints=pool)
             round_rows.append(total)
             rounds += 1
         leave(True)
-        status = main["status"]
-        status.copy_(torch.where(status == 2, status, (limited[:K] > 0).to(status.dtype)))
-        if own_pools:
-            torch.cuda.current_stream().synchronize()  # the pools go with the call
-        out = {k: v for k, v in main.items() if not k.startswith("_") and k != "slot"}
-        out["rounds"], out["sub_instances"], out["round_rows"] = rounds, sum(round_rows), round_rows
-        return out
+        return sp.answer(main, rounds, round_rows)
 
     def clause_checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, stream=None,
                                    objective=None) -> torch.Tensor:
@@ -1363,75 +1297,39 @@ class Model:
         call's; `first` is a solution of value `best`, not necessarily the one call's row."""
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         if obj in (2, 3):
-            budgets = tuple(int(b) for b in budgets)
-            assert len(budgets) >= 1 and max_rounds >= 1 and max_rows >= 0
-            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-                own_pools = pools is None
-                pools = [None, None] if own_pools else list(pools)
-                try:
-                    return self._solve_many_clauses_spread_best(roots, obj, budgets, int(max_rounds), int(max_rows),
-                                                                bool(solutions), stream, int(pool_bytes), pools, own_pools)
-                finally:
-                    if own_pools:
-                        for p in pools:
-                            if p is not None:
-                                p.close()
+            return self._spread_call(functools.partial(self._solve_many_clauses_spread_best, obj), self.many_clause_checkpoints,
+                                     self.clause_checkpoint_bytes(), roots, budgets, max_rounds, max_rows, solutions, stream,
+                                     pool_bytes, pools)
         assert obj == 1, "solve_many_clauses_spread walks under ALL, or under the model's MIN / MAX"
         family = dict(solve=self.solve_many_clauses, resume=self.resume_many_clauses, children=self.clause_checkpoint_children,
                       fanout=self.clause_checkpoint_fanout, make_pool=self.many_clause_checkpoints,
                       slot_bytes=self.clause_checkpoint_bytes(), qualifies=self.qualifies_many_clauses())
-        return self._spread_call(family, roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
+        return self._spread_call(functools.partial(self._solve_many_spread, family), family["make_pool"], family["slot_bytes"],
+                                 roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
 
-    def _solve_many_clauses_spread_best(self, roots, obj, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools,
-                                        own_pools) -> dict:
+    def _solve_many_clauses_spread_best(self, obj, sp, roots, max_rounds, max_rows, solutions, stream) -> dict:
         """the driver of solve_many_clauses_spread under MIN / MAX: the rounds of _solve_many_spread, with the incumbents"""
-        slot_bytes = max(self.clause_checkpoint_bytes(), 1)
         minimise = obj == 2
-
-        def pool_for(rnd, batch):
-            k = rnd % 2
-            need = max(1, min(batch, pool_bytes // slot_bytes))
-            if own_pools and (pools[k] is None or pools[k].capacity < need):
-                if pools[k] is not None:
-                    pools[k].close()
-                pools[k] = self.many_clause_checkpoints(need)
-            else:
-                pools[k].reset(stream)
-            return pools[k]
-
-        def budget(rnd):
-            return budgets[min(rnd, len(budgets) - 1)]
-
         if not self.qualifies_many_clauses() or self.objective != obj:  # the call says why, as it does without the spread
-            self.solve_many_clauses(roots, obj, max_nodes=budget(0), solutions=solutions, stream=stream)
-        pool = pool_for(0, int(roots.shape[0]))
-        main = self.solve_many_clauses(roots, obj, max_nodes=budget(0), solutions=solutions, stream=stream, checkpoints=pool)
-        K = main["status"].shape[0]
-        dev = main["status"].device
-        limited = torch.zeros((max(K, 1),), dtype=torch.int32, device=dev)  # owners that end LIMIT
+            self.solve_many_clauses(roots, obj, max_nodes=sp.budget(0), solutions=solutions, stream=stream)
+        pool = sp.pool_for(0, int(roots.shape[0]))
+        main = self.solve_many_clauses(roots, obj, max_nodes=sp.budget(0), solutions=solutions, stream=stream, checkpoints=pool)
+        K, dev = sp.begin(main)
         has = None  # per owner: it holds a solution; its value is main["best"], its row main["first"]
-        batch, owner = main, None  # owner: int32 [T], None for round 0 (every instance is its own)
+        batch = main
         rounds, round_rows = 1, []
-
-        def owners_of(index):
-            return index if owner is None else owner.long()[index]
 
         def leave(last):
             """fold the batch: the counters, then the best values, which replace an owner's only when strictly better; its
             stopped instances without a slot (`last`: all its stopped instances) make their owners LIMIT"""
             nonlocal has
             T = batch["status"].shape[0]
-            rows = torch.arange(T, dtype=torch.int64, device=dev)
-            stopped = batch["status"] == 1
-            if not last:
-                stopped = stopped & (batch["slot"] < 0)
-            stopped = stopped | (batch["status"] == 3)  # (a resume in place refused its slot: BAD_SLOT)
-            limited.index_add_(0, owners_of(rows), stopped.to(torch.int32))
-            if owner is None:
+            sp.count_stopped(batch, last)
+            if sp.owner is None:
                 has = batch["solutions"] > 0
                 return
-            self.fold_many(batch, owner, main, stream)
-            found, value, row = self.fold_many_best(batch, owner, K, obj, stream)
+            self.fold_many(batch, sp.owner, main, stream)
+            found, value, row = self.fold_many_best(batch, sp.owner, K, obj, stream)
             mine = main["best"]
             take = found & (~has | (value < mine if minimise else value > mine))
             if solutions:
@@ -1450,32 +1348,26 @@ class Model:
             torch.cumsum(children.clamp(min=0), 0, out=offsets[1:])
             total = int(offsets[-1].item())
             if total > max_rows:  # too wide to fan out: the stopped walks go on where they are
-                self.resume_many_clauses(batch, max_nodes=budget(rounds), stream=stream, own_solutions=owner is not None)
+                self.resume_many_clauses(batch, max_nodes=sp.budget(rounds), stream=stream, own_solutions=sp.owner is not None)
                 round_rows.append(0)
                 rounds += 1
                 continue
-            limited.index_add_(0, owners_of(index), (children < 0).to(torch.int32))  # refused slots: their work is lost
+            sp.count_refused(index, children)
             if total == 0:
                 break
             leave(False)  # before the fan-out: the children start from their owners' best after this fold
-            whose = owners_of(index)
+            whose = sp.owners_of(index)
             owner_start = torch.stack([main["best"][whose], has[whose].to(torch.int32)], 1).contiguous()
             rows, came_from, start = self.clause_checkpoint_fanout(pool, slots, offsets, total, stream=stream, objective=obj,
                                                                    owner_start=owner_start)
-            owner = whose[came_from.long()].to(torch.int32).contiguous()
-            pool = pool_for(rounds, total)
-            batch = self.solve_many_clauses(rows, obj, max_nodes=budget(rounds), solutions=solutions, stream=stream,
+            sp.owner = whose[came_from.long()].to(torch.int32).contiguous()
+            pool = sp.pool_for(rounds, total)
+            batch = self.solve_many_clauses(rows, obj, max_nodes=sp.budget(rounds), solutions=solutions, stream=stream,
                                             checkpoints=pool, start=start)
             round_rows.append(total)
             rounds += 1
         leave(True)
-        status = main["status"]
-        status.copy_(torch.where(status == 2, status, (limited[:K] > 0).to(status.dtype)))
-        if own_pools:
-            torch.cuda.current_stream().synchronize()  # the pools go with the call
-        out = {k: v for k, v in main.items() if not k.startswith("_") and k != "slot"}
-        out["rounds"], out["sub_instances"], out["round_rows"] = rounds, sum(round_rows), round_rows
-        return out
+        return sp.answer(main, rounds, round_rows)
 
     def _many_symbol(self, export: str):
         """the instantiation a family of solve_many launches for this model (template-id), by the library's `export`;
@@ -1666,6 +1558,66 @@ class Model:
         st, rounds = C.c_int32(), C.c_int32()
         check(load_library().csgpu_model_root_propagate_limit(self._h, limit, C.byref(st), C.byref(rounds)))
         return st.value, rounds.value
+
+
+class _SpreadRounds:
+    """what the rounds of the two spread drivers share (Model._solve_many_spread, Model._solve_many_clauses_spread_best):
+    the two alternating pools, the budgets, the owners of a batch's rows, the owners that end LIMIT and the answer.
+    pools: the caller's two, or None: pools of make_pool() that go with the call"""
+
+    def __init__(self, make_pool, slot_bytes, budgets, stream, pool_bytes, pools):
+        self.make_pool, self.slot_bytes, self.budgets, self.stream = make_pool, max(slot_bytes, 1), budgets, stream
+        self.pool_bytes, self.own_pools = pool_bytes, pools is None
+        self.pools = [None, None] if pools is None else list(pools)
+        self.owner = None  # int32 [T]: the owner of every row of the batch; None for round 0 (every instance is its own)
+
+    def pool_for(self, rnd, batch):
+        """the pool of round `rnd`, empty: the one of round rnd - 1 is still read by the fan-out"""
+        k = rnd % 2
+        need = max(1, min(batch, self.pool_bytes // self.slot_bytes))
+        if self.own_pools and (self.pools[k] is None or self.pools[k].capacity < need):
+            if self.pools[k] is not None:
+                self.pools[k].close()
+            self.pools[k] = self.make_pool(need)
+        else:
+            self.pools[k].reset(self.stream)
+        return self.pools[k]
+
+    def budget(self, rnd):
+        return self.budgets[min(rnd, len(self.budgets) - 1)]
+
+    def begin(self, main):
+        """round 0's answer `main` holds the owners -> (K, their device)"""
+        self.K, self.dev = main["status"].shape[0], main["status"].device
+        self.limited = torch.zeros((max(self.K, 1),), dtype=torch.int32, device=self.dev)  # owners that end LIMIT
+        return self.K, self.dev
+
+    def owners_of(self, index):
+        return index if self.owner is None else self.owner.long()[index]
+
+    def count_stopped(self, batch, last):
+        """the batch is left: its stopped instances without a slot (`last`: all its stopped instances) make their owners
+        LIMIT -> the batch's row numbers"""
+        rows = torch.arange(batch["status"].shape[0], dtype=torch.int64, device=self.dev)
+        stopped = batch["status"] == 1
+        if not last:
+            stopped = stopped & (batch["slot"] < 0)
+        stopped = stopped | (batch["status"] == 3)  # (a resume in place refused its slot: BAD_SLOT)
+        self.limited.index_add_(0, self.owners_of(rows), stopped.to(torch.int32))
+        return rows
+
+    def count_refused(self, index, children):
+        """refused slots (children < 0) among the stopped instances `index`: their work is lost"""
+        self.limited.index_add_(0, self.owners_of(index), (children < 0).to(torch.int32))
+
+    def answer(self, main, rounds, round_rows):
+        status = main["status"]
+        status.copy_(torch.where(status == 2, status, (self.limited[:self.K] > 0).to(status.dtype)))
+        if self.own_pools:
+            torch.cuda.current_stream().synchronize()  # the pools go with the call
+        out = {k: v for k, v in main.items() if not k.startswith("_") and k != "slot"}
+        out["rounds"], out["sub_instances"], out["round_rows"] = rounds, sum(round_rows), round_rows
+        return out
 
 
 class ManyCheckpoints:
