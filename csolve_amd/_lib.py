@@ -310,6 +310,13 @@ def load_library():
     L.csgpu_many_clauses_ordered_frames.argtypes = [vp, C.c_int32]
     L.csgpu_many_clauses_ordered_frames.restype = i64
     L.csgpu_internal_many_clauses_order_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_many_clause_ordered_checkpoint_bytes.argtypes = [vp, C.c_int32]
+    L.csgpu_many_clause_ordered_checkpoint_bytes.restype = C.c_size_t
+    L.csgpu_many_clause_ordered_checkpoints_create.argtypes = [vp, i64, C.c_int32, C.POINTER(vp)]
+    L.csgpu_solve_many_clauses_ordered_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyOrderOptions), vp, vp, vp, vp, vp, vp,
+                                                                vp]
+    L.csgpu_solve_many_clauses_ordered_resume.argtypes = [vp, i64, C.POINTER(ManyOrderOptions), vp, vp, vp, vp, vp, vp, vp]
+    L.csgpu_internal_many_clauses_order_resume_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_many_value.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, Val, C.c_uint32, C.c_int32]
     L.csgpu_many_value.restype = C.c_int32
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -66,10 +66,11 @@ static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "c
 #define MANY_BY_ALLOWED(family) ((family) >= MANY_ALLOWED && (family) <= MANY_ALLOWED_UPTO_CK)
 #define CS_DIVE_ALLOWED_WIDTH 128 /* the widest root domain the allowed sets of cs_dive_allowed hold (four 32-bit words) */
 
-/* the kernels of the csgpu_solve_many_clauses family (cs_walk.hip.h): one loop on kernel 6's fixpoint, compiled seven times */
-enum { WALK_PLAIN, WALK_CK, WALK_UPTO, WALK_RESTART, WALK_STREAM, WALK_FROM, WALK_ORDER, WALK_FAMILIES };
+/* the kernels of the csgpu_solve_many_clauses family (cs_walk.hip.h): one loop on kernel 6's fixpoint, compiled eight times */
+enum { WALK_PLAIN, WALK_CK, WALK_UPTO, WALK_RESTART, WALK_STREAM, WALK_FROM, WALK_ORDER, WALK_ORDER_CK, WALK_FAMILIES };
 static const char *const walk_kernel_name[WALK_FAMILIES] = { "cs_walk_clauses", "cs_walk_resume", "cs_walk_upto", "cs_walk_restart",
-                                                             "cs_walk_stream", "cs_walk_from", "cs_walk_order" };
+                                                             "cs_walk_stream", "cs_walk_from", "cs_walk_order",
+                                                             "cs_walk_order_resume" };
 
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
 struct cs_kernel_plan {
@@ -854,6 +855,7 @@ static const void *walk_kernel(int family, int cpl, int tree) {
   case WALK_STREAM: CS_PICK(cs_walk_stream)   /* ALL, every solution appended to a shared stream (csgpu_solve_many_clauses_stream) */
   case WALK_FROM: CS_PICK(cs_walk_from)       /* MIN / MAX from a start incumbent (csgpu_solve_many_clauses_from / _from_resume) */
   case WALK_ORDER: CS_PICK(cs_walk_order)     /* the five variable orders, interval halving (csgpu_solve_many_clauses_ordered) */
+  case WALK_ORDER_CK: CS_PICK(cs_walk_order_resume) /* that walk with checkpoints (csgpu_solve_many_clauses_ordered_checkpointed / _resume) */
   default: CS_PICK(cs_walk_clauses)
   }
 #undef CS_PICK
@@ -1373,6 +1375,7 @@ MANY_SYMBOL(csgpu_internal_many_clauses_restart_symbol, walk, walk_kernel_name, 
 MANY_SYMBOL(csgpu_internal_many_clauses_stream_symbol, walk, walk_kernel_name, WALK_STREAM)
 MANY_SYMBOL(csgpu_internal_many_clauses_from_symbol, walk, walk_kernel_name, WALK_FROM)
 MANY_SYMBOL(csgpu_internal_many_clauses_order_symbol, walk, walk_kernel_name, WALK_ORDER)
+MANY_SYMBOL(csgpu_internal_many_clauses_order_resume_symbol, walk, walk_kernel_name, WALK_ORDER_CK)
 #undef MANY_SYMBOL
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
@@ -1649,12 +1652,17 @@ struct csgpu_many_checkpoints {
   cs_val *d_pool;
   unsigned long long *d_next; /* slots handed out since the last reset */
   int counted;                /* the model counts this pool among the objects that hold its device tables */
-  int kind;                   /* MANY_POOL_DIVE: of csgpu_many_checkpoints_create; MANY_POOL_WALK: of the clause one */
-  int *d_zero;                /* MANY_POOL_WALK: n_vars zeros, the offsets cs_dive_export adds to absolute bounds */
+  int kind;                   /* MANY_POOL_DIVE: of csgpu_many_checkpoints_create; MANY_POOL_WALK: of the clause one;
+                                 MANY_POOL_ORDER: of csgpu_many_clause_ordered_checkpoints_create */
+  int *d_zero;                /* the clause kinds: n_vars zeros, the offsets cs_dive_export adds to absolute bounds */
+  int frames;                 /* the frames a slot has for a stack: n_vars, MANY_POOL_ORDER: csgpu_many_clauses_ordered_frames */
+  int split_width;            /* MANY_POOL_ORDER: the split_width the pool was made for (never 0: 256 stands there) */
 };
-enum { MANY_POOL_DIVE, MANY_POOL_WALK };
+enum { MANY_POOL_DIVE, MANY_POOL_WALK, MANY_POOL_ORDER };
 #define MANY_POOL_KIND "the checkpoint pool is of the other kind: csgpu_many_checkpoints_create makes the pools of csgpu_solve_many, " \
                        "csgpu_many_clause_checkpoints_create those of csgpu_solve_many_clauses"
+#define MANY_POOL_KIND_ORDER "the checkpoint pool is of the other kind: csgpu_many_clause_ordered_checkpoints_create makes the pools of " \
+                             "csgpu_solve_many_clauses_ordered_checkpointed / _resume, and only those"
 
 extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count) {
   if (m == NULL || !m->finalized || m->plan.dive[MANY_PLAIN].fn == NULL || count < 1) return 0;
@@ -1788,7 +1796,7 @@ extern "C" size_t csgpu_many_checkpoint_bytes(const csgpu_model *m) {
 
 /* the pool of either kind, after the checks of its create call; `qualifies`: may the model's kernels of that kind run? */
 static int many_pool_create(const csgpu_model *m, int64_t capacity, int kind, int qualifies, const char *limit, size_t slot_bytes,
-                            csgpu_many_checkpoints **out) {
+                            int frames, int split_width, csgpu_many_checkpoints **out) {
   if (m == NULL || out == NULL) return set_err(CSGPU_E_ARG, "null argument");
   if (capacity < 1) return set_err(CSGPU_E_ARG, "a checkpoint pool has at least one slot");
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
@@ -1800,13 +1808,15 @@ static int many_pool_create(const csgpu_model *m, int64_t capacity, int kind, in
   ck->capacity = capacity;
   ck->slot_bytes = slot_bytes;
   ck->kind = kind;
+  ck->frames = frames;
+  ck->split_width = split_width;
   const size_t zero_bytes = (size_t)m->host->n_vars * sizeof(int);
   hipError_t e;
   if ((e = hipMalloc((void **)&ck->d_pool, (size_t)capacity * ck->slot_bytes)) != hipSuccess ||
       (e = hipMalloc((void **)&ck->d_next, sizeof *ck->d_next)) != hipSuccess ||
       (e = hipMemset(ck->d_pool, 0, (size_t)capacity * ck->slot_bytes)) != hipSuccess || /* no slot holds a checkpoint */
       (e = hipMemset(ck->d_next, 0, sizeof *ck->d_next)) != hipSuccess ||
-      (kind == MANY_POOL_WALK && ((e = hipMalloc((void **)&ck->d_zero, zero_bytes)) != hipSuccess ||
+      (kind != MANY_POOL_DIVE && ((e = hipMalloc((void **)&ck->d_zero, zero_bytes)) != hipSuccess ||
                                   (e = hipMemset(ck->d_zero, 0, zero_bytes)) != hipSuccess))) {
     csgpu_many_checkpoints_free(ck);
     return set_err(CSGPU_E_HIP, "checkpoint pool of %lld slots: %s", (long long)capacity, hipGetErrorString(e));
@@ -1819,7 +1829,8 @@ static int many_pool_create(const csgpu_model *m, int64_t capacity, int kind, in
 
 extern "C" int csgpu_many_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out) {
   return many_pool_create(m, capacity, MANY_POOL_DIVE, m != NULL && m->finalized && m->plan.dive[MANY_CK].fn != NULL,
-                          MANY_NOT_QUALIFIED ", which csgpu_solve_many is built on", csgpu_many_checkpoint_bytes(m), out);
+                          MANY_NOT_QUALIFIED ", which csgpu_solve_many is built on", csgpu_many_checkpoint_bytes(m),
+                          m != NULL ? m->host->n_vars : 0, 0, out);
 }
 
 extern "C" int csgpu_many_checkpoints_reset(csgpu_many_checkpoints *ck, void *stream) {
@@ -1863,28 +1874,29 @@ extern "C" int csgpu_solve_many_resume(const csgpu_model *m, int64_t count, cons
   return many_ck_call(m, NULL, count, options, d_results, d_solutions, ck, d_slots, 1, stream);
 }
 
-/* the open subtrees of a slot of either kind: `head`, if wanted, receives the header's first two entries.  A clause pool
- * holds absolute bounds: cs_dive_export adds the pool's zeros to them */
+/* the open subtrees of a slot of any kind: `head`, if wanted, receives the header's first two entries.  A clause pool
+ * holds absolute bounds: cs_dive_export adds the pool's zeros to them.  A slot has ck->frames + 1 frames, depth < ck->frames */
 static int many_pool_states(const csgpu_many_checkpoints *ck, int kind, int32_t slot, csgpu_val *d_states, int64_t cap,
                             int64_t *count, cs_val *head2, void *stream) {
   if (ck == NULL || d_states == NULL || count == NULL || cap < 0) return set_err(CSGPU_E_ARG, "null argument");
   if (ck->kind != kind) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
   if (slot < 0 || slot >= ck->capacity) return set_err(CSGPU_E_ARG, "no slot %d in a pool of %lld", slot, (long long)ck->capacity);
   const int n = ck->m->host->n_vars;
-  const cs_val *base = ck->d_pool + (size_t)slot * ((size_t)n + 1) * ((size_t)n + 1);
+  const cs_val *base = ck->d_pool + (size_t)slot * ((size_t)ck->frames + 1) * ((size_t)n + 1);
   cs_val header[2];
   HIP_TRY(hipMemcpyAsync(header, base, sizeof header, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   const cs_val head = header[0];
-  const int magic_ok = kind == MANY_POOL_WALK ? head.hi == CS_WALK_CK_MAGIC /* a dive pool: a slot of either walk */
-                                              : head.hi == CS_DIVE_CK_MAGIC || head.hi == CS_DIVE_CK_MAGIC_ALLOWED;
-  if (!magic_ok || head.lo < 0 || head.lo >= n)
+  const int magic_ok = kind == MANY_POOL_WALK    ? head.hi == CS_WALK_CK_MAGIC
+                       : kind == MANY_POOL_ORDER ? head.hi == CS_WALK_CK_MAGIC_ORDER /* a dive pool: a slot of either walk */
+                                                 : head.hi == CS_DIVE_CK_MAGIC || head.hi == CS_DIVE_CK_MAGIC_ALLOWED;
+  if (!magic_ok || head.lo < 0 || head.lo >= ck->frames)
     return set_err(CSGPU_E_STATE, "slot %d holds no checkpoint", slot);
   if (head2 != NULL) { head2[0] = header[0]; head2[1] = header[1]; }
   *count = (int64_t)head.lo + 1;
   if (cap < *count)
     return set_err(CSGPU_E_LIMIT, "the checkpoint has %lld open subtrees, the buffer holds %lld", (long long)*count, (long long)cap);
-  const int *root_lo_d = kind == MANY_POOL_WALK ? ck->d_zero : ck->m->d_root_lo;
+  const int *root_lo_d = kind != MANY_POOL_DIVE ? ck->d_zero : ck->m->d_root_lo;
   hipLaunchKernelGGL(cs_dive_export, dim3((unsigned)*count), dim3(CS_WAVE), 0, (hipStream_t)stream, n, root_lo_d, base,
                      (cs_val *)d_states);
   HIP_TRY(hipGetLastError());
@@ -2270,10 +2282,11 @@ struct many_clauses_bufs {
   int32_t *d_slots;
 };
 
-static int many_clauses_check_pool(const csgpu_model *m, const many_clauses_bufs *b) {
+/* `kind`: MANY_POOL_WALK, or the ordered entries' MANY_POOL_ORDER, which take no pool of either older kind */
+static int many_clauses_check_pool(const csgpu_model *m, const many_clauses_bufs *b, int kind) {
   if (b->ck == NULL || b->d_slots == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
   if (b->ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
-  if (b->ck->kind != MANY_POOL_WALK) return set_err(CSGPU_E_ARG, MANY_POOL_KIND);
+  if (b->ck->kind != kind) return set_err(CSGPU_E_ARG, kind == MANY_POOL_ORDER ? MANY_POOL_KIND_ORDER : MANY_POOL_KIND);
   return CSGPU_OK;
 }
 
@@ -2357,7 +2370,7 @@ extern "C" size_t csgpu_many_clause_checkpoint_bytes(const csgpu_model *m) {
 extern "C" int csgpu_many_clause_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out) {
   return many_pool_create(m, capacity, MANY_POOL_WALK, csgpu_model_qualifies_many_clauses(m),
                           "model does not qualify for csgpu_solve_many_clauses (kernel 6 planned, its LDS slices fit a CU)",
-                          csgpu_many_clause_checkpoint_bytes(m), out);
+                          csgpu_many_clause_checkpoint_bytes(m), m != NULL ? m->host->n_vars : 0, 0, out);
 }
 
 /* the checkpointed call and its resume (no roots): cs_walk_resume under the options' objective, which is the checkpoints' code */
@@ -2365,7 +2378,7 @@ static int many_clauses_pooled(const csgpu_model *m, const many_clauses_bufs *b,
   const int null_arg = m == NULL || (!resume && b->d_roots == NULL) || b->d_results == NULL || options == NULL;
   int rc;
   if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, "slice")) ||
-      (rc = many_clauses_check_model(m, options->objective, b->count)) || (rc = many_clauses_check_pool(m, b)))
+      (rc = many_clauses_check_model(m, options->objective, b->count)) || (rc = many_clauses_check_pool(m, b, MANY_POOL_WALK)))
     return rc;
   cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective);
   return many_clauses_launch(m, WALK_CK, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, NULL);
@@ -2390,7 +2403,9 @@ extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints 
                                                    int64_t *count, int32_t *best, int32_t *have_best, void *stream) {
   if (best == NULL || have_best == NULL) return set_err(CSGPU_E_ARG, "null argument");
   cs_val header[2] = { cs_interval(0, 0), cs_interval(0, 0) };
-  const int rc = many_pool_states(ck, MANY_POOL_WALK, slot, d_states, cap, count, header, stream);
+  /* a pool of either clause kind: an ordered one has the same frames, more of them, under its own magic */
+  const int kind = ck != NULL && ck->kind == MANY_POOL_ORDER ? MANY_POOL_ORDER : MANY_POOL_WALK;
+  const int rc = many_pool_states(ck, kind, slot, d_states, cap, count, header, stream);
   if (rc == CSGPU_OK || rc == CSGPU_E_LIMIT) { /* (a buffer too small: *count and the incumbent are set all the same) */
     *best = header[1].lo;
     *have_best = header[1].hi & 1;
@@ -2469,7 +2484,7 @@ static int many_clauses_from(const csgpu_model *m, const many_clauses_bufs *b, c
   if ((b->ck == NULL) != (b->d_slots == NULL))
     return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers, a plain one neither");
   if (resume && b->ck == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
-  if (b->ck != NULL && (rc = many_clauses_check_pool(m, b))) return rc;
+  if (b->ck != NULL && (rc = many_clauses_check_pool(m, b, MANY_POOL_WALK))) return rc;
   cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective);
   const cs_walk_start *starts = (const cs_walk_start *)d_start;
   return many_clauses_launch(m, WALK_FROM, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, &starts);
@@ -2545,7 +2560,7 @@ static int many_clauses_upto(const csgpu_model *m, const many_clauses_bufs *b, c
   if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, pooled ? "slice" : "instance"))) return rc;
   if (options->max_solutions < 1)
     return set_err(CSGPU_E_ARG, "max_solutions must be at least 1: an instance stops at its k-th solution");
-  if ((rc = many_clauses_check_model(m, CS_OBJ_ALL, b->count)) || (pooled && (rc = many_clauses_check_pool(m, b)))) return rc;
+  if ((rc = many_clauses_check_model(m, CS_OBJ_ALL, b->count)) || (pooled && (rc = many_clauses_check_pool(m, b, MANY_POOL_WALK)))) return rc;
   cs_walk_ck wk = many_clauses_ck_arg(b, resume, CS_WALK_CK_UPTO);
   int upto = options->max_solutions;
   return many_clauses_launch(m, WALK_UPTO, m->host->n_vars, CS_OBJ_ALL, options->max_nodes, b, resume, &wk, &upto);
@@ -2598,13 +2613,15 @@ extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csg
 
 /* ---- the engine's five variable orders and interval halving for the instances of a clause model (cs_walk_order) ---- */
 
-extern "C" int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
-                                                const csgpu_many_order_options *options, csgpu_many_result *d_results,
-                                                int32_t *d_solutions, int32_t *d_best, int64_t *d_halvings, void *stream) {
-  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+/* the three entries: the plain call, and with `pooled` the checkpointed call and its `resume` (no roots): cs_walk_order, or
+ * cs_walk_order_resume on a pool of the ordered kind.  The checks, none of which touches the device, in the documented
+ * order: csgpu_solve_many_clauses's own, this walk's three, then what a pooled call adds */
+static int many_clauses_ordered(const csgpu_model *m, const many_clauses_bufs *b, const csgpu_many_order_options *options,
+                                int64_t *d_halvings, int pooled, int resume) {
+  const int null_arg = m == NULL || (!resume && b->d_roots == NULL) || b->d_results == NULL || options == NULL;
   int rc;
-  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance")) ||
-      (rc = many_clauses_check_model(m, options->objective, count)))
+  if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, pooled ? "slice" : "instance")) ||
+      (rc = many_clauses_check_model(m, options->objective, b->count)))
     return rc;
   /* after csgpu_solve_many_clauses's own errors, before any device call */
   if (options->order < 0 || options->order > 4)
@@ -2616,9 +2633,60 @@ extern "C" int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgp
   wo.order = options->order;
   wo.split_width = options->split_width != 0 ? options->split_width : 256;
   wo.halvings = (long long *)d_halvings;
+  if (!pooled)
+    return many_clauses_launch(m, WALK_ORDER, (int)many_clauses_ordered_frames(m, options->split_width), options->objective,
+                               options->max_nodes, b, 0, &wo, NULL);
+  if (d_halvings == NULL)
+    return set_err(CSGPU_E_ARG, "null argument: d_halvings, which a resumed instance's halving count goes on from");
+  if ((rc = many_clauses_check_pool(m, b, MANY_POOL_ORDER))) return rc;
+  if (b->ck->split_width != wo.split_width)
+    return set_err(CSGPU_E_ARG, "the checkpoint pool was made for split_width %d, the call asks for %d: the frames of a slot differ",
+                   b->ck->split_width, wo.split_width);
+  /* a checkpoint goes on under the objective and the order it was made under: another of either is another tree */
+  cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective | options->order << 3);
+  return many_clauses_launch(m, WALK_ORDER_CK, b->ck->frames, options->objective, options->max_nodes, b, resume, &wk, &wo);
+}
+
+extern "C" int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                const csgpu_many_order_options *options, csgpu_many_result *d_results,
+                                                int32_t *d_solutions, int32_t *d_best, int64_t *d_halvings, void *stream) {
   const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best };
-  return many_clauses_launch(m, WALK_ORDER, (int)many_clauses_ordered_frames(m, options->split_width), options->objective,
-                             options->max_nodes, &b, 0, &wo, NULL);
+  return many_clauses_ordered(m, &b, options, d_halvings, 0, 0);
+}
+
+/* ---- the ordered walk in slices (cs_walk_order_resume): a pool whose slots have the frames of that walk ---- */
+
+extern "C" size_t csgpu_many_clause_ordered_checkpoint_bytes(const csgpu_model *m, int32_t split_width) {
+  if (m == NULL || split_width < 0 || !many_clauses_qualifies(m)) return 0;
+  /* the header frame and the frames of a wave's stack (at most 33 n of them): 64 bits throughout */
+  return ((size_t)many_clauses_ordered_frames(m, split_width) + 1) * ((size_t)m->host->n_vars + 1) * sizeof(cs_val);
+}
+
+extern "C" int csgpu_many_clause_ordered_checkpoints_create(const csgpu_model *m, int64_t capacity, int32_t split_width,
+                                                            csgpu_many_checkpoints **out) {
+  if (split_width < 0) return set_err(CSGPU_E_ARG, "split_width must not be negative (0: the engine's 256)");
+  const int qualifies = csgpu_model_qualifies_many_clauses(m);
+  return many_pool_create(m, capacity, MANY_POOL_ORDER, qualifies,
+                          "model does not qualify for csgpu_solve_many_clauses (kernel 6 planned, its LDS slices fit a CU)",
+                          csgpu_many_clause_ordered_checkpoint_bytes(m, split_width),
+                          qualifies ? (int)many_clauses_ordered_frames(m, split_width) : 0, split_width != 0 ? split_width : 256, out);
+}
+
+extern "C" int csgpu_solve_many_clauses_ordered_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                             const csgpu_many_order_options *options,
+                                                             csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                                             int64_t *d_halvings, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                                             void *stream) {
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_ordered(m, &b, options, d_halvings, 1, 0);
+}
+
+extern "C" int csgpu_solve_many_clauses_ordered_resume(const csgpu_model *m, int64_t count, const csgpu_many_order_options *options,
+                                                       csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                                       int64_t *d_halvings, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                                       void *stream) {
+  const many_clauses_bufs b = { NULL, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_ordered(m, &b, options, d_halvings, 1, 1);
 }
 
 /* ---- every solution of every instance of a clause model under ALL, through one bounded stream (cs_walk_stream) ---- */
@@ -2639,7 +2707,7 @@ extern "C" int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu
   many_clauses_bufs b = { d_roots, count, d_results, stream }; /* no rows of its own: they go to *out */
   b.ck = ck;
   b.d_slots = d_slots;
-  if ((rc = many_clauses_check_model(m, CS_OBJ_ALL, count)) || (rc = many_clauses_check_pool(m, &b))) return rc;
+  if ((rc = many_clauses_check_model(m, CS_OBJ_ALL, count)) || (rc = many_clauses_check_pool(m, &b, MANY_POOL_WALK))) return rc;
   /* not a resume: d_slots says per instance whether it starts or goes on, so the workspace is a fresh call's */
   cs_walk_ck wk = many_clauses_ck_arg(&b, 0, CS_WALK_CK_STREAM);
   cs_dive_out ok;

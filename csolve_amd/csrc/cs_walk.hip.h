@@ -94,7 +94,24 @@
  * values makes two children, [lo, mid] and [mid + 1, hi], in place of one per value.  Kind and mid are scalars read from
  * the node as it was entered; a frame's {variable, next} keeps its 8 bytes, next = mid + 1 for a halving node, whose kind
  * is read back from the frame's row.  A pushed halving parent values no variable, so the frames per wave are the host's
- * bound n + sum of h(v), not n. */
+ * bound n + sum of h(v), not n.
+ *
+ * The ordered walk with checkpoints (cs_walk_order_resume, csgpu_solve_many_clauses_ordered_checkpointed / _resume): the
+ * same loop an eighth time, CS_WALK_CK 1 and CS_WALK_ORDER 1.  With F = io.frames, the host's bound above:
+ *
+ *   slot = F + 1 frames of n + 1 entries (8 bytes each), bounds absolute
+ *   frame 0           the header: entry 0 = {depth, CS_WALK_CK_MAGIC_ORDER}, entry 1 = {best, have_best | code << 1},
+ *                     code = objective | order << 3
+ *   frame 1 + d       pushed frame d (d < depth <= F - 1): the row, then {variable, next value or mid + 1}
+ *   frame 1 + depth   the current node as it was entered, with {bv, nv} behind it
+ *
+ * F + 1 and not n + 1 frames, because up to F - 1 parents are pushed under the current node.  A resume under another
+ * objective or another order would walk another tree: its code differs, CSGPU_MANY_BAD_SLOT.  A pool is made for one
+ * split_width (the host compares it), which fixes F for the fresh and the resume launch.  The halving count goes on from
+ * ord.halvings[inst] as the other counters go on from the record; a walk stopped between the two halves of a node finds
+ * nv == mid + 1 in its frame and counts the parent once.  cs_walk_children / cs_walk_fanout do not read these slots (the
+ * host refuses the pool): a fan-out of halves would have to account for `halvings`.
+ * Resources (-Rpass-analysis=kernel-resource-usage, gfx950) are in DESIGN.md 3.10. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
 
@@ -143,12 +160,12 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk
 
 /* the checkpoint pool and the slot numbers of a call (cs_walk_resume) */
 struct cs_walk_ck {
-  cs_val *pool;             /* [capacity][n + 1][n + 1] */
+  cs_val *pool;             /* [capacity][n + 1][n + 1]; cs_walk_order_resume: [capacity][io.frames + 1][n + 1] */
   unsigned long long *next; /* slots handed out since the last reset (it counts on past capacity) */
   int capacity;             /* cs_walk_upto: 0 = no pool (pool, next and slots are not touched) */
   int resume;               /* 0: fresh instances from io.roots; 1: instance i goes on from slot slots[i] */
   int code;                 /* the call's objective, 0 ANY .. 3 MAX, CS_WALK_CK_UPTO or CS_WALK_CK_STREAM: a checkpoint goes on
-                               under the one it was made under */
+                               under the one it was made under; cs_walk_order_resume: objective | order << 3 */
   int *slots;               /* [count]: the slot of an instance stopped with a checkpoint, else -1 */
 };
 
@@ -256,7 +273,7 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_from(cs_tables T, cs_walk_io
 struct cs_walk_ord {
   int order;           /* cs_order_key's: 0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value */
   int split_width;     /* >= 1: a branching variable of more values is halved, not enumerated */
-  long long *halvings; /* [count] or NULL: parents split in two */
+  long long *halvings; /* [count] or NULL: parents split in two; cs_walk_order_resume: [count], read back by a resumed instance */
 };
 
 /* cs_walk_clauses's walk under one of the engine's five variable orders, with intervals of more than split_width values
@@ -266,6 +283,28 @@ struct cs_walk_ord {
 template <int CPL, bool HAS_TREE>
 __global__ __launch_bounds__(CS_BLOCK) void cs_walk_order(cs_tables T, cs_walk_io io, cs_walk_ord ord) {
 #define CS_WALK_CK 0
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
+#define CS_WALK_ORDER 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
+#undef CS_WALK_FROM
+#undef CS_WALK_STREAM
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+#define CS_WALK_CK_MAGIC_ORDER 0x776f6b70 /* header entry 0 .hi of a slot of cs_walk_order_resume: F + 1 frames, not n + 1 */
+
+/* cs_walk_order's walk with cs_walk_resume's checkpoints (csgpu_solve_many_clauses_ordered_checkpointed / _resume): the same
+ * loop an eighth time, CS_WALK_CK 1 and CS_WALK_ORDER 1.  A slot is io.frames + 1 frames, ck.code objective | order << 3,
+ * ord.halvings is required and read back by a resumed instance */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_order_resume(cs_tables T, cs_walk_io io, cs_walk_ck ck, cs_walk_ord ord) {
+#define CS_WALK_CK 1
 #define CS_WALK_UPTO 0
 #define CS_WALK_RESTART 0
 #define CS_WALK_STREAM 0

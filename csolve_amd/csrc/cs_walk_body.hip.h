@@ -1,4 +1,4 @@
-/* cs_walk_body.hip.h -- the body of the seven kernels of cs_walk.hip.h, which includes it inside each of them under six
+/* cs_walk_body.hip.h -- the body of the eight kernels of cs_walk.hip.h, which includes it inside each of them under six
  * switches (the fifth, CS_WALK_FROM, is 1 for cs_walk_from alone: cs_walk_resume's row, and `start`; the sixth,
  * CS_WALK_ORDER, for cs_walk_order alone: cs_walk_clauses's row, and `ord`):
  *                      CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART  CS_WALK_STREAM
@@ -8,6 +8,7 @@
  *   cs_walk_restart        0           0              1              0       one more argument, `rs` (the walk is defined in csolve_gpu.h)
  *   cs_walk_stream         1           0              0              1       `ck` and `out`, the solution stream of the call
  *   cs_walk_order          0           0              0              0       one more argument, `ord`: the order, split_width, the halving counts
+ *   cs_walk_order_resume   1           0              0              0       CS_WALK_ORDER 1 as well: `ck`, then `ord`
  * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of a switch stands under its `#if`, so a kernel
  * that defines it 0 sees the text it saw before the switch was there and compiles to the same instructions.
  * CS_WALK_CK: an instance that stops at its budget leaves its frames, its current node, {bv, nv} and its incumbent in a
@@ -39,7 +40,13 @@
  * was entered (the slice when `fresh`, else its frame's row), before lane 0 writes the child and the incumbent's bound, so
  * a popped frame makes the same children; nv is the child's lower bound in both kinds, and a frame's entry {variable,
  * next}: the next value, or mid + 1.  io.frames is the host's bound (csgpu_many_clauses_ordered_frames).  New per-instance
- * state is scalars only: halvings, then. */
+ * state is scalars only: halvings, then.
+ * CS_WALK_CK && CS_WALK_ORDER (cs_walk_order_resume alone): the ordered walk with cs_walk_resume's checkpoints.  A pushed
+ * halving parent values no variable, so a slot has io.frames + 1 frames, not n + 1 (CS_WALK_SLOT), its depth is bounded
+ * by io.frames, not n (CS_WALK_SLOT_FRAMES), and its header carries a magic of its own (CS_WALK_SLOT_MAGIC); the three
+ * names stand for the old text in every other kernel.  ck.code is objective | order << 3, and a resumed instance's
+ * halving count goes on from ord.halvings[inst].  A frame needs nothing new: {bv, nv} says where a halving node stands
+ * (nv == lo: no half tried yet, nv == mid + 1: the second is next), kind and mid are read back from the frame's row. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -65,6 +72,16 @@
   unsigned *my_ticket = io.tickets + (size_t)shard * CS_DIVE_TICKET_STRIDE;
   const size_t fstride = (size_t)n + 1;
   cs_val *const wave_stack = io.stack + (size_t)wave_global * (size_t)io.frames * fstride;
+  /* a slot's entries, the frames it has for a stack, and the word that marks its header */
+#if CS_WALK_CK && CS_WALK_ORDER
+#define CS_WALK_SLOT (((size_t)io.frames + 1) * fstride)
+#define CS_WALK_SLOT_FRAMES io.frames
+#define CS_WALK_SLOT_MAGIC CS_WALK_CK_MAGIC_ORDER
+#else
+#define CS_WALK_SLOT (fstride * fstride)
+#define CS_WALK_SLOT_FRAMES n
+#define CS_WALK_SLOT_MAGIC CS_WALK_CK_MAGIC
+#endif
 
   for (;;) {
     /* the wave meets here before lane 0 draws (cs_dive_body.hip.h: without it the launch never ends) */
@@ -115,20 +132,20 @@
 #endif
       cs_val head = cs_interval(-1, 0), inc = cs_interval(0, -2);
       if (slot < ck.capacity) { /* compared before it is read; the two header entries, nothing else of the slot yet */
-        const cs_val *base = ck.pool + (size_t)slot * (fstride * fstride);
+        const cs_val *base = ck.pool + (size_t)slot * CS_WALK_SLOT;
         head = base[0];
         inc = base[1];
       }
       depth0 = __builtin_amdgcn_readfirstlane(head.lo);
       const int word = __builtin_amdgcn_readfirstlane(inc.hi); /* have_best | objective code << 1 */
-      if (depth0 < 0 || depth0 >= n || __builtin_amdgcn_readfirstlane(head.hi) != CS_WALK_CK_MAGIC || (word >> 1) != ck.code) {
+      if (depth0 < 0 || depth0 >= CS_WALK_SLOT_FRAMES || __builtin_amdgcn_readfirstlane(head.hi) != CS_WALK_SLOT_MAGIC || (word >> 1) != ck.code) {
         if (lane == 0) io.results[inst].status = 3; /* CSGPU_MANY_BAD_SLOT */
         continue;
       }
       resumed = true;
       best0 = __builtin_amdgcn_readfirstlane(inc.lo);
       have_best0 = (word & 1) != 0;
-      stack = ck.pool + (size_t)slot * (fstride * fstride) + fstride;
+      stack = ck.pool + (size_t)slot * CS_WALK_SLOT + fstride;
     }
 #endif
 #if CS_WALK_FROM
@@ -170,6 +187,9 @@
       props = cs_dive_uniform(was->props);
       sols = cs_dive_uniform(was->solutions);
       nodes = nodes0;
+#if CS_WALK_ORDER
+      halvings = cs_dive_uniform(ord.halvings[inst]); /* the host requires the array: the count goes on as the record's do */
+#endif
       best = best0;
       have_best = have_best0;
 #if CS_WALK_UPTO
@@ -259,9 +279,9 @@
               const unsigned dhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(drawn >> 32));
               slot = dhi == 0u && dlo < (unsigned)ck.capacity ? (int)dlo : -1;
             }
-            if (depth >= n) slot = -1; /* cannot happen (at most n frames in use): never write past the slot */
+            if (depth >= CS_WALK_SLOT_FRAMES) slot = -1; /* cannot happen (at most n frames in use; cs_walk_order_resume: io.frames): never write past the slot */
             if (slot >= 0) {
-              cs_val *base = ck.pool + (size_t)slot * (fstride * fstride);
+              cs_val *base = ck.pool + (size_t)slot * CS_WALK_SLOT;
               cs_val *frames = base + fstride;
               if (!resumed) { /* the frames in use and the current node's, every lane the entries it wrote */
                 for (int d = 0; d <= depth; d++) {
@@ -273,7 +293,7 @@
               }
               if (lane == 0) {
                 frames[(size_t)depth * fstride + n] = cs_interval(bv, nv);
-                base[0] = cs_interval(depth, CS_WALK_CK_MAGIC);
+                base[0] = cs_interval(depth, CS_WALK_SLOT_MAGIC);
                 base[1] = cs_interval(best, (have_best ? 1 : 0) | (ck.code << 1));
               }
             }
@@ -512,3 +532,6 @@
     }
     cs_wave_sync(); /* the next instance's root row goes into the slice only after every lane has left this one */
   }
+#undef CS_WALK_SLOT_MAGIC
+#undef CS_WALK_SLOT_FRAMES
+#undef CS_WALK_SLOT

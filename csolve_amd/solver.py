@@ -604,7 +604,7 @@ class Model:
     MANY_ORDERS = {"none": 0, "smallest-domain": 1, "largest-domain": 2, "smallest-value": 3, "largest-value": 4}
 
     def solve_many_clauses_ordered(self, roots, objective="ANY", *, max_nodes, order="smallest-domain", split_width=256,
-                                   solutions=True, stream=None) -> dict:
+                                   solutions=True, stream=None, checkpoints=None) -> dict:
         """solve_many_clauses under one of the engine's five variable orders, with wide intervals halved
         (csgpu_solve_many_clauses_ordered): the same walk, but the branching variable is the open one the order puts
         first -- "none", "smallest-domain", "largest-domain", "smallest-value", "largest-value", the names of
@@ -612,7 +612,12 @@ class Model:
         values (>= 1) has two children, [lo, mid] and [mid + 1, hi] with mid = (lo + hi) >> 1, instead of one per value.
         A row that leaves a variable at its root width (an open `end` of a schedule) is then bisected, not enumerated.
         roots, objective, max_nodes, solutions, stream: as solve_many_clauses.  -> the dict of solve_many_clauses and
-        `halvings` [K] int64: the parents split in two.  No checkpoints, no start incumbents."""
+        `halvings` [K] int64: the parents split in two.  No start incumbents.
+        checkpoints: a pool of many_clause_ordered_checkpoints(capacity, split_width), made for this split_width: an
+        instance that stops at max_nodes keeps its walk, its incumbent and its place between two halves in a slot of it
+        (csgpu_solve_many_clauses_ordered_checkpointed); the answer then has `slot` [K] int32 (-1: no checkpoint) and is
+        what resume_many_clauses() continues, under the same objective, order and split_width.  A walk in slices is the one
+        call with the summed budget, field for field, `halvings` included.  Without it nothing changes."""
         L = load_library()
         n = self.n_vars
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
@@ -627,11 +632,22 @@ class Model:
         first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
         best = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if obj in (2, 3) else None
         halvings = torch.zeros((max(K, 1),), dtype=torch.int64, device=roots.device)
-        check(L.csgpu_solve_many_clauses_ordered(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
-                                                 buf.data_ptr(), first.data_ptr() if solutions and K else None,
-                                                 best.data_ptr() if best is not None else None, halvings.data_ptr(),
-                                                 _stream_ptr(stream)))
-        out = self._many_answer(buf, K, first)
+        if checkpoints is None:
+            check(L.csgpu_solve_many_clauses_ordered(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
+                                                     buf.data_ptr(), first.data_ptr() if solutions and K else None,
+                                                     best.data_ptr() if best is not None else None, halvings.data_ptr(),
+                                                     _stream_ptr(stream)))
+            out = self._many_answer(buf, K, first)
+        else:
+            slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
+            check(L.csgpu_solve_many_clauses_ordered_checkpointed(
+                self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt), buf.data_ptr(),
+                first.data_ptr() if solutions and K else None, best.data_ptr() if best is not None else None,
+                halvings.data_ptr(), checkpoints._h, slots.data_ptr(), _stream_ptr(stream)))
+            out = self._many_answer(buf, K, first, slots, checkpoints)
+            # resume_many_clauses goes on under the same objective, order and split_width, from these counts
+            out["_objective"], out["_best"] = obj, best
+            out["_order"], out["_split_width"], out["_halvings"] = opt.order, opt.split_width, halvings
         if best is not None:
             out["best"] = best[:K]
         out["halvings"] = halvings[:K]
@@ -646,6 +662,22 @@ class Model:
         """the cs_walk_order instantiation solve_many_clauses_ordered launches, or None"""
         return self._many_symbol("csgpu_internal_many_clauses_order_symbol")
 
+    def many_clauses_order_resume_kernel(self):
+        """the cs_walk_order_resume instantiation the checkpointed ordered calls launch, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_order_resume_symbol")
+
+    def many_clause_ordered_checkpoints(self, capacity: int, split_width=256) -> "ManyCheckpoints":
+        """a pool of `capacity` checkpoint slots for solve_many_clauses_ordered(..., split_width=split_width, checkpoints=)
+        (csgpu_many_clause_ordered_checkpoints_create): a ManyCheckpoints of the ordered clause kind, whose slots have
+        the many_clauses_ordered_frames(split_width) + 1 frames that walk needs.  Every other call refuses it, as the
+        ordered calls refuse a pool of many_clause_checkpoints() or one made for another split_width"""
+        return ManyCheckpoints(self, capacity, clauses=True, split_width=split_width)
+
+    def clause_ordered_checkpoint_bytes(self, split_width=256) -> int:
+        """bytes of one ordered clause checkpoint slot, (many_clauses_ordered_frames(split_width) + 1) x (n_vars + 1) x 8,
+        or 0 if the model does not qualify or split_width is negative (host only: after build_tables or finalize)"""
+        return int(load_library().csgpu_many_clause_ordered_checkpoint_bytes(self._h, int(split_width)))
+
     def resume_many_clauses(self, result: dict, *, max_nodes, stream=None, max_solutions=None, own_solutions=False) -> dict:
         """continue, in place, the instances of a checkpointed solve_many_clauses answer that stopped with a checkpoint
         (csgpu_solve_many_clauses_resume): `max_nodes` more nodes each, under the answer's objective.  Counters
@@ -657,7 +689,22 @@ class Model:
         in resume_many().
         own_solutions: continue through csgpu_solve_many_clauses_from_resume (MIN / MAX answers): `best` is written only
         for an instance with a solution of its own, never with the start incumbent its checkpoint carries.  A checkpoint
-        of either MIN / MAX call may be continued either way."""
+        of either MIN / MAX call may be continued either way.
+        An answer of solve_many_clauses_ordered(..., checkpoints=pool) goes on through
+        csgpu_solve_many_clauses_ordered_resume under its order and split_width; `halvings` accumulates with the other
+        counters.  max_solutions and own_solutions are not for it."""
+        if "_checkpoints" in result and "_order" in result:
+            if max_solutions is not None or own_solutions:
+                raise ValueError("max_solutions and own_solutions do not continue an answer of solve_many_clauses_ordered: "
+                                 "the ordered walk has neither up to k solutions nor start incumbents")
+            opt = ManyOrderOptions(result["_objective"], result["_order"], result["_split_width"], 0, int(max_nodes))
+            first, best = result.get("first"), result["_best"]
+            K = result["status"].shape[0]
+            check(load_library().csgpu_solve_many_clauses_ordered_resume(
+                self._h, K, C.byref(opt), result["_records"].data_ptr(), first.data_ptr() if first is not None and K else None,
+                best.data_ptr() if best is not None else None, result["_halvings"].data_ptr(), result["_checkpoints"]._h,
+                result["_slots"].data_ptr(), _stream_ptr(stream)))
+            return result
         if "_checkpoints" in result and "_upto" in result:
             return self._resume_many_upto(result, int(max_nodes), max_solutions, stream,
                                           entry="csgpu_solve_many_clauses_upto_resume")
@@ -761,11 +808,13 @@ class Model:
         """-> (states, best): the open subtrees of the clause checkpoint in `slot` as states [depth + 1, n_vars, 2] int32
         on the device, the oldest frame (the largest subtree) first, and the instance's incumbent or None
         (csgpu_many_clause_checkpoint_states).  The states are not at the fixpoint and not under the incumbent's bound
-        yet: see open_clause_subtrees()."""
+        yet: see open_clause_subtrees().  A pool of many_clause_ordered_checkpoints() is taken as well: up to
+        many_clauses_ordered_frames() states, a pushed halving parent's being its second half."""
         n = self.n_vars
-        out = torch.empty((n, n, 2), dtype=torch.int32, device="cuda")  # depth + 1 <= n
+        rows = checkpoints.frames if checkpoints.ordered else n  # depth + 1 <= n; an ordered pool: <= its frames
+        out = torch.empty((rows, n, 2), dtype=torch.int32, device="cuda")
         count, best, have = C.c_int64(), C.c_int32(), C.c_int32()
-        check(load_library().csgpu_many_clause_checkpoint_states(checkpoints._h, int(slot), out.data_ptr(), n, C.byref(count),
+        check(load_library().csgpu_many_clause_checkpoint_states(checkpoints._h, int(slot), out.data_ptr(), rows, C.byref(count),
                                                                  C.byref(best), C.byref(have), _stream_ptr(stream)))
         return out[: count.value], (int(best.value) if have.value else None)
 
@@ -788,7 +837,8 @@ class Model:
         return out[alive & ~complete].contiguous(), out[alive & complete].contiguous(), best
 
     def solve_many_clauses_sliced(self, roots, objective="ANY", *, budgets, finish="resume", solutions=True,
-                                  pool_capacity=1 << 18, max_children=1 << 14, checkpoints=None, max_solutions=None) -> dict:
+                                  pool_capacity=1 << 18, max_children=1 << 14, checkpoints=None, max_solutions=None,
+                                  order=None, split_width=256) -> dict:
         """solve_many_clauses in slices: a checkpointed call with budgets[0], then a resume with each following budget
         while an instance is at LIMIT -- a small budget for everybody, more for the few that need it.
         finish="resume": that is all (instances still at LIMIT stay so, with their slots and the best found so far).
@@ -804,26 +854,42 @@ class Model:
         -> the dict of solve_many_clauses plus `slot` and `sliced`: {"slices": calls made, "searched": instances finished
         by the Search}
         max_solutions=k: the slices are solve_many_clauses_upto calls (`objective` does not apply, the answer has
-        `rows`), with finish="resume" only."""
+        `rows`), with finish="resume" only.
+        order (one of MANY_ORDERS, with split_width): the slices are solve_many_clauses_ordered calls on a pool of
+        many_clause_ordered_checkpoints(K, split_width) -- `checkpoints`, if given, must be one of those, made for this
+        split_width -- the answer has `halvings`, and with finish="search" the Search is given the same order
+        (set_strategy).  Not together with max_solutions."""
         assert finish in ("resume", "search") and len(budgets) >= 1
+        if order is not None and max_solutions is not None:
+            raise ValueError("order with max_solutions: the ordered walk has no up to k solutions")
         if max_solutions is not None and finish == "search":
             raise ValueError("finish=\"search\" with max_solutions: an engine search cannot stop at a k-th solution "
                              "per instance")
         obj = None if max_solutions is not None else self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
         if finish == "search" and obj != self.objective:
             raise ValueError("finish=\"search\": a Search walks with the model's own objective, which must be the one asked for")
-        pool = checkpoints.reset() if checkpoints is not None else self.many_clause_checkpoints(max(roots.shape[0], 1))
-        if max_solutions is not None:  # resume_many_clauses takes the k from the answer
+        if checkpoints is not None:
+            pool = checkpoints.reset()
+        elif order is not None:
+            pool = self.many_clause_ordered_checkpoints(max(roots.shape[0], 1), split_width)
+        else:
+            pool = self.many_clause_checkpoints(max(roots.shape[0], 1))
+        if order is not None:  # resume_many_clauses takes the order and the split_width from the answer
+            out = self.solve_many_clauses_ordered(roots, objective, max_nodes=budgets[0], order=order, split_width=split_width,
+                                                  solutions=solutions, checkpoints=pool)
+        elif max_solutions is not None:  # resume_many_clauses takes the k from the answer
             out = self.solve_many_clauses_upto(roots, max_solutions, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
         else:
             out = self.solve_many_clauses(roots, objective, max_nodes=budgets[0], solutions=solutions, checkpoints=pool)
         return self._many_slices(out, pool, budgets, self.resume_many_clauses, obj,
-                                 self.open_clause_subtrees if finish == "search" else None, pool_capacity, max_children)
+                                 self.open_clause_subtrees if finish == "search" else None, pool_capacity, max_children, order)
 
-    def _many_slices(self, out: dict, pool, budgets, resume, obj, open_subtrees, pool_capacity, max_children) -> dict:
+    def _many_slices(self, out: dict, pool, budgets, resume, obj, open_subtrees, pool_capacity, max_children,
+                     order=None) -> dict:
         """solve_many_sliced and solve_many_clauses_sliced after their first slice `out`: `resume` with each following
         budget while an instance is at LIMIT; then, where the finish is a Search, every instance still at LIMIT with a slot
-        hands the (states, complete, best) of `open_subtrees` (else None) to one reused Search"""
+        hands the (states, complete, best) of `open_subtrees` (else None) to one reused Search, which walks under
+        `order` where the slices did"""
         slices = 1
         for budget in budgets[1:]:
             if not bool((out["status"] == 1).any()):
@@ -835,6 +901,8 @@ class Model:
             left = torch.nonzero((out["status"] == 1) & (out["slot"] >= 0)).flatten().tolist()
             if left:
                 search = Search(self, pool_capacity, max_children)
+                if order is not None:
+                    search.set_strategy(order)
                 for i in left:
                     self._finish_by_search(search, out, i, obj, *open_subtrees(pool, int(out["slot"][i])))
                     searched += 1
@@ -1621,15 +1689,25 @@ class _SpreadRounds:
 
 
 class ManyCheckpoints:
-    """A pool of checkpoint slots of one finalized model (csgpu_many_checkpoints), of one of two kinds: for solve_many
-    (Model.many_checkpoints) or for solve_many_clauses (Model.many_clause_checkpoints).  It holds the model."""
+    """A pool of checkpoint slots of one finalized model (csgpu_many_checkpoints), of one of three kinds: for solve_many
+    (Model.many_checkpoints), for solve_many_clauses (Model.many_clause_checkpoints) or for solve_many_clauses_ordered
+    (Model.many_clause_ordered_checkpoints).  It holds the model."""
 
-    def __init__(self, model: Model, capacity: int, clauses: bool = False):
+    def __init__(self, model: Model, capacity: int, clauses: bool = False, split_width=None):
         self.model = model
         self.capacity = int(capacity)
         self.clauses = bool(clauses)  # the kind: of solve_many_clauses (csgpu_many_clause_checkpoints_create), else of solve_many
+        # the third kind, of solve_many_clauses_ordered (csgpu_many_clause_ordered_checkpoints_create): made for one
+        # split_width, a slot has `frames` + 1 frames
+        self.ordered = split_width is not None
+        self.split_width = int(split_width) if self.ordered else None
         self._h = C.c_void_p()
         L = load_library()
+        if self.ordered:
+            assert self.clauses, "an ordered pool is a clause pool"
+            check(L.csgpu_many_clause_ordered_checkpoints_create(model._h, self.capacity, self.split_width, C.byref(self._h)))
+            self.frames = model.many_clauses_ordered_frames(self.split_width)
+            return
         create = L.csgpu_many_clause_checkpoints_create if self.clauses else L.csgpu_many_checkpoints_create
         check(create(model._h, self.capacity, C.byref(self._h)))
 

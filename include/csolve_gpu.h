@@ -960,8 +960,9 @@ int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu_val *d_roo
  * Errors before any HIP call: csgpu_solve_many_clauses's in its order (options is this entry's struct), then an order
  * outside 0 .. 4, a negative split_width or a non-zero `reserved` -> CSGPU_E_ARG.  count == 0 -> CSGPU_OK, nothing is
  * launched.
- * Not on this walk: checkpoints and resume, up to k solutions, the solution stream, the spread over idle waves, restarts,
- * prefer-failing, and the kernel-7 walks of csgpu_solve_many, which keep their one rule. */
+ * Not on this walk: up to k solutions, the solution stream, the spread over idle waves, restarts, start incumbents,
+ * prefer-failing, and the kernel-7 walks of csgpu_solve_many, which keep their one rule.  Checkpoints and resume are the
+ * section after this one. */
 typedef struct csgpu_many_order_options {
   int32_t objective;   /* 0 ANY, 1 ALL, 2 MIN, 3 MAX */
   int32_t order;       /* 0..4, csgpu_search_set_strategy's numbers */
@@ -974,6 +975,62 @@ int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgpu_val *d_ro
                                      int32_t *d_solutions /* NULL or [count][n_vars] */, int32_t *d_best /* NULL or [count] */,
                                      int64_t *d_halvings /* NULL or [count] */, void *stream);
 int64_t csgpu_many_clauses_ordered_frames(const csgpu_model *m, int32_t split_width);
+
+/* ---- ordered clause checkpoints: csgpu_solve_many_clauses_ordered in slices ----
+ * A launch of csgpu_solve_many_clauses_ordered lasts as long as its deepest instance.  These calls are to it what
+ * csgpu_solve_many_clauses_checkpointed / _resume are to csgpu_solve_many_clauses: a small budget for everybody, then more
+ * for the few that need it, or the rest handed to one csgpu_search.
+ *
+ * The walk is csgpu_solve_many_clauses_ordered's, the contract csgpu_solve_many_clauses_checkpointed / _resume's: max_nodes
+ * is the budget of THIS call; instances with d_slots[i] < 0 are untouched by a resume (record, row, best, halving count);
+ * an instance ends DONE with d_slots[i] = -1, or LIMIT with its header and {variable, next} back in the same slot; once
+ * the pool is exhausted an instance ends LIMIT with slot -1, as without checkpoints; one call is in flight per model, and
+ * calls may be queued on one stream.  A resume takes no roots and needs no workspace.
+ * Guarantee: a walk in slices gives, field for field and row for row, d_halvings included, the one
+ * csgpu_solve_many_clauses_ordered call with the summed budget.
+ *
+ * The pool.  A pushed halving parent values no variable, so a stack is deeper than n_vars and a slot of
+ * csgpu_many_clause_checkpoints_create does not hold it.  With F = csgpu_many_clauses_ordered_frames(m, split_width):
+ *   slot = F + 1 frames of n_vars + 1 entries of 8 bytes, bounds absolute
+ *   frame 0           the header: entry 0 = {depth, magic}, entry 1 = {best, have_best | code << 1}, code = objective |
+ *                     order << 3; the magic is not that of a csgpu_many_clause_checkpoints_create slot
+ *   frame 1 + d       pushed frame d < depth: the row, then {variable, next}: the next value, or mid + 1 of a halving node
+ *   frame 1 + depth   the current node as it was entered and {variable, next}: next == lo of a halving node means that
+ *                     neither half was tried, next == mid + 1 that the second half is next
+ * F + 1 frames because F - 1 parents at most are pushed under the current node, and frame 0 is the header.  Whether a
+ * frame's node halves, and its mid, are read back from the frame's row, so a walk stopped between the two halves counts
+ * the parent once.  csgpu_many_clause_ordered_checkpoint_bytes(m, split_width) is the bytes of a slot, (F + 1) * (n_vars +
+ * 1) * 8 in 64 bits, without a HIP call (0 means 256); 0 for NULL, a model that does not qualify or a negative
+ * split_width.  csgpu_many_clause_ordered_checkpoints_create makes a pool for ONE split_width (a negative one ->
+ * CSGPU_E_ARG; everything else as csgpu_many_clause_checkpoints_create); csgpu_many_checkpoints_reset / _free serve it.
+ * A resume under another objective or another order would walk another tree: the slot's code differs and the instance ends
+ * CSGPU_MANY_BAD_SLOT, as for a slot number outside the pool or a slot that holds no checkpoint, with only its status
+ * word written.  The halving count of a resumed instance goes on from d_halvings[i], as the other counters go on from the
+ * record: d_halvings is required.
+ *
+ * Errors before any HIP call, in this order: csgpu_solve_many_clauses_checkpointed's null arguments, count and max_nodes;
+ * csgpu_solve_many_clauses's objective, model and count checks; an order outside 0 .. 4, a negative split_width, a
+ * non-zero `reserved` -> CSGPU_E_ARG; d_halvings NULL -> CSGPU_E_ARG; ck or d_slots NULL, a pool of another model, a pool
+ * of csgpu_many_checkpoints_create or csgpu_many_clause_checkpoints_create -> CSGPU_E_ARG; a pool made for another
+ * split_width (both normalised, 0 to 256) -> CSGPU_E_ARG.  count == 0 -> CSGPU_OK, nothing is launched.
+ * csgpu_many_clause_checkpoint_states takes a pool of this kind as well and returns up to F states by the one rule: a frame
+ * {row, variable, next} is the row with the variable narrowed to [next, hi] -- for a pushed halving parent exactly its
+ * second half, for a current node before its first half the whole node.  Every other entry that takes a clause pool
+ * refuses this kind with CSGPU_E_ARG: csgpu_solve_many_clauses_checkpointed / _resume, the up-to-k calls, _from /
+ * _from_resume, the stream, and csgpu_many_clause_checkpoint_children / _fanout and their _obj forms.
+ * Not built on the ordered walk: up to k solutions, the solution stream, restarts, start incumbents, prefer-failing, and
+ * the spread over idle waves -- a fan-out of halves has to account for `halvings`. */
+size_t csgpu_many_clause_ordered_checkpoint_bytes(const csgpu_model *m, int32_t split_width);
+int csgpu_many_clause_ordered_checkpoints_create(const csgpu_model *m, int64_t capacity, int32_t split_width,
+                                                 csgpu_many_checkpoints **out);
+int csgpu_solve_many_clauses_ordered_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                  const csgpu_many_order_options *options, csgpu_many_result *d_results,
+                                                  int32_t *d_solutions /* NULL or [count][n_vars] */,
+                                                  int32_t *d_best /* NULL or [count] */, int64_t *d_halvings /* [count] */,
+                                                  csgpu_many_checkpoints *ck, int32_t *d_slots /* [count] */, void *stream);
+int csgpu_solve_many_clauses_ordered_resume(const csgpu_model *m, int64_t count, const csgpu_many_order_options *options,
+                                            csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                            int64_t *d_halvings, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
 
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */

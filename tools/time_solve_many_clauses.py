@@ -54,7 +54,15 @@ of solve_many_clauses on the same rows and the same budget, alternating in this 
 tests/many_clause_sets.py or of tests/many_walk_ordered.py, e.g. schedule5_open_min, whose rows leave `end` at its root
 width; repeated up to --count): medians and ranges of both, both node totals, how many rows each leaves at LIMIT, the
 time per node of both, whether every field equals the plain call's (what smallest-domain gives where nothing halves),
-and the seeded sample of the ordered answers re-checked against the host walk (tests/many_walk_ordered.py)."""
+and the seeded sample of the ordered answers re-checked against the host walk (tests/many_walk_ordered.py).
+
+--order NAME --split W --sliced B1,B2,... [--finish resume|search] times the sliced ordered route
+(Model.solve_many_clauses_sliced(order=NAME, split_width=W) on one reused pool of many_clause_ordered_checkpoints) beside
+the ONE ordered call with the summed budget, alternating in this process after a warm-up; the first slice -- the fresh
+checkpointed call with B1 -- is timed on its own as well, so `--sliced N` with an N no instance reaches is the cost of the
+checkpoint switch alone.  Every field of the sliced answer must equal the one call's (--finish resume; with --finish
+search every instance ends DONE and `best` is the one call's where that one is DONE), and the seeded sample is re-checked
+against the host walk."""
 import argparse
 import json
 import os
@@ -112,9 +120,9 @@ def main():
     ap.add_argument("--split", type=int, default=256, help="with --order: split_width")
     args = ap.parse_args()
     if args.order is not None:
-        if args.spread is not None or args.stream is not None or args.sliced or args.upto is not None or args.restarts is not None:
-            ap.error("--order NAME: without --spread, --stream, --sliced, --upto and --restarts")
-        return order_route(args)
+        if args.spread is not None or args.stream is not None or args.upto is not None or args.restarts is not None:
+            ap.error("--order NAME: without --spread, --stream, --upto and --restarts")
+        return order_sliced_route(args) if args.sliced else order_route(args)
     if args.spread is not None:
         if args.stream is not None or args.sliced or args.upto is not None or args.restarts is not None:
             ap.error("--spread B1,B2,...: without --stream, --sliced, --upto and --restarts")
@@ -282,6 +290,79 @@ def order_route(args):
         "oracle_checked": len(picks), "oracle_ok": bool(ok),
     }))
     return 0 if ok else 1
+
+
+def order_sliced_route(args):
+    """the sliced ordered route beside the one ordered call with the summed budget, same rows, same build"""
+    import many_clause_sets as sets
+    import many_walk_ordered as O
+    name = args.set or "schedule5_min"
+    if name not in sets.SETS and name not in O.SETS:
+        raise SystemExit(f"--order: --set is one of {sorted(set(sets.SETS) | set(O.SETS))}")
+    if args.order not in O.ORDERS or args.split < 1:
+        raise SystemExit(f"--order is one of {O.ORDERS}, --split at least 1")
+    text, base, objective, _ = (sets if name in sets.SETS else O).build(name)
+    budgets = tuple(int(b) for b in args.sliced.split(","))
+    budget = sum(budgets)
+    roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
+    count = len(roots)
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+    rng = np.random.default_rng(args.seed)
+    pool = model.many_clause_ordered_checkpoints(count, args.split)
+    how = dict(order=args.order, split_width=args.split)
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    calls = {"one": lambda: model.solve_many_clauses_ordered(dev, objective, max_nodes=budget, **how),
+             "first": lambda: model.solve_many_clauses_ordered(dev, objective, max_nodes=budgets[0], checkpoints=pool.reset(), **how),
+             "sliced": lambda: model.solve_many_clauses_sliced(dev, objective, budgets=budgets, finish=args.finish,
+                                                               checkpoints=pool, **how)}
+    for _ in range(2):  # warm-up: code load, workspace, the engine's buffers
+        for call in calls.values():
+            timed(call)
+    times, outs = {k: [] for k in calls}, {}
+    for _ in range(args.reps):  # alternating: a drift of the machine falls on all alike
+        for k, call in calls.items():
+            dt, outs[k] = timed(call)
+            times[k].append(dt)
+    sliced_info = outs["sliced"]["sliced"]
+    host = {k: {f: v.cpu().numpy() for f, v in o.items() if torch.is_tensor(v) and not f.startswith("_")} for k, o in outs.items()}
+    one, got = host["one"], host["sliced"]
+    if args.finish == "resume":
+        same = all(bool((got[f] == one[f]).all()) for f in one)
+    else:
+        done = (one["status"] == 0) & (one["solutions"] > 0)
+        same = bool((got["status"] == 0).all())
+        if objective in ("MIN", "MAX"):
+            same = same and bool((got["best"][done] == one["best"][done]).all())
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    want = O.walk_many(text, roots[picks], objective, budget, args.order, args.split)
+    has = want["solutions"] > 0
+    ok = all((one[f][picks] == want[f]).all() for f in ("status", "nodes", "cuts", "solutions", "halvings")) and \
+        bool((one["first"][picks][has] == want["first"][has]).all())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(json.dumps({
+        "tool": "time_solve_many_clauses", "route": "order-sliced", "commit": commit(), "command": " ".join(sys.argv), "set": name,
+        "objective": objective, "order": args.order, "split_width": args.split, "instances": count, "n_vars": model.n_vars,
+        "clauses": model.n_clauses, "order_kernel": model.many_clauses_order_kernel(),
+        "order_resume_kernel": model.many_clauses_order_resume_kernel(), "waves": model.many_clauses_waves(count),
+        "frames_per_wave": model.many_clauses_ordered_frames(args.split), "slot_bytes": model.clause_ordered_checkpoint_bytes(args.split),
+        "one_call_max_nodes": budget, "one_call_status_counts": np.bincount(one["status"], minlength=3).tolist(),
+        "one_call_nodes": int(one["nodes"].sum()), "one_call_largest_tree": int(one["nodes"].max()), "one_call_ms": spread(times["one"]),
+        "budgets": list(budgets), "finish": args.finish, "sliced": sliced_info,
+        "stopped_after_the_first_slice": int((host["first"]["status"] == 1).sum()),
+        "first_slice_ms": spread(times["first"]), "sliced_ms": spread(times["sliced"]),
+        "sliced_status_counts": np.bincount(got["status"], minlength=3).tolist(), "sliced_nodes": int(got["nodes"].sum()),
+        "first_slice_over_one_call": round(med["first"] / med["one"], 4), "sliced_over_one_call": round(med["sliced"] / med["one"], 4),
+        "sliced_equals_the_one_call": bool(same), "oracle_checked": len(picks), "oracle_ok": bool(ok),
+    }))
+    return 0 if ok and same else 1
 
 
 def restart_route(args):
