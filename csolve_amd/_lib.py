@@ -317,6 +317,12 @@ def load_library():
                                                                 vp]
     L.csgpu_solve_many_clauses_ordered_resume.argtypes = [vp, i64, C.POINTER(ManyOrderOptions), vp, vp, vp, vp, vp, vp, vp]
     L.csgpu_internal_many_clauses_order_resume_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_solve_many_clauses_ordered_from.argtypes = [vp, vp, vp, i64, C.POINTER(ManyOrderOptions), vp, vp, vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_clauses_ordered_from_resume.argtypes = [vp, i64, C.POINTER(ManyOrderOptions), vp, vp, vp, vp, vp, vp, vp]
+    L.csgpu_many_clause_ordered_checkpoint_children.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp]
+    L.csgpu_many_clause_ordered_checkpoint_fanout.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, vp]
+    L.csgpu_many_fold_halvings.argtypes = [vp, vp, i64, vp, vp]
+    L.csgpu_internal_many_clauses_order_from_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.csgpu_many_value.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, Val, C.c_uint32, C.c_int32]
     L.csgpu_many_value.restype = C.c_int32
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

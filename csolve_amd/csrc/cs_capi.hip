@@ -66,11 +66,12 @@ static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "c
 #define MANY_BY_ALLOWED(family) ((family) >= MANY_ALLOWED && (family) <= MANY_ALLOWED_UPTO_CK)
 #define CS_DIVE_ALLOWED_WIDTH 128 /* the widest root domain the allowed sets of cs_dive_allowed hold (four 32-bit words) */
 
-/* the kernels of the csgpu_solve_many_clauses family (cs_walk.hip.h): one loop on kernel 6's fixpoint, compiled eight times */
-enum { WALK_PLAIN, WALK_CK, WALK_UPTO, WALK_RESTART, WALK_STREAM, WALK_FROM, WALK_ORDER, WALK_ORDER_CK, WALK_FAMILIES };
+/* the kernels of the csgpu_solve_many_clauses family (cs_walk.hip.h): one loop on kernel 6's fixpoint, compiled nine times */
+enum { WALK_PLAIN, WALK_CK, WALK_UPTO, WALK_RESTART, WALK_STREAM, WALK_FROM, WALK_ORDER, WALK_ORDER_CK, WALK_ORDER_FROM,
+       WALK_FAMILIES };
 static const char *const walk_kernel_name[WALK_FAMILIES] = { "cs_walk_clauses", "cs_walk_resume", "cs_walk_upto", "cs_walk_restart",
                                                              "cs_walk_stream", "cs_walk_from", "cs_walk_order",
-                                                             "cs_walk_order_resume" };
+                                                             "cs_walk_order_resume", "cs_walk_order_from" };
 
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
 struct cs_kernel_plan {
@@ -856,6 +857,7 @@ static const void *walk_kernel(int family, int cpl, int tree) {
   case WALK_FROM: CS_PICK(cs_walk_from)       /* MIN / MAX from a start incumbent (csgpu_solve_many_clauses_from / _from_resume) */
   case WALK_ORDER: CS_PICK(cs_walk_order)     /* the five variable orders, interval halving (csgpu_solve_many_clauses_ordered) */
   case WALK_ORDER_CK: CS_PICK(cs_walk_order_resume) /* that walk with checkpoints (csgpu_solve_many_clauses_ordered_checkpointed / _resume) */
+  case WALK_ORDER_FROM: CS_PICK(cs_walk_order_from) /* and from a start incumbent (csgpu_solve_many_clauses_ordered_from / _from_resume) */
   default: CS_PICK(cs_walk_clauses)
   }
 #undef CS_PICK
@@ -1376,6 +1378,7 @@ MANY_SYMBOL(csgpu_internal_many_clauses_stream_symbol, walk, walk_kernel_name, W
 MANY_SYMBOL(csgpu_internal_many_clauses_from_symbol, walk, walk_kernel_name, WALK_FROM)
 MANY_SYMBOL(csgpu_internal_many_clauses_order_symbol, walk, walk_kernel_name, WALK_ORDER)
 MANY_SYMBOL(csgpu_internal_many_clauses_order_resume_symbol, walk, walk_kernel_name, WALK_ORDER_CK)
+MANY_SYMBOL(csgpu_internal_many_clauses_order_from_symbol, walk, walk_kernel_name, WALK_ORDER_FROM)
 #undef MANY_SYMBOL
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
@@ -2306,10 +2309,10 @@ static cs_walk_ck many_clauses_ck_arg(const many_clauses_bufs *b, int resume, in
 
 /* The one launch of a cs_walk_* kernel, after the checks.  `frames` per wave: at most n - 1 pushed frames and the current
  * node's; cs_walk_restart: and the root node's; cs_walk_order: and the halving parents' (at most 33 n, n <= 5118: an int).
- * `tail0`, `tail1`: the family's own kernel arguments after the tables and the cs_walk_io (NULL where it has fewer).
+ * `tail0` .. `tail2`: the family's own kernel arguments after the tables and the cs_walk_io (NULL where it has fewer).
  * `resume`: the instances go on in the frames of their checkpoint slots, so the call brings no roots and needs no stacks. */
 static int many_clauses_launch(const csgpu_model *m, int family, int frames, int objective, int64_t max_nodes,
-                               const many_clauses_bufs *b, int resume, void *tail0, void *tail1) {
+                               const many_clauses_bufs *b, int resume, void *tail0, void *tail1, void *tail2) {
   if (b->count == 0) return CSGPU_OK;
   csgpu_model *mm = const_cast<csgpu_model *>(m);
   const cs_planned *k = &m->plan.walk[family];
@@ -2331,7 +2334,7 @@ static int many_clauses_launch(const csgpu_model *m, int family, int frames, int
   io.frames = frames;
   io.tickets = mm->d_many_tickets;
   cs_tables tab = m->tab;
-  void *args[] = { &tab, &io, tail0, tail1 };
+  void *args[] = { &tab, &io, tail0, tail1, tail2 };
   HIP_TRY(hipLaunchKernel(k->fn, dim3((unsigned)(waves / k->waves)), dim3((unsigned)(k->waves * CS_WAVE)), args, k->lds,
                           (hipStream_t)b->stream));
   return CSGPU_OK;
@@ -2346,7 +2349,7 @@ extern "C" int csgpu_solve_many_clauses(const csgpu_model *m, const csgpu_val *d
       (rc = many_clauses_check_model(m, options->objective, count)))
     return rc;
   const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best };
-  return many_clauses_launch(m, WALK_PLAIN, m->host->n_vars, options->objective, options->max_nodes, &b, 0, NULL, NULL);
+  return many_clauses_launch(m, WALK_PLAIN, m->host->n_vars, options->objective, options->max_nodes, &b, 0, NULL, NULL, NULL);
 }
 
 
@@ -2381,7 +2384,7 @@ static int many_clauses_pooled(const csgpu_model *m, const many_clauses_bufs *b,
       (rc = many_clauses_check_model(m, options->objective, b->count)) || (rc = many_clauses_check_pool(m, b, MANY_POOL_WALK)))
     return rc;
   cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective);
-  return many_clauses_launch(m, WALK_CK, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, NULL);
+  return many_clauses_launch(m, WALK_CK, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, NULL, NULL);
 }
 
 extern "C" int csgpu_solve_many_clauses_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
@@ -2487,7 +2490,7 @@ static int many_clauses_from(const csgpu_model *m, const many_clauses_bufs *b, c
   if (b->ck != NULL && (rc = many_clauses_check_pool(m, b, MANY_POOL_WALK))) return rc;
   cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective);
   const cs_walk_start *starts = (const cs_walk_start *)d_start;
-  return many_clauses_launch(m, WALK_FROM, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, &starts);
+  return many_clauses_launch(m, WALK_FROM, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, &starts, NULL);
 }
 
 extern "C" int csgpu_solve_many_clauses_from(const csgpu_model *m, const csgpu_val *d_roots, const csgpu_many_start *d_start,
@@ -2563,7 +2566,7 @@ static int many_clauses_upto(const csgpu_model *m, const many_clauses_bufs *b, c
   if ((rc = many_clauses_check_model(m, CS_OBJ_ALL, b->count)) || (pooled && (rc = many_clauses_check_pool(m, b, MANY_POOL_WALK)))) return rc;
   cs_walk_ck wk = many_clauses_ck_arg(b, resume, CS_WALK_CK_UPTO);
   int upto = options->max_solutions;
-  return many_clauses_launch(m, WALK_UPTO, m->host->n_vars, CS_OBJ_ALL, options->max_nodes, b, resume, &wk, &upto);
+  return many_clauses_launch(m, WALK_UPTO, m->host->n_vars, CS_OBJ_ALL, options->max_nodes, b, resume, &wk, &upto, NULL);
 }
 
 extern "C" int csgpu_solve_many_clauses_upto(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
@@ -2608,10 +2611,36 @@ extern "C" int csgpu_solve_many_clauses_restarts(const csgpu_model *m, const csg
   dr.flags = options->flags;
   const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions };
   return many_clauses_launch(m, WALK_RESTART, m->host->n_vars + 1 /* and the root node's */, CS_OBJ_ANY, options->max_nodes, &b, 0,
-                             &dr, NULL);
+                             &dr, NULL, NULL);
 }
 
 /* ---- the engine's five variable orders and interval halving for the instances of a clause model (cs_walk_order) ---- */
+
+/* what every ordered entry checks of its options, after csgpu_solve_many_clauses's own errors: the order, split_width,
+ * `reserved`; *wo is then what the kernel takes */
+static int many_clauses_ordered_options(const csgpu_many_order_options *options, int64_t *d_halvings, cs_walk_ord *wo) {
+  if (options->order < 0 || options->order > 4)
+    return set_err(CSGPU_E_ARG, "no variable order %d (0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value)",
+                   (int)options->order);
+  if (options->split_width < 0) return set_err(CSGPU_E_ARG, "split_width must not be negative (0: the engine's 256)");
+  if (options->reserved != 0) return set_err(CSGPU_E_ARG, "reserved must be 0");
+  wo->order = options->order;
+  wo->split_width = options->split_width != 0 ? options->split_width : 256;
+  wo->halvings = (long long *)d_halvings;
+  return CSGPU_OK;
+}
+
+/* and what every ordered entry with a pool adds, last: the halving counts, the pool, its kind and its split_width */
+static int many_clauses_ordered_pool(const csgpu_model *m, const many_clauses_bufs *b, const cs_walk_ord *wo) {
+  int rc;
+  if (wo->halvings == NULL)
+    return set_err(CSGPU_E_ARG, "null argument: d_halvings, which a resumed instance's halving count goes on from");
+  if ((rc = many_clauses_check_pool(m, b, MANY_POOL_ORDER))) return rc;
+  if (b->ck->split_width != wo->split_width)
+    return set_err(CSGPU_E_ARG, "the checkpoint pool was made for split_width %d, the call asks for %d: the frames of a slot differ",
+                   b->ck->split_width, wo->split_width);
+  return CSGPU_OK;
+}
 
 /* the three entries: the plain call, and with `pooled` the checkpointed call and its `resume` (no roots): cs_walk_order, or
  * cs_walk_order_resume on a pool of the ordered kind.  The checks, none of which touches the device, in the documented
@@ -2624,27 +2653,15 @@ static int many_clauses_ordered(const csgpu_model *m, const many_clauses_bufs *b
       (rc = many_clauses_check_model(m, options->objective, b->count)))
     return rc;
   /* after csgpu_solve_many_clauses's own errors, before any device call */
-  if (options->order < 0 || options->order > 4)
-    return set_err(CSGPU_E_ARG, "no variable order %d (0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value)",
-                   (int)options->order);
-  if (options->split_width < 0) return set_err(CSGPU_E_ARG, "split_width must not be negative (0: the engine's 256)");
-  if (options->reserved != 0) return set_err(CSGPU_E_ARG, "reserved must be 0");
   cs_walk_ord wo;
-  wo.order = options->order;
-  wo.split_width = options->split_width != 0 ? options->split_width : 256;
-  wo.halvings = (long long *)d_halvings;
+  if ((rc = many_clauses_ordered_options(options, d_halvings, &wo))) return rc;
   if (!pooled)
     return many_clauses_launch(m, WALK_ORDER, (int)many_clauses_ordered_frames(m, options->split_width), options->objective,
-                               options->max_nodes, b, 0, &wo, NULL);
-  if (d_halvings == NULL)
-    return set_err(CSGPU_E_ARG, "null argument: d_halvings, which a resumed instance's halving count goes on from");
-  if ((rc = many_clauses_check_pool(m, b, MANY_POOL_ORDER))) return rc;
-  if (b->ck->split_width != wo.split_width)
-    return set_err(CSGPU_E_ARG, "the checkpoint pool was made for split_width %d, the call asks for %d: the frames of a slot differ",
-                   b->ck->split_width, wo.split_width);
+                               options->max_nodes, b, 0, &wo, NULL, NULL);
+  if ((rc = many_clauses_ordered_pool(m, b, &wo))) return rc;
   /* a checkpoint goes on under the objective and the order it was made under: another of either is another tree */
   cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective | options->order << 3);
-  return many_clauses_launch(m, WALK_ORDER_CK, b->ck->frames, options->objective, options->max_nodes, b, resume, &wk, &wo);
+  return many_clauses_launch(m, WALK_ORDER_CK, b->ck->frames, options->objective, options->max_nodes, b, resume, &wk, &wo, NULL);
 }
 
 extern "C" int csgpu_solve_many_clauses_ordered(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
@@ -2689,6 +2706,120 @@ extern "C" int csgpu_solve_many_clauses_ordered_resume(const csgpu_model *m, int
   return many_clauses_ordered(m, &b, options, d_halvings, 1, 1);
 }
 
+/* ---- the ordered walk from a start incumbent, and stopped ordered walks spread over the next launch (cs_walk_order_from;
+ * cs_walk_order_children / cs_walk_order_fanout; cs_walk_fold_halvings) ---- */
+
+/* the start call, checkpointed with a pool and slot numbers and plain with neither, and its resume (no roots, no starts),
+ * which is checkpointed: cs_walk_order_from under MIN / MAX.  The checks, none of which touches the device, in the
+ * documented order: csgpu_solve_many_clauses's own, the ordered walk's three, csgpu_solve_many_clauses_from's (the start,
+ * the objective, the pool and the slots together), then what an ordered pool adds */
+static int many_clauses_ordered_from(const csgpu_model *m, const many_clauses_bufs *b, const csgpu_many_start *d_start,
+                                     const csgpu_many_order_options *options, int64_t *d_halvings, int resume) {
+  const int null_arg = m == NULL || (!resume && b->d_roots == NULL) || b->d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, resume ? "slice" : "instance")) ||
+      (rc = many_clauses_check_model(m, options->objective, b->count)))
+    return rc;
+  cs_walk_ord wo;
+  if ((rc = many_clauses_ordered_options(options, d_halvings, &wo))) return rc;
+  if (!resume && d_start == NULL) return set_err(CSGPU_E_ARG, "null argument: d_start, the incumbents the instances start with");
+  if (options->objective != CS_OBJ_MIN && options->objective != CS_OBJ_MAX)
+    return set_err(CSGPU_E_ARG, "a start incumbent bounds a MIN / MAX walk (objective 2 or 3), not objective %d", options->objective);
+  if ((b->ck == NULL) != (b->d_slots == NULL))
+    return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers, a plain one neither");
+  if (resume && b->ck == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
+  if (b->ck != NULL && (rc = many_clauses_ordered_pool(m, b, &wo))) return rc;
+  const int frames = b->ck != NULL ? b->ck->frames : (int)many_clauses_ordered_frames(m, options->split_width);
+  cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective | options->order << 3);
+  const cs_walk_start *starts = (const cs_walk_start *)d_start;
+  return many_clauses_launch(m, WALK_ORDER_FROM, frames, options->objective, options->max_nodes, b, resume, &wk, &wo, &starts);
+}
+
+extern "C" int csgpu_solve_many_clauses_ordered_from(const csgpu_model *m, const csgpu_val *d_roots, const csgpu_many_start *d_start,
+                                                     int64_t count, const csgpu_many_order_options *options,
+                                                     csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                                     int64_t *d_halvings, csgpu_many_checkpoints *ck, int32_t *d_slots,
+                                                     void *stream) {
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_ordered_from(m, &b, d_start, options, d_halvings, 0);
+}
+
+extern "C" int csgpu_solve_many_clauses_ordered_from_resume(const csgpu_model *m, int64_t count,
+                                                            const csgpu_many_order_options *options, csgpu_many_result *d_results,
+                                                            int32_t *d_solutions, int32_t *d_best, int64_t *d_halvings,
+                                                            csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
+  const many_clauses_bufs b = { NULL, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_clauses_ordered_from(m, &b, NULL, options, d_halvings, 1);
+}
+
+/* what the count and the fan-out of an ordered pool check alike, after their null arguments and counts: the objective, the
+ * order, the kind of the pool, the number of instances */
+static int many_clause_ordered_fan_check(const csgpu_many_checkpoints *ck, int64_t count, int objective, int order) {
+  if (objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
+    return set_err(CSGPU_E_ARG, "the checkpoints of an ALL, a MIN or a MAX walk are asked for (objective 1, 2 or 3), not objective %d",
+                   objective);
+  if (order < 0 || order > 4)
+    return set_err(CSGPU_E_ARG, "no variable order %d (0 none, 1 smallest domain, 2 largest domain, 3 smallest value, 4 largest value)",
+                   order);
+  if (ck->kind != MANY_POOL_ORDER) return set_err(CSGPU_E_ARG, MANY_POOL_KIND_ORDER);
+  if (count > 0x7fffffff) return set_err(CSGPU_E_LIMIT, MANY_FAN_LIMIT);
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_clause_ordered_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                             int objective, int order, int64_t *d_children, int32_t *d_unsplit,
+                                                             void *stream) {
+  if (ck == NULL || d_slots == NULL || d_children == NULL || d_unsplit == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  int rc;
+  if ((rc = many_clause_ordered_fan_check(ck, count, objective, order))) return rc;
+  if (count == 0) return CSGPU_OK;
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  hipLaunchKernelGGL(cs_walk_order_children, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream,
+                     m->host->n_vars, ck->frames, ck->split_width, (const cs_val *)m->d_walk_root, (const cs_val *)ck->d_pool,
+                     (int)ck->capacity, (const int *)d_slots, (long long)count, (long long *)d_children, (int *)d_unsplit,
+                     objective | order << 3);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_clause_ordered_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                           int objective, int order, const csgpu_many_start *d_owner_start,
+                                                           const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner,
+                                                           csgpu_many_start *d_start, int64_t total, void *stream) {
+  if (ck == NULL || d_slots == NULL || d_offsets == NULL || d_rows == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (count < 0) return set_err(CSGPU_E_ARG, "negative instance count");
+  if (total < 0) return set_err(CSGPU_E_ARG, "negative row count");
+  int rc;
+  if ((rc = many_clause_ordered_fan_check(ck, count, objective, order))) return rc;
+  if (objective == CS_OBJ_ALL && (d_owner_start != NULL || d_start != NULL))
+    return set_err(CSGPU_E_ARG, "start incumbents travel with objective MIN / MAX: d_owner_start and d_start are NULL under ALL");
+  if (objective != CS_OBJ_ALL && d_start == NULL)
+    return set_err(CSGPU_E_ARG, "null argument: d_start, where the start incumbent of every row goes under MIN / MAX");
+  if (count == 0 || total == 0) return CSGPU_OK;
+  const csgpu_model *m = ck->m;
+  const unsigned grid = (unsigned)((count + CS_DIVE_FAN_WAVES - 1) / CS_DIVE_FAN_WAVES);
+  hipLaunchKernelGGL(cs_walk_order_fanout, dim3(grid), dim3(CS_DIVE_FAN_WAVES * CS_WAVE), 0, (hipStream_t)stream, m->host->n_vars,
+                     ck->frames, ck->split_width, (const cs_val *)m->d_walk_root, (const cs_val *)ck->d_pool, (int)ck->capacity,
+                     (const int *)d_slots, (long long)count, (const long long *)d_offsets, (long long)total, (cs_val *)d_rows,
+                     (int *)d_owner, objective | order << 3, (const cs_walk_start *)d_owner_start, (cs_walk_start *)d_start);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_many_fold_halvings(const int64_t *d_sub_halvings, const int32_t *d_owner, int64_t total, int64_t *d_halvings,
+                                        void *stream) {
+  if (d_sub_halvings == NULL || d_owner == NULL || d_halvings == NULL) return set_err(CSGPU_E_ARG, "null argument");
+  if (total < 0) return set_err(CSGPU_E_ARG, "negative record count");
+  if (total > 256ll * 0x7fffffff) return set_err(CSGPU_E_LIMIT, "more than 2^39 - 256 records in one call");
+  if (total == 0) return CSGPU_OK;
+  hipLaunchKernelGGL(cs_walk_fold_halvings, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const long long *)d_sub_halvings, (const int *)d_owner, (long long)total, (long long *)d_halvings);
+  HIP_TRY(hipGetLastError());
+  return CSGPU_OK;
+}
+
 /* ---- every solution of every instance of a clause model under ALL, through one bounded stream (cs_walk_stream) ---- */
 
 extern "C" int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
@@ -2715,7 +2846,7 @@ extern "C" int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu
   ok.owner = out->d_owner;
   ok.count = (unsigned long long *)out->d_count;
   ok.capacity = (long long)out->capacity;
-  return many_clauses_launch(m, WALK_STREAM, m->host->n_vars, CS_OBJ_ALL, options->max_nodes, &b, 0, &wk, &ok);
+  return many_clauses_launch(m, WALK_STREAM, m->host->n_vars, CS_OBJ_ALL, options->max_nodes, &b, 0, &wk, &ok, NULL);
 }
 
 #ifdef CS_SHAVE_TIMELINE

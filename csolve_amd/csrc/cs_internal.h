@@ -84,6 +84,8 @@ int csgpu_internal_many_clauses_from_symbol(const csgpu_model *m, char *buf, siz
 int csgpu_internal_many_clauses_order_symbol(const csgpu_model *m, char *buf, size_t len);
 /* and for cs_walk_order_resume (csgpu_solve_many_clauses_ordered_checkpointed / _resume) */
 int csgpu_internal_many_clauses_order_resume_symbol(const csgpu_model *m, char *buf, size_t len);
+/* and for cs_walk_order_from (csgpu_solve_many_clauses_ordered_from / _from_resume) */
+int csgpu_internal_many_clauses_order_from_symbol(const csgpu_model *m, char *buf, size_t len);
 
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */
 typedef struct csgpu_step_launch {

@@ -110,7 +110,13 @@
  * split_width (the host compares it), which fixes F for the fresh and the resume launch.  The halving count goes on from
  * ord.halvings[inst] as the other counters go on from the record; a walk stopped between the two halves of a node finds
  * nv == mid + 1 in its frame and counts the parent once.  cs_walk_children / cs_walk_fanout do not read these slots (the
- * host refuses the pool): a fan-out of halves would have to account for `halvings`.
+ * host refuses the pool): a fan-out of halves has to account for `halvings`, which cs_walk_order_children /
+ * cs_walk_order_fanout below do.
+ *
+ * The ordered walk from a start incumbent (cs_walk_order_from, csgpu_solve_many_clauses_ordered_from / _from_resume): the
+ * same loop a ninth time, CS_WALK_CK 1, CS_WALK_ORDER 1 and CS_WALK_FROM 1 -- cs_walk_order_resume's slots and code,
+ * cs_walk_from's `start`, own-solutions report and "ck.capacity == 0: no pool".  It walks the children that
+ * cs_walk_order_fanout makes of a stopped MIN / MAX walk.
  * Resources (-Rpass-analysis=kernel-resource-usage, gfx950) are in DESIGN.md 3.10. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
@@ -442,6 +448,194 @@ __global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_fanout(in
       if (start_out != nullptr && lane == 0) start_out[row] = st;
     }
   }
+}
+
+/* cs_walk_order's walk with checkpoints AND cs_walk_from's start incumbents (csgpu_solve_many_clauses_ordered_from /
+ * _from_resume): the same loop a ninth time, CS_WALK_CK 1, CS_WALK_ORDER 1 and CS_WALK_FROM 1.  Fresh instances are
+ * cs_walk_order_resume's MIN / MAX walk and may begin with start[inst] under cs_walk_from's own-solutions rule; the slots
+ * are cs_walk_order_resume's (same magic, same code), so a checkpoint of either kernel goes on under the other.
+ * ck.capacity == 0: no pool, and then ord.halvings may be NULL (nothing is resumed) */
+template <int CPL, bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_order_from(cs_tables T, cs_walk_io io, cs_walk_ck ck, cs_walk_ord ord,
+                                                               const cs_walk_start *start) {
+#define CS_WALK_CK 1
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
+#define CS_WALK_FROM 1
+#define CS_WALK_ORDER 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_ORDER
+#undef CS_WALK_FROM
+#undef CS_WALK_STREAM
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+/* ---- a stopped ORDERED walk spread over the waves of the next launch (csgpu_many_clause_ordered_checkpoint_children /
+ * _fanout; the records fold with cs_dive_fold, the best values with cs_walk_fold_best, the halving counts with
+ * cs_walk_fold_halvings)
+ *
+ * What cs_walk_children / cs_walk_fanout are to a plain clause pool, for a pool of cs_walk_order_resume: a slot is
+ * `frames` + 1 frames under CS_WALK_CK_MAGIC_ORDER, its code objective | order << 3.  The children of a frame {row f, bv,
+ * next}, lo, hi = f[bv], are the walk's own (cs_walk_body.hip.h reads kind and mid back from the frame's row in the same
+ * way), mid = (lo + hi) >> 1 in 64 bits:
+ *   enumerating (hi - lo + 1 <= split_width), next in [lo, hi]   the rows bv = [v, v], v = next .. hi
+ *   halving, next == mid + 1                                    one child, bv = [mid + 1, hi]
+ *   halving, next == lo (the current node only)                 two children, [lo, mid] then [mid + 1, hi]
+ * In the third case the walk had not yet counted the parent in `halvings` (it does when the first half is tried), so the
+ * instance owes one halving that no record holds: unsplit = 1.  Walk order: the current node's children, then those of
+ * the frame below it, down to frame 1.  A child as a root row of its own is what the walk makes of it -- the row narrowed,
+ * then cs_rounds_body.hip.h, then the branching variable chosen anew -- so under ALL the fold is exact, `halvings`
+ * included: owner + unsplit + the sum of the sub-instances'.  Under MIN / MAX (code's objective 2 or 3) the fan-out
+ * writes the start incumbent of every row as cs_walk_fanout does, and the rows are walked by cs_walk_order_from.
+ * One wave per instance, CS_DIVE_FAN_WAVES instances per workgroup, 64-bit counts and row indices, no atomics.  Everything
+ * is compared before what depends on it is read; -1 (never a partial count) for a slot number outside the pool, another
+ * magic, a depth outside [0, frames), another code, a frame whose bv is outside [0, n), whose bounds of bv are empty or
+ * outside the root domain, an enumerating frame whose next is outside [lo, hi], a halving frame whose next is neither
+ * mid + 1 nor (current node only) lo. */
+static __device__ __forceinline__ long long cs_walk_order_slot_children(int n, int frames, int split_width,
+                                                                        const cs_val *__restrict__ root_dom,
+                                                                        const cs_val *__restrict__ pool, int capacity,
+                                                                        int slot, int lane, int code, int *unsplit) {
+  *unsplit = 0;
+  if (slot < 0) return 0;
+  if (slot >= capacity) return -1;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (((size_t)frames + 1) * fstride);
+  const cs_val head = base[0];
+  const int depth = __builtin_amdgcn_readfirstlane(head.lo);
+  if (__builtin_amdgcn_readfirstlane(head.hi) != CS_WALK_CK_MAGIC_ORDER || depth < 0 || depth >= frames) return -1;
+  if ((__builtin_amdgcn_readfirstlane(base[1].hi) >> 1) != code) return -1; /* have_best | code << 1 */
+  long long mine = 0;
+  bool bad = false, owes = false;
+  for (int d = lane; d <= depth && !bad; d += CS_WAVE) {
+    const cs_val *f = base + fstride * (1 + (size_t)d);
+    const cs_val meta = f[n];
+    if (meta.lo < 0 || meta.lo >= n) {
+      bad = true;
+    } else {
+      const cs_val node = f[meta.lo], r = root_dom[meta.lo];
+      if (node.lo < r.lo || node.hi > r.hi || node.lo > node.hi) {
+        bad = true;
+      } else if ((long long)node.hi - (long long)node.lo + 1 > (long long)split_width) { /* halves: lo < mid + 1 <= hi */
+        const int mid = (int)(((long long)node.lo + (long long)node.hi) >> 1);
+        if (meta.hi == mid + 1) {
+          mine += 1;
+        } else if (d == depth && meta.hi == node.lo) {
+          mine += 2;
+          owes = true;
+        } else {
+          bad = true;
+        }
+      } else if (meta.hi < node.lo || meta.hi > node.hi) {
+        bad = true;
+      } else {
+        mine += (long long)node.hi - (long long)meta.hi + 1;
+      }
+    }
+  }
+  if (__ballot(bad) != 0ull) return -1;
+  if (__ballot(owes) != 0ull) *unsplit = 1;
+  for (int o = CS_WAVE / 2; o > 0; o >>= 1) mine += __shfl_xor(mine, o, CS_WAVE);
+  return cs_dive_uniform(mine);
+}
+
+/* children[i] = the untried children of the ordered checkpoint in slot slots[i]: 0 for slots[i] < 0, -1 for a refused slot;
+ * unsplit[i] = 1 where the current node is a halving one with neither half tried, else 0 (a refused slot: 0) */
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_order_children(
+    int n, int frames, int split_width, const cs_val *__restrict__ root_dom, const cs_val *__restrict__ pool, int capacity,
+    const int *__restrict__ slots, long long count, long long *__restrict__ children, int *__restrict__ unsplit, int code) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
+  int owes = 0;
+  const long long c = cs_walk_order_slot_children(n, frames, split_width, root_dom, pool, capacity, slot, lane, code, &owes);
+  if (lane == 0) {
+    children[i] = c;
+    unsplit[i] = c > 0 ? owes : 0;
+  }
+}
+
+/* rows[offsets[i] ..] = the children of instance i in walk order, owner[row] = i and, under MIN / MAX, start_out[row] as
+ * cs_walk_fanout writes it.  The instance is counted again first: it writes nothing unless offsets[i + 1] - offsets[i] is
+ * its count and its rows lie inside [0, total) */
+__global__ __launch_bounds__(CS_DIVE_FAN_WAVES * CS_WAVE) void cs_walk_order_fanout(
+    int n, int frames, int split_width, const cs_val *__restrict__ root_dom, const cs_val *__restrict__ pool, int capacity,
+    const int *__restrict__ slots, long long count, const long long *__restrict__ offsets, long long total,
+    cs_val *__restrict__ rows, int *__restrict__ owner, int code, const cs_walk_start *__restrict__ owner_start,
+    cs_walk_start *__restrict__ start_out) {
+  const int lane = (int)(threadIdx.x % CS_WAVE);
+  const long long i = (long long)blockIdx.x * CS_DIVE_FAN_WAVES + (long long)(threadIdx.x / CS_WAVE);
+  if (i >= count) return;
+  const int slot = __builtin_amdgcn_readfirstlane(slots[i]);
+  if (slot < 0) return;
+  int owes = 0;
+  const long long mine = cs_walk_order_slot_children(n, frames, split_width, root_dom, pool, capacity, slot, lane, code, &owes);
+  const long long off = cs_dive_uniform(offsets[i]), end = cs_dive_uniform(offsets[i + 1]);
+  if (mine <= 0 || off < 0 || end > total || end - off != mine) return;
+  const size_t fstride = (size_t)n + 1;
+  const cs_val *base = pool + (size_t)slot * (((size_t)frames + 1) * fstride);
+  const int depth = __builtin_amdgcn_readfirstlane(base[0].lo);
+  cs_walk_start st; /* what every child of this slot starts with: the header's incumbent, or the owner's better one */
+  st.best = 0;
+  st.have = 0;
+  if (start_out != nullptr) {
+    const int sense = (code & 7) == 2 ? 1 : 2;
+    st.have = __builtin_amdgcn_readfirstlane(base[1].hi) & 1;
+    if (st.have != 0) st.best = __builtin_amdgcn_readfirstlane(base[1].lo);
+    if (owner_start != nullptr) {
+      const int ohave = __builtin_amdgcn_readfirstlane(owner_start[i].have);
+      if (ohave != 0) {
+        const int obest = __builtin_amdgcn_readfirstlane(owner_start[i].best);
+        if (st.have == 0 || cs_objective_better(sense, cs_interval(obest, obest), st.best)) st.best = obest;
+        st.have = 1;
+      }
+    }
+  }
+  long long row = off;
+  for (int d = depth; d >= 0; d--) {
+    const cs_val *f = base + fstride * (1 + (size_t)d);
+    const cs_val meta = f[n];
+    const int bv = __builtin_amdgcn_readfirstlane(meta.lo);
+    const int next = __builtin_amdgcn_readfirstlane(meta.hi);
+    const int lo = __builtin_amdgcn_readfirstlane(f[bv].lo), hi = __builtin_amdgcn_readfirstlane(f[bv].hi);
+    const bool halves = (long long)hi - (long long)lo + 1 > (long long)split_width;
+    const int mid = (int)(((long long)lo + (long long)hi) >> 1);
+    /* child c of the frame is bv = [a, b]: a value each, or the halves that are left (next == lo: both) */
+    const long long kids = halves ? (next == lo ? 2 : 1) : (long long)hi - (long long)next + 1;
+    for (long long c = 0; c < kids && row < end; c++, row++) {
+      int a, b;
+      if (!halves) {
+        a = b = (int)((long long)next + c);
+      } else if (next == lo && c == 0) {
+        a = lo;
+        b = mid;
+      } else {
+        a = mid + 1;
+        b = hi;
+      }
+      cs_val *dst = rows + (size_t)row * (size_t)n;
+      for (int x = lane; x < n; x += CS_WAVE) dst[x] = x == bv ? cs_interval(a, b) : f[x];
+      if (owner != nullptr && lane == 0) owner[row] = (int)i;
+      if (start_out != nullptr && lane == 0) start_out[row] = st;
+    }
+  }
+}
+
+/* csgpu_many_fold_halvings: halvings[owner[t]] += sub_halvings[t] for every t < total with owner[t] >= 0, one relaxed
+ * agent-scope 64-bit add each; shaped like cs_dive_fold */
+__global__ __launch_bounds__(256) void cs_walk_fold_halvings(const long long *__restrict__ sub_halvings,
+                                                             const int *__restrict__ owner, long long total,
+                                                             long long *halvings) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int o = owner[t];
+  if (o < 0) return;
+  const long long h = sub_halvings[t];
+  if (h != 0) __hip_atomic_fetch_add(halvings + o, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 /* csgpu_many_fold_best: every sub-record with a solution offers (rank(best) << 32) | row to its owner's key, one relaxed

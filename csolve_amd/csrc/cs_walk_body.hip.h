@@ -1,6 +1,6 @@
-/* cs_walk_body.hip.h -- the body of the eight kernels of cs_walk.hip.h, which includes it inside each of them under six
- * switches (the fifth, CS_WALK_FROM, is 1 for cs_walk_from alone: cs_walk_resume's row, and `start`; the sixth,
- * CS_WALK_ORDER, for cs_walk_order alone: cs_walk_clauses's row, and `ord`):
+/* cs_walk_body.hip.h -- the body of the nine kernels of cs_walk.hip.h, which includes it inside each of them under six
+ * switches (the fifth, CS_WALK_FROM, is 1 for cs_walk_from -- cs_walk_resume's row, and `start` -- and for
+ * cs_walk_order_from; the sixth, CS_WALK_ORDER, for the three cs_walk_order* kernels: `ord`):
  *                      CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART  CS_WALK_STREAM
  *   cs_walk_clauses        0           0              0              0       csgpu_solve_many_clauses
  *   cs_walk_resume         1           0              0              0       one more argument, `ck`: the pool and the slots of the call
@@ -9,6 +9,7 @@
  *   cs_walk_stream         1           0              0              1       `ck` and `out`, the solution stream of the call
  *   cs_walk_order          0           0              0              0       one more argument, `ord`: the order, split_width, the halving counts
  *   cs_walk_order_resume   1           0              0              0       CS_WALK_ORDER 1 as well: `ck`, then `ord`
+ *   cs_walk_order_from     1           0              0              0       CS_WALK_ORDER 1 and CS_WALK_FROM 1: `ck`, `ord`, `start`
  * Text, not a __device__ function, as cs_dive_body.hip.h.  Every line of a switch stands under its `#if`, so a kernel
  * that defines it 0 sees the text it saw before the switch was there and compiles to the same instructions.
  * CS_WALK_CK: an instance that stops at its budget leaves its frames, its current node, {bv, nv} and its incumbent in a
@@ -33,7 +34,7 @@
  * round: DONE, no node).  io.best[inst] is written only when the instance has a solution of its own (sols > 0, the record's
  * count included when it is resumed): one that proves that nothing beats its start leaves best and its row alone.
  * ck.capacity == 0 means "no pool" as under CS_WALK_UPTO.  New per-instance state is scalars only: start_have, start_best.
- * CS_WALK_ORDER (a sixth switch, 1 for cs_walk_order alone, every other switch 0): cs_walk_clauses's walk with one more
+ * CS_WALK_ORDER (a sixth switch; alone, every other switch 0, it is cs_walk_order): cs_walk_clauses's walk with one more
  * argument `ord` -- the branching variable is the open one with the smallest cs_order_key(ord.order, d) (cs_arith.h) in
  * place of the width in the two wave minima, and a node whose branching variable has more than ord.split_width values has
  * two children, [lo, mid] and [mid + 1, hi], mid = (lo + hi) >> 1 in 64 bits.  Kind and mid are read from the node as it
@@ -46,7 +47,13 @@
  * by io.frames, not n (CS_WALK_SLOT_FRAMES), and its header carries a magic of its own (CS_WALK_SLOT_MAGIC); the three
  * names stand for the old text in every other kernel.  ck.code is objective | order << 3, and a resumed instance's
  * halving count goes on from ord.halvings[inst].  A frame needs nothing new: {bv, nv} says where a halving node stands
- * (nv == lo: no half tried yet, nv == mid + 1: the second is next), kind and mid are read back from the frame's row. */
+ * (nv == lo: no half tried yet, nv == mid + 1: the second is next), kind and mid are read back from the frame's row.
+ * CS_WALK_CK && CS_WALK_ORDER && CS_WALK_FROM (cs_walk_order_from alone): the two above together.  Every line of
+ * CS_WALK_FROM stands under an `#if` of its own and reads nothing that CS_WALK_ORDER changes: the root row takes the start's
+ * bound before the root node's rounds whatever the order, the header's incumbent is `best` / `have_best` (the start's until
+ * the instance has a solution of its own), the report writes io.best at sols > 0 and ord.halvings beside it, and
+ * ck.capacity == 0 draws no slot and leaves ck.slots alone.  A resumed instance reads ord.halvings[inst], so the host
+ * requires the array with a pool; without one nothing is resumed and it may be NULL. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

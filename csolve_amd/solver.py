@@ -604,7 +604,7 @@ class Model:
     MANY_ORDERS = {"none": 0, "smallest-domain": 1, "largest-domain": 2, "smallest-value": 3, "largest-value": 4}
 
     def solve_many_clauses_ordered(self, roots, objective="ANY", *, max_nodes, order="smallest-domain", split_width=256,
-                                   solutions=True, stream=None, checkpoints=None) -> dict:
+                                   solutions=True, stream=None, checkpoints=None, start=None) -> dict:
         """solve_many_clauses under one of the engine's five variable orders, with wide intervals halved
         (csgpu_solve_many_clauses_ordered): the same walk, but the branching variable is the open one the order puts
         first -- "none", "smallest-domain", "largest-domain", "smallest-value", "largest-value", the names of
@@ -612,12 +612,15 @@ class Model:
         values (>= 1) has two children, [lo, mid] and [mid + 1, hi] with mid = (lo + hi) >> 1, instead of one per value.
         A row that leaves a variable at its root width (an open `end` of a schedule) is then bisected, not enumerated.
         roots, objective, max_nodes, solutions, stream: as solve_many_clauses.  -> the dict of solve_many_clauses and
-        `halvings` [K] int64: the parents split in two.  No start incumbents.
+        `halvings` [K] int64: the parents split in two.
         checkpoints: a pool of many_clause_ordered_checkpoints(capacity, split_width), made for this split_width: an
         instance that stops at max_nodes keeps its walk, its incumbent and its place between two halves in a slot of it
         (csgpu_solve_many_clauses_ordered_checkpointed); the answer then has `slot` [K] int32 (-1: no checkpoint) and is
         what resume_many_clauses() continues, under the same objective, order and split_width.  A walk in slices is the one
-        call with the summed budget, field for field, `halvings` included.  Without it nothing changes."""
+        call with the summed budget, field for field, `halvings` included.  Without it nothing changes.
+        start: int32 [K, 2] on the device, {best, have} per instance, as solve_many_clauses(..., start=) and with its rules
+        (csgpu_solve_many_clauses_ordered_from, MIN / MAX only, with or without a pool): `first` / `best` are written only
+        for solutions of the instance's own.  have == 0 everywhere is the call without `start`, `halvings` included."""
         L = load_library()
         n = self.n_vars
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
@@ -625,6 +628,8 @@ class Model:
                                int(max_nodes))
         bad = obj not in (0, 1) and (obj not in (2, 3) or self.objective != obj or self.objective_var < 0)
         bad = bad or not 0 <= opt.order <= 4 or opt.split_width < 0
+        if start is not None:
+            return self._solve_many_clauses_ordered_from(roots, obj, opt, bad, solutions, stream, checkpoints, start)
         roots, K = self._many_roots(roots, bad, lambda ptr, count: check(
             L.csgpu_solve_many_clauses_ordered(self._h, ptr, count, C.byref(opt), ptr, None, None, None, None)),
             qualifies=self.qualifies_many_clauses())
@@ -652,6 +657,37 @@ class Model:
             out["best"] = best[:K]
         out["halvings"] = halvings[:K]
         return out
+
+    def _solve_many_clauses_ordered_from(self, roots, obj, opt, bad, solutions, stream, checkpoints, start) -> dict:
+        """solve_many_clauses_ordered with start incumbents: the one entry, with or without a pool"""
+        L = load_library()
+        n = self.n_vars
+        roots, K = self._many_roots(roots, bad or obj not in (2, 3), lambda ptr, count: check(
+            L.csgpu_solve_many_clauses_ordered_from(self._h, ptr, ptr, count, C.byref(opt), ptr, None, None, None, None, None,
+                                                    None)), qualifies=self.qualifies_many_clauses())
+        assert torch.is_tensor(start) and start.is_cuda and start.dtype == torch.int32 and start.is_contiguous() and \
+            tuple(start.shape) == (K, 2), "start is int32 [K, 2] on the device: {best, have}"
+        buf = self._many_records(K, roots.device)
+        first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
+        best = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device)
+        halvings = torch.zeros((max(K, 1),), dtype=torch.int64, device=roots.device)
+        slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device) if checkpoints is not None else None
+        check(L.csgpu_solve_many_clauses_ordered_from(
+            self._h, roots.data_ptr() if K else buf.data_ptr(), start.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
+            buf.data_ptr(), first.data_ptr() if solutions and K else None, best.data_ptr(), halvings.data_ptr(),
+            checkpoints._h if checkpoints is not None else None, slots.data_ptr() if slots is not None else None,
+            _stream_ptr(stream)))
+        out = self._many_answer(buf, K, first, slots, checkpoints)
+        if checkpoints is not None:
+            out["_objective"], out["_best"] = obj, best
+            out["_order"], out["_split_width"], out["_halvings"] = opt.order, opt.split_width, halvings
+        out["best"] = best[:K]
+        out["halvings"] = halvings[:K]
+        return out
+
+    def many_clauses_order_from_kernel(self):
+        """the cs_walk_order_from instantiation solve_many_clauses_ordered(..., start=) launches, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_order_from_symbol")
 
     def many_clauses_ordered_frames(self, split_width=256) -> int:
         """frames per wave of a solve_many_clauses_ordered call (csgpu_many_clauses_ordered_frames): n_vars + for every
@@ -692,15 +728,22 @@ class Model:
         of either MIN / MAX call may be continued either way.
         An answer of solve_many_clauses_ordered(..., checkpoints=pool) goes on through
         csgpu_solve_many_clauses_ordered_resume under its order and split_width; `halvings` accumulates with the other
-        counters.  max_solutions and own_solutions are not for it."""
+        counters.  max_solutions is not for it; own_solutions continues a MIN / MAX answer through
+        csgpu_solve_many_clauses_ordered_from_resume under the own-solutions rule (an answer of another objective, or one
+        that does not say under which it was made: ValueError)."""
         if "_checkpoints" in result and "_order" in result:
-            if max_solutions is not None or own_solutions:
-                raise ValueError("max_solutions and own_solutions do not continue an answer of solve_many_clauses_ordered: "
-                                 "the ordered walk has neither up to k solutions nor start incumbents")
+            if max_solutions is not None:
+                raise ValueError("max_solutions does not continue an answer of solve_many_clauses_ordered: the ordered walk "
+                                 "has no up to k solutions")
+            if own_solutions and result.get("_objective") not in (2, 3):
+                raise ValueError("own_solutions continues a MIN / MAX answer of solve_many_clauses_ordered: only such a walk "
+                                 "has an incumbent")
             opt = ManyOrderOptions(result["_objective"], result["_order"], result["_split_width"], 0, int(max_nodes))
             first, best = result.get("first"), result["_best"]
             K = result["status"].shape[0]
-            check(load_library().csgpu_solve_many_clauses_ordered_resume(
+            L = load_library()
+            entry = L.csgpu_solve_many_clauses_ordered_from_resume if own_solutions else L.csgpu_solve_many_clauses_ordered_resume
+            check(entry(
                 self._h, K, C.byref(opt), result["_records"].data_ptr(), first.data_ptr() if first is not None and K else None,
                 best.data_ptr() if best is not None else None, result["_halvings"].data_ptr(), result["_checkpoints"]._h,
                 result["_slots"].data_ptr(), _stream_ptr(stream)))
@@ -1207,7 +1250,8 @@ class Model:
         """the driver of solve_many_spread and solve_many_clauses_spread under ALL.  `family`: what the two differ in --
         `solve` (the family's solve_many, walked under "ALL"), `resume` (its resume in place), `children` and `fanout` (its
         count and fan-out of a pool), `make_pool`, `slot_bytes` and `qualifies` (False: the solve call itself refuses the
-        model, before a pool is made for it)"""
+        model, before a pool is made for it); `halvings` (the ordered walk): `children` gives (children, unsplit), and the
+        answers' `halvings` are folded beside the records (fold_many_halvings, and the unsplit of every fanned slot)"""
         BIG = 1 << 62  # "no solution yet": above every row number
         solve, resume = family["solve"], family["resume"]
         if not family["qualifies"]:  # the call says why, as it does without the spread
@@ -1227,6 +1271,8 @@ class Model:
             rows = sp.count_stopped(batch, last)
             if sp.owner is not None:
                 self.fold_many(batch, sp.owner, main, stream)
+                if family.get("halvings"):
+                    self.fold_many_halvings(batch, sp.owner, main, stream)
             if not solutions:
                 return
             has = batch["solutions"] > 0
@@ -1247,7 +1293,7 @@ class Model:
             if S == 0:
                 break
             slots = batch["slot"][index].contiguous()
-            children = family["children"](pool, slots, stream)
+            children, unsplit = sp.counted(family["children"](pool, slots, stream))
             offsets = torch.zeros((S + 1,), dtype=torch.int64, device=dev)
             torch.cumsum(children.clamp(min=0), 0, out=offsets[1:])
             total = int(offsets[-1].item())
@@ -1259,6 +1305,7 @@ class Model:
             sp.count_refused(index, children)
             if total == 0:
                 break
+            sp.owe(main, index, unsplit)
             rows, came_from = family["fanout"](pool, slots, offsets, total, stream=stream)
             leave(False)
             if solutions:
@@ -1340,8 +1387,84 @@ class Model:
         best = torch.where(has, rank - (1 << 31) if obj == 2 else (1 << 31) - 1 - rank, torch.zeros_like(rank))
         return has, best.to(torch.int32), torch.where(has, key & 0xFFFFFFFF, torch.zeros_like(key))
 
+    def _ordered_code(self, objective, order):
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        return obj, self.MANY_ORDERS[order] if isinstance(order, str) else int(order)
+
+    def clause_ordered_checkpoint_children(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, objective, order,
+                                           stream=None):
+        """clause_checkpoint_children for a pool of many_clause_ordered_checkpoints()
+        (csgpu_many_clause_ordered_checkpoint_children): the untried children, halves included, of the checkpoints in
+        `slots` (int32 [S] on the device) that were written under `objective` ("ALL", "MIN" or "MAX") and `order` ->
+        (children int64 [S]: 0 for a slot < 0, -1 for a refused slot; unsplit int32 [S]: 1 where the current node is a
+        halving one with neither half tried, the halving its owner owes)"""
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+        obj, order = self._ordered_code(objective, order)
+        S = slots.shape[0]
+        children = torch.empty((max(S, 1),), dtype=torch.int64, device=slots.device)
+        unsplit = torch.zeros((max(S, 1),), dtype=torch.int32, device=slots.device)
+        check(load_library().csgpu_many_clause_ordered_checkpoint_children(
+            checkpoints._h, slots.data_ptr(), S, obj, order, children.data_ptr(), unsplit.data_ptr(), _stream_ptr(stream)))
+        return children[:S], unsplit[:S]
+
+    def clause_ordered_checkpoint_fanout(self, checkpoints: "ManyCheckpoints", slots: torch.Tensor, objective, order,
+                                         offsets: torch.Tensor, total: int, rows: torch.Tensor = None,
+                                         owner: torch.Tensor = None, stream=None, owner_start: torch.Tensor = None,
+                                         start: torch.Tensor = None):
+        """clause_checkpoint_fanout for a pool of many_clause_ordered_checkpoints()
+        (csgpu_many_clause_ordered_checkpoint_fanout): the children of the checkpoints in `slots` as root rows of
+        solve_many_clauses_ordered, in walk order, a half a row with its variable narrowed to that half.  offsets, total,
+        rows, owner: as checkpoint_fanout.  -> (rows, owner) under "ALL"; under "MIN" / "MAX" (rows, owner, start), start
+        int32 [total, 2] the {best, have} every row begins with in solve_many_clauses_ordered(..., start=): the strictly
+        better of its checkpoint's incumbent and owner_start[i] (int32 [S, 2] on the device, or None)"""
+        n, S, total = self.n_vars, slots.shape[0], int(total)
+        obj, order = self._ordered_code(objective, order)
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and slots.dim() == 1
+        assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and tuple(offsets.shape) == (S + 1,)
+        if rows is None:
+            rows = torch.empty((max(total, 1), n, 2), dtype=torch.int32, device=slots.device)
+        if owner is None:
+            owner = torch.empty((max(total, 1),), dtype=torch.int32, device=slots.device)
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= total * n * 2
+        assert owner.dtype == torch.int32 and owner.is_contiguous() and owner.numel() >= total
+        if obj in (2, 3) and start is None:
+            start = torch.empty((max(total, 1), 2), dtype=torch.int32, device=slots.device)
+        assert start is None or (start.dtype == torch.int32 and start.is_contiguous() and start.numel() >= total * 2)
+        assert owner_start is None or (owner_start.is_cuda and owner_start.dtype == torch.int32 and
+                                       owner_start.is_contiguous() and tuple(owner_start.shape) == (S, 2))
+        check(load_library().csgpu_many_clause_ordered_checkpoint_fanout(
+            checkpoints._h, slots.data_ptr(), S, obj, order, owner_start.data_ptr() if owner_start is not None and S else None,
+            offsets.data_ptr(), rows.data_ptr(), owner.data_ptr(), start.data_ptr() if start is not None else None, total,
+            _stream_ptr(stream)))
+        if start is not None:
+            return rows[:total], owner[:total], start[:total]
+        return rows[:total], owner[:total]
+
+    def fold_many_halvings(self, sub: dict, owner: torch.Tensor, result: dict, stream=None) -> dict:
+        """add the `halvings` of the sub-instances `sub` (a solve_many_clauses_ordered answer over fanned rows) to their
+        owners' in `result` (csgpu_many_fold_halvings): owner int32 [T] indexes result's instances, rows with owner < 0
+        are skipped.  Exactly once per batch, beside fold_many"""
+        T = sub["status"].shape[0]
+        assert owner.is_cuda and owner.dtype == torch.int32 and owner.is_contiguous() and owner.shape[0] == T
+        check(load_library().csgpu_many_fold_halvings(sub["halvings"].data_ptr(), owner.data_ptr(), T,
+                                                      result["halvings"].data_ptr(), _stream_ptr(stream)))
+        return result
+
+    def _ordered_spread_family(self, obj, order, split_width) -> dict:
+        """what the two spread drivers run over on the ordered walk: its calls, its pools, and the halving counts"""
+        W = int(split_width)
+        return dict(
+            solve=functools.partial(self.solve_many_clauses_ordered, order=order, split_width=W),
+            resume=self.resume_many_clauses,
+            children=lambda pool, slots, stream=None: self.clause_ordered_checkpoint_children(pool, slots, obj, order, stream),
+            fanout=lambda pool, slots, offsets, total, stream=None, **kw: self.clause_ordered_checkpoint_fanout(
+                pool, slots, obj, order, offsets, total, stream=stream, **kw),
+            make_pool=lambda capacity: self.many_clause_ordered_checkpoints(capacity, W),
+            slot_bytes=self.clause_ordered_checkpoint_bytes(W), qualifies=self.qualifies_many_clauses(), halvings=True)
+
     def solve_many_clauses_spread(self, roots, objective="ALL", *, budgets=(256, 4096), max_rounds=64, max_rows=1 << 18,
-                                  solutions=True, stream=None, pool_bytes=1 << 30, pools=None) -> dict:
+                                  solutions=True, stream=None, pool_bytes=1 << 30, pools=None, order=None,
+                                  split_width=256) -> dict:
         """solve_many_spread for the clause models: solve_many_clauses under ALL whose stopped instances are spread over the
         idle waves, by the same driver over solve_many_clauses, resume_many_clauses, clause_checkpoint_children,
         clause_checkpoint_fanout and fold_many.  The split is exact here too: the kernel runs a root row and a child
@@ -1362,26 +1485,42 @@ class Model:
         Promised: status 0 and `best` are those of solve_many_clauses(roots, objective) with a budget that finishes the
         instance, and the whole answer is deterministic in (roots, budgets, max_rounds, max_rows).
         Not promised: nodes / cuts / props / solutions are those of the walk that was made, which is larger than the one
-        call's; `first` is a solution of value `best`, not necessarily the one call's row."""
+        call's; `first` is a solution of value `best`, not necessarily the one call's row.
+        order (a name of solve_many_clauses_ordered, with split_width): the same two drivers over the ordered walk --
+        solve_many_clauses_ordered(..., start=), resume_many_clauses, clause_ordered_checkpoint_children,
+        clause_ordered_checkpoint_fanout, two pools of many_clause_ordered_checkpoints(capacity, split_width) -- with the
+        same promises against solve_many_clauses_ordered(roots, objective, order=, split_width=).  The answer adds
+        `halvings` [K]: an owner's own count, plus 1 for each of its fanned checkpoints whose current node was a halving
+        one with neither half tried, plus the counts of its sub-instances (fold_many_halvings, once per batch): under ALL
+        the one call's.  None: the plain walk, exactly as before."""
         obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
-        if obj in (2, 3):
-            return self._spread_call(functools.partial(self._solve_many_clauses_spread_best, obj), self.many_clause_checkpoints,
-                                     self.clause_checkpoint_bytes(), roots, budgets, max_rounds, max_rows, solutions, stream,
-                                     pool_bytes, pools)
-        assert obj == 1, "solve_many_clauses_spread walks under ALL, or under the model's MIN / MAX"
-        family = dict(solve=self.solve_many_clauses, resume=self.resume_many_clauses, children=self.clause_checkpoint_children,
-                      fanout=self.clause_checkpoint_fanout, make_pool=self.many_clause_checkpoints,
-                      slot_bytes=self.clause_checkpoint_bytes(), qualifies=self.qualifies_many_clauses())
-        return self._spread_call(functools.partial(self._solve_many_spread, family), family["make_pool"], family["slot_bytes"],
-                                 roots, budgets, max_rounds, max_rows, solutions, stream, pool_bytes, pools)
+        assert obj in (1, 2, 3), "solve_many_clauses_spread walks under ALL, or under the model's MIN / MAX"
+        if order is not None:
+            family = self._ordered_spread_family(obj, order, split_width)
+        else:
+            family = dict(solve=self.solve_many_clauses, resume=self.resume_many_clauses,
+                          children=self.clause_checkpoint_children, fanout=self.clause_checkpoint_fanout,
+                          make_pool=self.many_clause_checkpoints, slot_bytes=self.clause_checkpoint_bytes(),
+                          qualifies=self.qualifies_many_clauses())
+            if obj in (2, 3):
+                family.update(
+                    children=lambda pool, slots, stream=None: self.clause_checkpoint_children(pool, slots, stream, objective=obj),
+                    fanout=functools.partial(self.clause_checkpoint_fanout, objective=obj))
+        driver = functools.partial(self._solve_many_clauses_spread_best, obj, family) if obj in (2, 3) else \
+            functools.partial(self._solve_many_spread, family)
+        return self._spread_call(driver, family["make_pool"], family["slot_bytes"], roots, budgets, max_rounds, max_rows,
+                                 solutions, stream, pool_bytes, pools)
 
-    def _solve_many_clauses_spread_best(self, obj, sp, roots, max_rounds, max_rows, solutions, stream) -> dict:
-        """the driver of solve_many_clauses_spread under MIN / MAX: the rounds of _solve_many_spread, with the incumbents"""
+    def _solve_many_clauses_spread_best(self, obj, family, sp, roots, max_rounds, max_rows, solutions, stream) -> dict:
+        """the driver of solve_many_clauses_spread under MIN / MAX: the rounds of _solve_many_spread, with the incumbents.
+        `family`: as there -- `solve` takes `start`, `resume` takes `own_solutions`, `fanout` takes `owner_start` and gives
+        (rows, owner, start)"""
         minimise = obj == 2
-        if not self.qualifies_many_clauses() or self.objective != obj:  # the call says why, as it does without the spread
-            self.solve_many_clauses(roots, obj, max_nodes=sp.budget(0), solutions=solutions, stream=stream)
+        solve = family["solve"]
+        if not family["qualifies"] or self.objective != obj:  # the call says why, as it does without the spread
+            solve(roots, obj, max_nodes=sp.budget(0), solutions=solutions, stream=stream)
         pool = sp.pool_for(0, int(roots.shape[0]))
-        main = self.solve_many_clauses(roots, obj, max_nodes=sp.budget(0), solutions=solutions, stream=stream, checkpoints=pool)
+        main = solve(roots, obj, max_nodes=sp.budget(0), solutions=solutions, stream=stream, checkpoints=pool)
         K, dev = sp.begin(main)
         has = None  # per owner: it holds a solution; its value is main["best"], its row main["first"]
         batch = main
@@ -1397,6 +1536,8 @@ class Model:
                 has = batch["solutions"] > 0
                 return
             self.fold_many(batch, sp.owner, main, stream)
+            if family.get("halvings"):
+                self.fold_many_halvings(batch, sp.owner, main, stream)
             found, value, row = self.fold_many_best(batch, sp.owner, K, obj, stream)
             mine = main["best"]
             take = found & (~has | (value < mine if minimise else value > mine))
@@ -1411,12 +1552,12 @@ class Model:
             if S == 0:
                 break
             slots = batch["slot"][index].contiguous()
-            children = self.clause_checkpoint_children(pool, slots, stream, objective=obj)
+            children, unsplit = sp.counted(family["children"](pool, slots, stream))
             offsets = torch.zeros((S + 1,), dtype=torch.int64, device=dev)
             torch.cumsum(children.clamp(min=0), 0, out=offsets[1:])
             total = int(offsets[-1].item())
             if total > max_rows:  # too wide to fan out: the stopped walks go on where they are
-                self.resume_many_clauses(batch, max_nodes=sp.budget(rounds), stream=stream, own_solutions=sp.owner is not None)
+                family["resume"](batch, max_nodes=sp.budget(rounds), stream=stream, own_solutions=sp.owner is not None)
                 round_rows.append(0)
                 rounds += 1
                 continue
@@ -1424,14 +1565,14 @@ class Model:
             if total == 0:
                 break
             leave(False)  # before the fan-out: the children start from their owners' best after this fold
+            sp.owe(main, index, unsplit)
             whose = sp.owners_of(index)
             owner_start = torch.stack([main["best"][whose], has[whose].to(torch.int32)], 1).contiguous()
-            rows, came_from, start = self.clause_checkpoint_fanout(pool, slots, offsets, total, stream=stream, objective=obj,
-                                                                   owner_start=owner_start)
+            rows, came_from, start = family["fanout"](pool, slots, offsets, total, stream=stream, owner_start=owner_start)
             sp.owner = whose[came_from.long()].to(torch.int32).contiguous()
             pool = sp.pool_for(rounds, total)
-            batch = self.solve_many_clauses(rows, obj, max_nodes=sp.budget(rounds), solutions=solutions, stream=stream,
-                                            checkpoints=pool, start=start)
+            batch = solve(rows, obj, max_nodes=sp.budget(rounds), solutions=solutions, stream=stream, checkpoints=pool,
+                          start=start)
             round_rows.append(total)
             rounds += 1
         leave(True)
@@ -1673,6 +1814,17 @@ class _SpreadRounds:
         stopped = stopped | (batch["status"] == 3)  # (a resume in place refused its slot: BAD_SLOT)
         self.limited.index_add_(0, self.owners_of(rows), stopped.to(torch.int32))
         return rows
+
+    @staticmethod
+    def counted(children):
+        """what a family's `children` gave -> (children, unsplit): unsplit is None for a walk without halving counts"""
+        return children if isinstance(children, tuple) else (children, None)
+
+    def owe(self, main, index, unsplit):
+        """the stopped instances `index` are fanned out: the halving each owes (its current node had neither half tried,
+        so no record counts that parent) goes to its owner, once"""
+        if unsplit is not None:
+            main["halvings"].index_add_(0, self.owners_of(index), unsplit.to(torch.int64))
 
     def count_refused(self, index, children):
         """refused slots (children < 0) among the stopped instances `index`: their work is lost"""

@@ -960,9 +960,9 @@ int csgpu_solve_many_clauses_stream(const csgpu_model *m, const csgpu_val *d_roo
  * Errors before any HIP call: csgpu_solve_many_clauses's in its order (options is this entry's struct), then an order
  * outside 0 .. 4, a negative split_width or a non-zero `reserved` -> CSGPU_E_ARG.  count == 0 -> CSGPU_OK, nothing is
  * launched.
- * Not on this walk: up to k solutions, the solution stream, the spread over idle waves, restarts, start incumbents,
- * prefer-failing, and the kernel-7 walks of csgpu_solve_many, which keep their one rule.  Checkpoints and resume are the
- * section after this one. */
+ * Not on this walk: up to k solutions, the solution stream, restarts, prefer-failing, and the kernel-7 walks of
+ * csgpu_solve_many, which keep their one rule.  Checkpoints and resume are the section after this one, start incumbents
+ * and the spread over idle waves the one after that. */
 typedef struct csgpu_many_order_options {
   int32_t objective;   /* 0 ANY, 1 ALL, 2 MIN, 3 MAX */
   int32_t order;       /* 0..4, csgpu_search_set_strategy's numbers */
@@ -1017,9 +1017,9 @@ int64_t csgpu_many_clauses_ordered_frames(const csgpu_model *m, int32_t split_wi
  * {row, variable, next} is the row with the variable narrowed to [next, hi] -- for a pushed halving parent exactly its
  * second half, for a current node before its first half the whole node.  Every other entry that takes a clause pool
  * refuses this kind with CSGPU_E_ARG: csgpu_solve_many_clauses_checkpointed / _resume, the up-to-k calls, _from /
- * _from_resume, the stream, and csgpu_many_clause_checkpoint_children / _fanout and their _obj forms.
- * Not built on the ordered walk: up to k solutions, the solution stream, restarts, start incumbents, prefer-failing, and
- * the spread over idle waves -- a fan-out of halves has to account for `halvings`. */
+ * _from_resume, the stream, and csgpu_many_clause_checkpoint_children / _fanout and their _obj forms.  The spread over
+ * idle waves has entries of its own for this kind (the next section): a fan-out of halves has to account for `halvings`.
+ * Not built on the ordered walk: up to k solutions, the solution stream, restarts and prefer-failing. */
 size_t csgpu_many_clause_ordered_checkpoint_bytes(const csgpu_model *m, int32_t split_width);
 int csgpu_many_clause_ordered_checkpoints_create(const csgpu_model *m, int64_t capacity, int32_t split_width,
                                                  csgpu_many_checkpoints **out);
@@ -1031,6 +1031,86 @@ int csgpu_solve_many_clauses_ordered_checkpointed(const csgpu_model *m, const cs
 int csgpu_solve_many_clauses_ordered_resume(const csgpu_model *m, int64_t count, const csgpu_many_order_options *options,
                                             csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
                                             int64_t *d_halvings, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+
+/* ---- the ordered walk: start incumbents, and stopped walks spread over the waves of the next call ----
+ * What "start incumbents" and the two spreads above are to csgpu_solve_many_clauses, for csgpu_solve_many_clauses_ordered:
+ * a launch lasts as long as its deepest instance, so the open children of the stopped instances -- halves included -- are
+ * counted and fanned out on the device, walked by the other waves, and folded back into their owners.
+ *
+ * Start incumbents (kernel cs_walk_order_from).  csgpu_solve_many_clauses_ordered_from / _from_resume are
+ * csgpu_solve_many_clauses_from / _from_resume on the ordered walk: `starting`, `own solutions` and `resuming` above hold
+ * word for word, with csgpu_solve_many_clauses_ordered[_checkpointed] for csgpu_solve_many_clauses[_checkpointed] -- with
+ * have == 0 everywhere the call is that one, field for field and row for row, d_halvings included -- and the slots are
+ * those of a csgpu_many_clause_ordered_checkpoints_create pool, code = objective | order << 3.  MIN / MAX only.  A
+ * checkpoint of either ordered MIN / MAX call may be resumed by either ordered resume.
+ *   csgpu_solve_many_clauses_ordered_from         d_start [count] is required; ck == NULL and d_slots == NULL: the plain call
+ *                                                 (d_halvings NULL or [count]); both given: the checkpointed call (d_halvings
+ *                                                 [count] is required, as for every ordered call with a pool)
+ *   csgpu_solve_many_clauses_ordered_from_resume  as csgpu_solve_many_clauses_ordered_resume
+ * Errors before any HIP call, in this order: those of csgpu_solve_many_clauses, in its order and with its codes; an order
+ * outside 0 .. 4, a negative split_width, a non-zero `reserved` -> CSGPU_E_ARG; a null d_start, an objective ANY / ALL,
+ * exactly one of ck / d_slots null (the resume: either) -> CSGPU_E_ARG; with a pool: d_halvings NULL, a pool of another
+ * model, a pool of csgpu_many_checkpoints_create or csgpu_many_clause_checkpoints_create, a pool made for another
+ * split_width -> CSGPU_E_ARG; then count == 0 -> CSGPU_OK.
+ *
+ * The children of a stopped walk.  A slot's frame {row f, variable bv, next}, with lo, hi = f[bv] and mid = (lo + hi) >> 1
+ * taken in 64 bits, has the children the walk itself would try next:
+ *   enumerating (hi - lo + 1 <= split_width), next in [lo, hi]   the rows bv = [v, v] for v = next .. hi
+ *   halving, next == mid + 1 (the second half is left)           one child, bv = [mid + 1, hi]
+ *   halving, next == lo (neither half tried)                     two children, bv = [lo, mid], then bv = [mid + 1, hi]
+ * The third case is possible for the current node only (frame 1 + depth).  There the walk has not yet counted the parent in
+ * its halving count (it does when the first half is tried): the instance owes one halving that no record holds, and
+ * d_unsplit[i] = 1 for such a slot, else 0.  Walk order: the current node's children first, then those of the frame below
+ * it, down to the oldest.  The split width is the pool's.
+ *   csgpu_many_clause_ordered_checkpoint_children  d_children[i] = the children of slot d_slots[i], in 64 bits: 0 for
+ *                                                  d_slots[i] < 0, -1 for a refused slot; d_unsplit [count] int32
+ *   csgpu_many_clause_ordered_checkpoint_fanout    d_rows[d_offsets[i] ..] = the children of instance i as root rows in walk
+ *                                                  order, d_owner[row] = i (d_owner may be NULL); d_offsets [count + 1].
+ *                                                  The slot is counted again first: nothing of instance i is written unless
+ *                                                  d_offsets[i + 1] - d_offsets[i] is exactly its count and its rows lie
+ *                                                  inside [0, total)
+ * Everything is compared before what depends on it is read.  A slot is refused -- count -1, nothing written, never a
+ * partial count -- for a slot number at or above the capacity, another magic, a depth outside [0, F), a code that is not
+ * exactly objective | order << 3 of the call, a frame whose bv is outside [0, n_vars), a frame whose bounds of bv are
+ * empty or outside the root domain, an enumerating frame whose next lies outside [lo, hi], a halving frame whose next is
+ * neither mid + 1 nor, for the current node only, lo.
+ * objective is ALL, MIN or MAX.  Under ALL d_owner_start and d_start must be NULL and the rows are walked by
+ * csgpu_solve_many_clauses_ordered_checkpointed; under MIN / MAX d_start [total] is required, d_start[row] is the better --
+ * strictly, by csgpu_objective_better's order -- of the slot's header incumbent and d_owner_start[i] (NULL, or [count];
+ * have == 0: none), as csgpu_many_clause_checkpoint_fanout_obj writes it, and the rows are walked by
+ * csgpu_solve_many_clauses_ordered_from.
+ * Errors before any HIP call, in this order: a null ck / d_slots / d_children / d_unsplit (the fan-out: ck / d_slots /
+ * d_offsets / d_rows), count < 0, (the fan-out) total < 0 -> CSGPU_E_ARG; an objective other than ALL / MIN / MAX (ANY
+ * among them), an order outside 0 .. 4 -> CSGPU_E_ARG; a pool of csgpu_many_checkpoints_create or
+ * csgpu_many_clause_checkpoints_create -> CSGPU_E_ARG; count > 2^31 - 1 -> CSGPU_E_LIMIT; (the fan-out) under ALL a
+ * d_owner_start or d_start that is not NULL, under MIN / MAX a null d_start -> CSGPU_E_ARG; then count == 0 (the fan-out:
+ * or total == 0) -> CSGPU_OK.
+ *
+ * The fold.  A child walked as a root row of its own is what the walk makes of it: the row narrowed, the fixpoint, the
+ * branching variable chosen anew.  The records fold with the unchanged csgpu_many_fold and the best values with the
+ * unchanged csgpu_many_fold_best.  An owner's halving count is its own, plus d_unsplit of each of its fanned slots, plus
+ * the counts of its sub-instances:
+ *   csgpu_many_fold_halvings   for every t < total with d_owner[t] >= 0: one relaxed agent-scope 64-bit add of
+ *                              d_sub_halvings[t] to d_halvings[d_owner[t]].  Once per batch.  Errors: a null pointer,
+ *                              total < 0 -> CSGPU_E_ARG; total > 2^39 - 256 -> CSGPU_E_LIMIT; then total == 0 -> CSGPU_OK
+ * Under ALL the fold is exact: an owner whose sub-instances all ended DONE has the record of the one
+ * csgpu_solve_many_clauses_ordered call, field for field, and its halving count.  Under MIN / MAX it is exact for the
+ * optimum and its proof (status DONE and best are the one call's); the walk that was made is larger than the one call's. */
+int csgpu_solve_many_clauses_ordered_from(const csgpu_model *m, const csgpu_val *d_roots, const csgpu_many_start *d_start,
+                                          int64_t count, const csgpu_many_order_options *options, csgpu_many_result *d_results,
+                                          int32_t *d_solutions, int32_t *d_best, int64_t *d_halvings, csgpu_many_checkpoints *ck,
+                                          int32_t *d_slots, void *stream);
+int csgpu_solve_many_clauses_ordered_from_resume(const csgpu_model *m, int64_t count, const csgpu_many_order_options *options,
+                                                 csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                                 int64_t *d_halvings, csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+int csgpu_many_clause_ordered_checkpoint_children(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                  int objective, int order, int64_t *d_children, int32_t *d_unsplit, void *stream);
+int csgpu_many_clause_ordered_checkpoint_fanout(const csgpu_many_checkpoints *ck, const int32_t *d_slots, int64_t count,
+                                                int objective, int order, const csgpu_many_start *d_owner_start,
+                                                const int64_t *d_offsets, csgpu_val *d_rows, int32_t *d_owner,
+                                                csgpu_many_start *d_start, int64_t total, void *stream);
+int csgpu_many_fold_halvings(const int64_t *d_sub_halvings, const int32_t *d_owner, int64_t total, int64_t *d_halvings,
+                             void *stream);
 
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */

@@ -49,6 +49,11 @@ field of every instance -- props and root_props included -- and every first solu
 (solve_many_clauses_spread(roots, "MIN" / "MAX"): start incumbents); the check is then that every instance the one call
 ends is ended by the spread with the same optimum, and the spread's own nodes are printed beside the one call's.
 
+--spread B1,B2,... --order NAME --split W [--spread-objective own] times the ORDERED spread
+(solve_many_clauses_spread(..., order=NAME, split_width=W)) beside the one solve_many_clauses_ordered call of the same rows
+and prints the nodes and the halving counts of both, as --spread does; --set may then be a set of
+tests/many_walk_ordered.py as well (schedule5_open_min: the rows that leave `end` at its root width).
+
 --order NAME --split W [--budget N] times Model.solve_many_clauses_ordered(order=NAME, split_width=W) beside the plain call
 of solve_many_clauses on the same rows and the same budget, alternating in this process after a warm-up (--set: a set of
 tests/many_clause_sets.py or of tests/many_walk_ordered.py, e.g. schedule5_open_min, whose rows leave `end` at its root
@@ -119,9 +124,9 @@ def main():
     ap.add_argument("--order", default=None, help="NAME: time solve_many_clauses_ordered beside the plain call (with --split)")
     ap.add_argument("--split", type=int, default=256, help="with --order: split_width")
     args = ap.parse_args()
-    if args.order is not None:
-        if args.spread is not None or args.stream is not None or args.upto is not None or args.restarts is not None:
-            ap.error("--order NAME: without --spread, --stream, --upto and --restarts")
+    if args.order is not None and args.spread is None:
+        if args.stream is not None or args.upto is not None or args.restarts is not None:
+            ap.error("--order NAME: without --stream, --upto and --restarts")
         return order_sliced_route(args) if args.sliced else order_route(args)
     if args.spread is not None:
         if args.stream is not None or args.sliced or args.upto is not None or args.restarts is not None:
@@ -513,12 +518,20 @@ def stream_route(args):
 
 
 def spread_route(args):
-    """the spread beside the counting ALL call of the same rows, same budget, same build"""
+    """the spread beside the counting ALL call of the same rows, same budget, same build; with --order NAME --split W the
+    ordered spread beside the one ordered call"""
     import many_clause_sets as sets
     name = args.set or "linear20_all"
-    if name not in sets.SETS:
-        raise SystemExit(f"--spread: --set is one of {sorted(sets.SETS)}")
-    text, base, objective, budget = sets.build(name)
+    ordered = args.order is not None
+    source = sets
+    if ordered:
+        import many_walk_ordered as O
+        if args.order not in O.ORDERS or args.split < 1:
+            raise SystemExit(f"--order is one of {O.ORDERS}, --split at least 1")
+        source = sets if name in sets.SETS else O
+    if name not in source.SETS:
+        raise SystemExit(f"--spread: --set is one of {sorted(source.SETS)}")
+    text, base, objective, budget = source.build(name)
     own = args.spread_objective == "own"
     if own and objective not in ("MIN", "MAX"):
         raise SystemExit(f"--spread-objective own: {name} is walked under {objective}, not MIN / MAX")
@@ -530,9 +543,15 @@ def spread_route(args):
     model = solve_root(text)
     dev = torch.from_numpy(roots).cuda()
     fields = ("status", "root_props", "nodes", "cuts", "props", "solutions", "first")
-    slot_bytes = model.clause_checkpoint_bytes()
+    walk = dict(order=args.order, split_width=args.split) if ordered else {}
+    solve = model.solve_many_clauses_ordered if ordered else model.solve_many_clauses
+    make_pool = (lambda capacity: model.many_clause_ordered_checkpoints(capacity, args.split)) if ordered else \
+        model.many_clause_checkpoints
+    if ordered:
+        fields += ("halvings",)
+    slot_bytes = model.clause_ordered_checkpoint_bytes(args.split) if ordered else model.clause_checkpoint_bytes()
     per_pool = max(1, min(max(count, args.spread_rows), (1 << 30) // slot_bytes))  # a slot per row, 1 GiB at the most
-    pools = (model.many_clause_checkpoints(per_pool), model.many_clause_checkpoints(per_pool))  # kept: a caller that repeats the call
+    pools = (make_pool(per_pool), make_pool(per_pool))  # kept: a caller that repeats the call
 
     def timed(call):
         torch.cuda.synchronize()
@@ -541,9 +560,9 @@ def spread_route(args):
         torch.cuda.synchronize()
         return time.perf_counter() - t, out
 
-    calls = {"all": lambda: model.solve_many_clauses(dev, objective, max_nodes=budget),
+    calls = {"all": lambda: solve(dev, objective, max_nodes=budget, **walk),
              "spread": lambda: model.solve_many_clauses_spread(dev, objective, budgets=budgets, max_rows=args.spread_rows,
-                                                               pools=pools)}
+                                                               pools=pools, **walk)}
     for call in calls.values():  # warm-up: code load, workspace, the allocator's blocks
         timed(call)
         timed(call)
@@ -554,8 +573,8 @@ def spread_route(args):
             times[k].append(dt)
     one, got = outs["all"], outs["spread"]
     # where the time of the spread goes: the launch of round 0 alone
-    first_ms = statistics.median(timed(lambda: model.solve_many_clauses(dev, objective, max_nodes=budgets[0],
-                                                                        checkpoints=pools[0].reset()))[0] for _ in range(3)) * 1e3
+    first_ms = statistics.median(timed(lambda: solve(dev, objective, max_nodes=budgets[0], checkpoints=pools[0].reset(),
+                                                     **walk))[0] for _ in range(3)) * 1e3
     done = one["status"] == 0  # (an instance the one call leaves at LIMIT has no whole record to compare with)
     if own:  # the optimum and DONE are promised, the walk that was made is another
         fields = ("status", "best")
@@ -565,8 +584,12 @@ def spread_route(args):
     print(json.dumps({
         "tool": "time_solve_many_clauses", "route": "spread", "commit": commit(), "command": " ".join(sys.argv), "set": name,
         "objective": objective, "spread_nodes": int(got["nodes"].sum()),
+        **({"order": args.order, "split_width": args.split, "halvings": int(one["halvings"].sum()),
+            "spread_halvings": int(got["halvings"].sum()), "order_from_kernel": model.many_clauses_order_from_kernel()}
+           if ordered else {}),
         "instances": count, "max_nodes_of_the_one_call": budget, "n_vars": model.n_vars, "clauses": model.n_clauses,
-        "kernel": model.many_clauses_kernel(), "resume_kernel": model.many_clauses_resume_kernel(),
+        "kernel": model.many_clauses_order_kernel() if ordered else model.many_clauses_kernel(),
+        "resume_kernel": model.many_clauses_order_resume_kernel() if ordered else model.many_clauses_resume_kernel(),
         "waves": model.many_clauses_waves(count), "slot_bytes": slot_bytes, "budgets": list(budgets), "max_rows": args.spread_rows,
         "all_ms": spread(times["all"]), "spread_ms": spread(times["spread"]),
         "all_over_spread": round(med["all"] / med["spread"], 3),
