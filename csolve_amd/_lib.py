@@ -182,6 +182,8 @@ def load_library():
     L.csgpu_propagate_batch_obj.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp]
     # the incumbent read from device memory (cs_internal.h): what the device-driven search iterations launch; tests only
     L.csgpu_internal_propagate_objdev.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, i32, vp, C.c_int, vp]
+    L.csgpu_internal_propagate_fb.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+    L.csgpu_internal_shave_launch.argtypes = [vp, i64, C.POINTER(i64 * 3)]
     L.csgpu_model_forbidden_words.argtypes = [vp]
     L.csgpu_propagate_batch_fb.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.csgpu_eval_batch.argtypes = [vp, vp, vp, i64, vp]

@@ -1616,17 +1616,40 @@ static unsigned *ticket_slot(csgpu_model *m, void *stream) {
   return slot < 0 ? NULL : m->d_tickets + (size_t)slot * CS_TICKET_SLOT_WORDS;
 }
 
-static int launch_shave(const csgpu_model *m, const csgpu_val *d_states_in, const csgpu_node *d_nodes,
-                        csgpu_val *d_states_out, csgpu_result *d_results, int64_t batch, const uint64_t *d_batch,
-                        void *stream) {
+/* the geometry of a kernel 7 launch of `batch` nodes: nodes per chunk, and the grid in workgroups of plan.shave.waves */
+static void shave_geometry(const csgpu_model *m, int64_t batch, int *csz_out, int64_t *grid_out) {
   const cs_planned *k = &m->plan.shave;
   /* four or two nodes per chunk (four per ticket when a node is one register per lane); fewer while that would leave a
    * wave with less than four chunks */
-  int csz = shrink_chunk(m->host->n_vars <= CS_WAVE ? 2 * CS_SHAVE_CHUNK : CS_SHAVE_CHUNK, batch, 4 * (int64_t)m->n_cus * 32);
+  const int csz = shrink_chunk(m->host->n_vars <= CS_WAVE ? 2 * CS_SHAVE_CHUNK : CS_SHAVE_CHUNK, batch, 4 * (int64_t)m->n_cus * 32);
   const int64_t chunks = (batch + csz - 1) / csz;
   int64_t g = (int64_t)m->n_cus * (int64_t)k->per_cu; /* the resident grid: persistent waves, work drawn by ticket */
   const int64_t need_wg = (chunks + k->waves - 1) / k->waves;
   if (g > need_wg) g = need_wg;
+  *csz_out = csz;
+  *grid_out = g;
+}
+
+extern "C" int csgpu_internal_shave_launch(const csgpu_model *m, int64_t batch, int64_t out[3]) {
+  if (m == NULL || out == NULL || batch < 1) return set_err(CSGPU_E_ARG, "bad argument");
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (!kernel_qualifies(m, 7)) return set_err(CSGPU_E_LIMIT, "model does not qualify for the interval-only shaving kernel");
+  int csz;
+  int64_t g;
+  shave_geometry(m, batch, &csz, &g);
+  out[0] = g;
+  out[1] = m->plan.shave.waves;
+  out[2] = csz;
+  return CSGPU_OK;
+}
+
+static int launch_shave(const csgpu_model *m, const csgpu_val *d_states_in, const csgpu_node *d_nodes,
+                        csgpu_val *d_states_out, csgpu_result *d_results, int64_t batch, const uint64_t *d_batch,
+                        void *stream) {
+  const cs_planned *k = &m->plan.shave;
+  int csz;
+  int64_t g;
+  shave_geometry(m, batch, &csz, &g);
   int n = m->host->n_vars, slots = m->img->dense_slots, dmin_d = m->img->dense_dmin;
   const void *tab_d = m->d_dense_tab;
   const int *root_lo_d = m->d_root_lo, *sym_off = m->d_sym_off;

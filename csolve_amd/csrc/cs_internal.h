@@ -29,6 +29,10 @@ int csgpu_internal_propagate_objdev(const csgpu_model *m, const csgpu_val *d_sta
                                     csgpu_val *d_states_out, csgpu_result *d_results, int64_t batch,
                                     const uint64_t *d_batch, int32_t obj_lo, int32_t obj_hi, const int32_t *d_best,
                                     int sense, void *stream);
+/* the geometry kernel 7 is launched with for a batch of `batch` nodes (or that upper bound of a device-counted one), from
+ * the launcher's own sizing: out = { workgroups, waves per workgroup, nodes per chunk }.  Read-only; the tests place
+ * their batch sizes around "chunks = resident waves" with it, where a shard changes from static shares to tickets. */
+int csgpu_internal_shave_launch(const csgpu_model *m, int64_t batch, int64_t out[3]);
 /* root lower bounds of the variables in device memory (NULL unless the model qualifies for the forbidden-set
  * kernels): bit k of a set word = value root_lo + k */
 const int32_t *csgpu_internal_root_lo(const csgpu_model *m);

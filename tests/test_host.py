@@ -25,6 +25,22 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, n), n
 
 
+def test_the_launch_geometry_accessor_is_internal_and_checks_its_arguments():
+    """csgpu_internal_shave_launch and csgpu_internal_propagate_fb (tests/test_gpu_launch_modes.py): exported and
+    prototyped, declared in cs_internal.h only; the accessor refuses what it cannot answer"""
+    from csolve_amd import _lib
+    from csolve_amd.solver import Model
+    L = _lib.load_library()
+    for name, args in (("csgpu_internal_shave_launch", 3), ("csgpu_internal_propagate_fb", 10)):
+        assert name not in _lib.declared_symbols() and len(getattr(L, name).argtypes) == args, name
+    out = (C.c_int64 * 3)(-7, -7, -7)
+    assert L.csgpu_internal_shave_launch(None, 1, C.byref(out)) == -1
+    m = Model.from_text(open(golden("problems", "queens8.txt")).read())
+    assert L.csgpu_internal_shave_launch(m._h, 1, None) == -1 and L.csgpu_internal_shave_launch(m._h, 0, C.byref(out)) == -1
+    assert L.csgpu_internal_shave_launch(m._h, 1, C.byref(out)) == -5 and b"finalized" in L.csgpu_last_error()
+    assert list(out) == [-7, -7, -7]
+
+
 def test_no_device_means_loud_failure():
     """Without a HIP device the compute entry points fail with the library's error; nothing
     falls back to a CPU implementation."""
