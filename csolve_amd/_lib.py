@@ -325,6 +325,17 @@ def load_library():
     L.csgpu_many_clause_ordered_checkpoint_fanout.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, vp]
     L.csgpu_many_fold_halvings.argtypes = [vp, vp, i64, vp, vp]
     L.csgpu_internal_many_clauses_order_from_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_model_qualifies_many_clauses_wide.argtypes = [vp]
+    L.csgpu_solve_many_clauses_wide.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp]
+    L.csgpu_many_clause_wide_checkpoint_bytes.argtypes = [vp]
+    L.csgpu_many_clause_wide_checkpoint_bytes.restype = C.c_size_t
+    L.csgpu_many_clause_wide_checkpoints_create.argtypes = [vp, i64, C.POINTER(vp)]
+    L.csgpu_solve_many_clauses_wide_checkpointed.argtypes = [vp, vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp, vp]
+    L.csgpu_solve_many_clauses_wide_resume.argtypes = [vp, i64, C.POINTER(ManyOptions), vp, vp, vp, vp, vp, vp]
+    L.csgpu_internal_many_clauses_wide_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_internal_many_clauses_wide_resume_symbol.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.csgpu_internal_many_clauses_wide_waves.argtypes = [vp, i64]
+    L.csgpu_internal_many_clauses_wide_waves.restype = i64
     L.csgpu_many_value.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, Val, C.c_uint32, C.c_int32]
     L.csgpu_many_value.restype = C.c_int32
     L.csgpu_debug_one_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

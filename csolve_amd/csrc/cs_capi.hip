@@ -66,12 +66,15 @@ static const char *const many_kernel_name[MANY_FAMILIES] = { "cs_dive_shave", "c
 #define MANY_BY_ALLOWED(family) ((family) >= MANY_ALLOWED && (family) <= MANY_ALLOWED_UPTO_CK)
 #define CS_DIVE_ALLOWED_WIDTH 128 /* the widest root domain the allowed sets of cs_dive_allowed hold (four 32-bit words) */
 
-/* the kernels of the csgpu_solve_many_clauses family (cs_walk.hip.h): one loop on kernel 6's fixpoint, compiled nine times */
+/* the kernels of the csgpu_solve_many_clauses family (cs_walk.hip.h): one loop on kernel 6's fixpoint, compiled nine times
+ * with the records in registers (WALK_FAMILIES of them, planned together for at most 512 clauses) and twice with the
+ * records in LDS (WALK_WIDE, WALK_WIDE_CK: csgpu_solve_many_clauses_wide, planned for themselves) */
 enum { WALK_PLAIN, WALK_CK, WALK_UPTO, WALK_RESTART, WALK_STREAM, WALK_FROM, WALK_ORDER, WALK_ORDER_CK, WALK_ORDER_FROM,
-       WALK_FAMILIES };
-static const char *const walk_kernel_name[WALK_FAMILIES] = { "cs_walk_clauses", "cs_walk_resume", "cs_walk_upto", "cs_walk_restart",
-                                                             "cs_walk_stream", "cs_walk_from", "cs_walk_order",
-                                                             "cs_walk_order_resume", "cs_walk_order_from" };
+       WALK_FAMILIES, WALK_WIDE = WALK_FAMILIES, WALK_WIDE_CK, WALK_SLOTS };
+static const char *const walk_kernel_name[WALK_SLOTS] = { "cs_walk_clauses", "cs_walk_resume", "cs_walk_upto", "cs_walk_restart",
+                                                          "cs_walk_stream", "cs_walk_from", "cs_walk_order",
+                                                          "cs_walk_order_resume", "cs_walk_order_from", "cs_walk_wide",
+                                                          "cs_walk_wide_resume" };
 
 /* every kernel of the batched fixpoint, its tracing variants, the search steps and the server, for one model */
 struct cs_kernel_plan {
@@ -88,7 +91,8 @@ struct cs_kernel_plan {
   cs_planned step_shave, step_packed, step_import;
   cs_planned dive[MANY_FAMILIES];  /* by MANY_*: the first five all or none, the four MANY_ALLOWED* with them unless the
                                       domains are too wide; not among csgpu_internal_plan_symbol's families */
-  cs_planned walk[WALK_FAMILIES];  /* by WALK_*: kernel 6's instantiation of each, all or none; no plan families either */
+  cs_planned walk[WALK_SLOTS];     /* by WALK_*: kernel 6's instantiation of each of the first WALK_FAMILIES, all or none;
+                                      WALK_WIDE and WALK_WIDE_CK, both or neither; no plan families either */
   int full;                        /* the variables fill the lanes of a wave (64, 128 or 256 of them) */
   int step_kind;                   /* csgpu_internal_step_kind */
   int max_width;                   /* widest root interval, at least 2 */
@@ -983,6 +987,13 @@ static int drop_entailed_clauses(csgpu_model *m) {
   return rc;
 }
 
+/* dynamic LDS of a cs_walk_wide workgroup: the staged block -- the clause records, then two literal records per
+ * two-literal disjunction, 16 bytes each -- and behind it the slices of its waves (kernel 6's: n intervals and the flag) */
+static size_t many_wide_lds(int n_vars, int n_clauses, int n_lits) {
+  const size_t slice = ((size_t)n_vars * sizeof(cs_val) + 16 + 15) & ~(size_t)15;
+  return ((size_t)n_clauses + (size_t)n_lits) * 16 + slice * CS_WAVES_PER_BLOCK;
+}
+
 /* kernels every model runs: the general kernel (1) and its tracing variant, the clause-resident kernel (6), the
  * clause evaluation */
 static int plan_general(csgpu_model *m) {
@@ -1041,6 +1052,23 @@ static int plan_general(csgpu_model *m) {
       }
       if ((rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
     }
+  }
+  /* the two cs_walk_wide kernels: the records in LDS, so no clause count of their own -- every model with a clause whose
+   * staged block and slices fit a CU, those of at most 512 clauses as well */
+  const size_t wide = many_wide_lds(h->n_vars, m->tab.n_clauses, m->tab.n_lits);
+  if (m->tab.n_clauses > 0 && wide <= CS_CU_LDS) {
+    for (int family = WALK_WIDE; family <= WALK_WIDE_CK; family++) {
+      cs_planned *k = &m->plan.walk[family];
+      const void *fn = family == WALK_WIDE ? (m->has_tree_adj ? (const void *)cs_walk_wide<true> : (const void *)cs_walk_wide<false>)
+                                           : (m->has_tree_adj ? (const void *)cs_walk_wide_resume<true>
+                                                              : (const void *)cs_walk_wide_resume<false>);
+      if ((rc = plan_kernel(k, fn, wide, CS_WAVES_PER_BLOCK))) return rc;
+      int occ = 0; /* persistent waves, as the other walks: what stays resident with its registers, scratch and LDS */
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k->fn, CS_BLOCK, k->lds) == hipSuccess && occ >= 1 && occ < k->per_cu)
+        k->per_cu = occ;
+      if (k->per_cu < 1) k->per_cu = 1;
+    }
+    if (m->d_walk_root == NULL && (rc = upload(h->dom, (size_t)h->n_vars * sizeof(cs_val), (int **)&m->d_walk_root))) return rc;
   }
   m->plan.max_width = 2;
   for (int32_t v = 0; v < h->n_vars; v++) {
@@ -1379,6 +1407,8 @@ MANY_SYMBOL(csgpu_internal_many_clauses_from_symbol, walk, walk_kernel_name, WAL
 MANY_SYMBOL(csgpu_internal_many_clauses_order_symbol, walk, walk_kernel_name, WALK_ORDER)
 MANY_SYMBOL(csgpu_internal_many_clauses_order_resume_symbol, walk, walk_kernel_name, WALK_ORDER_CK)
 MANY_SYMBOL(csgpu_internal_many_clauses_order_from_symbol, walk, walk_kernel_name, WALK_ORDER_FROM)
+MANY_SYMBOL(csgpu_internal_many_clauses_wide_symbol, walk, walk_kernel_name, WALK_WIDE)
+MANY_SYMBOL(csgpu_internal_many_clauses_wide_resume_symbol, walk, walk_kernel_name, WALK_WIDE_CK)
 #undef MANY_SYMBOL
 
 extern "C" void csgpu_internal_engine_ref(const csgpu_model *m, int delta) {
@@ -1679,16 +1709,19 @@ struct csgpu_many_checkpoints {
   unsigned long long *d_next; /* slots handed out since the last reset */
   int counted;                /* the model counts this pool among the objects that hold its device tables */
   int kind;                   /* MANY_POOL_DIVE: of csgpu_many_checkpoints_create; MANY_POOL_WALK: of the clause one;
-                                 MANY_POOL_ORDER: of csgpu_many_clause_ordered_checkpoints_create */
+                                 MANY_POOL_ORDER: of csgpu_many_clause_ordered_checkpoints_create; MANY_POOL_WIDE: of
+                                 csgpu_many_clause_wide_checkpoints_create */
   int *d_zero;                /* the clause kinds: n_vars zeros, the offsets cs_dive_export adds to absolute bounds */
   int frames;                 /* the frames a slot has for a stack: n_vars, MANY_POOL_ORDER: csgpu_many_clauses_ordered_frames */
   int split_width;            /* MANY_POOL_ORDER: the split_width the pool was made for (never 0: 256 stands there) */
 };
-enum { MANY_POOL_DIVE, MANY_POOL_WALK, MANY_POOL_ORDER };
+enum { MANY_POOL_DIVE, MANY_POOL_WALK, MANY_POOL_ORDER, MANY_POOL_WIDE };
 #define MANY_POOL_KIND "the checkpoint pool is of the other kind: csgpu_many_checkpoints_create makes the pools of csgpu_solve_many, " \
                        "csgpu_many_clause_checkpoints_create those of csgpu_solve_many_clauses"
 #define MANY_POOL_KIND_ORDER "the checkpoint pool is of the other kind: csgpu_many_clause_ordered_checkpoints_create makes the pools of " \
                              "csgpu_solve_many_clauses_ordered_checkpointed / _resume, and only those"
+#define MANY_POOL_KIND_WIDE "the checkpoint pool is of the other kind: csgpu_many_clause_wide_checkpoints_create makes the pools of " \
+                            "csgpu_solve_many_clauses_wide_checkpointed / _wide_resume, and only those"
 
 extern "C" int64_t csgpu_internal_many_waves(const csgpu_model *m, int64_t count) {
   if (m == NULL || !m->finalized || m->plan.dive[MANY_PLAIN].fn == NULL || count < 1) return 0;
@@ -2273,8 +2306,8 @@ extern "C" int64_t csgpu_many_clauses_ordered_frames(const csgpu_model *m, int32
 /* The checks of every clause entry, none of which touches the device: many_check_head, the entry's own checks of its
  * options (and the stream's of its stream), many_clauses_check_model, what the start and the ordered entries add, and
  * many_clauses_check_pool for a call that has a pool.  This one: the objective the call walks under, against the model;
- * then the model and the count. */
-static int many_clauses_check_model(const csgpu_model *m, int objective, int64_t count) {
+ * then the model and the count.  The objective's half stands alone for the wide entries, whose model check is their own. */
+static int many_clauses_check_objective(const csgpu_model *m, int objective) {
   if (objective != CS_OBJ_ANY && objective != CS_OBJ_ALL && objective != CS_OBJ_MIN && objective != CS_OBJ_MAX)
     return set_err(CSGPU_E_ARG, "no objective %d", objective);
   if (objective == CS_OBJ_MIN || objective == CS_OBJ_MAX) {
@@ -2284,6 +2317,12 @@ static int many_clauses_check_model(const csgpu_model *m, int objective, int64_t
       return set_err(CSGPU_E_ARG, "the model's objective is %s: it cannot be searched with %s",
                      m->host->objective == CS_OBJ_MIN ? "MIN" : "MAX", objective == CS_OBJ_MIN ? "MIN" : "MAX");
   }
+  return CSGPU_OK;
+}
+
+static int many_clauses_check_model(const csgpu_model *m, int objective, int64_t count) {
+  int rc;
+  if ((rc = many_clauses_check_objective(m, objective))) return rc;
   if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
   if (m->plan.walk[WALK_PLAIN].fn == NULL) {
     if (m->plan.rounds_cpl == 0)
@@ -2308,11 +2347,13 @@ struct many_clauses_bufs {
   int32_t *d_slots;
 };
 
-/* `kind`: MANY_POOL_WALK, or the ordered entries' MANY_POOL_ORDER, which take no pool of either older kind */
+/* `kind`: MANY_POOL_WALK, the ordered entries' MANY_POOL_ORDER, which take no pool of either older kind, or the wide
+ * entries' MANY_POOL_WIDE, which take no other either */
 static int many_clauses_check_pool(const csgpu_model *m, const many_clauses_bufs *b, int kind) {
   if (b->ck == NULL || b->d_slots == NULL) return set_err(CSGPU_E_ARG, "null argument: a checkpointed call has a pool and slot numbers");
   if (b->ck->m != m) return set_err(CSGPU_E_ARG, "the checkpoint pool was created for another model");
-  if (b->ck->kind != kind) return set_err(CSGPU_E_ARG, kind == MANY_POOL_ORDER ? MANY_POOL_KIND_ORDER : MANY_POOL_KIND);
+  if (b->ck->kind != kind)
+    return set_err(CSGPU_E_ARG, kind == MANY_POOL_ORDER ? MANY_POOL_KIND_ORDER : kind == MANY_POOL_WIDE ? MANY_POOL_KIND_WIDE : MANY_POOL_KIND);
   return CSGPU_OK;
 }
 
@@ -2437,6 +2478,96 @@ extern "C" int csgpu_many_clause_checkpoint_states(const csgpu_many_checkpoints 
     *have_best = header[1].hi & 1;
   }
   return rc;
+}
+
+/* ---- clause models past 512 clauses: csgpu_solve_many_clauses_wide, the records in LDS (cs_walk_wide, cs_walk_wide_resume) ---- */
+
+/* does the model run the cs_walk_wide kernels?  What finalize planned; before finalize, the same rule on the host tables
+ * (csgpu_model_build_tables) as they stand.  `bytes`, if wanted: the LDS a workgroup needs (0 without tables) */
+static int many_wide_qualifies(const csgpu_model *m, size_t *bytes) {
+  if (bytes != NULL) *bytes = 0;
+  if (m->img == NULL) return 0;
+  const size_t lds = m->finalized ? many_wide_lds(m->host->n_vars, m->tab.n_clauses, m->tab.n_lits)
+                                  : many_wide_lds(m->host->n_vars, m->img->n_clauses, m->img->n_lits);
+  if (bytes != NULL) *bytes = lds;
+  if (m->finalized) return m->plan.walk[WALK_WIDE].fn != NULL;
+  return m->img->n_clauses > 0 && lds <= CS_CU_LDS;
+}
+
+extern "C" int csgpu_model_qualifies_many_clauses_wide(const csgpu_model *m) {
+  return m != NULL && many_wide_qualifies(m, NULL);
+}
+
+extern "C" size_t csgpu_many_clause_wide_checkpoint_bytes(const csgpu_model *m) {
+  if (m == NULL || !many_wide_qualifies(m, NULL)) return 0;
+  const size_t n = (size_t)m->host->n_vars;
+  return (n + 1) * (n + 1) * sizeof(cs_val); /* cs_walk_resume's slot: the header frame, n - 1 pushed frames at most, the current node */
+}
+
+extern "C" int csgpu_many_clause_wide_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out) {
+  return many_pool_create(m, capacity, MANY_POOL_WIDE, m != NULL && m->finalized && m->plan.walk[WALK_WIDE_CK].fn != NULL,
+                          "model does not qualify for csgpu_solve_many_clauses_wide (a clause, and its records and LDS slices fit a CU)",
+                          csgpu_many_clause_wide_checkpoint_bytes(m), m != NULL ? m->host->n_vars : 0, 0, out);
+}
+
+/* the one model check of the wide entries: many_clauses_check_model's objective checks, then the model and the count */
+static int many_wide_check_model(const csgpu_model *m, int objective, int64_t count) {
+  int rc;
+  if ((rc = many_clauses_check_objective(m, objective))) return rc;
+  if (!m->finalized) return set_err(CSGPU_E_STATE, "model is not finalized");
+  if (m->plan.walk[WALK_WIDE].fn == NULL) {
+    size_t bytes = 0;
+    (void)many_wide_qualifies(m, &bytes);
+    if (m->tab.n_clauses <= 0) return set_err(CSGPU_E_LIMIT, "csgpu_solve_many_clauses_wide walks on clause records: this model has none");
+    return set_err(CSGPU_E_LIMIT, "csgpu_solve_many_clauses_wide: %d clause and %d literal records and the LDS slices of the %d waves "
+                                  "of a workgroup need %zu bytes of LDS, more than the 160 KiB (%u bytes) of a CU",
+                   (int)m->tab.n_clauses, (int)m->tab.n_lits, CS_WAVES_PER_BLOCK, bytes, CS_CU_LDS);
+  }
+  if (count > 0x7fffffff - CS_DIVE_SHARDS) return set_err(CSGPU_E_LIMIT, "more than 2^31 - 65 instances in one call");
+  return CSGPU_OK;
+}
+
+extern "C" int csgpu_solve_many_clauses_wide(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                             const csgpu_many_options *options, csgpu_many_result *d_results,
+                                             int32_t *d_solutions, int32_t *d_best, void *stream) {
+  const int null_arg = m == NULL || d_roots == NULL || d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, count, null_arg ? 0 : options->max_nodes, "instance")) ||
+      (rc = many_wide_check_model(m, options->objective, count)))
+    return rc;
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best };
+  return many_clauses_launch(m, WALK_WIDE, m->host->n_vars, options->objective, options->max_nodes, &b, 0, NULL, NULL, NULL);
+}
+
+/* the checkpointed call and its resume (no roots): cs_walk_wide_resume under the options' objective, the checkpoints' code */
+static int many_wide_pooled(const csgpu_model *m, const many_clauses_bufs *b, const csgpu_many_options *options, int resume) {
+  const int null_arg = m == NULL || (!resume && b->d_roots == NULL) || b->d_results == NULL || options == NULL;
+  int rc;
+  if ((rc = many_check_head(null_arg, b->count, null_arg ? 0 : options->max_nodes, "slice")) ||
+      (rc = many_wide_check_model(m, options->objective, b->count)) || (rc = many_clauses_check_pool(m, b, MANY_POOL_WIDE)))
+    return rc;
+  cs_walk_ck wk = many_clauses_ck_arg(b, resume, options->objective);
+  return many_clauses_launch(m, WALK_WIDE_CK, m->host->n_vars, options->objective, options->max_nodes, b, resume, &wk, NULL, NULL);
+}
+
+extern "C" int csgpu_solve_many_clauses_wide_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                                          const csgpu_many_options *options, csgpu_many_result *d_results,
+                                                          int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
+                                                          int32_t *d_slots, void *stream) {
+  const many_clauses_bufs b = { d_roots, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_wide_pooled(m, &b, options, 0);
+}
+
+extern "C" int csgpu_solve_many_clauses_wide_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                                    csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                                    csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream) {
+  const many_clauses_bufs b = { NULL, count, d_results, stream, d_solutions, d_best, ck, d_slots };
+  return many_wide_pooled(m, &b, options, 1);
+}
+
+extern "C" int64_t csgpu_internal_many_clauses_wide_waves(const csgpu_model *m, int64_t count) {
+  if (m == NULL || !m->finalized || m->plan.walk[WALK_WIDE].fn == NULL || count < 1) return 0;
+  return many_clauses_waves(m, &m->plan.walk[WALK_WIDE], count, m->host->n_vars);
 }
 
 /* ---- stopped ALL walks of a clause model spread over the next launch (cs_walk_children, cs_walk_fanout); the fold is

@@ -90,6 +90,11 @@ int csgpu_internal_many_clauses_order_symbol(const csgpu_model *m, char *buf, si
 int csgpu_internal_many_clauses_order_resume_symbol(const csgpu_model *m, char *buf, size_t len);
 /* and for cs_walk_order_from (csgpu_solve_many_clauses_ordered_from / _from_resume) */
 int csgpu_internal_many_clauses_order_from_symbol(const csgpu_model *m, char *buf, size_t len);
+/* and for cs_walk_wide (csgpu_solve_many_clauses_wide) and cs_walk_wide_resume (.._wide_checkpointed / _wide_resume); the
+ * waves a wide call of `count` instances launches (0 if the model does not qualify) */
+int csgpu_internal_many_clauses_wide_symbol(const csgpu_model *m, char *buf, size_t len);
+int csgpu_internal_many_clauses_wide_resume_symbol(const csgpu_model *m, char *buf, size_t len);
+int64_t csgpu_internal_many_clauses_wide_waves(const csgpu_model *m, int64_t count);
 
 /* ---- one level of the search tree in one launch (cs_step.hip.h): branch + fixpoints of the children + store ---- */
 typedef struct csgpu_step_launch {

@@ -117,6 +117,29 @@
  * same loop a ninth time, CS_WALK_CK 1, CS_WALK_ORDER 1 and CS_WALK_FROM 1 -- cs_walk_order_resume's slots and code,
  * cs_walk_from's `start`, own-solutions report and "ck.capacity == 0: no pool".  It walks the children that
  * cs_walk_order_fanout makes of a stopped MIN / MAX walk.
+ *
+ * Past 512 clauses (cs_walk_wide, cs_walk_wide_resume; csgpu_solve_many_clauses_wide / _wide_checkpointed / _wide_resume):
+ * the same loop a tenth and an eleventh time, CS_WALK_WIDE 1 with CS_WALK_CK 0 and 1.  The 512 are the register file's,
+ * not the walk's: the rounds read rec[q], lit0[q], lit1[q], and here those are LDS reads of one block per workgroup --
+ * T.clause_by_kind, then T.lit -- staged before the ticket loop behind one __syncthreads() (cs_walk_body.hip.h), with the
+ * round loop of cs_rounds_wide_body.hip.h: a run-time slot loop over ceil(n_clauses / 64) slots, clause lane + 64 q in
+ * slot q.  That is kernel 6's lane-to-clause assignment and slot order, so on a model of at most 512 clauses every field
+ * of the answer, props included, is cs_walk_clauses's.  Dynamic LDS per workgroup: 16 (n_clauses + n_lits) bytes and the
+ * four slices.  The switch table, with the two new rows:
+ *                        CS_WALK_CK  UPTO  RESTART  STREAM  FROM  ORDER  WIDE
+ *   cs_walk_clauses          0        0      0        0      0     0      0
+ *   cs_walk_resume           1        0      0        0      0     0      0
+ *   cs_walk_upto             1        1      0        0      0     0      0
+ *   cs_walk_restart          0        0      1        0      0     0      0
+ *   cs_walk_stream           1        0      0        1      0     0      0
+ *   cs_walk_from             1        0      0        0      1     0      0
+ *   cs_walk_order            0        0      0        0      0     1      0
+ *   cs_walk_order_resume     1        0      0        0      0     1      0
+ *   cs_walk_order_from       1        0      0        0      1     1      0
+ *   cs_walk_wide             0        0      0        0      0     0      1
+ *   cs_walk_wide_resume      1        0      0        0      0     0      1
+ * A slot of cs_walk_wide_resume is cs_walk_resume's (n + 1 frames, CS_WALK_CK_MAGIC, the objective as its code); the host
+ * keeps the pools apart by a kind of their own, so that no entry of the older families is handed a model it refuses.
  * Resources (-Rpass-analysis=kernel-resource-usage, gfx950) are in DESIGN.md 3.10. */
 #ifndef CS_WALK_HIP_H
 #define CS_WALK_HIP_H
@@ -151,7 +174,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_clauses(cs_tables T, cs_walk
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
 #define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -184,7 +209,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_resume(cs_tables T, cs_walk_
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
 #define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -202,7 +229,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_upto(cs_tables T, cs_walk_io
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
 #define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -221,7 +250,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_restart(cs_tables T, cs_walk
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
 #define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -241,7 +272,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_stream(cs_tables T, cs_walk_
 #define CS_WALK_STREAM 1
 #define CS_WALK_FROM 0
 #define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -266,7 +299,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_from(cs_tables T, cs_walk_io
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 1
 #define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -294,7 +329,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_order(cs_tables T, cs_walk_i
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
 #define CS_WALK_ORDER 1
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -316,7 +353,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_order_resume(cs_tables T, cs
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 0
 #define CS_WALK_ORDER 1
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -464,7 +503,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cs_walk_order_from(cs_tables T, cs_w
 #define CS_WALK_STREAM 0
 #define CS_WALK_FROM 1
 #define CS_WALK_ORDER 1
+#define CS_WALK_WIDE 0
 #include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
 #undef CS_WALK_ORDER
 #undef CS_WALK_FROM
 #undef CS_WALK_STREAM
@@ -636,6 +677,49 @@ __global__ __launch_bounds__(256) void cs_walk_fold_halvings(const long long *__
   if (o < 0) return;
   const long long h = sub_halvings[t];
   if (h != 0) __hip_atomic_fetch_add(halvings + o, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* ---- clause models past 512 clauses: the records in LDS (csgpu_solve_many_clauses_wide; CS_WALK_WIDE of
+ * cs_walk_body.hip.h, the rounds of cs_rounds_wide_body.hip.h).  cs_walk_clauses's walk and arguments; the dynamic LDS is
+ * the staged block, 16 (T.n_clauses + T.n_lits) bytes, and behind it the slices of the workgroup's waves */
+template <bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_wide(cs_tables T, cs_walk_io io) {
+#define CS_WALK_CK 0
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
+#define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
+#undef CS_WALK_ORDER
+#undef CS_WALK_FROM
+#undef CS_WALK_STREAM
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
+}
+
+/* the same with cs_walk_resume's checkpoints and arguments (csgpu_solve_many_clauses_wide_checkpointed / _wide_resume): the
+ * slot layout, the header, CS_WALK_CK_MAGIC and the objective code are cs_walk_resume's */
+template <bool HAS_TREE>
+__global__ __launch_bounds__(CS_BLOCK) void cs_walk_wide_resume(cs_tables T, cs_walk_io io, cs_walk_ck ck) {
+#define CS_WALK_CK 1
+#define CS_WALK_UPTO 0
+#define CS_WALK_RESTART 0
+#define CS_WALK_STREAM 0
+#define CS_WALK_FROM 0
+#define CS_WALK_ORDER 0
+#define CS_WALK_WIDE 1
+#include "cs_walk_body.hip.h"
+#undef CS_WALK_WIDE
+#undef CS_WALK_ORDER
+#undef CS_WALK_FROM
+#undef CS_WALK_STREAM
+#undef CS_WALK_RESTART
+#undef CS_WALK_UPTO
+#undef CS_WALK_CK
 }
 
 /* csgpu_many_fold_best: every sub-record with a solution offers (rank(best) << 32) | row to its owner's key, one relaxed

@@ -1,5 +1,6 @@
-/* cs_walk_body.hip.h -- the body of the nine kernels of cs_walk.hip.h, which includes it inside each of them under six
- * switches (the fifth, CS_WALK_FROM, is 1 for cs_walk_from -- cs_walk_resume's row, and `start` -- and for
+/* cs_walk_body.hip.h -- the body of the eleven kernels of cs_walk.hip.h, which includes it inside each of them under seven
+ * switches (the seventh, CS_WALK_WIDE, is described at the end of this comment; the fifth, CS_WALK_FROM, is 1 for
+ * cs_walk_from -- cs_walk_resume's row, and `start` -- and for
  * cs_walk_order_from; the sixth, CS_WALK_ORDER, for the three cs_walk_order* kernels: `ord`):
  *                      CS_WALK_CK  CS_WALK_UPTO  CS_WALK_RESTART  CS_WALK_STREAM
  *   cs_walk_clauses        0           0              0              0       csgpu_solve_many_clauses
@@ -53,16 +54,41 @@
  * bound before the root node's rounds whatever the order, the header's incumbent is `best` / `have_best` (the start's until
  * the instance has a solution of its own), the report writes io.best at sols > 0 and ord.halvings beside it, and
  * ck.capacity == 0 draws no slot and leaves ck.slots alone.  A resumed instance reads ord.halvings[inst], so the host
- * requires the array with a pool; without one nothing is resumed and it may be NULL. */
+ * requires the array with a pool; without one nothing is resumed and it may be NULL.
+ * CS_WALK_WIDE (a seventh switch; cs_walk_wide with every other switch 0, cs_walk_wide_resume with CS_WALK_CK 1; the
+ * nine kernels above define it 0):
+ *                        CS_WALK_CK  CS_WALK_WIDE
+ *   cs_walk_wide             0            1       cs_walk_clauses's arguments   csgpu_solve_many_clauses_wide
+ *   cs_walk_wide_resume      1            1       cs_walk_resume's arguments    .._wide_checkpointed / _wide_resume
+ * The clause records live in LDS, one copy per workgroup, not in a register array per lane, so the clause count has no
+ * bound but the LDS of a CU.  The three register arrays and their load loop are gone; the workgroup stages
+ * T.clause_by_kind (n_clauses records) and behind it T.lit (two literal records per CS_CL_OR2 clause) once, before its
+ * waves draw their first ticket -- every thread its share, 16 bytes a load and a store -- and one __syncthreads() stands
+ * between the copy and the ticket loop, which no wave can have left before.  Nothing writes the block afterwards.  The
+ * waves' node slices lie behind it (a multiple of 16 bytes, so they stay 16-byte aligned), and the rounds are
+ * cs_rounds_wide_body.hip.h.  No CPL: the kernels are templated on HAS_TREE alone.  The walk, the frames, the slots and
+ * their magic, the counters and every store to device memory are the old text. */
   extern __shared__ __attribute__((aligned(16))) unsigned char cs_lds[];
   const int lane = threadIdx.x & (CS_WAVE - 1);
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wave_global = (int)blockIdx.x * CS_WAVES_PER_BLOCK + wave_in_block;
   const int n = T.n_vars;
   const size_t slice_al = ((size_t)n * sizeof(cs_val) + 16 + 15) & ~(size_t)15;
+#if CS_WALK_WIDE
+  /* the staged block: the clause records, then the literal records; the slices behind it */
+  int4 *const wrec = (int4 *)cs_lds;
+  int4 *const wlit = wrec + T.n_clauses;
+  cs_val *dom = (cs_val *)(cs_lds + ((size_t)T.n_clauses + (size_t)T.n_lits) * sizeof(int4) + wave_in_block * slice_al);
+#else
   cs_val *dom = (cs_val *)(cs_lds + wave_in_block * slice_al);
+#endif
   unsigned *flag = (unsigned *)(dom + n); /* [0]: something changed this round */
 
+#if CS_WALK_WIDE
+  for (int i = (int)threadIdx.x; i < T.n_clauses; i += CS_BLOCK) wrec[i] = T.clause_by_kind[i];
+  for (int i = (int)threadIdx.x; i < T.n_lits; i += CS_BLOCK) wlit[i] = T.lit[i];
+  __syncthreads(); /* the one workgroup barrier: every wave is still here */
+#else
   int4 rec[CPL], lit0[CPL], lit1[CPL];
 #pragma unroll
   for (int q = 0; q < CPL; q++) {
@@ -71,6 +97,7 @@
     lit0[q] = rec[q].x == CS_CL_OR2 ? T.lit[rec[q].y] : make_int4(0, 0, 0, 0);
     lit1[q] = rec[q].x == CS_CL_OR2 ? T.lit[rec[q].y + 1] : make_int4(0, 0, 0, 0);
   }
+#endif
 
   const int nsh = (int)gridDim.x < CS_DIVE_SHARDS ? (int)gridDim.x : CS_DIVE_SHARDS;
   const int shard = (int)(blockIdx.x % nsh);
@@ -348,7 +375,11 @@
         }
         cs_wave_sync();
 
+#if CS_WALK_WIDE
+#include "cs_rounds_wide_body.hip.h"
+#else
 #include "cs_rounds_body.hip.h"
+#endif
         (void)rounds;
 
         /* the open variables of a consistent node, and this lane's candidate for the branching variable */

@@ -131,6 +131,60 @@ def sudoku_roots(box: int, revealed: float, seeds, objective: str = "ANY"):
     return text, roots
 
 
+def _less_pairs(box: int, seed: int, pairs: int):
+    """the `pairs` horizontally adjacent cell pairs of sudoku_less(box, seed, pairs), each as (smaller cell, larger cell)
+    in sudoku_solution(box, seed), sorted by position"""
+    n = box * box
+    grid = sudoku_solution(box, seed)
+    rng = LCG(seed ^ 0xC2B2AE3D27D4EB4F)
+    places = [(r, c) for r in range(n) for c in range(n - 1)]
+    assert 0 <= pairs <= len(places), f"at most {len(places)} horizontally adjacent pairs"
+    rng.shuffle(places)
+    out = []
+    for r, c in sorted(places[:pairs]):
+        a, b = (r, c), (r, c + 1)
+        out.append((a, b) if grid[r][c] < grid[r][c + 1] else (b, a))
+    return out
+
+
+def sudoku_less(box: int, seed: int, pairs: int, objective: str = "ANY") -> str:
+    """A "greater-than sudoku" (futoshiki): the EMPTY box^2 x box^2 model of sudoku_roots() plus `pairs` strict
+    inequalities between horizontally adjacent cells, all true in sudoku_solution(box, seed); the pairs are chosen with
+    the module's LCG.  A != network plus `<` relations: no model of solve_many (kernel 7), and at box = 3 past the 512
+    clauses of kernel 6.  Cells are numbered row by row as in sudoku_roots()."""
+    n = box * box
+    text, _ = sudoku_roots(box, 0.0, [], objective)
+    lines = [line for line in text.split("\n") if line and not line.startswith("#")]
+    lines.insert(0, f"# sudoku {n}x{n}, no givens, {pairs} inequalities of grid {seed}: the model of sudoku_less_roots")
+    for (ra, ca), (rb, cb) in _less_pairs(box, seed, pairs):
+        lines.append(f"{_cell(ra, ca)} < {_cell(rb, cb)};")
+    return "\n".join(lines) + "\n"
+
+
+def sudoku_less_roots(box: int, seed: int, pairs: int, revealed, dom=None, objective: str = "ANY"):
+    """Instances of sudoku_less(box, seed, pairs) -> (its text, int32 array [len(revealed), n_cells, 2] of root rows).
+    Row k reveals int(round(revealed[k] * n_cells)) cells of sudoku_solution(box, seed) as single values -- which cells,
+    the module's LCG seeded with (seed, k) says -- and leaves the others open, so every row has that grid for a solution.
+    dom: the model's root domains, int [n_cells, 2] (Model.domains() of the solved root).  The root fixpoint of the
+    inequalities narrows them below 1 .. box^2 (the smaller cell of a pair cannot be box^2), and an open cell of a row
+    is its root domain: a row outside the root domains is BAD_ROOT to the solve_many family.  None: 1 .. box^2."""
+    import numpy as np
+    n = box * box
+    grid = sudoku_solution(box, seed)
+    roots = np.empty((len(revealed), n * n, 2), dtype=np.int32)
+    if dom is None:
+        roots[:, :, 0], roots[:, :, 1] = 1, n
+    else:
+        roots[:] = np.asarray(dom, dtype=np.int32).reshape(1, n * n, 2)
+    for k, share in enumerate(revealed):
+        rng = LCG((seed * 1000003 + k) ^ 0x9E3779B97F4A7C15)
+        cells = [(r, c) for r in range(n) for c in range(n)]
+        rng.shuffle(cells)
+        for r, c in cells[: int(round(share * n * n))]:
+            roots[k, r * n + c] = grid[r][c]
+    return sudoku_less(box, seed, pairs, objective), roots
+
+
 def schedule(tasks: int = 16, seed: int = 1, horizon_slack: int = 3) -> str:
     """Single-machine scheduling after examples/schedule.txt: per task release, WCET and
     deadline, pairwise non-overlap disjunctions, MIN end."""

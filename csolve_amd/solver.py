@@ -847,6 +847,94 @@ class Model:
         """the cs_walk_resume instantiation the checkpointed clause calls launch, or None"""
         return self._many_symbol("csgpu_internal_many_clauses_resume_symbol")
 
+    # ---- clause models past 512 clauses: the records in LDS (csgpu_solve_many_clauses_wide) ----
+
+    def qualifies_many_clauses_wide(self) -> bool:
+        """may solve_many_clauses_wide run this model: at least one clause, and its clause records, the literal records of
+        its two-literal disjunctions and the LDS slices of a workgroup's four waves fit the 160 KiB of a CU?  Models of at
+        most 512 clauses qualify too.  Host only: what finalize planned, or after build_tables the same rule on the
+        host tables"""
+        return bool(load_library().csgpu_model_qualifies_many_clauses_wide(self._h))
+
+    def many_clauses_wide_kernel(self):
+        """the cs_walk_wide instantiation solve_many_clauses_wide launches, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_wide_symbol")
+
+    def many_clauses_wide_resume_kernel(self):
+        """the cs_walk_wide_resume instantiation the checkpointed wide calls launch, or None"""
+        return self._many_symbol("csgpu_internal_many_clauses_wide_resume_symbol")
+
+    def many_clauses_wide_waves(self, count: int) -> int:
+        """waves a solve_many_clauses_wide of `count` instances launches (0 if the model does not qualify)"""
+        return int(load_library().csgpu_internal_many_clauses_wide_waves(self._h, int(count)))
+
+    def solve_many_clauses_wide(self, roots, objective="ANY", *, max_nodes, solutions=True, stream=None,
+                                checkpoints=None) -> dict:
+        """solve_many_clauses for clause models past 512 clauses (csgpu_solve_many_clauses_wide): the same walk -- the
+        branching rule, the private incumbent under "MIN" / "MAX", the counters, the statuses, max_nodes -- with the
+        clause records in LDS, one copy per workgroup, in place of kernel 6's registers.  The model must satisfy
+        qualifies_many_clauses_wide(); on a model that solve_many_clauses takes as well the two answers are equal field
+        for field, props included.  roots, objective, max_nodes, solutions, stream and the answer: as solve_many_clauses.
+        checkpoints: a pool of many_clause_wide_checkpoints(): an instance that stops at max_nodes keeps its walk and its
+        incumbent in a slot of it (csgpu_solve_many_clauses_wide_checkpointed); the answer then has `slot` [K] int32 (-1:
+        no checkpoint) and is what resume_many_clauses_wide() continues.
+        Not on this walk: up to k solutions, the stream, restarts, the variable orders and halving, start incumbents, the
+        spread over idle waves, clause_checkpoint_states and the Search finish, the sliced drivers."""
+        L = load_library()
+        n = self.n_vars
+        obj = self.MANY_OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        opt = ManyOptions(obj, 0, int(max_nodes))
+        bad = obj not in (0, 1) and (obj not in (2, 3) or self.objective != obj or self.objective_var < 0)
+        roots, K = self._many_roots(roots, bad, lambda ptr, count: check(
+            L.csgpu_solve_many_clauses_wide(self._h, ptr, count, C.byref(opt), ptr, None, None, None)),
+            qualifies=self.finalized and self.qualifies_many_clauses_wide())
+        buf = self._many_records(K, roots.device)
+        first = self._many_rows(bool(solutions), (K, n), "[K, n_vars]", roots.device)
+        best = torch.zeros((max(K, 1),), dtype=torch.int32, device=roots.device) if obj in (2, 3) else None
+        if checkpoints is None:
+            check(L.csgpu_solve_many_clauses_wide(self._h, roots.data_ptr() if K else buf.data_ptr(), K, C.byref(opt),
+                                                  buf.data_ptr(), first.data_ptr() if solutions and K else None,
+                                                  best.data_ptr() if best is not None else None, _stream_ptr(stream)))
+            out = self._many_answer(buf, K, first)
+        else:
+            slots = torch.full((max(K, 1),), -1, dtype=torch.int32, device=roots.device)
+            check(L.csgpu_solve_many_clauses_wide_checkpointed(self._h, roots.data_ptr() if K else buf.data_ptr(), K,
+                                                               C.byref(opt), buf.data_ptr(),
+                                                               first.data_ptr() if solutions and K else None,
+                                                               best.data_ptr() if best is not None else None, checkpoints._h,
+                                                               slots.data_ptr(), _stream_ptr(stream)))
+            out = self._many_answer(buf, K, first, slots, checkpoints)
+            out["_objective"], out["_best"] = obj, best  # resume_many_clauses_wide goes on under the same objective
+        if best is not None:
+            out["best"] = best[:K]
+        return out
+
+    def many_clause_wide_checkpoints(self, capacity: int) -> "ManyCheckpoints":
+        """a pool of `capacity` checkpoint slots for solve_many_clauses_wide(..., checkpoints=)
+        (csgpu_many_clause_wide_checkpoints_create): a ManyCheckpoints of the wide clause kind.  Every other call that
+        takes a pool refuses it, as the wide calls refuse a pool of any other kind"""
+        return ManyCheckpoints(self, capacity, clauses=True, wide=True)
+
+    def clause_wide_checkpoint_bytes(self) -> int:
+        """bytes of one wide clause checkpoint slot, (n_vars + 1)^2 x 8, or 0 if the model does not qualify for
+        solve_many_clauses_wide (host only: after build_tables or finalize)"""
+        return int(load_library().csgpu_many_clause_wide_checkpoint_bytes(self._h))
+
+    def resume_many_clauses_wide(self, result: dict, *, max_nodes, stream=None) -> dict:
+        """continue, in place, the instances of a checkpointed solve_many_clauses_wide answer that stopped with a
+        checkpoint (csgpu_solve_many_clauses_wide_resume): `max_nodes` more nodes each, under the answer's objective,
+        exactly as resume_many_clauses() continues an answer of solve_many_clauses.  -> result"""
+        assert "_checkpoints" in result and "_objective" in result and result["_checkpoints"].wide, \
+            "an answer of solve_many_clauses_wide(..., checkpoints=pool)"
+        opt = ManyOptions(result["_objective"], 0, int(max_nodes))
+        first, best = result.get("first"), result["_best"]
+        K = result["status"].shape[0]
+        check(load_library().csgpu_solve_many_clauses_wide_resume(
+            self._h, K, C.byref(opt), result["_records"].data_ptr(), first.data_ptr() if first is not None and K else None,
+            best.data_ptr() if best is not None else None, result["_checkpoints"]._h, result["_slots"].data_ptr(),
+            _stream_ptr(stream)))
+        return result
+
     def clause_checkpoint_states(self, checkpoints: "ManyCheckpoints", slot: int, stream=None):
         """-> (states, best): the open subtrees of the clause checkpoint in `slot` as states [depth + 1, n_vars, 2] int32
         on the device, the oldest frame (the largest subtree) first, and the instance's incumbent or None
@@ -1841,11 +1929,12 @@ class _SpreadRounds:
 
 
 class ManyCheckpoints:
-    """A pool of checkpoint slots of one finalized model (csgpu_many_checkpoints), of one of three kinds: for solve_many
-    (Model.many_checkpoints), for solve_many_clauses (Model.many_clause_checkpoints) or for solve_many_clauses_ordered
-    (Model.many_clause_ordered_checkpoints).  It holds the model."""
+    """A pool of checkpoint slots of one finalized model (csgpu_many_checkpoints), of one of four kinds: for solve_many
+    (Model.many_checkpoints), for solve_many_clauses (Model.many_clause_checkpoints), for solve_many_clauses_ordered
+    (Model.many_clause_ordered_checkpoints) or for solve_many_clauses_wide (Model.many_clause_wide_checkpoints).  It
+    holds the model."""
 
-    def __init__(self, model: Model, capacity: int, clauses: bool = False, split_width=None):
+    def __init__(self, model: Model, capacity: int, clauses: bool = False, split_width=None, wide: bool = False):
         self.model = model
         self.capacity = int(capacity)
         self.clauses = bool(clauses)  # the kind: of solve_many_clauses (csgpu_many_clause_checkpoints_create), else of solve_many
@@ -1853,12 +1942,18 @@ class ManyCheckpoints:
         # split_width, a slot has `frames` + 1 frames
         self.ordered = split_width is not None
         self.split_width = int(split_width) if self.ordered else None
+        # the fourth kind, of solve_many_clauses_wide (csgpu_many_clause_wide_checkpoints_create)
+        self.wide = bool(wide)
         self._h = C.c_void_p()
         L = load_library()
         if self.ordered:
             assert self.clauses, "an ordered pool is a clause pool"
             check(L.csgpu_many_clause_ordered_checkpoints_create(model._h, self.capacity, self.split_width, C.byref(self._h)))
             self.frames = model.many_clauses_ordered_frames(self.split_width)
+            return
+        if self.wide:
+            assert self.clauses, "a wide pool is a clause pool"
+            check(L.csgpu_many_clause_wide_checkpoints_create(model._h, self.capacity, C.byref(self._h)))
             return
         create = L.csgpu_many_clause_checkpoints_create if self.clauses else L.csgpu_many_checkpoints_create
         check(create(model._h, self.capacity, C.byref(self._h)))

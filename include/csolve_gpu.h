@@ -1112,6 +1112,52 @@ int csgpu_many_clause_ordered_checkpoint_fanout(const csgpu_many_checkpoints *ck
 int csgpu_many_fold_halvings(const int64_t *d_sub_halvings, const int32_t *d_owner, int64_t total, int64_t *d_halvings,
                              void *stream);
 
+/* ---- clause models past 512 clauses: csgpu_solve_many_clauses with the clause records in LDS ----
+ * csgpu_solve_many_clauses and everything built on it walk on kernel 6's fixpoint, which keeps every clause record in
+ * registers: 512 clauses at most, CSGPU_E_LIMIT above.  That limit is the register file's, not the walk's.  These calls
+ * are an entry of their own, opt-in, for which a workgroup stages the records once in LDS -- 16 bytes per clause and 32
+ * more per two-literal disjunction, one copy for the workgroup's four waves -- and every wave reads its clause of a slot
+ * from there (cs_walk_wide, cs_walk_wide_resume).  The existing entries keep refusing what they refused.
+ * THE WALK IS csgpu_solve_many_clauses's, by reference: the node, the branching variable (smallest hi - lo, ties to the
+ * lowest index), the ascending values, the child and its rounds, the private incumbent under MIN / MAX, the stored row,
+ * d_best, the counters (nodes, cuts, solutions, props, root_props), the statuses (DONE, LIMIT, BAD_ROOT; BAD_SLOT from a
+ * resume), max_nodes compared before a child is tried, a root row outside the root domains, the objective checks, the
+ * concurrency rule and count == 0 are all defined there and in "clause checkpoints" above.  Two things differ:
+ *   where the records live   in LDS, not in registers.  The order is the same (the records sorted by kind, clause
+ *                            lane + 64 q in slot q, the slots in ascending order), so on a model both entries take every
+ *                            field of every record is the same, props and root_props included
+ *   which models qualify     every finalized model with at least one clause whose staged block and the LDS slices of a
+ *                            workgroup's four waves fit the 160 KiB of a CU: 16 (clauses + 2 disjunctions) +
+ *                            4 ((8 n_vars + 16) rounded up to 16) bytes.  Models of at most 512 clauses qualify too.
+ *                            csgpu_model_qualifies_many_clauses_wide says so: after finalize what was planned, after
+ *                            csgpu_model_build_tables alone the same rule on the host tables (no HIP call)
+ * A model that does not fit -> CSGPU_E_LIMIT, and the message names the bytes it needs and the 160 KiB.
+ * Checkpoints: csgpu_solve_many_clauses_wide_checkpointed / _wide_resume are csgpu_solve_many_clauses_checkpointed /
+ * _resume, slot layout, header and codes included; a slot is csgpu_many_clause_wide_checkpoint_bytes(m) =
+ * (n_vars + 1)^2 x 8 bytes (0 if the model does not qualify, and for NULL; no HIP call).  The pool is of a kind of its
+ * own, made by csgpu_many_clause_wide_checkpoints_create: every other entry that takes a pool -- the resumes, _children,
+ * _fanout and _states of all three older kinds -- refuses it with CSGPU_E_ARG, as the wide entries refuse a pool of
+ * another kind; csgpu_many_checkpoints_reset and _free serve it as any pool.  A resume under another objective than the
+ * checkpoint's is CSGPU_MANY_BAD_SLOT per instance, as on the plain walk.
+ * Errors before any HIP call, in csgpu_solve_many_clauses's order and with its codes, the model's own check in the place
+ * of "at most 512 clauses".
+ * Not here (each is out of scope for the wide walk and stays with the entries above, at most 512 clauses): up to k
+ * solutions, the stream and restarts; the variable orders and halving; start incumbents; the spread over idle waves and
+ * csgpu_many_clause_checkpoint_states with the Search finish; the sliced drivers.  Kernel 6 itself (csgpu_propagate_batch
+ * with kernel 6, the engine) keeps its 512, and a model whose block does not fit LDS is not read through L2 instead. */
+int csgpu_model_qualifies_many_clauses_wide(const csgpu_model *m);
+int csgpu_solve_many_clauses_wide(const csgpu_model *m, const csgpu_val *d_roots, int64_t count, const csgpu_many_options *options,
+                                  csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best, void *stream);
+size_t csgpu_many_clause_wide_checkpoint_bytes(const csgpu_model *m);
+int csgpu_many_clause_wide_checkpoints_create(const csgpu_model *m, int64_t capacity, csgpu_many_checkpoints **out);
+int csgpu_solve_many_clauses_wide_checkpointed(const csgpu_model *m, const csgpu_val *d_roots, int64_t count,
+                                               const csgpu_many_options *options, csgpu_many_result *d_results,
+                                               int32_t *d_solutions, int32_t *d_best, csgpu_many_checkpoints *ck,
+                                               int32_t *d_slots, void *stream);
+int csgpu_solve_many_clauses_wide_resume(const csgpu_model *m, int64_t count, const csgpu_many_options *options,
+                                         csgpu_many_result *d_results, int32_t *d_solutions, int32_t *d_best,
+                                         csgpu_many_checkpoints *ck, int32_t *d_slots, void *stream);
+
 /* Three-valued evaluation of the root wide-and for a batch of states:
  * d_truth[i] = 1 (all clauses true), 0 (some clause false), 2 (undecided). */
 int csgpu_eval_batch(const csgpu_model *m, const csgpu_val *d_states, int32_t *d_truth, int64_t batch,

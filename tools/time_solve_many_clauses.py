@@ -67,7 +67,17 @@ the ONE ordered call with the summed budget, alternating in this process after a
 checkpointed call with B1 -- is timed on its own as well, so `--sliced N` with an N no instance reaches is the cost of the
 checkpoint switch alone.  Every field of the sliced answer must equal the one call's (--finish resume; with --finish
 search every instance ends DONE and `best` is the one call's where that one is DONE), and the seeded sample is re-checked
-against the host walk."""
+against the host walk.
+
+--wide [--set NAME] [--budget N] times Model.solve_many_clauses_wide (the clause records in LDS, no 512-clause limit).  NAME
+is a case of tests/many_clause_wide_sets.py (default sudoku_less_any; schedule32_min, ...: past 512 clauses), whose rows are
+repeated up to --count: the wide call beside one Search per instance -- the only other route for such a model -- on a
+sample, alternating in this process after a warm-up.  Or NAME is a set of tests/many_clause_sets.py (at most 512 clauses):
+then the wide call beside the plain call of solve_many_clauses on the same rows and budget -- the price of LDS records --
+with every field compared, and the Search loop beside both.  The output has the resident workgroups per CU and the LDS
+per workgroup of the kernels, and the seeded sample re-checked against the host walk.  --loop-iterations N stops the engine
+after N iterations per instance (a MIN row without a deadline has no end a measurement could wait for); the output says
+how many instances of the sample that left unfinished."""
 import argparse
 import json
 import os
@@ -123,7 +133,16 @@ def main():
                     help="own: walk a MIN / MAX set under its objective (the spread with start incumbents)")
     ap.add_argument("--order", default=None, help="NAME: time solve_many_clauses_ordered beside the plain call (with --split)")
     ap.add_argument("--split", type=int, default=256, help="with --order: split_width")
+    ap.add_argument("--loop-iterations", type=int, default=1 << 62, help="with --wide: at most so many engine iterations per "
+                                                                         "instance of the Search loop (default: to the end)")
+    ap.add_argument("--wide", action="store_true", help="time solve_many_clauses_wide beside one Search per instance, and on a "
+                                                        "set of at most 512 clauses beside the plain call as well")
     args = ap.parse_args()
+    if args.wide:
+        if args.order is not None or args.spread is not None or args.stream is not None or args.sliced or \
+                args.upto is not None or args.restarts is not None:
+            ap.error("--wide: without --order, --spread, --stream, --sliced, --upto and --restarts")
+        return wide_route(args)
     if args.order is not None and args.spread is None:
         if args.stream is not None or args.upto is not None or args.restarts is not None:
             ap.error("--order NAME: without --stream, --upto and --restarts")
@@ -228,6 +247,94 @@ def main():
         "oracle_checked": len(picks), "oracle_ok": bool(ok),
     }))
     return 0 if ok and same_optimum is not False else 1
+
+
+def wide_route(args):
+    """the wide call beside one Search per instance and, at most 512 clauses, beside the plain call"""
+    import many_clause_sets as sets
+    import many_clause_wide_sets as wsets
+    import many_walk_objective as W
+    name = args.set or "sudoku_less_any"
+    if name not in wsets.CASES and name not in sets.SETS:
+        raise SystemExit(f"--wide: --set is one of {sorted(wsets.CASES)} or of {sorted(sets.SETS)}")
+    text, base, objective, budget = (wsets if name in wsets.CASES else sets).build(name)
+    budget = args.budget or budget
+    roots = np.tile(np.array(base), (-(-args.count // len(base)), 1, 1))[:args.count]
+    count = len(roots)
+    model = solve_root(text)
+    dev = torch.from_numpy(roots).cuda()
+    rng = np.random.default_rng(args.seed)
+    sample = np.sort(rng.choice(count, size=min(args.loop_sample, count), replace=False))
+    search = Search(model, 1 << 18, 1 << 14)
+    node = torch.tensor([[-1, 0, 0, 0]], dtype=torch.int32, device="cuda")
+    plain = model.qualifies_many_clauses()
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+
+    def loop():  # the engine has no node budget per instance: --loop-iterations bounds its steps instead
+        total, unfinished = 0, 0
+        for i in sample:
+            state, res = model.propagate(dev[i:i + 1], node)
+            if int(res[0, 0]) <= 0:  # inconsistent, or solved by the root node
+                continue
+            search.reset()
+            search.put(state)
+            st = search.run(args.loop_iterations)
+            total += st["nodes"]
+            unfinished += st["done"] == 0
+        return total, unfinished
+
+    calls = {"wide": lambda: model.solve_many_clauses_wide(dev, objective, max_nodes=budget), "loop": loop}
+    if plain:
+        calls["plain"] = lambda: model.solve_many_clauses(dev, objective, max_nodes=budget)
+    for _ in range(2):  # warm-up: code load, workspace, the engine's buffers
+        for call in calls.values():
+            timed(call)
+    times, outs = {k: [] for k in calls}, {}
+    for _ in range(args.reps):  # alternating: a drift of the machine falls on all alike
+        for k, call in calls.items():
+            dt, outs[k] = timed(call)
+            times[k].append(dt)
+    host = {k: {f: v.cpu().numpy() for f, v in outs[k].items() if torch.is_tensor(v)} for k in calls if k != "loop"}
+    got = host["wide"]
+    same = all(bool((got[f] == host["plain"][f]).all()) for f in got) if plain else None
+    picks = rng.choice(count, size=min(args.check, count), replace=False)
+    want = W.walk_many(text, roots[picks], objective, budget)
+    has = want["solutions"] > 0
+    ok = all((got[f][picks] == want[f]).all() for f in W.FIELDS) and bool((got["first"][picks][has] == want["first"][has]).all())
+    if objective in ("MIN", "MAX"):
+        ok = ok and bool((got["best"][picks][has] == want["best"][has]).all())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    wide_rate, loop_rate = count / med["wide"], len(sample) / med["loop"]
+    waves = model.many_clauses_wide_waves(1 << 30)
+    record = {
+        "tool": "time_solve_many_clauses", "route": "wide", "commit": commit(), "command": " ".join(sys.argv), "set": name,
+        "objective": objective, "instances": count, "max_nodes": budget, "n_vars": model.n_vars, "clauses": model.n_clauses,
+        "wide_kernel": model.many_clauses_wide_kernel(), "wide_waves": model.many_clauses_wide_waves(count),
+        "wide_resident_waves": waves, "compute_units": torch.cuda.get_device_properties(0).multi_processor_count,
+        "wide_workgroups_per_cu": waves // 4 // torch.cuda.get_device_properties(0).multi_processor_count,
+        "status_counts": np.bincount(got["status"], minlength=3).tolist(), "nodes": int(got["nodes"].sum()),
+        "largest_tree": int(got["nodes"].max()), "solutions": int(got["solutions"].sum()),
+        "wide_ms": spread(times["wide"]), "wide_instances_per_s": round(wide_rate),
+        "wide_ns_per_node": round(med["wide"] * 1e9 / max(int(got["nodes"].sum()), 1), 2),
+        "loop_instances": len(sample), "loop_nodes": int(outs["loop"][0]), "loop_iterations_at_most": args.loop_iterations,
+        "loop_unfinished": int(outs["loop"][1]), "loop_s": spread(times["loop"], 1.0),
+        "loop_instances_per_s": round(loop_rate), "wide_over_loop_instances_per_s": round(wide_rate / loop_rate, 1),
+    }
+    if plain:
+        pw = model.many_clauses_waves(1 << 30)
+        record.update({"plain_kernel": model.many_clauses_kernel(), "plain_ms": spread(times["plain"]),
+                       "plain_resident_waves": pw,
+                       "plain_workgroups_per_cu": pw // 4 // torch.cuda.get_device_properties(0).multi_processor_count,
+                       "wide_over_plain": round(med["wide"] / med["plain"], 4), "every_field_equals_the_plain_call": same})
+    record.update({"oracle_checked": len(picks), "oracle_ok": bool(ok)})
+    print(json.dumps(record))
+    return 0 if ok and same is not False else 1
 
 
 def order_route(args):
